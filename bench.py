@@ -2,6 +2,7 @@
 """Benchmark of the CenterNet DLA-34 hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--task infer|train] [--batch B] [--precision f16x3|f16|f32]
+                    [--dump-outputs DIR]
 
 N = 1 workload (BASELINE.json configs[1]): DLA-34 CenterNet inference, batch 64, 512x512 synthetic uint8
 images resident in HBM; one step = the whole eval forward of the meta-architecture (preprocess, backbone, heads,
@@ -419,6 +420,33 @@ def timed_infer(model, images, steps, warmup, dist, backend, device):
     return elapsed, out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: write `arrays` (name -> array) as out_dir/<name>.npy; floating arrays keep float64, everything else
+    becomes float32 (class ids and counts are exact in it)"""
+    import numpy as np
+
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def detection_arrays(out):
+    """the Instances of one inference step as flat arrays: every image's detections in image order, and the count per image"""
+    inst = [o["instances"] for o in out]
+    return {"boxes": torch.cat([i.pred_boxes.tensor.reshape(-1, 4) for i in inst]).float().cpu(),
+            "scores": torch.cat([i.scores.reshape(-1) for i in inst]).float().cpu(),
+            "classes": torch.cat([i.pred_classes.reshape(-1) for i in inst]).float().cpu(),
+            "detections_per_image": torch.tensor([len(i) for i in inst], dtype=torch.float32)}
+
+
 def train_roofline(model, cfg, B, size, rank, device):
     """one instrumented eager training step (no graph): HIP events around the backward-side launches and every conv"""
     from detectron2_centernet_amd import ops
@@ -525,8 +553,9 @@ def self_launch(args):
 
 
 def infer_record(precision, state, images, steps, warmup, dist, backend, device, world, config, with_roofline, headline,
-                 oracle_out, size):
-    """one precision of the inference workload: timed serving loop, roofline of its kernels, accuracy against the oracle"""
+                 oracle_out, size, dump_dir=None):
+    """one precision of the inference workload: timed serving loop, roofline of its kernels, accuracy against the oracle;
+    with `dump_dir` the detections of the last timed step are written there"""
     model, cfg = build_model(precision, device, calibrate=state is None, config=config)
     if state is not None:
         model.load_state_dict(state)      # the same weights and calibrated BatchNorm statistics in every mode
@@ -534,6 +563,8 @@ def infer_record(precision, state, images, steps, warmup, dist, backend, device,
     B = images.shape[0]
     elapsed, out = timed_infer(model, images, steps, warmup, dist, backend, device)
     assert len(out) == B
+    if dump_dir is not None:
+        dump_outputs(detection_arrays(out), dump_dir)
     rec = {"value": world * B * steps / elapsed, "unit": "images/s", "ms_per_step": 1000.0 * elapsed / steps, "steps": steps,
            "warmup": warmup, "dtype": precision, "note": MODE_NOTES[precision],
            "detections_per_image": sum(len(o["instances"]) for o in out) / max(1, len(out)),
@@ -567,7 +598,12 @@ def main():
     ap.add_argument("--no-f16", action="store_true", help="skip the f16 inference sub-record")
     ap.add_argument("--no-train", action="store_true", help="skip the training sub-records")
     ap.add_argument("--require-graph", action="store_true", help="fail if the training step did not replay as a HIP graph")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned (rank 0) as DIR/<name>.npy: the detections "
+                         "(boxes, scores, classes, detections_per_image) for --task infer, the losses for --task train")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
@@ -615,6 +651,8 @@ def main():
         from detectron2_centernet_amd.engine.bench_train import run_train_bench
         model, cfg = build_model(args.precision, device, config=args.config)
         result = run_train_bench(model, cfg, args, args.batch or 16, rank, world, device, dist)
+        if rank == 0 and args.dump_outputs is not None:
+            dump_outputs({"loss_" + k: v for k, v in result["config"]["final_losses"].items()}, args.dump_outputs)
         if rank == 0 and not args.no_roofline:
             result["roofline"] = train_roofline(model, cfg, args.batch or 16, args.size, rank, device)
         if args.require_graph and world == 1 and result["config"]["graph_state"] != "captured":
@@ -625,7 +663,8 @@ def main():
         images = synthetic_images(B, args.size, rank, device)
         solo = rank == 0 and world == 1
         rec, model, cfg = infer_record(args.precision, None, images, args.steps, args.warmup, dist, backend, device, world,
-                                       args.config, rank == 0 and not args.no_roofline, headline, None, args.size)
+                                       args.config, rank == 0 and not args.no_roofline, headline, None, args.size,
+                                       dump_dir=args.dump_outputs if rank == 0 else None)
         result = {
             "metric": "images/sec at 512x512 (infer bs=64)" if headline else
                       f"images/sec at {args.size}x{args.size} (infer bs={B})",

@@ -497,6 +497,14 @@ def main():
     assert em.get_input_names() == ["images", "im_info"]
     np.savez_compressed(os.path.join(HERE, "g15_export_split.npz"), x=x.numpy(), hm=res["hm"].numpy(), wh=res["wh"].numpy(),
                         reg=res["reg"].numpy(), output_names=np.array(em.get_output_names()))
+
+    # G16: the reference's COCO-Detection config files, byte for byte -- data the config loader must accept unchanged
+    cfg_src = os.path.join(REF, "projects", "CenterNet", "configs", "COCO-Detection")
+    cfg_dst = os.path.join(HERE, "g16_configs")
+    os.makedirs(cfg_dst, exist_ok=True)
+    for name in ("Base-CenterNet.yaml", "ctdet_dla_34_1x.yaml", "ctdet_res_50_1x.yaml"):
+        with open(os.path.join(cfg_src, name), "rb") as fi, open(os.path.join(cfg_dst, name), "wb") as fo:
+            fo.write(fi.read())
     print("golden vectors written to", HERE)
 
 

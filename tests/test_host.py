@@ -72,11 +72,11 @@ def test_yaml_with_base_and_tuple_strings(tmp_path):
     assert cfg.MODEL.DEVICE == "cpu"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree only exists in the build container")
 def test_reference_yamls_load_unchanged():
+    """the reference's own config files (tests/golden/g16_configs, copied byte for byte by make_golden.py G16)"""
     from detectron2_centernet_amd.config import get_cfg
 
-    d = "/root/reference/projects/CenterNet/configs/COCO-Detection"
+    d = os.path.join(ROOT, "tests", "golden", "g16_configs")
     cfg = get_cfg()
     cfg.merge_from_file(os.path.join(d, "ctdet_dla_34_1x.yaml"))
     assert cfg.MODEL.META_ARCHITECTURE == "CenterNet" and cfg.SOLVER.MAX_ITER == 265000
@@ -382,3 +382,35 @@ def test_tap_pair_weight_images_reproduce_the_convolution(cin):
             X, Y = blk[:, 0, :, o], blk[:, 1, :, o]                               # [row, q, j]: w_hi, w_lo
             out += torch.einsum("rqj,qjyx->ryx", X, hi) + torch.einsum("rqj,qjyx->ryx", Y, hi) + torch.einsum("rqj,qjyx->ryx", X, lo)
     assert (out - ref).abs().max().item() < 1e-6 * max(1.0, ref.abs().max().item())
+
+
+def test_bench_dump_outputs_writes_the_step_results(tmp_path):
+    """bench.py --dump-outputs: the Instances of a step as flat float32 arrays in image order, losses as float64 scalars"""
+    import numpy as np
+
+    import bench
+    from detectron2_centernet_amd.structures import Boxes, Instances
+
+    g = torch.Generator().manual_seed(0)
+    out = []
+    for n in (3, 0, 2):
+        r = Instances((64, 96))
+        r.pred_boxes = Boxes(torch.rand(n, 4, generator=g))
+        r.scores = torch.rand(n, generator=g)
+        r.pred_classes = torch.randint(0, 80, (n,), generator=g, dtype=torch.int32)
+        out.append({"instances": r})
+    bench.dump_outputs(bench.detection_arrays(out), str(tmp_path / "infer"))
+    got = {f[:-4]: np.load(tmp_path / "infer" / f) for f in os.listdir(tmp_path / "infer")}
+    assert sorted(got) == ["boxes", "classes", "detections_per_image", "scores"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["detections_per_image"].tolist() == [3, 0, 2]
+    inst = [o["instances"] for o in out]
+    assert np.array_equal(got["boxes"], torch.cat([i.pred_boxes.tensor for i in inst]).numpy())
+    assert np.array_equal(got["scores"], torch.cat([i.scores for i in inst]).numpy())
+    assert got["classes"].tolist() == torch.cat([i.pred_classes for i in inst]).tolist()
+
+    bench.dump_outputs({"loss_hm": 1.25, "loss_wh": 0.5}, str(tmp_path / "train"))
+    hm = np.load(tmp_path / "train" / "loss_hm.npy")
+    assert hm.dtype == np.float64 and hm.shape == () and float(hm) == 1.25
+    with pytest.raises(SystemExit):
+        bench.dump_outputs({"big": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)}, str(tmp_path / "big"))
