@@ -20,7 +20,12 @@ __device__ __forceinline__ float wsum(float v) {
 
 // ------------------------------------------------------------------------------------------------
 // per-channel reductions over the M rows of an NHWC tensor: thread = (row lane, 8-channel vector)
-//   mode 0 (BN forward stats):  r0 = sum y,        r1 = sum y^2
+//   mode 0 (BN forward stats):  r0 = sum y,        r1 = sum y^2                      (f16 tensors)
+//                               r0 = sum (y-K),    r1 = sum (y-K)^2                  (f32 tensors)
+//     K = the channel's value in row 0 (pivot, stored by block 0 for chan_finalize): still one pass, but the f32 sums no
+//     longer carry mean^2 -- plain sums of y, y^2 lost the variance of channels with |mean| >> std (E[y^2] - mean^2: invstd
+//     off by 1.4e-5 at mean/std = 100, M = 4.2M).  f16 tensors keep the plain sums: there y itself is stored to
+//     ulp(mean) ~ 5e-4 mean, far above that cancellation, and their statistics stay those the f16 mode always had.
 //   mode 1 (BN/act backward):   g = dz * (z > 0 if relu);  r0 = sum g,  r1 = sum g * xhat   (xhat = (y-mean)*invstd)
 // partial[blk][2][C] f32, reduced in fixed order by chan_finalize (f64) => deterministic.
 // ------------------------------------------------------------------------------------------------
@@ -37,12 +42,14 @@ struct ChanRedArgs {
   const float* mean; const float* invstd;
   int M, C, mode, relu;
   float* partial;
+  float* pivot;                  // mode 0, f32 tensors: [C], written by block 0
 };
 
 template <typename T>
 __global__ void __launch_bounds__(256) chan_reduce_kernel(ChanRedArgs<T> a) {
   typedef typename VecT<T>::type V;
   constexpr int N = VecT<T>::N;
+  constexpr bool PIVOT = std::is_same<T, float>::value;
   __shared__ float red[2][256][N];
   const int CV = a.C / N;
   const int rows_per_pass = 256 / CV;  // CV <= 256
@@ -54,6 +61,15 @@ __global__ void __launch_bounds__(256) chan_reduce_kernel(ChanRedArgs<T> a) {
   if (a.mode == 1 && a.y) {
 #pragma unroll
     for (int e = 0; e < N; ++e) { mu[e] = a.mean[cv * N + e]; is[e] = a.invstd[cv * N + e]; }
+  }
+  if (PIVOT && a.mode == 0) {   // mu = the pivot K
+    const V v = *(const V*)(a.y + cv * N);
+#pragma unroll
+    for (int e = 0; e < N; ++e) mu[e] = (float)v[e];
+    if (blockIdx.x == 0 && rl == 0) {
+#pragma unroll
+      for (int e = 0; e < N; ++e) a.pivot[cv * N + e] = mu[e];
+    }
   }
   if (rl < rows_per_pass) {
     const long step = (long)gridDim.x * rows_per_pass;
@@ -68,7 +84,7 @@ __global__ void __launch_bounds__(256) chan_reduce_kernel(ChanRedArgs<T> a) {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-          for (int e = 0; e < N; ++e) { const float f = (float)v[u][e]; s0[e] += f; s1[e] += f * f; }
+          for (int e = 0; e < N; ++e) { const float f = PIVOT ? (float)v[u][e] - mu[e] : (float)v[u][e]; s0[e] += f; s1[e] += f * f; }
       }
     } else {
       for (; m + step < a.M; m += 2 * step) {      // two rows of the (up to) three tensors in flight
@@ -94,7 +110,7 @@ __global__ void __launch_bounds__(256) chan_reduce_kernel(ChanRedArgs<T> a) {
       if (a.mode == 0) {
         const V v = *(const V*)(a.y + m * a.y_stride + cv * N);
 #pragma unroll
-        for (int e = 0; e < N; ++e) { const float f = (float)v[e]; s0[e] += f; s1[e] += f * f; }
+        for (int e = 0; e < N; ++e) { const float f = PIVOT ? (float)v[e] - mu[e] : (float)v[e]; s0[e] += f; s1[e] += f * f; }
       } else {
         const V g = *(const V*)(a.dz + m * a.dz_stride + cv * N);
         V zz = g, yy = g;
@@ -135,7 +151,8 @@ __global__ void __launch_bounds__(256) chan_reduce_kernel(ChanRedArgs<T> a) {
   }
 }
 
-// mode 0: mean/invstd/scale/shift (+ running stats);  mode 1: out0 = sum g (dbeta / dbias), out1 = sum g*xhat (dgamma)
+// mode 0: mean/invstd/scale/shift (+ running stats) from the sums around the pivot (null: plain sums);
+// mode 1: out0 = sum g (dbeta / dbias), out1 = sum g*xhat (dgamma)
 // threads stride over the block partials, fixed-order f64 shuffle + LDS reduction (deterministic)
 __global__ void __launch_bounds__(256) chan_finalize_kernel(const float* __restrict__ partial, int nblocks, int C, int M,
                                                             int mode, float eps, float momentum,
@@ -143,7 +160,8 @@ __global__ void __launch_bounds__(256) chan_finalize_kernel(const float* __restr
                                                             float* __restrict__ out0, float* __restrict__ out1,
                                                             float* __restrict__ scale, float* __restrict__ shift,
                                                             float* __restrict__ running_mean,
-                                                            float* __restrict__ running_var) {
+                                                            float* __restrict__ running_var,
+                                                            const float* __restrict__ pivot) {
   // one workgroup per channel (the kernel sits on the step's dependency chain 146 times: with one wave per channel and 16
   // serial loads per lane it took 6 us)
   __shared__ double sh[2][4];
@@ -159,8 +177,9 @@ __global__ void __launch_bounds__(256) chan_finalize_kernel(const float* __restr
   s0 = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
   s1 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
   if (mode == 0) {
-    const double mean = s0 / M;
-    double var = s1 / M - mean * mean;
+    const double dm = s0 / M;                   // mean - K
+    const double mean = pivot ? (double)pivot[c] + dm : dm;
+    double var = s1 / M - dm * dm;
     if (var < 0) var = 0;
     const double invstd = 1.0 / sqrt(var + (double)eps);
     out0[c] = (float)mean;
@@ -1335,10 +1354,12 @@ static int launch_bn_train_fwd_t(const T* y, int y_stride, const T* res, int res
               "bn: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
   ChanRedArgs<T> a = {};
   a.y = y; a.y_stride = y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)workspace;
+  // f32 tensors: the pivot goes to the backward's [2][C] sums slot, free in the forward
+  a.pivot = std::is_same<T, float>::value ? (float*)workspace + (size_t)1024 * 2 * C : nullptr;
   const int nb = chan_blocks(M, C, N);
   hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
   hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 0, eps,
-                     momentum, gamma, beta, mean, invstd, scale, shift, running_mean, running_var);
+                     momentum, gamma, beta, mean, invstd, scale, shift, running_mean, running_var, (const float*)a.pivot);
   const int CV = C / N;
   if ((CV & (CV - 1)) == 0) {
     int sh = 0;
@@ -1372,7 +1393,7 @@ static int launch_bn_train_bwd_t(const T* dz, int dz_stride, const T* z, int z_s
   float* sums = (float*)workspace + (size_t)1024 * 2 * C;   // [2][C]: sum g, sum g*xhat
   hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 1,
                      grad_mult, 0.f, (const float*)nullptr, (const float*)nullptr, dbeta, dgamma, sums, sums + C,
-                     (float*)nullptr, (float*)nullptr);
+                     (float*)nullptr, (float*)nullptr, (const float*)nullptr);
   const int CV = C / N;
   if ((CV & (CV - 1)) == 0 && CV <= 256) {
     int sh = 0;
