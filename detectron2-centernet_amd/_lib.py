@@ -63,6 +63,13 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _i32, _i32, _vp]),
     "ctdet_bn_train_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32,
                                    _vp, _vp, _f32, _vp, _i32, _vp]),
+    "ctdet_bn_local_stats": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "ctdet_bn_sync_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _i32, _i32, _vp]),
+    "ctdet_bn_local_grad_sums": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                         _f32, _vp, _i32, _vp]),
+    "ctdet_bn_sync_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32,
+                                  _vp, _i32, _i32, _vp]),
     "ctdet_conv_wgrad": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _vp, _f32, _vp]),
     "ctdet_conv_wgrad_oihw": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_grad_scatter_oihw": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),

@@ -71,6 +71,13 @@ int launch_bn_train_fwd_f32(const float*, int, const float*, int, float*, int, i
                             float, float*, float*, float*, float*, float*, float*, void*, int, hipStream_t);
 int launch_bn_train_bwd_f32(const float*, int, const float*, int, const float*, int, const float*, const float*, const float*,
                             int, int, int, float*, int, float*, int, float*, float*, float, void*, hipStream_t);
+int launch_bn_local_stats(const void*, int, int, int, int, int, double*, void*, int, hipStream_t);
+int launch_bn_sync_fwd(const void*, int, const void*, int, void*, int, int, int, const double*, int, const float*, const float*,
+                       float, float, float*, float*, float*, float*, float*, float*, int, int, hipStream_t);
+int launch_bn_local_grad_sums(const void*, int, const void*, int, const void*, int, const float*, const float*, int, int, int, int,
+                              int, double*, float*, float*, float, void*, int, hipStream_t);
+int launch_bn_sync_bwd(const void*, int, const void*, int, const void*, int, const float*, const float*, const float*,
+                       const double*, const double*, int, int, int, int, void*, int, void*, int, int, hipStream_t);
 int launch_maxpool2x2_bwd_f32(const float*, int, const float*, int, float*, int, int, int, int, int, hipStream_t);
 int launch_maxpool3x3s2_bwd(const void*, int, const void*, int, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
 int launch_ese_dot(const void*, int, const void*, int, int, int, int, int, float*, hipStream_t);
@@ -512,6 +519,56 @@ int32_t ctdet_bn_train_bwd(const void* dz, int32_t dz_stride, const void* z, int
   return launch_bn_train_bwd((const f16*)dz, dz_stride, (const f16*)z, z_stride, (const f16*)y, y_stride, mean, invstd,
                              scale, M, C, relu, (f16*)dy, dy_stride, (f16*)dres, dres_stride, dgamma, dbeta, grad_mult,
                              workspace, (hipStream_t)stream);
+}
+
+static const int SYNC_BN_MAX_WORLD = 4096;
+
+int32_t ctdet_bn_local_stats(const void* y, int32_t y_stride, int32_t M, int32_t C, int32_t rank, int32_t world,
+                             double* stats, void* workspace, int32_t dtype, void* stream) {
+  CTDET_CHECK(M > 0, "bn_local_stats: empty batch on rank %d (SyncBatchNorm needs at least one row on every rank)", rank);
+  CTDET_CHECK(y && stats && workspace, "bn_local_stats: null pointer");
+  CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD && rank >= 0 && rank < world, "bn_local_stats: rank %d of world %d",
+              rank, world);
+  return launch_bn_local_stats(y, y_stride, M, C, rank, world, stats, workspace, dtype == CTDET_DT_F32, (hipStream_t)stream);
+}
+
+int32_t ctdet_bn_sync_fwd(const void* y, int32_t y_stride, const void* res, int32_t res_stride, void* z, int32_t z_stride,
+                          int32_t M, int32_t C, const double* stats, int32_t world, const float* gamma, const float* beta,
+                          float eps, float momentum, float* running_mean, float* running_var, float* save_mean,
+                          float* save_invstd, float* scale, float* shift, int32_t relu, int32_t dtype, void* stream) {
+  CTDET_CHECK(y && z && stats && gamma && beta && save_mean && save_invstd && scale && shift, "bn_sync_fwd: null pointer");
+  CTDET_CHECK(!running_mean == !running_var, "bn_sync_fwd: running_mean and running_var go together");
+  CTDET_CHECK(M > 0, "bn_sync_fwd: empty batch");
+  CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD, "bn_sync_fwd: world %d", world);
+  return launch_bn_sync_fwd(y, y_stride, res, res_stride, z, z_stride, M, C, stats, world, gamma, beta, eps, momentum,
+                            running_mean, running_var, save_mean, save_invstd, scale, shift, relu, dtype == CTDET_DT_F32,
+                            (hipStream_t)stream);
+}
+
+int32_t ctdet_bn_local_grad_sums(const void* dz, int32_t dz_stride, const void* z, int32_t z_stride, const void* y,
+                                 int32_t y_stride, const float* mean, const float* invstd, int32_t M, int32_t C, int32_t relu,
+                                 int32_t rank, int32_t world, double* sums, float* dgamma, float* dbeta, float grad_mult,
+                                 void* workspace, int32_t dtype, void* stream) {
+  CTDET_CHECK(dz && sums && dgamma && dbeta && workspace, "bn_local_grad_sums: null pointer");
+  CTDET_CHECK(!relu || z, "bn_local_grad_sums: relu backward needs z");
+  CTDET_CHECK(!y || (mean && invstd), "bn_local_grad_sums: statistics missing");
+  CTDET_CHECK(M > 0, "bn_local_grad_sums: empty batch on rank %d", rank);
+  CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD && rank >= 0 && rank < world,
+              "bn_local_grad_sums: rank %d of world %d", rank, world);
+  return launch_bn_local_grad_sums(dz, dz_stride, z, z_stride, y, y_stride, mean, invstd, M, C, relu, rank, world, sums, dgamma,
+                                   dbeta, grad_mult, workspace, dtype == CTDET_DT_F32, (hipStream_t)stream);
+}
+
+int32_t ctdet_bn_sync_bwd(const void* dz, int32_t dz_stride, const void* z, int32_t z_stride, const void* y, int32_t y_stride,
+                          const float* mean, const float* invstd, const float* scale, const double* stats,
+                          const double* sums, int32_t world, int32_t M, int32_t C, int32_t relu, void* dy, int32_t dy_stride,
+                          void* dres, int32_t dres_stride, int32_t dtype, void* stream) {
+  CTDET_CHECK(dz && y && mean && invstd && scale && stats && sums && dy, "bn_sync_bwd: null pointer");
+  CTDET_CHECK(!relu || z, "bn_sync_bwd: relu backward needs z");
+  CTDET_CHECK(M > 0, "bn_sync_bwd: empty batch");
+  CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD, "bn_sync_bwd: world %d", world);
+  return launch_bn_sync_bwd(dz, dz_stride, z, z_stride, y, y_stride, mean, invstd, scale, stats, sums, world, M, C, relu, dy,
+                            dy_stride, dres, dres_stride, dtype == CTDET_DT_F32, (hipStream_t)stream);
 }
 
 int32_t ctdet_conv_wgrad(const ctdet_conv_desc* d, const void* x, const void* dy, float* dw, float scale, void* stream) {

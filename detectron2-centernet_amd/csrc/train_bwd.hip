@@ -1441,6 +1441,346 @@ int launch_bn_train_bwd_f32(const float* dz, int dz_stride, const float* z, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// SyncBatchNorm (torch.nn.SyncBatchNorm semantics): the fused pipeline above split around one collective per direction.
+// Statistics travel in rank-slot buffers, f64 [world][K][C]: a rank writes its own slot and zeros into every other one, so
+// a SUM all-reduce of the buffer is an exact all-gather (x + 0 == x) on any backend, and every rank then combines the
+// slots in the same fixed rank order -- bit-identical statistics on every rank and from run to run.
+//   forward  K = 3: (row count, mean, biased variance) of the rank's rows (chan_reduce's partials, f32 pivot as above)
+//   backward K = 2: (sum g, sum g * xhat), g = dz * (z > 0 if relu)
+// ------------------------------------------------------------------------------------------------
+
+// per channel: chan_reduce's block partials reduced in f64 in chan_finalize's order into this rank's slot, zeros into
+// the others.  mode 0: (M, mean, var) exactly as chan_finalize derives them.  mode 1: (sum g, sum g*xhat), and the
+// parameter gradients from these LOCAL sums times grad_mult (the bucketed exchange averages them like any parameter)
+__global__ void __launch_bounds__(256) bn_slot_finalize_kernel(const float* __restrict__ partial, int nblocks, int C, int M,
+                                                               int mode, const float* __restrict__ pivot,
+                                                               double* __restrict__ slots, int rank, int world,
+                                                               float grad_mult, float* __restrict__ dgamma,
+                                                               float* __restrict__ dbeta) {
+  __shared__ double sh[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x;
+  double s0 = 0, s1 = 0;
+  for (int b = threadIdx.x; b < nblocks; b += 256) { s0 += partial[((long)b * 2 + 0) * C + c]; s1 += partial[((long)b * 2 + 1) * C + c]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_down(s0, o, 64); s1 += __shfl_down(s1, o, 64); }
+  if (lane == 0) { sh[0][wave] = s0; sh[1][wave] = s1; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  s0 = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
+  s1 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
+  double v[3];
+  int K;
+  if (mode == 0) {
+    const double dm = s0 / M;
+    double var = s1 / M - dm * dm;
+    if (var < 0) var = 0;
+    v[0] = (double)M;
+    v[1] = pivot ? (double)pivot[c] + dm : dm;
+    v[2] = var;
+    K = 3;
+  } else {
+    v[0] = s0;
+    v[1] = s1;
+    dbeta[c] = (float)s0 * grad_mult;
+    dgamma[c] = (float)s1 * grad_mult;
+    K = 2;
+  }
+  for (int r = 0; r < world; ++r)
+    for (int k = 0; k < K; ++k) slots[((long)r * K + k) * C + c] = r == rank ? v[k] : 0.0;
+}
+
+// Chan et al.'s pairwise update of (count, mean, variance) over the forward slots in rank order.  The first slot is taken
+// as it stands, so a single slot yields exactly the statistics of the fused kernels.
+__device__ __forceinline__ void bn_slot_combine(const double* __restrict__ slots, int C, int c, int world, double& n,
+                                                double& mean, double& var) {
+  n = 0; mean = 0; var = 0;
+  for (int r = 0; r < world; ++r) {
+    const double nb = slots[((long)r * 3 + 0) * C + c];
+    if (!(nb > 0)) continue;
+    const double mb = slots[((long)r * 3 + 1) * C + c], vb = slots[((long)r * 3 + 2) * C + c];
+    if (n == 0) { n = nb; mean = mb; var = vb; continue; }
+    const double nt = n + nb, d = mb - mean;
+    const double m2 = var * n + vb * nb + d * d * (n * nb / nt);
+    mean += d * (nb / nt);
+    var = m2 / nt;
+    n = nt;
+  }
+  if (var < 0) var = 0;
+}
+
+// element index -> (row, channel vector): shift and mask when the vector count is a power of two
+__device__ __forceinline__ void sb_split(long idx, int CV, int cv_shift, long& m, int& cv) {
+  if (cv_shift >= 0) { m = idx >> cv_shift; cv = (int)(idx & (CV - 1)); }
+  else { m = idx / CV; cv = (int)(idx % CV); }
+}
+
+// forward after the collective, one launch: every workgroup combines the slots of all C channels into LDS (world x 3
+// loads per channel), workgroup 0 also writes the saved and running statistics, then z = act(y*scale + shift + res) for
+// SB_ROWS x 256 channel vectors (the fused kernels' expression).  Dynamic LDS: 2*C floats.
+constexpr int SB_ROWS = 8;
+template <typename T>
+__global__ void __launch_bounds__(256) bn_sync_fwd_apply_kernel(const T* __restrict__ y, int y_stride, const T* __restrict__ res,
+                                                                int res_stride, T* __restrict__ z, int z_stride, long M, int C,
+                                                                int cv_shift, const double* __restrict__ slots, int world,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                float eps, float momentum, float* __restrict__ running_mean,
+                                                                float* __restrict__ running_var, float* __restrict__ save_mean,
+                                                                float* __restrict__ save_invstd, float* __restrict__ scale_out,
+                                                                float* __restrict__ shift_out, int relu) {
+  typedef typename VecT<T>::type V;
+  constexpr int N = VecT<T>::N;
+  extern __shared__ float sb_coef[];          // [2][C]: scale, shift
+  for (int c = threadIdx.x; c < C; c += 256) {
+    double n, mean, var;
+    bn_slot_combine(slots, C, c, world, n, mean, var);
+    const double invstd = 1.0 / sqrt(var + (double)eps);
+    const float sc = gamma[c] * (float)invstd;
+    const float sf = beta[c] - (float)mean * sc;
+    sb_coef[c] = sc;
+    sb_coef[C + c] = sf;
+    if (blockIdx.x == 0) {
+      save_mean[c] = (float)mean;
+      save_invstd[c] = (float)invstd;
+      scale_out[c] = sc;
+      shift_out[c] = sf;
+      if (running_mean) {
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
+        const double unbiased = n > 1 ? var * n / (n - 1) : var;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+      }
+    }
+  }
+  __syncthreads();
+  const int CV = C / N;
+  const long total = M * CV;
+  const long base = (long)blockIdx.x * 256 * SB_ROWS + threadIdx.x;
+  V v[SB_ROWS], r[SB_ROWS];
+#pragma unroll
+  for (int u = 0; u < SB_ROWS; ++u) {           // all rows' loads in flight before the first use
+    const long idx = base + (long)u * 256;
+    if (idx < total) {
+      long m; int cv;
+      sb_split(idx, CV, cv_shift, m, cv);
+      v[u] = *(const V*)(y + m * y_stride + cv * N);
+      r[u] = v[u];
+      if (res) r[u] = *(const V*)(res + m * res_stride + cv * N);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < SB_ROWS; ++u) {
+    const long idx = base + (long)u * 256;
+    if (idx < total) {
+      long m; int cv;
+      sb_split(idx, CV, cv_shift, m, cv);
+      V o;
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        float f = (float)v[u][e] * sb_coef[cv * N + e] + sb_coef[C + cv * N + e];   // same expression as the fused kernels
+        if (res) f += (float)r[u][e];
+        if (relu) f = fmaxf(f, 0.f);
+        o[e] = (T)f;
+      }
+      *(V*)(z + m * z_stride + cv * N) = o;
+    }
+  }
+}
+
+// backward after the collective: every workgroup sums the gathered (sum g, sum g*xhat) slots and the forward slots' row
+// counts in rank order into LDS coefficients (the global sums over the global count), then
+// dy = scale*(g - sum g/N - xhat * sum g*xhat/N) (bn_bwd_apply_rows_kernel's expression), dres = g.  Dynamic LDS: 5*C floats.
+template <typename T>
+__global__ void __launch_bounds__(256) bn_sync_bwd_apply_kernel(const T* __restrict__ dz, int dz_stride, const T* __restrict__ z,
+                                                                int z_stride, const T* __restrict__ y, int y_stride,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                const float* __restrict__ scale,
+                                                                const double* __restrict__ stats, const double* __restrict__ sums,
+                                                                int world, T* __restrict__ dy, int dy_stride, T* __restrict__ dres,
+                                                                int dres_stride, long M, int C, int cv_shift, int relu) {
+  typedef typename VecT<T>::type V;
+  constexpr int N = VecT<T>::N;
+  extern __shared__ float sb_coef[];          // [5][C]: mean, invstd, scale, sum g / N, sum g*xhat / N
+  for (int c = threadIdx.x; c < C; c += 256) {
+    double s0 = 0, s1 = 0, n = 0;
+    for (int r = 0; r < world; ++r) {
+      s0 += sums[((long)r * 2 + 0) * C + c];
+      s1 += sums[((long)r * 2 + 1) * C + c];
+      n += stats[((long)r * 3 + 0) * C + c];
+    }
+    const float invN = 1.f / (float)n;
+    sb_coef[c] = mean[c];
+    sb_coef[C + c] = invstd[c];
+    sb_coef[2 * C + c] = scale[c];
+    sb_coef[3 * C + c] = (float)s0 * invN;
+    sb_coef[4 * C + c] = (float)s1 * invN;
+  }
+  __syncthreads();
+  const int CV = C / N;
+  const long total = M * CV;
+  const long base = (long)blockIdx.x * 256 * SB_ROWS + threadIdx.x;
+#pragma unroll
+  for (int r0 = 0; r0 < SB_ROWS; r0 += 4) {
+    V g[4], zz[4], yy[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long idx = base + (long)(r0 + u) * 256;
+      if (idx < total) {
+        long m; int cv;
+        sb_split(idx, CV, cv_shift, m, cv);
+        g[u] = *(const V*)(dz + m * dz_stride + cv * N);
+        zz[u] = g[u];
+        if (relu) zz[u] = *(const V*)(z + m * z_stride + cv * N);
+        yy[u] = *(const V*)(y + m * y_stride + cv * N);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long idx = base + (long)(r0 + u) * 256;
+      if (idx < total) {
+        long m; int cv;
+        sb_split(idx, CV, cv_shift, m, cv);
+        V o, gr;
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+          const int c = cv * N + e;
+          const float gf = (relu && !((float)zz[u][e] > 0.f)) ? 0.f : (float)g[u][e];
+          gr[e] = (T)gf;
+          const float xh = ((float)yy[u][e] - sb_coef[c]) * sb_coef[C + c];
+          o[e] = (T)(sb_coef[2 * C + c] * (gf - sb_coef[3 * C + c] - xh * sb_coef[4 * C + c]));
+        }
+        *(V*)(dy + m * dy_stride + cv * N) = o;
+        if (dres) *(V*)(dres + m * dres_stride + cv * N) = gr;
+      }
+    }
+  }
+}
+
+static int sb_cv_shift(int CV) {
+  if (CV & (CV - 1)) return -1;
+  int sh = 0;
+  while ((1 << sh) < CV) ++sh;
+  return sh;
+}
+
+template <typename T>
+static int launch_bn_local_stats_t(const T* y, int y_stride, int M, int C, int rank, int world, double* stats, void* workspace,
+                                   hipStream_t s) {
+  constexpr int N = VecT<T>::N;
+  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_local_stats: unsupported channel count %d", C);
+  CTDET_CHECK(y_stride % N == 0 && ((size_t)y & 15) == 0,
+              "bn_local_stats: y must be 16-byte aligned with a pixel stride that is a multiple of %d", N);
+  ChanRedArgs<T> a = {};
+  a.y = y; a.y_stride = y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)workspace;
+  a.pivot = std::is_same<T, float>::value ? (float*)workspace + (size_t)1024 * 2 * C : nullptr;
+  const int nb = chan_blocks(M, C, N);
+  hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 0,
+                     (const float*)a.pivot, stats, rank, world, 0.f, (float*)nullptr, (float*)nullptr);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int launch_bn_sync_fwd_t(const T* y, int y_stride, const T* res, int res_stride, T* z, int z_stride, int M, int C,
+                                const double* stats, int world, const float* gamma, const float* beta, float eps, float momentum,
+                                float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
+                                float* shift, int relu, hipStream_t s) {
+  constexpr int N = VecT<T>::N;
+  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_sync_fwd: unsupported channel count %d", C);
+  CTDET_CHECK(y_stride % N == 0 && z_stride % N == 0 && (!res || res_stride % N == 0) && ((((size_t)y | (size_t)z | (size_t)res)) & 15) == 0,
+              "bn_sync_fwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
+  const int CV = C / N;
+  const long total = (long)M * CV;
+  const unsigned grid = (unsigned)((total + 256L * SB_ROWS - 1) / (256L * SB_ROWS));
+  hipLaunchKernelGGL(bn_sync_fwd_apply_kernel<T>, dim3(grid), dim3(256), 2 * C * sizeof(float), s, y, y_stride, res,
+                     res_stride, z, z_stride, (long)M, C, sb_cv_shift(CV), stats, world, gamma, beta, eps, momentum,
+                     running_mean, running_var, save_mean, save_invstd, scale, shift, relu);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int launch_bn_local_grad_sums_t(const T* dz, int dz_stride, const T* z, int z_stride, const T* y, int y_stride,
+                                       const float* mean, const float* invstd, int M, int C, int relu, int rank, int world,
+                                       double* sums, float* dgamma, float* dbeta, float grad_mult, void* workspace,
+                                       hipStream_t s) {
+  constexpr int N = VecT<T>::N;
+  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_local_grad_sums: unsupported channel count %d", C);
+  CTDET_CHECK(dz_stride % N == 0 && (!z || z_stride % N == 0) && (!y || y_stride % N == 0) &&
+                  ((((size_t)dz | (size_t)z | (size_t)y)) & 15) == 0,
+              "bn_local_grad_sums: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
+  ChanRedArgs<T> a = {};
+  a.y = y; a.y_stride = y_stride; a.dz = dz; a.dz_stride = dz_stride; a.z = z; a.z_stride = z_stride;
+  a.mean = mean; a.invstd = invstd; a.M = M; a.C = C; a.mode = 1; a.relu = relu; a.partial = (float*)workspace;
+  const int nb = chan_blocks(M, C, N);
+  hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 1,
+                     (const float*)nullptr, sums, rank, world, grad_mult, dgamma, dbeta);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int launch_bn_sync_bwd_t(const T* dz, int dz_stride, const T* z, int z_stride, const T* y, int y_stride,
+                                const float* mean, const float* invstd, const float* scale, const double* stats,
+                                const double* sums, int world, int M, int C, int relu, T* dy, int dy_stride, T* dres,
+                                int dres_stride, hipStream_t s) {
+  constexpr int N = VecT<T>::N;
+  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_sync_bwd: unsupported channel count %d", C);
+  CTDET_CHECK(dz_stride % N == 0 && dy_stride % N == 0 && (!z || z_stride % N == 0) && y_stride % N == 0 &&
+                  (!dres || dres_stride % N == 0) && ((((size_t)dz | (size_t)z | (size_t)y | (size_t)dy | (size_t)dres)) & 15) == 0,
+              "bn_sync_bwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
+  const int CV = C / N;
+  const long total = (long)M * CV;
+  const unsigned grid = (unsigned)((total + 256L * SB_ROWS - 1) / (256L * SB_ROWS));
+  hipLaunchKernelGGL(bn_sync_bwd_apply_kernel<T>, dim3(grid), dim3(256), 5 * C * sizeof(float), s, dz, dz_stride, z, z_stride,
+                     y, y_stride, mean, invstd, scale, stats, sums, world, dy, dy_stride, dres, dres_stride, (long)M, C,
+                     sb_cv_shift(CV), relu);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_bn_local_stats(const void* y, int y_stride, int M, int C, int rank, int world, double* stats, void* workspace,
+                          int f32, hipStream_t s) {
+  if (f32) return launch_bn_local_stats_t<float>((const float*)y, y_stride, M, C, rank, world, stats, workspace, s);
+  return launch_bn_local_stats_t<f16>((const f16*)y, y_stride, M, C, rank, world, stats, workspace, s);
+}
+int launch_bn_sync_fwd(const void* y, int y_stride, const void* res, int res_stride, void* z, int z_stride, int M, int C,
+                       const double* stats, int world, const float* gamma, const float* beta, float eps, float momentum,
+                       float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
+                       float* shift, int relu, int f32, hipStream_t s) {
+  if (f32)
+    return launch_bn_sync_fwd_t<float>((const float*)y, y_stride, (const float*)res, res_stride, (float*)z, z_stride, M, C,
+                                       stats, world, gamma, beta, eps, momentum, running_mean, running_var, save_mean,
+                                       save_invstd, scale, shift, relu, s);
+  return launch_bn_sync_fwd_t<f16>((const f16*)y, y_stride, (const f16*)res, res_stride, (f16*)z, z_stride, M, C, stats,
+                                   world, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd,
+                                   scale, shift, relu, s);
+}
+int launch_bn_local_grad_sums(const void* dz, int dz_stride, const void* z, int z_stride, const void* y, int y_stride,
+                              const float* mean, const float* invstd, int M, int C, int relu, int rank, int world,
+                              double* sums, float* dgamma, float* dbeta, float grad_mult, void* workspace, int f32,
+                              hipStream_t s) {
+  if (f32)
+    return launch_bn_local_grad_sums_t<float>((const float*)dz, dz_stride, (const float*)z, z_stride, (const float*)y,
+                                              y_stride, mean, invstd, M, C, relu, rank, world, sums, dgamma, dbeta,
+                                              grad_mult, workspace, s);
+  return launch_bn_local_grad_sums_t<f16>((const f16*)dz, dz_stride, (const f16*)z, z_stride, (const f16*)y, y_stride, mean,
+                                          invstd, M, C, relu, rank, world, sums, dgamma, dbeta, grad_mult, workspace, s);
+}
+int launch_bn_sync_bwd(const void* dz, int dz_stride, const void* z, int z_stride, const void* y, int y_stride,
+                       const float* mean, const float* invstd, const float* scale, const double* stats, const double* sums,
+                       int world, int M, int C, int relu, void* dy, int dy_stride, void* dres, int dres_stride, int f32,
+                       hipStream_t s) {
+  if (f32)
+    return launch_bn_sync_bwd_t<float>((const float*)dz, dz_stride, (const float*)z, z_stride, (const float*)y, y_stride,
+                                       mean, invstd, scale, stats, sums, world, M, C, relu, (float*)dy, dy_stride,
+                                       (float*)dres, dres_stride, s);
+  return launch_bn_sync_bwd_t<f16>((const f16*)dz, dz_stride, (const f16*)z, z_stride, (const f16*)y, y_stride, mean, invstd,
+                                   scale, stats, sums, world, M, C, relu, (f16*)dy, dy_stride, (f16*)dres, dres_stride, s);
+}
+
+// ------------------------------------------------------------------------------------------------
 // 3x3 / stride 1 / pad 1 weight gradient, window form (maps divisible by 8x32, Cin % 32 == 0).  The generic kernel above
 // gathers every tap's pixels separately (nine reads of the input through L2) and ends in 8192 f32 atomics per workgroup on
 // ~1000 workgroups.  Here a workgroup owns 32 couts x 32 cin x all 9 taps and walks 8x32-pixel tiles: per tile the dY rows

@@ -5,7 +5,7 @@ import time
 import torch
 
 from .. import ops_train
-from ..solver import WarmupMultiStepLR, build_optimizer
+from ..solver import build_lr_scheduler, build_optimizer
 from . import graph_nodes, train_step
 from .reducer import BucketedReducer
 
@@ -27,8 +27,8 @@ class SimpleTrainer:
         self.reducer = BucketedReducer(self.optimizer, process_group=process_group, comm=self._rccl_comm(process_group))
         ops_train.set_world_size(self.reducer.world)
         self.reducer.broadcast_parameters([b for b in model.buffers() if b.dtype.is_floating_point])
-        self.scheduler = WarmupMultiStepLR(self.optimizer, cfg.SOLVER.STEPS, cfg.SOLVER.GAMMA, cfg.SOLVER.WARMUP_FACTOR,
-                                           cfg.SOLVER.WARMUP_ITERS, cfg.SOLVER.WARMUP_METHOD)
+        self.scheduler = build_lr_scheduler(cfg, self.optimizer)     # SOLVER.LR_SCHEDULER_NAME (solver/build.py:140-165)
+        ops_train.SYNC_BN_GROUP = process_group                       # SyncBatchNorm's collectives go over the trainer's group
         self.iter = 0
         self.last_losses = None
         import os
@@ -40,6 +40,14 @@ class SimpleTrainer:
         mode = os.environ.get("CTDET_TRAIN_GRAPH", "1")
         self.use_hip_graph = mode != "0"
         self.graph_ddp = mode not in ("0", "hooks")
+        # A trainable SyncBatchNorm issues a collective inside forward and backward, which a captured data-parallel step cannot
+        # hold: with more than one rank every step of such a model runs eagerly (the hooks path), on EVERY rank -- decided
+        # here, once, from the model and the world size alone, so that all ranks issue the same collectives in the same
+        # order (a rank replaying a graph while another runs eagerly would pair a bucket's all-reduce with a SyncBN one).
+        self.sync_bn = any(isinstance(m, torch.nn.SyncBatchNorm) and any(p.requires_grad for p in m.parameters())
+                           for m in model.modules())
+        if self.sync_bn and self.reducer.world > 1:
+            self.graph_ddp = False
         self._graphs = {}
 
     @staticmethod

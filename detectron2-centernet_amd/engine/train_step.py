@@ -14,7 +14,7 @@ import torch
 from .. import ops
 from ..layers import hipnn
 from ..ops_train import (BNActFn, ConvFn, ConvTransposeFn, DeformConvFn, DwConvTAddFn, EseFn, FocalLossFn, FrozenConvFn,
-                         MaxPool3x3s2Fn, MaxPoolFn, RegL1Fn)
+                         MaxPool3x3s2Fn, MaxPoolFn, RegL1Fn, SyncBNActFn, sync_bn_world)
 
 
 _COUNTERS = []
@@ -122,13 +122,31 @@ def _frozen_conv(x, conv, relu, res=None):
     return FrozenConvFn.apply(x, conv.weight, scale, bias, res, conv.stride[0], conv.padding[0], relu)
 
 
+def _bn_conv(x, conv, relu, res=None):
+    """Conv2d (no bias) + trainable BatchNorm2d / SyncBatchNorm in training mode (+ residual)(+ ReLU): ConvFn, then
+    BNActFn -- or SyncBNActFn, whose statistics span every rank, when a SyncBatchNorm runs with more than one rank"""
+    bn = conv.norm
+    y = ConvFn.apply(x, conv.weight, None, conv.stride[0], conv.padding[0], False, False)
+    _count(bn)
+    fn = SyncBNActFn if isinstance(bn, torch.nn.SyncBatchNorm) and sync_bn_world()[1] > 1 else BNActFn
+    return fn.apply(y, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu)
+
+
+def _resnet_conv(x, conv, relu, res=None):
+    if isinstance(conv.norm, torch.nn.modules.batchnorm._BatchNorm):
+        return _bn_conv(x, conv, relu, res)
+    return _frozen_conv(x, conv, relu, res)
+
+
 def resnet_block(m, x):
-    sc = x if m.shortcut is None else _frozen_conv(x, m.shortcut, False)
-    out = _frozen_conv(x, m.conv1, True)
+    """a block with frozen (FrozenBN) or trainable (BN / SyncBN, batch statistics) norms; the residual enters the block's
+    last norm, the 1x1 shortcut has no ReLU"""
+    sc = x if m.shortcut is None else _resnet_conv(x, m.shortcut, False)
+    out = _resnet_conv(x, m.conv1, True)
     if hasattr(m, "conv3"):              # BottleneckBlock
-        out = _frozen_conv(out, m.conv2, True)
-        return _frozen_conv(out, m.conv3, True, res=sc)
-    return _frozen_conv(out, m.conv2, True, res=sc)
+        out = _resnet_conv(out, m.conv2, True)
+        return _resnet_conv(out, m.conv3, True, res=sc)
+    return _resnet_conv(out, m.conv2, True, res=sc)
 
 
 def resnet_features(backbone, x, ctx, want="res4"):

@@ -29,13 +29,42 @@ class FrozenBatchNorm2d(nn.Module):
     def __repr__(self):
         return f"FrozenBatchNorm2d(num_features={self.num_features}, eps={self.eps})"
 
+    @classmethod
+    def convert_frozen_batchnorm(cls, module):
+        """batch_norm.py:92-125: BatchNorm2d / SyncBatchNorm modules (the module itself or any descendant) become
+        FrozenBatchNorm2d with the same affine parameters (copied) and running statistics (shared); returns the module,
+        or its replacement if it is a BatchNorm itself"""
+        res = module
+        if isinstance(module, (nn.BatchNorm2d, nn.SyncBatchNorm)):
+            res = cls(module.num_features)
+            if module.affine:
+                res.weight.data = module.weight.data.clone().detach()
+                res.bias.data = module.bias.data.clone().detach()
+            res.running_mean.data = module.running_mean.data
+            res.running_var.data = module.running_var.data
+            res.eps = module.eps
+        else:
+            for name, child in module.named_children():
+                new_child = cls.convert_frozen_batchnorm(child)
+                if new_child is not child:
+                    res.add_module(name, new_child)
+        return res
+
+
+def _naive_sync_bn(out_channels):
+    raise NotImplementedError("norm 'naiveSyncBN' (detectron2's NaiveSyncBatchNorm: per-rank statistics averaged with equal "
+                              "weight) is not built; 'SyncBN' gives nn.SyncBatchNorm's count-weighted statistics")
+
 
 def get_norm(norm, out_channels):
-    """batch_norm.py:102-131 for the norms the CenterNet configs use."""
+    """batch_norm.py:127-152 for the norms the CenterNet configs use.  "SyncBN" is nn.SyncBatchNorm as in the reference
+    (torch > 1.5): the training step runs it on the HIP SyncBatchNorm kernels (ops_train.SyncBNActFn); "nnSyncBN" is the
+    same module."""
     if norm is None or norm == "":
         return None
     if isinstance(norm, str):
-        norm = {"BN": nn.BatchNorm2d, "FrozenBN": FrozenBatchNorm2d}[norm]
+        norm = {"BN": nn.BatchNorm2d, "SyncBN": nn.SyncBatchNorm, "nnSyncBN": nn.SyncBatchNorm,
+                "naiveSyncBN": _naive_sync_bn, "FrozenBN": FrozenBatchNorm2d}[norm]
     return norm(out_channels)
 
 

@@ -29,9 +29,10 @@ class CNNBlockBase(nn.Module):
         self.in_channels, self.out_channels, self.stride = in_channels, out_channels, stride
 
     def freeze(self):
+        """layers/blocks.py:36-48: no parameter trains, and every BatchNorm2d / SyncBatchNorm becomes FrozenBatchNorm2d"""
         for p in self.parameters():
             p.requires_grad = False
-        # the reference converts BatchNorm to FrozenBatchNorm here; the configs in scope already use FrozenBN
+        FrozenBatchNorm2d.convert_frozen_batchnorm(self)
         return self
 
 

@@ -129,6 +129,70 @@ def bn_train_bwd(dz, z, y, mean, invstd, scale, relu=True, want_dres=False, grad
     return dy, dres, dgamma, dbeta
 
 
+def bn_local_stats(y, rank, world):
+    """this rank's (row count, mean, biased variance) per channel in slot `rank` of an f64 [world, 3, C] buffer, zeros in
+    every other slot: a SUM all-reduce of it is the exact all-gather ctdet_bn_sync_fwd combines"""
+    B, H, W, Cc = y.shape
+    stats = torch.empty(world, 3, Cc, dtype=torch.float64, device=y.device)
+    with ops.prof_region("bn_local_stats", flops=0.0, nbytes=float(B * H * W * Cc * y.element_size())):
+        rc = _lib.lib().ctdet_bn_local_stats(_ptr(y), _nhwc_stride(y), B * H * W, Cc, int(rank), int(world), _ptr(stats),
+                                             _ptr(_ws(Cc, y.device)), dt_of(y), _stream())
+    _lib.check(rc, "ctdet_bn_local_stats")
+    return stats
+
+
+def bn_sync_fwd(y, stats, gamma, beta, running_mean, running_var, eps, momentum, res=None, relu=True):
+    """bn_train_fwd with the statistics of the gathered rank slots (bn_local_stats after the all-reduce)"""
+    B, H, W, Cc = y.shape
+    dev = y.device
+    z = torch.empty(B, H, W, Cc, dtype=y.dtype, device=dev)
+    mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(4))
+    with ops.prof_region("bn_sync_fwd", flops=0.0, nbytes=float(B * H * W * Cc * y.element_size() * (2 if res is None else 3))):
+        rc = _lib.lib().ctdet_bn_sync_fwd(_ptr(y), _nhwc_stride(y), _ptr(res), _nhwc_stride(res) if res is not None else 0,
+                                          _ptr(z), _nhwc_stride(z), B * H * W, Cc, _ptr(stats), stats.shape[0], _ptr(gamma),
+                                          _ptr(beta), float(eps), float(momentum), _ptr(running_mean), _ptr(running_var),
+                                          _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), int(relu), dt_of(y), _stream())
+    _lib.check(rc, "ctdet_bn_sync_fwd")
+    return z, mean, invstd, scale
+
+
+def bn_local_grad_sums(dz, z, y, mean, invstd, rank, world, relu=True, grad_mult=None, into=None):
+    """this rank's (sum g, sum g*xhat) in slot `rank` of an f64 [world, 2, C] buffer (zeros elsewhere), and dgamma / dbeta
+    from these local sums times grad_mult (default PARAM_GRAD_MULT); into: as bn_train_bwd"""
+    B, H, W, Cc = dz.shape
+    dev = dz.device
+    sums = torch.empty(world, 2, Cc, dtype=torch.float64, device=dev)
+    slots = [t if t is not None and t.numel() == Cc and t.is_contiguous() else None for t in (into or (None, None))]
+    dgamma, dbeta = slots
+    if dgamma is None or dbeta is None:
+        dgb = torch.empty(2, Cc, dtype=torch.float32, device=dev)
+        dgamma, dbeta = (dgb[0] if dgamma is None else dgamma), (dgb[1] if dbeta is None else dbeta)
+    gm = PARAM_GRAD_MULT if grad_mult is None else grad_mult
+    with ops.prof_region("bn_local_grad_sums", flops=0.0, nbytes=float(B * H * W * Cc * dz.element_size() * 3)):
+        rc = _lib.lib().ctdet_bn_local_grad_sums(_ptr(dz), _nhwc_stride(dz), _ptr(z), _nhwc_stride(z) if z is not None else 0,
+                                                 _ptr(y), _nhwc_stride(y) if y is not None else 0, _ptr(mean), _ptr(invstd),
+                                                 B * H * W, Cc, int(relu), int(rank), int(world), _ptr(sums), _ptr(dgamma),
+                                                 _ptr(dbeta), float(gm), _ptr(_ws(Cc, dev)), dt_of(dz), _stream())
+    _lib.check(rc, "ctdet_bn_local_grad_sums")
+    return sums, dgamma, dbeta
+
+
+def bn_sync_bwd(dz, z, y, mean, invstd, scale, stats, sums, relu=True, want_dres=False):
+    """dy (and dres) from the gathered backward sums (bn_local_grad_sums after the all-reduce) over the global row count of
+    the gathered forward slots `stats`"""
+    B, H, W, Cc = dz.shape
+    dev = dz.device
+    dy = torch.empty(B, H, W, Cc, dtype=dz.dtype, device=dev)
+    dres = torch.empty(B, H, W, Cc, dtype=dz.dtype, device=dev) if want_dres else None
+    with ops.prof_region("bn_sync_bwd", flops=0.0, nbytes=float(B * H * W * Cc * dz.element_size() * (4 + int(want_dres)))):
+        rc = _lib.lib().ctdet_bn_sync_bwd(_ptr(dz), _nhwc_stride(dz), _ptr(z), _nhwc_stride(z) if z is not None else 0, _ptr(y),
+                                          _nhwc_stride(y), _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(stats), _ptr(sums),
+                                          stats.shape[0], B * H * W, Cc, int(relu), _ptr(dy), _nhwc_stride(dy), _ptr(dres),
+                                          _nhwc_stride(dres) if dres is not None else 0, dt_of(dz), _stream())
+    _lib.check(rc, "ctdet_bn_sync_bwd")
+    return dy, dres
+
+
 def conv_wgrad(x, dy, Cout, R, S, stride, pad, dil=1, scale=None, into=None, comp=None):
     """scale * dW, f32 [Cout, R*S*Cin] (tap-major) for y = conv(x, W); x, dy NHWC, both f16 or both f32 (comp F32: plain f32
     FMAs; F16X3: split products on the f16 matrix pipe).  scale defaults to PARAM_GRAD_MULT.
@@ -640,6 +704,72 @@ class BNActFn(torch.autograd.Function):
         if sb is not None:
             grad_done(beta)
         return dy, None if sg is not None else dgamma, None if sb is not None else dbeta, dres, None, None, None, None, None
+
+
+SYNC_BN_GROUP = None   # the trainer's process group for SyncBatchNorm's collectives (engine/train_loop.py); None: WORLD
+
+
+def sync_bn_world(group=None):
+    """(rank, world size) of SyncBatchNorm's process group; (0, 1) without torch.distributed"""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return 0, 1
+    g = SYNC_BN_GROUP if group is None else group
+    return dist.get_rank(g), dist.get_world_size(g)
+
+
+class SyncBNActFn(torch.autograd.Function):
+    """BNActFn with torch.nn.SyncBatchNorm's statistics: mean and variance over the rows of every rank of `group`, one SUM
+    all-reduce of an f64 rank-slot buffer per direction (ctdet_bn_local_stats / _sync_fwd, ctdet_bn_local_grad_sums /
+    _sync_bwd).  dX uses the global sums over the global count; dgamma / dbeta come from the rank-local sums (with
+    PARAM_GRAD_MULT's 1 / world, the gradient exchange then averages them like every other parameter).  At world size 1 it
+    is BNActFn: the fused kernels, no collective."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, res, running_mean, running_var, eps, momentum, relu, group=None):
+        import torch.distributed as dist
+        rank, world = sync_bn_world(group)
+        ctx.relu, ctx.has_res, ctx.params = relu, res is not None, (gamma, beta)
+        ctx.rank, ctx.world = rank, world
+        ctx.group = SYNC_BN_GROUP if group is None else group
+        if world == 1:
+            z, mean, invstd, scale = bn_train_fwd(y, gamma.detach(), beta.detach(), running_mean, running_var, eps, momentum,
+                                                  res=res, relu=relu)
+            stats = None
+        else:
+            stats = bn_local_stats(y, rank, world)
+            dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=ctx.group)
+            z, mean, invstd, scale = bn_sync_fwd(y, stats, gamma.detach(), beta.detach(), running_mean, running_var, eps,
+                                                 momentum, res=res, relu=relu)
+        ctx.stats = stats
+        ctx.save_for_backward(y, z, mean, invstd, scale)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        import torch.distributed as dist
+        y, z, mean, invstd, scale = ctx.saved_tensors
+        gamma, beta = ctx.params
+        sg, sb = grad_slot(gamma), grad_slot(beta)
+        if sg is not None and sg.numel() != y.shape[3]:
+            sg = None
+        if sb is not None and sb.numel() != y.shape[3]:
+            sb = None
+        dz = dz.contiguous()
+        if ctx.world == 1:
+            dy, dres, dgamma, dbeta = bn_train_bwd(dz, z, y, mean, invstd, scale, relu=ctx.relu, want_dres=ctx.has_res,
+                                                   into=(sg, sb))
+        else:
+            sums, dgamma, dbeta = bn_local_grad_sums(dz, z, y, mean, invstd, ctx.rank, ctx.world, relu=ctx.relu, into=(sg, sb))
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.group)
+            dy, dres = bn_sync_bwd(dz, z, y, mean, invstd, scale, ctx.stats, sums, relu=ctx.relu, want_dres=ctx.has_res)
+        ctx.stats = None
+        if sg is not None:
+            grad_done(gamma)
+        if sb is not None:
+            grad_done(beta)
+        return (dy, None if sg is not None else dgamma, None if sb is not None else dbeta, dres, None, None, None, None, None,
+                None)
 
 
 class MaxPoolFn(torch.autograd.Function):

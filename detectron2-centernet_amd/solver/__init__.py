@@ -1,4 +1,6 @@
 from .build import FlatSGD, build_optimizer, param_groups
-from .lr_scheduler import WarmupMultiStepLR, warmup_multistep_factor
+from .lr_scheduler import (WarmupCosineLR, WarmupMultiStepLR, build_lr_scheduler, warmup_cosine_factor,
+                           warmup_multistep_factor)
 
-__all__ = ["FlatSGD", "build_optimizer", "param_groups", "WarmupMultiStepLR", "warmup_multistep_factor"]
+__all__ = ["FlatSGD", "build_optimizer", "param_groups", "WarmupMultiStepLR", "WarmupCosineLR", "build_lr_scheduler",
+           "warmup_multistep_factor", "warmup_cosine_factor"]

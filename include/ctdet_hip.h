@@ -341,6 +341,32 @@ int32_t ctdet_bn_train_bwd(const void* dz, int32_t dz_stride, const void* z, int
                            int32_t y_stride, const float* mean, const float* invstd, const float* scale, int32_t M,
                            int32_t C, int32_t relu, void* dy, int32_t dy_stride, void* dres, int32_t dres_stride,
                            float* dgamma, float* dbeta, float grad_mult, void* workspace, int32_t dtype, void* stream);
+/* SyncBatchNorm (torch.nn.SyncBatchNorm): the two functions above split around one SUM all-reduce per direction of a
+ * rank-slot buffer, f64 [world][K][C].  Each rank writes its own slot and zeros into every other one, so the SUM is an
+ * exact all-gather on any backend; the slots are combined in rank order, so every rank gets bit-identical statistics.
+ * Forward: ctdet_bn_local_stats writes slot `rank` of stats [world][3][C] = (row count M, mean, biased variance) of this
+ * rank's rows (M > 0; workspace: ctdet_chan_workspace_bytes(C)); after the all-reduce ctdet_bn_sync_fwd combines the
+ * slots (Chan's parallel formula, f64), writes save_mean / save_invstd / scale / shift, updates the running stats with
+ * the unbiased variance over the global count, and applies z = act(y*scale + shift + res) -- one launch.
+ * Backward: ctdet_bn_local_grad_sums writes slot `rank` of sums [world][2][C] = (sum g, sum g*xhat) of this rank's rows,
+ * and dgamma / dbeta from these LOCAL sums times grad_mult (the gradient exchange averages them like any parameter);
+ * after the all-reduce ctdet_bn_sync_bwd writes dy = scale*(g - sum g/N - xhat*sum g*xhat/N) with the global sums and the
+ * global count N (from the forward's gathered stats), and dres = g.  Same channel / stride limits as the fused kernels.
+ * With world = 1 the results equal ctdet_bn_train_fwd / _bwd. */
+int32_t ctdet_bn_local_stats(const void* y, int32_t y_stride, int32_t M, int32_t C, int32_t rank, int32_t world,
+                             double* stats, void* workspace, int32_t dtype, void* stream);
+int32_t ctdet_bn_sync_fwd(const void* y, int32_t y_stride, const void* res, int32_t res_stride, void* z, int32_t z_stride,
+                          int32_t M, int32_t C, const double* stats, int32_t world, const float* gamma, const float* beta,
+                          float eps, float momentum, float* running_mean, float* running_var, float* save_mean,
+                          float* save_invstd, float* scale, float* shift, int32_t relu, int32_t dtype, void* stream);
+int32_t ctdet_bn_local_grad_sums(const void* dz, int32_t dz_stride, const void* z, int32_t z_stride, const void* y,
+                                 int32_t y_stride, const float* mean, const float* invstd, int32_t M, int32_t C, int32_t relu,
+                                 int32_t rank, int32_t world, double* sums, float* dgamma, float* dbeta, float grad_mult,
+                                 void* workspace, int32_t dtype, void* stream);
+int32_t ctdet_bn_sync_bwd(const void* dz, int32_t dz_stride, const void* z, int32_t z_stride, const void* y, int32_t y_stride,
+                          const float* mean, const float* invstd, const float* scale, const double* stats,
+                          const double* sums, int32_t world, int32_t M, int32_t C, int32_t relu, void* dy, int32_t dy_stride,
+                          void* dres, int32_t dres_stride, int32_t dtype, void* stream);
 /* weight gradient of a conv: dw f32 [Cout][R*S*Cin] (tap-major k) += scale * sum over pixels; dw must be zeroed by
  * the caller.  Geometry from the descriptor (out_stride = pixel stride of dy; compute_dtype = dtype of x and dy). */
 int32_t ctdet_conv_wgrad(const ctdet_conv_desc* d, const void* x, const void* dy, float* dw, float scale, void* stream);
