@@ -12,6 +12,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libctdet_hip.so")
 
 F16, F32, U8, F16X3 = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP = 0, 1, 2
+# mask mode of the DCN entry points (enum ctdet_dcn_mask; the argument named mask_is_prob): mask logits, probabilities, no mask
+DCN_MASK_LOGIT, DCN_MASK_PROB, DCN_MASK_NONE = 0, 1, 2
 
 
 class ConvDesc(C.Structure):

@@ -145,6 +145,8 @@ const char* ctdet_last_error(void) { return g_err; }
 int32_t ctdet_set_tuning_flags(uint32_t flags) { g_tuning.store(flags, std::memory_order_relaxed); return 0; }
 uint32_t ctdet_get_tuning_flags(void) { return g_tuning.load(std::memory_order_relaxed); }
 int32_t ctdet_abi_version(void) { return 7; }
+static_assert(CTDET_DCN_MASK_LOGIT == DCN_MASK_LOGIT && CTDET_DCN_MASK_PROB == DCN_MASK_PROB && CTDET_DCN_MASK_NONE == DCN_MASK_NONE,
+              "mask modes of the ABI and of the kernels");
 int32_t ctdet_conv_cout_tile(int32_t cout) {
   if (cout <= 16) return 16;
   if (cout <= 32) return 32;
@@ -214,7 +216,9 @@ int32_t ctdet_dcnv2_fwd(const ctdet_conv_desc* d, const void* x, const float* of
   if (rc) return rc;
   if (a.M == 0) return 0;
   CTDET_CHECK(x && w_packed && y && offset_mask, "dcnv2: null pointer");
-  CTDET_CHECK(om_stride >= 3 * d->R * d->S, "dcnv2: om_stride=%d < 3*R*S", om_stride);
+  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcnv2: mask mode %d", mask_is_prob);
+  CTDET_CHECK(om_stride >= (mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3) * d->R * d->S, "dcnv2: om_stride=%d < %d*R*S", om_stride,
+              mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3);
   // korder 0: tap-major weights -> gather-from-global kernel; korder 1: chunk-major -> LDS-window kernel
   a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;
   a.om = offset_mask; a.om_stride = om_stride; a.mask_is_prob = mask_is_prob;
@@ -241,7 +245,9 @@ int32_t ctdet_dcnv2_fwd_cols(const ctdet_conv_desc* d, const void* x, const floa
   if (rc) return rc;
   if (a.M == 0) return 0;
   CTDET_CHECK(x && w_packed && y && offset_mask && cols_out, "dcnv2_fwd_cols: null pointer");
-  CTDET_CHECK(om_stride >= 3 * d->R * d->S, "dcnv2: om_stride=%d < 3*R*S", om_stride);
+  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcnv2: mask mode %d", mask_is_prob);
+  CTDET_CHECK(om_stride >= (mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3) * d->R * d->S, "dcnv2: om_stride=%d < %d*R*S", om_stride,
+              mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3);
   CTDET_CHECK(d->compute_dtype == CTDET_DT_F16X3 && d->out_dtype == CTDET_DT_F32 && (((size_t)cols_out) & 15) == 0,
               "dcnv2_fwd_cols: the f16x3 mode's entry point (f32 tensors), 16-byte aligned columns");
   a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;
@@ -659,6 +665,7 @@ int32_t ctdet_dwconvT_bwd(const void* x, int32_t x_stride, const void* dz, int32
 int32_t ctdet_dcn_cols(const void* x, int32_t x_stride, const float* om, int32_t om_stride, void* col, int32_t B,
                        int32_t H, int32_t W, int32_t Cin, int32_t mask_is_prob, int32_t dtype, void* stream) {
   CTDET_CHECK(x && om && col, "dcn_cols: null pointer");
+  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcn_cols: mask mode %d", mask_is_prob);
   if (dtype == CTDET_DT_F32)
     return launch_dcn_cols_f32((const float*)x, x_stride, om, om_stride, (float*)col, B, H, W, Cin, mask_is_prob,
                                (hipStream_t)stream);
@@ -669,6 +676,8 @@ int32_t ctdet_dcn_col2im_coord(const void* dcol, const void* x, int32_t x_stride
                                float* dx, void* dom, int32_t dom_stride, int32_t dom_dtype, int32_t B, int32_t H, int32_t W,
                                int32_t Cin, int32_t mask_is_prob, int32_t dcol_chunked, int32_t dtype, void* stream) {
   CTDET_CHECK(dcol && x && om && dx && dom, "dcn_col2im_coord: null pointer");
+  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcn_col2im_coord: mask mode %d",
+              mask_is_prob);
   CTDET_CHECK(dom_dtype == CTDET_DT_F32 || (dom_dtype == CTDET_DT_F16 && dtype == CTDET_DT_F16),
               "dcn_col2im_coord: dom dtype %d with data dtype %d", dom_dtype, dtype);
   if (dtype == CTDET_DT_F32 || dtype == CTDET_DT_F16X3)
@@ -682,6 +691,8 @@ int32_t ctdet_dcn_col2im_fused(const float* dy, int32_t dy_stride, int32_t K, co
                                const float* x, int32_t x_stride, const float* om, int32_t om_stride, float* dx, float* dom,
                                int32_t dom_stride, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t mask_is_prob, void* stream) {
   CTDET_CHECK(dy && w_packed && w_scale && x && om && dx && dom, "dcn_col2im_fused: null pointer");
+  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcn_col2im_fused: mask mode %d",
+              mask_is_prob);
   return launch_dcn_col2im_fused(dy, dy_stride, K, w_packed, w_scale, x, x_stride, om, om_stride, dx, dom, dom_stride, B, H, W, Cin,
                                  mask_is_prob, (hipStream_t)stream);
 }

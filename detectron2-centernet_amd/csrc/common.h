@@ -33,6 +33,10 @@ void ctdet_set_error(const char* fmt, ...);
 
 enum { CTDET_F16 = 0, CTDET_F32 = 1, CTDET_U8 = 2, CTDET_F16X3 = 3 };
 enum { CTDET_ACT_NONE = 0, CTDET_ACT_RELU = 1, CTDET_ACT_SIGMOID_CLAMP = 2 };
+// DCN mask modes (ConvArgs::mask_is_prob and the DCN entry points' argument; CTDET_DCN_MASK_* in ctdet_hip.h)
+enum { DCN_MASK_LOGIT = 0, DCN_MASK_PROB = 1, DCN_MASK_NONE = 2 };
+// channels of an offset/mask row a DCN kernel reads: 18 offsets (+ 9 mask channels unless the mask is absent)
+__host__ __device__ inline int dcn_om_channels(int mask_mode) { return mask_mode == DCN_MASK_NONE ? 18 : 27; }
 
 // Kernel-side argument block for every conv-shaped contraction on the path
 // (plain conv, DCNv2 main contraction, offset/mask conv, head convs).
@@ -51,7 +55,8 @@ struct ConvArgs {
   int nsrc;
   const float* om;      // DCNv2 only: [M, om_stride] f32; ch 0..17 offsets (2k=dh,2k+1=dw), 18..26 mask logits
   int om_stride;
-  int mask_is_prob;     // DCNv2: 0 = mask channels are logits (sigmoid here), 1 = already probabilities
+  int mask_is_prob;     // DCN mask mode: 0 = mask channels are logits (sigmoid here), 1 = already probabilities,
+                        // 2 = no mask (DCNv1: om holds the 18 offset channels only, the kernels' NM instantiations)
   int B, H, W, Cin, in_stride;
   int Cout, Ho, Wo, out_stride, res_stride;
   int R, S, stride, pad, dil;

@@ -28,6 +28,8 @@ struct DcnSample {
 };
 
 // Sampling geometry of one (pixel, tap); follows deform_conv_cuda_kernel.cu:836-861 and :666-699.
+// NM (mask mode DCN_MASK_NONE): no mask channel is read, the mask is the constant 1.
+template <bool NM = false>
 __device__ __forceinline__ void dcn_setup(const ConvArgs& a, bool row_ok, int pix_base, int hb, int wb,
                                           int tr, int ts, const float* omrow, DcnSample& sp) {
   sp.off[0] = sp.off[1] = sp.off[2] = sp.off[3] = -1;
@@ -37,8 +39,12 @@ __device__ __forceinline__ void dcn_setup(const ConvArgs& a, bool row_ok, int pi
   if (!row_ok || tr >= a.R) return;
   const int tap = tr * a.S + ts;
   const float oh = omrow[2 * tap], ow = omrow[2 * tap + 1];
-  const float mraw = omrow[2 * a.R * a.S + tap];
-  sp.mask = a.mask_is_prob ? mraw : ctdet_sigmoid_exact(mraw);
+  if constexpr (NM) {
+    sp.mask = 1.f;
+  } else {
+    const float mraw = omrow[2 * a.R * a.S + tap];
+    sp.mask = a.mask_is_prob ? mraw : ctdet_sigmoid_exact(mraw);
+  }
   const float h_im = (float)(hb + tr * a.dil) + oh;
   const float w_im = (float)(wb + ts * a.dil) + ow;
   if (!(h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W)) return;

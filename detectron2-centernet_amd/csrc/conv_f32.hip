@@ -343,7 +343,7 @@ __global__ void __launch_bounds__(256, 2) conv_f32_uk_kernel(const ConvArgs a) {
 // corners of its (row, 4 channels) for the NEXT step before the MFMAs of the current one, blends after them and
 // writes the blended float4 where the LDS-DMA of the plain kernel would have put it; weights stream by LDS-DMA.
 // ------------------------------------------------------------------------------------------
-template <int BP, int BC, int WP, int WC_, bool SP>
+template <int BP, int BC, int WP, int WC_, bool SP, bool NM = false>
 __global__ void __launch_bounds__(256, 2) dcn_f32_mfma_kernel(const ConvArgs a) {
   constexpr int KS = 16, EPV = 4;
   constexpr int TP = BP / WP / 16;
@@ -404,7 +404,7 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_mfma_kernel(const ConvArgs a) 
 #pragma unroll
     for (int i = 0; i < A_LD; ++i) {
       DcnSample sp;
-      dcn_setup(a, rok[i], rpix[i], rhb[i], rwb[i], tr, ts, omrow[i], sp);
+      dcn_setup<NM>(a, rok[i], rpix[i], rhb[i], rwb[i], tr, ts, omrow[i], sp);
 #pragma unroll
       for (int q = 0; q < 4; ++q) { goff[i][q] = sp.off[q]; gwt[i][q] = sp.wt[q]; }
       gmask[i] = sp.mask;
@@ -504,7 +504,7 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_mfma_kernel(const ConvArgs a) 
 // (pixel, tap), staged in LDS.  Samples outside the window are gathered from global memory by the lanes concerned.
 // Weights stay tap-major in memory (k = tap*Cin + c): the K loop runs chunk-major and fetches the 64-byte piece it needs.
 // ------------------------------------------------------------------------------------------
-template <int BC, bool SP>
+template <int BC, bool SP, bool NM = false>
 __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a) {
   constexpr int TH = 8, TW = 16, BP = 128, MG = 4;
   constexpr int WR = TH + 2 + 2 * MG, WCOLS = TW + 2 + 2 * MG;  // 18 x 26 window pixels
@@ -585,9 +585,9 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
       if (t < 9) {
         const int tr = t / 3, ts = t - 3 * tr;
         const float h_im = (float)(py - 1 + tr) + omrow[2 * t], w_im = (float)(pxx - 1 + ts) + omrow[2 * t + 1];
-        const float mraw = omrow[18 + t];
+        const float mraw = NM ? 1.f : omrow[18 + t];                                                  // NM: no mask channel
         const bool valid = h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W;     // kernel.cu:852
-        const float mk = valid ? (a.mask_is_prob ? mraw : ctdet_sigmoid_exact(mraw)) : 0.f;           // invalid: contributes 0
+        const float mk = valid ? ((NM || a.mask_is_prob) ? mraw : ctdet_sigmoid_exact(mraw)) : 0.f;   // invalid: contributes 0
         const float fh = floorf(h_im), fw = floorf(w_im);
         const int h_low = (int)fh, w_low = (int)fw;
         const int wr = h_low - wy0, wcn = w_low - wx0;  // window coordinates of corner (h_low, w_low)
@@ -750,7 +750,7 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
 // ------------------------------------------------------------------------------------------
 // COLS: the instantiation that also writes the sampled columns (training forward); a template parameter so that the inference
 // kernel's register allocation does not carry the pointer and index (with it the <2,64> form spilled 14 registers: +8 % time)
-template <int TP, int BC, bool COLS = false>
+template <int TP, int BC, bool COLS = false, bool NM = false>
 __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_split_window_kernel(const ConvArgs a) {
   constexpr int TH = 8, TW = 16, BP = 128, MG = 4;
   constexpr int NT = 512 / TP;                                  // TP = 2: 4 waves of 32 pixels, TP = 1: 8 waves of 16
@@ -834,9 +834,9 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
       if (t < 9) {
         const int tr = t / 3, ts = t - 3 * tr;
         const float h_im = (float)(py - 1 + tr) + omrow[2 * t], w_im = (float)(pxx - 1 + ts) + omrow[2 * t + 1];
-        const float mraw = omrow[18 + t];
+        const float mraw = NM ? 1.f : omrow[18 + t];                                                  // NM: no mask channel
         const bool valid = h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W;     // kernel.cu:852
-        const float mk = valid ? (a.mask_is_prob ? mraw : ctdet_sigmoid_exact(mraw)) : 0.f;           // invalid: contributes 0
+        const float mk = valid ? ((NM || a.mask_is_prob) ? mraw : ctdet_sigmoid_exact(mraw)) : 0.f;   // invalid: contributes 0
         const float fh = floorf(h_im), fw = floorf(w_im);
         const int h_low = (int)fh, w_low = (int)fw;
         const float lh = valid ? h_im - fh : 0.f, lw = valid ? w_im - fw : 0.f, hh = 1.f - lh, hw = 1.f - lw;
@@ -1156,7 +1156,7 @@ static int launch_f32_win(const ConvArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 // Direct form: one thread per (pixel, cout), f32 FMA chain in k order (any Cin / stride).
 // ------------------------------------------------------------------------------------------
-template <bool DEFORM, bool SP>
+template <bool DEFORM, bool SP, bool NM = false>
 __global__ void __launch_bounds__(256) conv_direct_f32_kernel(const ConvArgs a) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const int CP = (a.Cout + 3) & ~3;
@@ -1192,7 +1192,7 @@ __global__ void __launch_bounds__(256) conv_direct_f32_kernel(const ConvArgs a) 
         for (int c = 0; c < a.Cin; ++c) acc = fmaf(xp[c], packed_w<SP>(w, kb + c), acc);
       } else {
         DcnSample sp;
-        dcn_setup(a, true, pix_base, hb, wb, tr, ts, a.om + (long)m * a.om_stride, sp);
+        dcn_setup<NM>(a, true, pix_base, hb, wb, tr, ts, a.om + (long)m * a.om_stride, sp);
         for (int c = 0; c < a.Cin; ++c) {
           const float v1 = sp.off[0] >= 0 ? x[(long)sp.off[0] + c] : 0.f;
           const float v2 = sp.off[1] >= 0 ? x[(long)sp.off[1] + c] : 0.f;
@@ -1248,11 +1248,11 @@ static int launch_f32_mfma(const ConvArgs& a, int kind, hipStream_t s) {   // ki
   return 0;
 }
 
-template <int BP, int BC, int WP, int WC_, bool SP>
+template <int BP, int BC, int WP, int WC_, bool SP, bool NM>
 static int launch_f32_dcn(const ConvArgs& a, hipStream_t s) {
   const int nbx = (a.M + BP - 1) / BP, nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
-  hipLaunchKernelGGL((dcn_f32_mfma_kernel<BP, BC, WP, WC_, SP>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((dcn_f32_mfma_kernel<BP, BC, WP, WC_, SP, NM>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -1268,6 +1268,51 @@ static bool f32_uniform_k_ok(const ConvArgs& a) {
     return true;
   }
   return a.Cin % 16 == 0;
+}
+
+// the deformable launches of launch_conv_f32_t, one instantiation per mask mode (NM: no mask, DCNv1)
+template <bool SP, bool NM>
+static int launch_f32_deform(const ConvArgs& a, bool vec, int bc, hipStream_t s) {
+  if (vec) {
+    if (a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.H % 8 == 0 && a.W % 16 == 0 &&
+        a.H <= 4094 && a.W <= 4094 && a.Kpad == a.K && a.Cout_pad % 64 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_F32_DCN_WINDOW)) {
+      // 64 couts per workgroup (128 would spill under two workgroups per CU); wider layers sample the window once per cout tile
+      const int nbx = a.B * (a.H / 8) * (a.W / 16);
+      dim3 grid(8 * ((nbx + 7) / 8) * (a.Cout_pad / 64));
+      if (SP && !(ctdet_tuning_flags() & CTDET_TUNE_DCN_WINDOW_V1)) {
+        // the sampling (conflict-laden LDS gathers, blend, split) is this kernel's larger half and is repeated for every cout
+        // tile: the 128- and 256-cout layers use 128-cout tiles -- eight 16-pixel waves, one workgroup per CU, the same
+        // eight waves per CU with half the gathers per MFMA (CTDET_TUNE_DCN_SPLIT_4W: 64-cout tiles everywhere)
+        if (a.Cout_pad % 128 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_DCN_SPLIT_4W)) {
+          dim3 grid128(8 * ((nbx + 7) / 8) * (a.Cout_pad / 128));
+          if (a.cols_out) hipLaunchKernelGGL((dcn_split_window_kernel<1, 128, true, NM>), grid128, dim3(512), 0, s, a);
+          else hipLaunchKernelGGL((dcn_split_window_kernel<1, 128, false, NM>), grid128, dim3(512), 0, s, a);
+        } else {
+          if (a.cols_out) hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, true, NM>), grid, dim3(256), 0, s, a);
+          else if (ctdet_tuning_flags() & CTDET_TUNE_DCN_SPLIT_8W64)
+            hipLaunchKernelGGL((dcn_split_window_kernel<1, 64, false, NM>), grid, dim3(512), 0, s, a);
+          else hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, false, NM>), grid, dim3(256), 0, s, a);
+        }
+      }
+      else
+        hipLaunchKernelGGL((dcn_f32_window_kernel<64, SP, NM>), grid, dim3(256), 0, s, a);
+      CTDET_LAUNCH_CHECK();
+      return 0;
+    }
+    {   // 128-pixel tiles: two or more workgroups per CU cover each other's gather latency
+      switch (bc) {
+        case 16: return launch_f32_dcn<128, 16, 4, 1, SP, NM>(a, s);
+        case 32: return launch_f32_dcn<128, 32, 4, 1, SP, NM>(a, s);
+        case 64: return launch_f32_dcn<64, 64, 2, 2, SP, NM>(a, s);
+        case 128: return launch_f32_dcn<128, 128, 2, 2, SP, NM>(a, s);
+      }
+    }
+  }
+  const int CP = (a.Cout + 3) & ~3;
+  const long total = (long)a.M * CP;
+  hipLaunchKernelGGL((conv_direct_f32_kernel<true, SP, NM>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+  CTDET_LAUNCH_CHECK();
+  return 0;
 }
 
 template <bool SP>
@@ -1302,41 +1347,10 @@ static int launch_conv_f32_t(const ConvArgs& a, bool deform, hipStream_t s) {
       if (rc <= 0) return rc;
     }
   }
+  if (deform)
+    return a.mask_is_prob == DCN_MASK_NONE ? launch_f32_deform<SP, true>(a, vec, bc, s) : launch_f32_deform<SP, false>(a, vec, bc, s);
   if (vec) {
     const bool big = ((long)a.M + 255) / 256 * (a.Cout_pad / bc) >= 512;
-    if (deform && a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.H % 8 == 0 && a.W % 16 == 0 &&
-        a.H <= 4094 && a.W <= 4094 && a.Kpad == a.K && a.Cout_pad % 64 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_F32_DCN_WINDOW)) {
-      // 64 couts per workgroup (128 would spill under two workgroups per CU); wider layers sample the window once per cout tile
-      const int nbx = a.B * (a.H / 8) * (a.W / 16);
-      dim3 grid(8 * ((nbx + 7) / 8) * (a.Cout_pad / 64));
-      if (SP && !(ctdet_tuning_flags() & CTDET_TUNE_DCN_WINDOW_V1)) {
-        // the sampling (conflict-laden LDS gathers, blend, split) is this kernel's larger half and is repeated for every cout
-        // tile: the 128- and 256-cout layers use 128-cout tiles -- eight 16-pixel waves, one workgroup per CU, the same
-        // eight waves per CU with half the gathers per MFMA (CTDET_TUNE_DCN_SPLIT_4W: 64-cout tiles everywhere)
-        if (a.Cout_pad % 128 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_DCN_SPLIT_4W)) {
-          dim3 grid128(8 * ((nbx + 7) / 8) * (a.Cout_pad / 128));
-          if (a.cols_out) hipLaunchKernelGGL((dcn_split_window_kernel<1, 128, true>), grid128, dim3(512), 0, s, a);
-          else hipLaunchKernelGGL((dcn_split_window_kernel<1, 128>), grid128, dim3(512), 0, s, a);
-        } else {
-          if (a.cols_out) hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, true>), grid, dim3(256), 0, s, a);
-          else if (ctdet_tuning_flags() & CTDET_TUNE_DCN_SPLIT_8W64)
-            hipLaunchKernelGGL((dcn_split_window_kernel<1, 64>), grid, dim3(512), 0, s, a);
-          else hipLaunchKernelGGL((dcn_split_window_kernel<2, 64>), grid, dim3(256), 0, s, a);
-        }
-      }
-      else
-        hipLaunchKernelGGL((dcn_f32_window_kernel<64, SP>), grid, dim3(256), 0, s, a);
-      CTDET_LAUNCH_CHECK();
-      return 0;
-    }
-    if (deform) {   // 128-pixel tiles: two or more workgroups per CU cover each other's gather latency
-      switch (bc) {
-        case 16: return launch_f32_dcn<128, 16, 4, 1, SP>(a, s);
-        case 32: return launch_f32_dcn<128, 32, 4, 1, SP>(a, s);
-        case 64: return launch_f32_dcn<64, 64, 2, 2, SP>(a, s);
-        case 128: return launch_f32_dcn<128, 128, 2, 2, SP>(a, s);
-      }
-    }
     const int kind = f32_uniform_k_ok(a) ? 1 : 0;
     switch (bc) {
       case 16: return launch_f32_mfma<256, 16, 4, 1, SP>(a, kind, s);
@@ -1348,10 +1362,7 @@ static int launch_conv_f32_t(const ConvArgs& a, bool deform, hipStream_t s) {
   const int CP = (a.Cout + 3) & ~3;
   const long total = (long)a.M * CP;
   dim3 grid((unsigned)((total + 255) / 256));
-  if (deform)
-    hipLaunchKernelGGL((conv_direct_f32_kernel<true, SP>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_direct_f32_kernel<false, SP>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((conv_direct_f32_kernel<false, SP>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }

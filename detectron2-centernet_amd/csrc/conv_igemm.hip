@@ -1698,7 +1698,8 @@ __device__ __forceinline__ u32x4 dcn_blend(const u32x4& v0, const u32x4& v1, con
 // stage stores the image coordinates of such samples and only those lanes go to global memory, the rest keep reading the
 // window -- 10 % / 35 % faster at offset sigma 2 / 4 px, 5 % slower when (almost) nothing leaves the window, which is the
 // regime of the benchmark's weights; a separate instantiation so that the default kernel's code is untouched.
-template <int BC, int NST, bool PARTIAL, typename TOut, bool MIXED = false>
+// NM: mask mode DCN_MASK_NONE (DCNv1) -- om rows hold the 18 offsets only, no mask is loaded or applied.
+template <int BC, int NST, bool PARTIAL, typename TOut, bool MIXED = false, bool NM = false>
 __global__ void __launch_bounds__(256, 2) dcn_window_kernel(const ConvArgs a) {
   constexpr int TH = 8, TW = 16, BP = 128, MG = 4;
   constexpr int WR = TH + 2 + 2 * MG, WCOLS = TW + 2 + 2 * MG;  // 18 x 26 window pixels
@@ -1794,7 +1795,7 @@ __global__ void __launch_bounds__(256, 2) dcn_window_kernel(const ConvArgs a) {
     for (int i = 0; i < 5; ++i) {
       const int t = 2 * i + gh;
       const bool on = t < 9 && pin;
-      oh[i] = on ? omrow[2 * t] : 0.f; ow[i] = on ? omrow[2 * t + 1] : 0.f; om_[i] = on ? omrow[18 + t] : 0.f;
+      oh[i] = on ? omrow[2 * t] : 0.f; ow[i] = on ? omrow[2 * t + 1] : 0.f; om_[i] = (on && !NM) ? omrow[18 + t] : 0.f;
     }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
@@ -1802,7 +1803,7 @@ __global__ void __launch_bounds__(256, 2) dcn_window_kernel(const ConvArgs a) {
       if (t < 9) {
         const int tr = t / 3, ts = t - 3 * tr;
         const float h_im = (float)(py - 1 + tr) + oh[i], w_im = (float)(pxx - 1 + ts) + ow[i];
-        const float mk = a.mask_is_prob ? om_[i] : __builtin_amdgcn_rcpf(1.f + __expf(-om_[i]));
+        const float mk = NM ? 1.f : a.mask_is_prob ? om_[i] : __builtin_amdgcn_rcpf(1.f + __expf(-om_[i]));
         const float fh = floorf(h_im), fw = floorf(w_im);
         const int h_low = (int)fh, w_low = (int)fw;
         const float lh = h_im - fh, lw = w_im - fw, hh = 1.f - lh, hw = 1.f - lw;
@@ -2071,8 +2072,10 @@ __global__ void __launch_bounds__(256, 2) dcn_window_kernel(const ConvArgs a) {
 // COLS: no contraction at all -- the sampled * mask operands are stored as the training backward's `columns` tensor
 // ([M][9*Cin] f16, tap-major; a.y), i.e. modulated_deformable_im2col (kernel.cu:786-868) with the gathers served from the LDS
 // window instead of 4 x 16 bytes per (pixel, tap, 8 channels) through L2.
-template <typename TOut, bool FUSED, bool COLS = false>
+// NM: mask mode DCN_MASK_NONE (DCNv1), as in dcn_window_kernel; not with FUSED (the offset conv there has 27 couts).
+template <typename TOut, bool FUSED, bool COLS = false, bool NM = false>
 __global__ void __launch_bounds__(256, 2) dcn_window_rows_kernel(const ConvArgs a) {
+  static_assert(!(FUSED && NM), "the fused offset conv is DCNv2's");
   constexpr int BC = 64, TH = 8, TW = 16, BP = 128, MG = 4, TP = 2, TC = 4;
   constexpr int WR = TH + 2 + 2 * MG, WCU = TW + 2 + 2 * MG, WCP = 32;   // 18 rows x 26 used of 32 columns
   constexpr int WINB = WR * WCP * 64;                                    // 36864
@@ -2211,7 +2214,7 @@ __global__ void __launch_bounds__(256, 2) dcn_window_rows_kernel(const ConvArgs 
     for (int i = 0; i < 5; ++i) {
       const int t = 2 * i + gh;
       const bool on = t < 9;
-      oh[i] = on ? omrow[2 * t] : 0.f; ow[i] = on ? omrow[2 * t + 1] : 0.f; om_[i] = on ? omrow[18 + t] : 0.f;
+      oh[i] = on ? omrow[2 * t] : 0.f; ow[i] = on ? omrow[2 * t + 1] : 0.f; om_[i] = (on && !NM) ? omrow[18 + t] : 0.f;
     }
     if constexpr (FUSED) __syncthreads();                // the records below overwrite the om tile
     unsigned far_lo = 0, far_hi = 0;     // taps with a far sample among lanes 0-31 / 32-63 (= consumer waves 2*(w&1), +1)
@@ -2221,7 +2224,7 @@ __global__ void __launch_bounds__(256, 2) dcn_window_rows_kernel(const ConvArgs 
       if (t < 9) {
         const int tr = t / 3, ts = t - 3 * tr;
         const float h_im = (float)(py - 1 + tr) + oh[i], w_im = (float)(pxx - 1 + ts) + ow[i];
-        const float mk = a.mask_is_prob ? om_[i] : __builtin_amdgcn_rcpf(1.f + __expf(-om_[i]));
+        const float mk = NM ? 1.f : a.mask_is_prob ? om_[i] : __builtin_amdgcn_rcpf(1.f + __expf(-om_[i]));
         const float fh = floorf(h_im), fw = floorf(w_im);
         const int h_low = (int)fh, w_low = (int)fw;
         const float lh = h_im - fh, lw = w_im - fw, hh = 1.f - lh, hw = 1.f - lw;
@@ -2432,7 +2435,10 @@ int launch_dcn_cols_window(const f16* x, int x_stride, const float* om, int om_s
   a.B = B; a.H = H; a.W = W; a.Ho = H; a.Wo = W; a.Cin = Cin; a.in_stride = x_stride; a.Cout = 64; a.Cout_pad = 64;
   a.R = a.S = 3; a.stride = 1; a.pad = 1; a.dil = 1; a.in_dil = 1; a.K = a.Kpad = 9 * Cin; a.M = B * H * W; a.korder = 1;
   const int nbx = B * (H / 8) * (W / 16);
-  hipLaunchKernelGGL((dcn_window_rows_kernel<f16, false, true>), dim3(8 * ((nbx + 7) / 8)), dim3(256), 0, s, a);
+  if (mask_is_prob == DCN_MASK_NONE)
+    hipLaunchKernelGGL((dcn_window_rows_kernel<f16, false, true, true>), dim3(8 * ((nbx + 7) / 8)), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((dcn_window_rows_kernel<f16, false, true>), dim3(8 * ((nbx + 7) / 8)), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -2445,26 +2451,33 @@ bool dcn_offset_fused_ok(const ConvArgs& a) {
          !(ctdet_tuning_flags() & (CTDET_TUNE_DCN_MIXED | CTDET_TUNE_DCN_WINDOW_V1));
 }
 
-template <int BC, int WP, int WC_, typename TOut>
-static int launch_dcn_window(const ConvArgs& a, hipStream_t s) {
+template <int BC, int WP, int WC_, typename TOut, bool NM>
+static int launch_dcn_window_t(const ConvArgs& a, hipStream_t s) {
   const int nbx = a.B * ((a.H + 7) / 8) * ((a.W + 15) / 16), nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
   const bool mixed = (ctdet_tuning_flags() & CTDET_TUNE_DCN_MIXED) != 0;
   if (BC == 64 && !mixed && a.H % 8 == 0 && a.W % 16 == 0 && a.H <= 65534 && a.W <= 65534 &&
       !(ctdet_tuning_flags() & CTDET_TUNE_DCN_WINDOW_V1)) {
-    if (a.w_off) hipLaunchKernelGGL((dcn_window_rows_kernel<TOut, true>), grid, dim3(256), 0, s, a);
+    if constexpr (NM) hipLaunchKernelGGL((dcn_window_rows_kernel<TOut, false, false, true>), grid, dim3(256), 0, s, a);
+    else if (a.w_off) hipLaunchKernelGGL((dcn_window_rows_kernel<TOut, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((dcn_window_rows_kernel<TOut, false>), grid, dim3(256), 0, s, a);
     CTDET_LAUNCH_CHECK();
     return 0;
   }
   if (mixed && a.H % 8 == 0 && a.W % 16 == 0 && a.H <= 4094 && a.W <= 4094)
-    hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), false, TOut, true>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), false, TOut, true, NM>), grid, dim3(256), 0, s, a);
   else if (a.H % 8 == 0 && a.W % 16 == 0)
-    hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), false, TOut>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), false, TOut, false, NM>), grid, dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), true, TOut>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), true, TOut, false, NM>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
+}
+template <int BC, int WP, int WC_, typename TOut>
+static int launch_dcn_window(const ConvArgs& a, hipStream_t s) {
+  CTDET_CHECK(!(a.w_off && a.mask_is_prob == DCN_MASK_NONE), "dcnv2(offset conv fused): modulated DCN only");
+  return a.mask_is_prob == DCN_MASK_NONE ? launch_dcn_window_t<BC, WP, WC_, TOut, true>(a, s)
+                                         : launch_dcn_window_t<BC, WP, WC_, TOut, false>(a, s);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -890,12 +890,15 @@ struct DcnGeom {
   float hh, hw, lh, lw, mask;
   bool inside;
 };
+// NM (mask mode CTDET_DCN_MASK_NONE, DCNv1): om holds the 18 offset channels only; the mask is the constant 1, never loaded
+template <bool NM = false>
 __device__ __forceinline__ DcnGeom dcn_geom(const float* om, int tap, int b, int ho, int wo, int H, int W, int stride_elems,
                                             int mask_is_prob) {
   DcnGeom g;
   const int tr = tap / 3, ts = tap - tr * 3;
   const float h_im = (float)(ho - 1 + tr) + om[2 * tap], w_im = (float)(wo - 1 + ts) + om[2 * tap + 1];
-  g.mask = mask_is_prob ? om[18 + tap] : ctdet_sigmoid_exact(om[18 + tap]);   // prob: the reference's functional form
+  if constexpr (NM) g.mask = 1.f;
+  else g.mask = mask_is_prob ? om[18 + tap] : ctdet_sigmoid_exact(om[18 + tap]);   // prob: the reference's functional form
   g.inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
 #pragma unroll
   for (int q = 0; q < 4; ++q) { g.off[q] = -1; g.w[q] = 0.f; }
@@ -914,20 +917,26 @@ __device__ __forceinline__ DcnGeom dcn_geom(const float* om, int tap, int b, int
 }
 
 // d(offset), d(mask) of one (pixel, tap) into the dom row (f32 or f16, row stride dom_stride); tap 0 also clears the padding
-// channels 27 .. dom_stride-1, so the caller does not have to zero the buffer
+// channels 27 .. dom_stride-1, so the caller does not have to zero the buffer.  NM: no d(mask); channels 18 .. dom_stride-1
+// are the padding
+template <bool NM = false>
 __device__ __forceinline__ void dom_store(void* dom, int dom_f16, long m, int dom_stride, int tap, float v_h, float v_w, float v_m) {
+  constexpr int PAD0 = NM ? 18 : 27;
   if (dom_f16) {
     f16* d = (f16*)dom + m * dom_stride;
-    d[2 * tap] = (f16)v_h; d[2 * tap + 1] = (f16)v_w; d[18 + tap] = (f16)v_m;
-    if (tap == 0) for (int c = 27; c < dom_stride; ++c) d[c] = (f16)0.f;
+    d[2 * tap] = (f16)v_h; d[2 * tap + 1] = (f16)v_w;
+    if constexpr (!NM) d[18 + tap] = (f16)v_m;
+    if (tap == 0) for (int c = PAD0; c < dom_stride; ++c) d[c] = (f16)0.f;
   } else {
     float* d = (float*)dom + m * dom_stride;
-    d[2 * tap] = v_h; d[2 * tap + 1] = v_w; d[18 + tap] = v_m;
-    if (tap == 0) for (int c = 27; c < dom_stride; ++c) d[c] = 0.f;
+    d[2 * tap] = v_h; d[2 * tap + 1] = v_w;
+    if constexpr (!NM) d[18 + tap] = v_m;
+    if (tap == 0) for (int c = PAD0; c < dom_stride; ++c) d[c] = 0.f;
   }
 }
 
 // col[m][tap*Cin + c] = mask * bilinear(x)   (the `columns` of the reference, f16, tap-major)
+template <bool NM>
 __global__ void __launch_bounds__(256) dcn_cols_kernel(const f16* __restrict__ x, int x_stride, const float* __restrict__ om,
                                                        int om_stride, f16* __restrict__ col, int B, int H, int W, int Cin, int mask_is_prob) {
   const int CV = Cin >> 3;
@@ -941,7 +950,7 @@ __global__ void __launch_bounds__(256) dcn_cols_kernel(const f16* __restrict__ x
   const int wo = (int)(m % W);
   const long t2 = m / W;
   const int ho = (int)(t2 % H), b = (int)(t2 / H);
-  const DcnGeom g = dcn_geom(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
+  const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
   float acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
@@ -962,6 +971,7 @@ __global__ void __launch_bounds__(256) dcn_cols_kernel(const f16* __restrict__ x
 // One wave per (pixel, tap) pass over the channels, one lane per channel: every atomic wave-instruction adds 64
 // consecutive floats (256 contiguous bytes, the shape the memory-side atomic units run at full rate with); the
 // three per-(pixel,tap) dot products are wave reductions.
+template <bool NM>
 __global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __restrict__ dcol, const f16* __restrict__ x,
                                                                int x_stride, const float* __restrict__ om, int om_stride,
                                                                float* __restrict__ dx, void* __restrict__ dom, int dom_stride,
@@ -976,7 +986,7 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __rest
     const int wo = (int)(m % W);
     const long t2 = m / W;
     const int ho = (int)(t2 % H), b = (int)(t2 / H);
-    const DcnGeom g = dcn_geom(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);  // wave-uniform
+    const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);  // wave-uniform
     float val_dot = 0.f, dh = 0.f, dwv = 0.f;
     if (g.inside) {
       // dcol row of a pixel: [tap][Cin], or chunked [Cin/32][tap][32]
@@ -986,7 +996,7 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __rest
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = g.off[q] >= 0 ? (float)x[g.off[q] + c] : 0.f;
-        val_dot += d * (g.w[0] * v[0] + g.w[1] * v[1] + g.w[2] * v[2] + g.w[3] * v[3]);
+        if constexpr (!NM) val_dot += d * (g.w[0] * v[0] + g.w[1] * v[1] + g.w[2] * v[2] + g.w[3] * v[3]);
         dh += d * (-g.hw * v[0] - g.lw * v[1] + g.hw * v[2] + g.lw * v[3]);   // d val / d h  (kernel.cu:754-766)
         dwv += d * (-g.hh * v[0] + g.hh * v[1] - g.lh * v[2] + g.lh * v[3]);  // d val / d w  (kernel.cu:767-779)
         const float dm = d * g.mask;
@@ -997,12 +1007,12 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __rest
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      val_dot += __shfl_down(val_dot, o, 64);
+      if constexpr (!NM) val_dot += __shfl_down(val_dot, o, 64);
       dh += __shfl_down(dh, o, 64);
       dwv += __shfl_down(dwv, o, 64);
     }
     if (lane == 0)   // the mask logit's gradient goes through its sigmoid
-      dom_store(dom, dom_f16, m, dom_stride, tap, dh * g.mask, dwv * g.mask, mask_is_prob ? val_dot : val_dot * g.mask * (1.f - g.mask));
+      dom_store<NM>(dom, dom_f16, m, dom_stride, tap, dh * g.mask, dwv * g.mask, mask_is_prob ? val_dot : val_dot * g.mask * (1.f - g.mask));
   }
 }
 
@@ -1062,7 +1072,7 @@ struct FusedDcol {
   const f16* wpk; const float* wscale;       // rows (Cin/32)*288 + tap*32 + c%32: K/8 groups of {hi[8], lo[8]}; per-row scale
 };
 
-template <int NT, typename T, bool FUSED = false>
+template <int NT, typename T, bool FUSED = false, bool NM = false>
 __global__ void __launch_bounds__(512) dcn_col2im_window_kernel(const T* __restrict__ dcol, const T* __restrict__ x,
                                                                 int x_stride, const float* __restrict__ om, int om_stride,
                                                                 float* __restrict__ dx, void* __restrict__ dom, int dom_stride,
@@ -1096,7 +1106,8 @@ __global__ void __launch_bounds__(512) dcn_col2im_window_kernel(const T* __restr
     const int tr = tap / 3, ts = tap - tr * 3;
     const float h_im = (float)(py - 1 + tr) + omr[2 * tap], w_im = (float)(pxx - 1 + ts) + omr[2 * tap + 1];
     ColGeo g;
-    g.mask = mask_is_prob ? omr[18 + tap] : ctdet_sigmoid_exact(omr[18 + tap]);
+    if constexpr (NM) g.mask = 1.f;
+    else g.mask = mask_is_prob ? omr[18 + tap] : ctdet_sigmoid_exact(omr[18 + tap]);
     g.off = 0; g.valid = 0; g.hh = g.hw = g.lh = g.lw = 0.f; g.pad = 0.f;
     if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
       const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
@@ -1275,11 +1286,12 @@ __global__ void __launch_bounds__(512) dcn_col2im_window_kernel(const T* __restr
         r[0] = sq[0]; r[1] = sq[1]; r[2] = sq[2]; r[3] = sq[3]; r[4] = g.hw; r[5] = g.lw; r[6] = __uint_as_float(g.off); r[7] = (float)inwin;
       }
 #endif
-      s_val[t] += w0 * sq[0] + w1 * sq[1] + w2 * sq[2] + w3 * sq[3];
+      if constexpr (!NM) s_val[t] += w0 * sq[0] + w1 * sq[1] + w2 * sq[2] + w3 * sq[3];
       s_dh[t] += -g.hw * sq[0] - g.lw * sq[1] + g.hw * sq[2] + g.lw * sq[3];    // d val / d h (kernel.cu:754-766)
       s_dw[t] += -g.hh * sq[0] + g.hh * sq[1] - g.lh * sq[2] + g.lh * sq[3];    // d val / d w (kernel.cu:767-779)
       // input-gradient scatter (kernel.cu:871-949)
-      const float wq[4] = {w0 * g.mask, w1 * g.mask, w2 * g.mask, w3 * g.mask};
+      const float mk = NM ? 1.f : g.mask;
+      const float wq[4] = {w0 * mk, w1 * mk, w2 * mk, w3 * mk};
       if (inwin) {
         int* a0 = dxw + base * 4 + q;
 #pragma unroll
@@ -1317,12 +1329,12 @@ __global__ void __launch_bounds__(512) dcn_col2im_window_kernel(const T* __restr
   for (int t = 0; t < NT; ++t) {
     if (t0 + t >= 9) continue;
     float a = s_val[t], bh = s_dh[t], bw = s_dw[t];
-    a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
+    if constexpr (!NM) { a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64); }
     bh += __shfl_xor(bh, 16, 64); bh += __shfl_xor(bh, 32, 64);
     bw += __shfl_xor(bw, 16, 64); bw += __shfl_xor(bw, 32, 64);
     if (q == 0) {
-      const float mk = geo[t * (TH * TW) + pl].mask;
-      dom_store(dom, dom_f16, m, dom_stride, t0 + t, bh * mk, bw * mk, mask_is_prob ? a : a * mk * (1.f - mk));  // through the sigmoid
+      const float mk = NM ? 1.f : geo[t * (TH * TW) + pl].mask;
+      dom_store<NM>(dom, dom_f16, m, dom_stride, t0 + t, bh * mk, bw * mk, mask_is_prob ? a : a * mk * (1.f - mk));  // through the sigmoid
     }
   }
 }
@@ -2276,33 +2288,48 @@ int launch_dcn_cols_window(const f16* x, int x_stride, const float* om, int om_s
                            int mask_is_prob, hipStream_t s);   // conv_igemm.hip: the sampling kernel's LDS window
 int launch_dcn_cols(const f16* x, int x_stride, const float* om, int om_stride, f16* col, int B, int H, int W, int Cin,
                     int mask_is_prob, hipStream_t s) {
-  CTDET_CHECK(Cin % 8 == 0 && om_stride >= 27, "dcn_cols: bad shape");
+  CTDET_CHECK(Cin % 8 == 0 && om_stride >= dcn_om_channels(mask_is_prob), "dcn_cols: bad shape");
   const long total = (long)B * H * W * 9 * (Cin / 8);
   if (total == 0) return 0;
   if (H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && x_stride % 8 == 0 && om_stride % 4 == 0 && H <= 65534 && W <= 65534 &&
       (((size_t)x | (size_t)col | (size_t)om) & 15) == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
     return launch_dcn_cols_window(x, x_stride, om, om_stride, col, B, H, W, Cin, mask_is_prob, s);
-  hipLaunchKernelGGL(dcn_cols_kernel, dim3(nblk256(total)), dim3(256), 0, s, x, x_stride, om, om_stride, col, B, H, W, Cin,
-                     mask_is_prob);
+  if (mask_is_prob == DCN_MASK_NONE)
+    hipLaunchKernelGGL(dcn_cols_kernel<true>, dim3(nblk256(total)), dim3(256), 0, s, x, x_stride, om, om_stride, col, B, H, W, Cin,
+                       mask_is_prob);
+  else
+    hipLaunchKernelGGL(dcn_cols_kernel<false>, dim3(nblk256(total)), dim3(256), 0, s, x, x_stride, om, om_stride, col, B, H, W, Cin,
+                       mask_is_prob);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
+template <typename T, bool FUSED = false, bool NM = false>
+static void launch_col2im_window_t(const T* dcol, const T* x, int x_stride, const float* om, int om_stride, float* dx, void* dom,
+                                   int dom_stride, int dom_f16, int B, int H, int W, int Cin, int mask_is_prob, int chunked,
+                                   hipStream_t s, const FusedDcol fz) {
+  const unsigned tiles = (unsigned)(B * (H / 8) * (W / 16));
+  const int ncu = ctdet_device_cu_count();    // one workgroup per CU at a time: with fewer tiles, split a tile's taps
+  if ((int)tiles * 3 <= ncu)
+    hipLaunchKernelGGL((dcn_col2im_window_kernel<3, T, FUSED, NM>), dim3(tiles, 3), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
+                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+  else if ((int)tiles * 2 <= ncu)
+    hipLaunchKernelGGL((dcn_col2im_window_kernel<5, T, FUSED, NM>), dim3(tiles, 2), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
+                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+  else
+    hipLaunchKernelGGL((dcn_col2im_window_kernel<9, T, FUSED, NM>), dim3(tiles), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
+                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+}
 template <typename T, bool FUSED = false>
 static void launch_col2im_window(const T* dcol, const T* x, int x_stride, const float* om, int om_stride, float* dx, void* dom,
                                  int dom_stride, int dom_f16, int B, int H, int W, int Cin, int mask_is_prob, int chunked,
                                  hipStream_t s, const FusedDcol fz = FusedDcol()) {
-  const unsigned tiles = (unsigned)(B * (H / 8) * (W / 16));
-  const int ncu = ctdet_device_cu_count();    // one workgroup per CU at a time: with fewer tiles, split a tile's taps
-  if ((int)tiles * 3 <= ncu)
-    hipLaunchKernelGGL((dcn_col2im_window_kernel<3, T, FUSED>), dim3(tiles, 3), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
-  else if ((int)tiles * 2 <= ncu)
-    hipLaunchKernelGGL((dcn_col2im_window_kernel<5, T, FUSED>), dim3(tiles, 2), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+  if (mask_is_prob == DCN_MASK_NONE)
+    launch_col2im_window_t<T, FUSED, true>(dcol, x, x_stride, om, om_stride, dx, dom, dom_stride, dom_f16, B, H, W, Cin, mask_is_prob,
+                                           chunked, s, fz);
   else
-    hipLaunchKernelGGL((dcn_col2im_window_kernel<9, T, FUSED>), dim3(tiles), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+    launch_col2im_window_t<T, FUSED, false>(dcol, x, x_stride, om, om_stride, dx, dom, dom_stride, dom_f16, B, H, W, Cin, mask_is_prob,
+                                            chunked, s, fz);
 }
 
 // d(columns) GEMM + scatter in one kernel (f16x3 training mode): dy f32 [M][dy_stride] with K channels (multiple of 32; channels
@@ -2311,7 +2338,7 @@ static void launch_col2im_window(const T* dcol, const T* x, int x_stride, const 
 int launch_dcn_col2im_fused(const float* dy, int dy_stride, int K, const void* wpk, const float* wscale, const float* x, int x_stride,
                             const float* om, int om_stride, float* dx, float* dom, int dom_stride, int B, int H, int W, int Cin,
                             int mask_is_prob, hipStream_t s) {
-  CTDET_CHECK(dom_stride >= 27 && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
+  CTDET_CHECK(dom_stride >= dcn_om_channels(mask_is_prob) && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
   if ((long)B * H * W == 0) return 0;
   if (!(H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && x_stride % 4 == 0 && K % 32 == 0 && K > 0 && dy_stride >= K && dy_stride % 4 == 0 &&
         ((((size_t)x | (size_t)dy | (size_t)wpk | (size_t)wscale)) & 15) == 0) || (ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
@@ -2326,7 +2353,7 @@ int launch_dcn_col2im_fused(const float* dy, int dy_stride, int K, const void* w
 int launch_dcn_col2im_coord(const f16* dcol, const f16* x, int x_stride, const float* om, int om_stride, float* dx,
                             void* dom, int dom_stride, int dom_f16, int B, int H, int W, int Cin, int mask_is_prob, int chunked,
                             hipStream_t s) {
-  CTDET_CHECK(dom_stride >= 27 && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
+  CTDET_CHECK(dom_stride >= dcn_om_channels(mask_is_prob) && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
   CTDET_CHECK(!chunked || Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", Cin);
   CTDET_CHECK(Cin % 8 == 0, "dcn_col2im: Cin=%d must be a multiple of 8", Cin);
   const long nwork = (long)B * H * W * 9;
@@ -2338,8 +2365,12 @@ int launch_dcn_col2im_coord(const f16* dcol, const f16* x, int x_stride, const f
   }
   long nb = (nwork + 3) / 4;
   if (nb > 256 * 32) nb = 256 * 32;
-  hipLaunchKernelGGL(dcn_col2im_coord_kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                     dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked);
+  if (mask_is_prob == DCN_MASK_NONE)
+    hipLaunchKernelGGL(dcn_col2im_coord_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
+                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked);
+  else
+    hipLaunchKernelGGL(dcn_col2im_coord_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
+                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -2401,6 +2432,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_f32_kernel(const WgradArgsF a)
 // (kernel.cu:666-699: v1 w1 + v2 w2 + v3 w3 + v4 w4, then * mask :854-861).
 struct ColsGeoS { float w[4]; int off[4]; float mask; };
 constexpr int COLS_PASSES = 8;
+template <bool NM>
 __global__ void __launch_bounds__(256) dcn_cols_f32_kernel(const float* __restrict__ x, int x_stride,
                                                            const float* __restrict__ om, int om_stride, float* __restrict__ col,
                                                            int B, int H, int W, int Cin, int mask_is_prob) {
@@ -2420,7 +2452,7 @@ __global__ void __launch_bounds__(256) dcn_cols_f32_kernel(const float* __restri
       const int wo = (int)(m % W);
       const long t2 = m / W;
       const int ho = (int)(t2 % H), b = (int)(t2 / H);
-      const DcnGeom g = dcn_geom(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
+      const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
       ColsGeoS o;
 #pragma unroll
       for (int q = 0; q < 4; ++q) { o.w[q] = g.w[q]; o.off[q] = (int)g.off[q]; }
@@ -2437,7 +2469,7 @@ __global__ void __launch_bounds__(256) dcn_cols_f32_kernel(const float* __restri
       for (int q = 0; q < 4; ++q) v[q] = g.off[q] >= 0 ? *(const f32x4*)(x + g.off[q] + cv * 4) : z4;
       f32x4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (g.w[0] * v[0][e] + g.w[1] * v[1][e] + g.w[2] * v[2][e] + g.w[3] * v[3][e]) * g.mask;
+      for (int e = 0; e < 4; ++e) o[e] = (g.w[0] * v[0][e] + g.w[1] * v[1][e] + g.w[2] * v[2][e] + g.w[3] * v[3][e]) * (NM ? 1.f : g.mask);
       const int tap = (int)(pr % 9);
       const long m = pr / 9;
       *(f32x4*)(col + m * (9L * Cin) + (long)tap * Cin + cv * 4) = o;
@@ -2446,6 +2478,7 @@ __global__ void __launch_bounds__(256) dcn_cols_f32_kernel(const float* __restri
 }
 
 // the generic coordinate / col2im kernel above for f32 columns and inputs (same wave-per-(pixel, tap) structure)
+template <bool NM>
 __global__ void __launch_bounds__(256) dcn_col2im_coord_f32_kernel(const float* __restrict__ dcol, const float* __restrict__ x,
                                                                    int x_stride, const float* __restrict__ om, int om_stride,
                                                                    float* __restrict__ dx, float* __restrict__ dom, int dom_stride, int B,
@@ -2459,7 +2492,7 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_f32_kernel(const float* 
     const int wo = (int)(m % W);
     const long t2 = m / W;
     const int ho = (int)(t2 % H), b = (int)(t2 / H);
-    const DcnGeom g = dcn_geom(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
+    const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
     float val_dot = 0.f, dh = 0.f, dwv = 0.f;
     if (g.inside) {
       // dcol row of a pixel: [tap][Cin], or chunked [Cin/32][tap][32]
@@ -2469,7 +2502,7 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_f32_kernel(const float* 
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = g.off[q] >= 0 ? x[g.off[q] + c] : 0.f;
-        val_dot += d * (g.w[0] * v[0] + g.w[1] * v[1] + g.w[2] * v[2] + g.w[3] * v[3]);
+        if constexpr (!NM) val_dot += d * (g.w[0] * v[0] + g.w[1] * v[1] + g.w[2] * v[2] + g.w[3] * v[3]);
         dh += d * (-g.hw * v[0] - g.lw * v[1] + g.hw * v[2] + g.lw * v[3]);
         dwv += d * (-g.hh * v[0] + g.hh * v[1] - g.lh * v[2] + g.lh * v[3]);
         const float dm = d * g.mask;
@@ -2480,12 +2513,12 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_f32_kernel(const float* 
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      val_dot += __shfl_down(val_dot, o, 64);
+      if constexpr (!NM) val_dot += __shfl_down(val_dot, o, 64);
       dh += __shfl_down(dh, o, 64);
       dwv += __shfl_down(dwv, o, 64);
     }
     if (lane == 0)
-      dom_store(dom, 0, m, dom_stride, tap, dh * g.mask, dwv * g.mask, mask_is_prob ? val_dot : val_dot * g.mask * (1.f - g.mask));
+      dom_store<NM>(dom, 0, m, dom_stride, tap, dh * g.mask, dwv * g.mask, mask_is_prob ? val_dot : val_dot * g.mask * (1.f - g.mask));
   }
 }
 
@@ -2510,15 +2543,19 @@ int launch_conv_wgrad_f32(const WgradArgs& h, hipStream_t s) {
 
 int launch_dcn_cols_f32(const float* x, int x_stride, const float* om, int om_stride, float* col, int B, int H, int W, int Cin,
                         int mask_is_prob, hipStream_t s) {
-  CTDET_CHECK(om_stride >= 27 && Cin % 4 == 0 && Cin >= 16 && Cin <= 1024 && x_stride % 4 == 0 && ((((size_t)x | (size_t)col)) & 15) == 0,
+  CTDET_CHECK(om_stride >= dcn_om_channels(mask_is_prob) && Cin % 4 == 0 && Cin >= 16 && Cin <= 1024 && x_stride % 4 == 0 && ((((size_t)x | (size_t)col)) & 15) == 0,
               "dcn_cols(f32): Cin=%d (16..1024) / x_stride=%d must be multiples of 4, tensors 16-byte aligned", Cin, x_stride);
   CTDET_CHECK((long)B * H * W * x_stride < (1L << 31), "dcn_cols(f32): input too large for 32-bit element offsets");
   const long npairs = (long)B * H * W * 9;
   if (npairs == 0) return 0;
   const int PP = 256 / (Cin / 4);
   const long per_block = (long)PP * COLS_PASSES;
-  hipLaunchKernelGGL(dcn_cols_f32_kernel, dim3((unsigned)((npairs + per_block - 1) / per_block)), dim3(256), 0, s, x, x_stride, om, om_stride,
-                     col, B, H, W, Cin, mask_is_prob);
+  if (mask_is_prob == DCN_MASK_NONE)
+    hipLaunchKernelGGL(dcn_cols_f32_kernel<true>, dim3((unsigned)((npairs + per_block - 1) / per_block)), dim3(256), 0, s, x, x_stride, om,
+                       om_stride, col, B, H, W, Cin, mask_is_prob);
+  else
+    hipLaunchKernelGGL(dcn_cols_f32_kernel<false>, dim3((unsigned)((npairs + per_block - 1) / per_block)), dim3(256), 0, s, x, x_stride, om,
+                       om_stride, col, B, H, W, Cin, mask_is_prob);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -2528,7 +2565,7 @@ int launch_dcn_cols_f32(const float* x, int x_stride, const float* om, int om_st
 int launch_dcn_col2im_coord_f32(const float* dcol, const float* x, int x_stride, const float* om, int om_stride, float* dx,
                                 float* dom, int dom_stride, int B, int H, int W, int Cin, int mask_is_prob, int chunked, int window,
                                 hipStream_t s) {
-  CTDET_CHECK(dom_stride >= 27 && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
+  CTDET_CHECK(dom_stride >= dcn_om_channels(mask_is_prob) && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
   const long nwork = (long)B * H * W * 9;
   if (nwork == 0) return 0;
   if (window && H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && x_stride % 4 == 0 && ((((size_t)x | (size_t)dcol)) & 15) == 0 &&
@@ -2540,8 +2577,12 @@ int launch_dcn_col2im_coord_f32(const float* dcol, const float* x, int x_stride,
   CTDET_CHECK(!chunked || Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", Cin);
   long nb = (nwork + 3) / 4;
   if (nb > 256 * 32) nb = 256 * 32;
-  hipLaunchKernelGGL(dcn_col2im_coord_f32_kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx,
-                     dom, dom_stride, B, H, W, Cin, mask_is_prob, chunked);
+  if (mask_is_prob == DCN_MASK_NONE)
+    hipLaunchKernelGGL(dcn_col2im_coord_f32_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx,
+                       dom, dom_stride, B, H, W, Cin, mask_is_prob, chunked);
+  else
+    hipLaunchKernelGGL(dcn_col2im_coord_f32_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx,
+                       dom, dom_stride, B, H, W, Cin, mask_is_prob, chunked);
   CTDET_LAUNCH_CHECK();
   return 0;
 }

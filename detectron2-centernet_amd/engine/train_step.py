@@ -13,8 +13,8 @@ import torch
 
 from .. import ops
 from ..layers import hipnn
-from ..ops_train import (BNActFn, ConvFn, ConvTransposeFn, DeformConvFn, DwConvTAddFn, EseFn, FocalLossFn, FrozenConvFn,
-                         MaxPool3x3s2Fn, MaxPoolFn, RegL1Fn, SyncBNActFn, sync_bn_world)
+from ..ops_train import (BNActFn, ConvFn, ConvTransposeFn, DCNFn, DeformConvFn, DwConvTAddFn, EseFn, FocalLossFn, FrozenConvFn,
+                         FrozenDCNFn, MaxPool3x3s2Fn, MaxPoolFn, RegL1Fn, SyncBNActFn, sync_bn_world)
 
 
 _COUNTERS = []
@@ -138,11 +138,30 @@ def _resnet_conv(x, conv, relu, res=None):
     return _frozen_conv(x, conv, relu, res)
 
 
+def _resnet_deform_conv(x, m):
+    """the deformable 3x3 of a DeformBottleneckBlock with its norm and ReLU: conv2_offset (3x3 with bias, f32 out), then the
+    DCN -- FrozenDCNFn with the FrozenBN affine folded in, or DCNFn followed by BNActFn / SyncBNActFn"""
+    off = m.conv2_offset
+    om = ConvFn.apply(x, off.weight, off.bias, off.stride[0], off.padding[0], False, True)
+    conv = m.conv2
+    bn = conv.norm
+    if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+        y = DCNFn.apply(x, om, conv.weight, None, m.mask_mode)
+        _count(bn)
+        fn = SyncBNActFn if isinstance(bn, torch.nn.SyncBatchNorm) and sync_bn_world()[1] > 1 else BNActFn
+        return fn.apply(y, bn.weight, bn.bias, None, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True)
+    scale, bias = hipnn.fold_bn(bn)
+    return FrozenDCNFn.apply(x, om, conv.weight, scale, bias, True, m.mask_mode)
+
+
 def resnet_block(m, x):
     """a block with frozen (FrozenBN) or trainable (BN / SyncBN, batch statistics) norms; the residual enters the block's
     last norm, the 1x1 shortcut has no ReLU"""
     sc = x if m.shortcut is None else _resnet_conv(x, m.shortcut, False)
     out = _resnet_conv(x, m.conv1, True)
+    if hasattr(m, "conv2_offset"):       # DeformBottleneckBlock
+        out = _resnet_deform_conv(out, m)
+        return _resnet_conv(out, m.conv3, True, res=sc)
     if hasattr(m, "conv3"):              # BottleneckBlock
         out = _resnet_conv(out, m.conv2, True)
         return _resnet_conv(out, m.conv3, True, res=sc)

@@ -1,7 +1,8 @@
-"""Modulated deformable convolution (DCNv2) modules and functional form, backed by the fused HIP kernel.
+"""Deformable convolution (DCNv1 and the modulated DCNv2) modules and functional forms, backed by the fused HIP kernels.
 
-Mirrors detectron2/layers/deform_conv.py: `modulated_deform_conv` (= `_ModulatedDeformConv.apply`, :180-306),
-`ModulatedDeformConv` (:406-495) and `DeformConvV2` (:498-519).  `DCN` is the class the reference imports from
+Mirrors detectron2/layers/deform_conv.py: `deform_conv` (= `_DeformConv.apply`, :16-178), `DeformConv` (:309-405),
+`modulated_deform_conv` (= `_ModulatedDeformConv.apply`, :180-306), `ModulatedDeformConv` (:406-495) and `DeformConvV2`
+(:498-519).  DCNv1 runs the kernels' mask-free variants (mask mode DCN_MASK_NONE), not the modulated path with a ones mask.  `DCN` is the class the reference imports from
 the un-vendored third-party DCNv2 repo (deform_conv.py:13, 505-513; version unpinned): a 3x3 `conv_offset_mask`
 conv producing 27 channels (zero-initialised), `offset = out[:, :18]`, `mask = sigmoid(out[:, 18:27])`, then the
 modulated deformable conv with `weight` ~ U(+-1/sqrt(Cin*k*k)) and zero `bias`.
@@ -13,7 +14,7 @@ from torch import nn
 from torch.nn.modules.utils import _pair
 
 from .. import ops
-from ..ops import ACT_NONE, ACT_RELU, F16, F32
+from ..ops import ACT_NONE, ACT_RELU, DCN_MASK_NONE, DCN_MASK_PROB, F16, F32
 from . import hipnn
 
 
@@ -33,29 +34,84 @@ def modulated_deform_conv(input, offset, mask, weight, bias=None, stride=1, padd
     if not input.is_cuda:
         raise NotImplementedError("Deformable Conv is not supported on CPUs!")  # deform_conv.py:203-204
     _check_supported(groups, deformable_groups, stride, dilation)
+    return _deform_conv_nchw(input, [offset, mask], weight, bias, stride, padding, dilation, DCN_MASK_PROB,
+                             "modulated_deform_conv")
+
+
+def _deform_conv_nchw(input, om_parts, weight, bias, stride, padding, dilation, mask_mode, name):
+    """NCHW input, offset (+ mask) -> NCHW output on the HIP kernels: DCNFn (differentiable) for 3x3/s1/p1/d1, the forward
+    kernel alone for other geometries"""
     from ..ops_train import DCNFn
 
     compute = F16 if input.dtype == torch.float16 else F32
     ctx = hipnn.Ctx(compute)
     Co, _, kh, kw = weight.shape
     x = input.permute(0, 2, 3, 1).to(ctx.dtype).contiguous()
-    B, Ho, Wo = offset.shape[0], offset.shape[2], offset.shape[3]
-    npad = ops.round_up(3 * kh * kw, 4) - 3 * kh * kw
-    parts = [offset.float(), mask.float()]
+    B, Ho, Wo = om_parts[0].shape[0], om_parts[0].shape[2], om_parts[0].shape[3]
+    nch = (2 if mask_mode == DCN_MASK_NONE else 3) * kh * kw
+    npad = ops.round_up(nch, 4) - nch          # offset rows padded to 16 bytes (the LDS-window kernels' operand alignment)
+    parts = [t.float() for t in om_parts]
     if npad:
         parts.append(torch.zeros(B, npad, Ho, Wo, dtype=torch.float32, device=input.device))
     om = torch.cat(parts, dim=1).permute(0, 2, 3, 1).contiguous()
-    needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset, mask, weight, bias))
+    needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, weight, bias, *om_parts))
     if (kh, kw) == (3, 3) and _pair(stride) == (1, 1) and _pair(padding) == (1, 1) and _pair(dilation) == (1, 1):
-        y = DCNFn.apply(x, om, weight, bias, True, 1.0)       # unscaled parameter gradients (no loss-scale protocol here)
+        y = DCNFn.apply(x, om, weight, bias, mask_mode, 1.0)   # unscaled parameter gradients (no loss-scale protocol here)
     else:
         if needs_grad:
-            raise NotImplementedError("modulated_deform_conv backward: only 3x3 / stride 1 / padding 1 / dilation 1")
+            raise NotImplementedError(f"{name} backward: only 3x3 / stride 1 / padding 1 / dilation 1")
         p = ops.PackedConv(weight, None, bias, stride=stride, pad=padding, dil=dilation, compute=compute,
                            cout_align=64 if compute == F16 else None)
-        y = ops.dcnv2(x, om, p, mask_is_prob=True)
+        y = ops.dcnv2(x, om, p, mask_is_prob=mask_mode)
     y = y[..., :Co].permute(0, 3, 1, 2)
     return y if y.dtype == input.dtype else y.to(input.dtype)
+
+
+def deform_conv(input, offset, weight, stride=1, padding=0, dilation=1, groups=1, deformable_groups=1, im2col_step=64):
+    """Functional DCNv1 with the reference's signature and contract (`_DeformConv.apply`, deform_conv.py:16-178): NCHW
+    `input`, `offset` [B,2*kh*kw,Ho,Wo] (ch 2k = dh, 2k+1 = dw of tap k), `weight` [Co,Ci,kh,kw], no bias; returns NCHW.
+    Differentiable in input, offset and weight for 3x3 / stride 1 / pad 1 / dilation 1, forward-only otherwise (as
+    modulated_deform_conv).  The kernels sample without a mask (DCN_MASK_NONE).  im2col_step is accepted for the signature:
+    the HIP kernels have no column buffer to batch."""
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    if not input.is_cuda:
+        raise NotImplementedError("Deformable Conv is not supported on CPUs!")  # deform_conv.py:52-53
+    _check_supported(groups, deformable_groups, stride, dilation)
+    return _deform_conv_nchw(input, [offset], weight, None, stride, padding, dilation, DCN_MASK_NONE, "deform_conv")
+
+
+class DeformConv(nn.Module):
+    """deform_conv.py:309-405: parameter `weight` (kaiming-uniform), no bias; optional `norm` and `activation` applied after
+    the conv, as in the reference."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
+                 deformable_groups=1, bias=False, norm=None, activation=None):
+        super().__init__()
+        assert not bias
+        assert in_channels % groups == 0, "in_channels {} cannot be divisible by groups {}".format(in_channels, groups)
+        assert out_channels % groups == 0, "out_channels {} cannot be divisible by groups {}".format(out_channels, groups)
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size = _pair(kernel_size)
+        self.stride, self.padding, self.dilation = _pair(stride), _pair(padding), _pair(dilation)
+        self.groups, self.deformable_groups = groups, deformable_groups
+        self.norm, self.activation = norm, activation
+        self.weight = nn.Parameter(torch.Tensor(out_channels, in_channels // self.groups, *self.kernel_size))
+        self.bias = None
+        nn.init.kaiming_uniform_(self.weight, nonlinearity="relu")
+
+    def forward(self, x, offset):
+        x = deform_conv(x, offset, self.weight, self.stride, self.padding, self.dilation, self.groups, self.deformable_groups)
+        if self.norm is not None:
+            x = self.norm(x)
+        if self.activation is not None:
+            x = self.activation(x)
+        return x
+
+    def extra_repr(self):
+        return (f"in_channels={self.in_channels}, out_channels={self.out_channels}, kernel_size={self.kernel_size}, "
+                f"stride={self.stride}, padding={self.padding}, dilation={self.dilation}, groups={self.groups}, "
+                f"deformable_groups={self.deformable_groups}, bias=False")
 
 
 class ModulatedDeformConv(nn.Module):

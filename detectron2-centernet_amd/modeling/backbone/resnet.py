@@ -1,18 +1,21 @@
 """ResNet backbones of the CenterNet ResNet configs, executed by the HIP kernels.
 
 Structure and parameter names follow detectron2/modeling/backbone/resnet.py (`BasicBlock` :32-112, `BottleneckBlock`
-:115-214, `BasicStem` :322-347, `ResNet` :350-558, `build_resnet_backbone` :561-644), so a reference state dict loads
-key-for-key (tests/golden/g9_resnet50_state_dict_keys.txt).  The nn modules are parameter containers; `hip_forward`
-runs NHWC kernels: every conv + norm (+ residual) + ReLU is one kernel launch, the stem pool is `maxpool3x3s2`.
-Not built: deformable bottlenecks (`DEFORM_ON_PER_STAGE`), grouped convs (`NUM_GROUPS > 1`), dilated res5.
+:115-214, `DeformBottleneckBlock` :215-320, `BasicStem` :322-347, `ResNet` :350-558, `build_resnet_backbone` :561-644), so a
+reference state dict loads key-for-key (tests/golden/g9_resnet50_state_dict_keys.txt, g18_*).  The nn modules are parameter
+containers; `hip_forward` runs NHWC kernels: every conv + norm (+ residual) + ReLU is one kernel launch, the stem pool is
+`maxpool3x3s2`; a deformable 3x3 (`DEFORM_ON_PER_STAGE`, modulated or not) is its offset conv plus one DCN launch with the
+norm folded in.
+Not built: grouped convs (`NUM_GROUPS > 1`), `DEFORM_NUM_GROUPS > 1`, a deformable 3x3 with stride or dilation (the
+`STRIDE_IN_1X1: False` and dilated-res5 forms), dilated res5.
 """
 import torch
 from torch import nn
 
 from ... import ops
-from ...layers import ShapeSpec, hipnn
+from ...layers import DeformConv, ModulatedDeformConv, ShapeSpec, hipnn
 from ...layers.batch_norm import Conv2d, FrozenBatchNorm2d, get_norm
-from ...ops import ACT_NONE, ACT_RELU, F16, F32
+from ...ops import ACT_NONE, ACT_RELU, DCN_MASK_LOGIT, DCN_MASK_NONE, F16, F32
 from .backbone import Backbone
 from .build import BACKBONE_REGISTRY
 
@@ -77,6 +80,58 @@ class BottleneckBlock(CNNBlockBase):
         out = _conv(x, self.conv1, ACT_RELU, ctx)
         out = _conv(out, self.conv2, ACT_RELU, ctx)
         return _conv(out, self.conv3, ACT_RELU, ctx, residual=sc)   # relu(conv3 + shortcut), resnet.py:209-212
+
+
+class DeformBottleneckBlock(CNNBlockBase):
+    """resnet.py:215-320: a BottleneckBlock whose 3x3 is deformable -- `conv2_offset` (3x3 with bias, 27 couts if modulated
+    else 18, zero-initialised) feeds `conv2` (ModulatedDeformConv / DeformConv, no bias, with the norm).  Modulated: the
+    reference's offset = cat(chunk0, chunk1) is channels 0..17 of conv2_offset's output and its mask = sigmoid(channels
+    18..26), i.e. the raw output with the sigmoid in the kernel; DCNv1 runs the mask-free kernels."""
+
+    def __init__(self, in_channels, out_channels, *, bottleneck_channels, stride=1, num_groups=1, norm="BN",
+                 stride_in_1x1=False, dilation=1, deform_modulated=False, deform_num_groups=1):
+        super().__init__(in_channels, out_channels, stride)
+        if num_groups != 1:
+            raise NotImplementedError("grouped bottlenecks (ResNeXt) are outside the CenterNet configs")
+        if deform_num_groups != 1:
+            raise NotImplementedError("MODEL.RESNETS.DEFORM_NUM_GROUPS > 1: the HIP DCN kernels have one deformable group")
+        s1, s3 = (stride, 1) if stride_in_1x1 else (1, stride)   # resnet.py:254
+        if s3 != 1 or dilation != 1:
+            raise NotImplementedError(
+                f"deformable 3x3 with stride {s3} / dilation {dilation} (STRIDE_IN_1X1: False or a dilated res5): the HIP "
+                "DCN backward serves stride 1, dilation 1 only")
+        self.deform_modulated = deform_modulated
+        self.shortcut = None
+        if in_channels != out_channels:
+            self.shortcut = Conv2d(in_channels, out_channels, kernel_size=1, stride=stride, bias=False,
+                                   norm=get_norm(norm, out_channels))
+        self.conv1 = Conv2d(in_channels, bottleneck_channels, kernel_size=1, stride=s1, bias=False,
+                            norm=get_norm(norm, bottleneck_channels))
+        deform_conv_op, offset_channels = (ModulatedDeformConv, 27) if deform_modulated else (DeformConv, 18)
+        self.conv2_offset = Conv2d(bottleneck_channels, offset_channels * deform_num_groups, kernel_size=3, stride=s3,
+                                   padding=1 * dilation, dilation=dilation)
+        self.conv2 = deform_conv_op(bottleneck_channels, bottleneck_channels, kernel_size=3, stride=s3, padding=1 * dilation,
+                                    bias=False, groups=num_groups, dilation=dilation, deformable_groups=deform_num_groups,
+                                    norm=get_norm(norm, bottleneck_channels))
+        self.conv3 = Conv2d(bottleneck_channels, out_channels, kernel_size=1, bias=False,
+                            norm=get_norm(norm, out_channels))
+        nn.init.constant_(self.conv2_offset.weight, 0)
+        nn.init.constant_(self.conv2_offset.bias, 0)
+
+    @property
+    def mask_mode(self):
+        return DCN_MASK_LOGIT if self.deform_modulated else DCN_MASK_NONE
+
+    def hip_forward(self, x, ctx):
+        sc = x if self.shortcut is None else _conv(x, self.shortcut, ACT_NONE, ctx)
+        out = _conv(x, self.conv1, ACT_RELU, ctx)
+        # f32 offsets (and mask logits) whatever the mode: the sampling coordinates keep full precision
+        om = hipnn.conv_module(out, self.conv2_offset, None, ACT_NONE, ctx=ctx, out_dtype=torch.float32)
+        c2 = self.conv2
+        p = hipnn.packed(c2, "dcn", ctx.compute, c2.weight, c2.norm, None, 1, 1, 1,
+                         cout_align=64 if ctx.compute == F16 else None)
+        out = ops.dcnv2(out, om, p, act=ACT_RELU, mask_is_prob=self.mask_mode)
+        return _conv(out, self.conv3, ACT_RELU, ctx, residual=sc)   # relu(conv3 + shortcut), resnet.py:316-320
 
 
 class BasicStem(CNNBlockBase):
@@ -173,12 +228,13 @@ def build_resnet_backbone(cfg, input_shape):
     bottleneck_channels = r.NUM_GROUPS * r.WIDTH_PER_GROUP
     in_channels, out_channels = r.STEM_OUT_CHANNELS, r.RES2_OUT_CHANNELS
     assert r.RES5_DILATION in (1, 2)
-    if any(r.DEFORM_ON_PER_STAGE):
-        raise NotImplementedError("deformable bottlenecks are not part of the CenterNet ResNet configs")
+    deform_on_per_stage = r.DEFORM_ON_PER_STAGE
     num_blocks_per_stage = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3],
                             152: [3, 8, 36, 3]}[depth]
     if depth in (18, 34):
-        assert out_channels == 64 and r.RES5_DILATION == 1 and r.NUM_GROUPS == 1
+        assert out_channels == 64, "Must set MODEL.RESNETS.RES2_OUT_CHANNELS = 64 for R18/R34"
+        assert not any(deform_on_per_stage), "MODEL.RESNETS.DEFORM_ON_PER_STAGE unsupported for R18/R34"
+        assert r.RES5_DILATION == 1 and r.NUM_GROUPS == 1
     max_stage_idx = max({"res2": 2, "res3": 3, "res4": 4, "res5": 5}[f] for f in r.OUT_FEATURES)
     stages = []
     for idx, stage_idx in enumerate(range(2, max_stage_idx + 1)):
@@ -192,6 +248,9 @@ def build_resnet_backbone(cfg, input_shape):
         else:
             kw.update(block_class=BottleneckBlock, bottleneck_channels=bottleneck_channels,
                       stride_in_1x1=r.STRIDE_IN_1X1, dilation=dilation, num_groups=r.NUM_GROUPS)
+            if deform_on_per_stage[idx]:   # resnet.py:629-636
+                kw.update(block_class=DeformBottleneckBlock, deform_modulated=r.DEFORM_MODULATED,
+                          deform_num_groups=r.DEFORM_NUM_GROUPS)
         stages.append(ResNet.make_stage(**kw))
         in_channels = out_channels
         out_channels *= 2

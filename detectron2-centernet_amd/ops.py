@@ -12,7 +12,8 @@ import math
 import torch
 
 from . import _lib
-from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, F16, F16X3, F32, U8, ConvDesc, HeadDesc
+from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, DCN_MASK_LOGIT, DCN_MASK_NONE, DCN_MASK_PROB, F16, F16X3, F32, U8,
+                   ConvDesc, HeadDesc)
 
 _TORCH_DT = {F16: torch.float16, F32: torch.float32}
 
@@ -653,12 +654,17 @@ HEADS_FUSED = os.environ.get("CTDET_NO_FUSED_HEADS", "0") != "1"
 
 
 def dcnv2(x, offset_mask, p, out=None, act=ACT_NONE, out_dtype=None, mask_is_prob=False, want_cols=False):
-    """Modulated deformable conv: offset_mask is the raw f32 NHWC output of conv_offset_mask (>= 27 ch);
-    with mask_is_prob the 9 mask channels already went through sigmoid.
+    """Deformable conv: offset_mask is the raw f32 NHWC output of conv_offset_mask (>= 27 ch);
+    mask_is_prob is the mask mode: False / DCN_MASK_LOGIT = mask logits (sigmoid in the kernel), True / DCN_MASK_PROB = the 9
+    mask channels already went through sigmoid, DCN_MASK_NONE = DCNv1, offset_mask holds the 18 offsets only (>= 18 ch; no
+    channel beyond them is read, the kernels' mask-free variants run).
     want_cols (f16x3, training): returns (y, cols) where cols f32 [B,H,W,9*Cin] are the sampled columns written by the same
     kernel, or (y, None) when the layer is not served by the LDS-window kernel."""
     _require_cuda(x, offset_mask, out)
     assert dt_of(x) == p.act_dt and offset_mask.dtype == torch.float32
+    mask_is_prob = int(mask_is_prob)
+    if mask_is_prob not in (DCN_MASK_LOGIT, DCN_MASK_PROB, DCN_MASK_NONE):
+        raise ValueError(f"dcnv2: mask mode {mask_is_prob}")
     if p.compute == F16 and p.Cout_pad % 64:
         raise ValueError(f"dcnv2 (f16) works on 64-cout tiles: pack the weights with PackedConv(..., cout_align=64) "
                          f"(Cout={p.Cout}, packed rows {p.Cout_pad})")

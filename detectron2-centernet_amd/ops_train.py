@@ -370,6 +370,7 @@ def dwconvT_bwd(x, dz, weight, f, wk=None, raw=False):
 
 
 def dcn_cols(x, om, mask_is_prob=False):
+    """the sampled columns [B, H, W, 9*Cin] (mask * bilinear(x), tap-major); mask_is_prob: the mask mode (ops.dcnv2)"""
     B, H, W, Cin = x.shape
     col = torch.empty(B, H, W, 9 * Cin, dtype=x.dtype, device=x.device)
     with ops.prof_region("dcn_cols", flops=0.0, nbytes=float(B * H * W * Cin * x.element_size() * 10 + B * H * W * 27 * 4)):
@@ -410,7 +411,8 @@ def dcn_dcol(dyp, weight, chunked, comp=None):
 def dcn_col2im_coord(dcol, x, om, mask_is_prob=False, dom_channels=None, dcol_chunked=False, comp=None):
     """dx (f32, atomically accumulated) and dom = d(offsets, mask logits).  dom_channels=None: f32, the shape of om;
     dom_channels=C (f16 data): an f16 [B, H, W, C] tensor whose channels 27.. are zero -- directly the dY of the offset conv's
-    backward, without a cast or a channel pad in between"""
+    backward, without a cast or a channel pad in between.  mask_is_prob = DCN_MASK_NONE (DCNv1): no d(mask), channels 18.. of
+    dom are zero"""
     B, H, W, Cin = x.shape
     dx = torch.zeros(B, H, W, Cin, dtype=torch.float32, device=x.device)
     if dom_channels is None or x.dtype == torch.float32:
@@ -878,12 +880,33 @@ class DwConvTAddFn(torch.autograd.Function):
         return dx, dw * PARAM_GRAD_MULT, dz, None
 
 
+def _dcn_backward(x, om, weight, dyp, mask_mode, comp, pgm, want_w=True):
+    """DCN backward (3x3/s1/p1) for dY = dyp (channel-padded): (dx, dom, dW [Cout, Cin, 3, 3] or None without want_w).  The
+    columns are materialised once (as the reference does for both directions, deform_conv_cuda.cu:874-917) so dW and
+    d(columns) are plain 1x1 contractions on the MFMA kernels; without want_w neither the columns nor dW are computed.  dom has
+    om's channels: d(offset) in 0..17, d(mask) in 18..26 (zeros without a mask)."""
+    Cout, Cin = weight.shape[:2]
+    chunked = comp != F32 and Cin % 32 == 0
+    dwt = None
+    if want_w:
+        col = dcn_cols(x, om, mask_mode)
+        dw = conv_wgrad(col, dyp, dyp.shape[3], 1, 1, 1, 0, scale=pgm, comp=comp)[:Cout]         # [Cout, 9*Cin]
+        dwt = dw.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)
+    fused = dcn_col2im_fused(dyp, weight, x, om, mask_mode) if (comp == F16X3 and FUSE_DCOL) else None
+    if fused is not None:
+        dx32, dom = fused
+    else:
+        dcol = dcn_dcol(dyp, weight, chunked, comp)                    # [M, 9*Cin]
+        dx32, dom = dcn_col2im_coord(dcol.contiguous(), x, om, mask_mode, dcol_chunked=chunked, comp=comp)
+    return dx32.to(x.dtype), dom, dwt
+
+
 class DCNFn(torch.autograd.Function):
-    """modulated deformable conv (3x3/s1/p1) for training.  Forward: the fused sampling + MFMA kernel of the inference path
-    (no column tensor).  Backward: the columns are materialised once there (as the reference does for both directions,
-    deform_conv_cuda.cu:874-917) so dW and d(columns) are plain 1x1 contractions on the MFMA kernels; nothing of size
-    9*Cin per pixel lives between forward and backward.  om: raw f32 [.., >=27] output of conv_offset_mask (mask logits);
-    mask_is_prob: the reference's functional form passes sigmoid-ed masks instead (deform_conv.py:182-194)."""
+    """deformable conv (3x3/s1/p1) for training.  Forward: the fused sampling + MFMA kernel of the inference path
+    (no column tensor).  Backward: _dcn_backward; nothing of size 9*Cin per pixel lives between forward and backward.
+    om: raw f32 [.., >=27] output of conv_offset_mask (mask logits); mask_is_prob is the mask mode (ops.dcnv2): True /
+    DCN_MASK_PROB -- the reference's functional form passes sigmoid-ed masks instead (deform_conv.py:182-194); DCN_MASK_NONE --
+    DCNv1 (deform_conv.py:16-178), om [.., >=18] holds the offsets only and its gradient carries zeros beyond channel 17."""
 
     @staticmethod
     def forward(ctx, x, om, weight, bias, mask_is_prob=False, param_grad_mult=None):
@@ -892,7 +915,7 @@ class DCNFn(torch.autograd.Function):
         comp = ctx.comp = comp_of(x)
         p = ops.PackedConv(weight.detach(), None, bias, stride=1, pad=1, compute=comp, cout_align=None if f32 else 64)
         y = ops.dcnv2(x, om, p, mask_is_prob=mask_is_prob)
-        ctx.mask_is_prob = mask_is_prob
+        ctx.mask_is_prob = int(mask_is_prob)
         ctx.has_bias = bias is not None
         ctx.save_for_backward(x, om, weight)
         return y
@@ -908,18 +931,43 @@ class DCNFn(torch.autograd.Function):
             dy = dy[..., :Cout].contiguous()
         comp = ctx.comp
         dyp = _pad_c(dy, comp)
-        col = dcn_cols(x, om, ctx.mask_is_prob)
-        chunked = comp != F32 and Cin % 32 == 0
         _, _, _, dbias = bn_train_bwd(dyp, None, None, None, None, None, relu=False, grad_mult=ctx.pgm)
-        dw = conv_wgrad(col, dyp, dyp.shape[3], 1, 1, 1, 0, scale=ctx.pgm, comp=comp)[:Cout]         # [Cout, 9*Cin]
-        dwt = dw.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)
-        fused = dcn_col2im_fused(dyp, weight, x, om, ctx.mask_is_prob) if (comp == F16X3 and FUSE_DCOL) else None
-        if fused is not None:
-            dx32, dom = fused
-        else:
-            dcol = dcn_dcol(dyp, weight, chunked, comp)                    # [M, 9*Cin]
-            dx32, dom = dcn_col2im_coord(dcol.contiguous(), x, om, ctx.mask_is_prob, dcol_chunked=chunked, comp=comp)
-        return dx32.to(x.dtype), dom, dwt, dbias[:Cout] if ctx.has_bias else None, None, None
+        dx, dom, dwt = _dcn_backward(x, om, weight, dyp, ctx.mask_is_prob, comp, ctx.pgm, want_w=ctx.needs_input_grad[2])
+        return dx, dom, dwt, dbias[:Cout] if ctx.has_bias else None, None, None
+
+
+class FrozenDCNFn(torch.autograd.Function):
+    """z = act(dcn(x, om, w) * scale + bias): a deformable conv (3x3/s1/p1, no bias) followed by FrozenBatchNorm2d (+ ReLU) --
+    the conv2 of a deformable ResNet bottleneck whose norm is frozen (resnet.py DeformBottleneckBlock), the affine folded into
+    the DCN kernel's epilogue.  Backward as FrozenConvFn: g = dz * (z > 0), the DCN backward of g * scale (dW, dx, d om).
+    mask_mode: as DCNFn's mask_is_prob (DCN_MASK_LOGIT: modulated, raw 27-channel om; DCN_MASK_NONE: DCNv1)."""
+
+    @staticmethod
+    def forward(ctx, x, om, weight, scale, bias, relu, mask_mode):
+        comp = ctx.comp = comp_of(x)
+        p = ops.PackedConv(weight.detach(), scale, bias, stride=1, pad=1, compute=comp, cout_align=64 if comp == F16 else None)
+        z = ops.dcnv2(x, om, p, act=ACT_RELU if relu else ACT_NONE, mask_is_prob=mask_mode)
+        ctx.cfg = (relu, int(mask_mode))
+        ctx.save_for_backward(x, om, weight, scale, z if relu else None)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, om, weight, scale, z = ctx.saved_tensors
+        relu, mask_mode = ctx.cfg
+        Cout = weight.shape[0]
+        comp = ctx.comp
+        dz = dz.contiguous().to(x.dtype)
+        if dz.shape[3] != Cout:
+            dz, z = dz[..., :Cout].contiguous(), (z[..., :Cout].contiguous() if z is not None else None)
+        dz = _pad_c(dz, comp)
+        g = dz
+        if relu:
+            g, _, _, _ = bn_train_bwd(dz, _pad_c(z, comp), None, None, None, None, relu=True)
+        sc = scale if g.shape[3] == Cout else ops.kpad(scale, (0, g.shape[3] - Cout))
+        dconv = g * sc.to(g.dtype)
+        dx, dom, dwt = _dcn_backward(x, om, weight, dconv, mask_mode, comp, None, want_w=ctx.needs_input_grad[2])
+        return dx, dom, dwt, None, None, None, None
 
 
 class DeformConvFn(torch.autograd.Function):

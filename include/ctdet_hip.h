@@ -93,12 +93,22 @@ int32_t ctdet_conv1x1_cat_fwd(const ctdet_conv_desc* d, const void* const* xs, c
                               const int32_t* strides, int32_t nsrc, const void* w_packed, const float* scale,
                               const float* bias, const void* residual, void* y, void* stream);
 
+/* Mask mode of every DCN entry point (the argument named mask_is_prob: ctdet_dcnv2_fwd, ctdet_dcnv2_fwd_cols, ctdet_dcn_cols,
+ * ctdet_dcn_col2im_coord, ctdet_dcn_col2im_fused).  LOGIT: channels 18..26 of the offset/mask rows are mask logits, the
+ * kernels apply the sigmoid.  PROB: they are probabilities (the reference's functional modulated_deform_conv).  NONE: there
+ * is no mask (DCNv1, the reference's DeformConv): the rows hold the 18 offset channels only (om_stride >= 2*R*S, 18 for
+ * 3x3), channels 18 and above are never read, and the mask is the constant 1 -- a compile-time variant of each kernel, not
+ * loaded, multiplied or passed through a sigmoid.  Its backward computes no d(mask): dom gets d(offset) in channels 0..17
+ * and zeros in 18..dom_stride-1 (dom_stride >= 18). */
+enum ctdet_dcn_mask { CTDET_DCN_MASK_LOGIT = 0, CTDET_DCN_MASK_PROB = 1, CTDET_DCN_MASK_NONE = 2 };
+
 /* Modulated deformable conv v2 forward, batched and fused (sampling -> MFMA, no columns buffer).
  * Replaces _C.modulated_deform_conv_forward (detectron2/layers/csrc/vision.cpp:85-88,
  * deform_conv_cuda.cu:804-927, deform_conv.py:214-234).  offset_mask is the raw f32 output of the
  * 27-channel conv_offset_mask conv, [B*Ho*Wo, om_stride]: ch 2k = dh, 2k+1 = dw of tap k, ch 18+k = mask
- * logit (sigmoid applied here) or, with mask_is_prob != 0, the already-sigmoided mask the reference's
- * functional API passes.  scale/bias fold the conv bias and the following BatchNorm. */
+ * logit (sigmoid applied here) or, with mask_is_prob = CTDET_DCN_MASK_PROB, the already-sigmoided mask the reference's
+ * functional API passes.  With CTDET_DCN_MASK_NONE it is the 18-channel offset tensor of DCNv1 (deform_conv.py:16-178;
+ * deform_conv_cuda.cu deform_conv_forward_cuda).  scale/bias fold the conv bias and the following BatchNorm. */
 int32_t ctdet_dcnv2_fwd(const ctdet_conv_desc* d, const void* x, const float* offset_mask, int32_t om_stride,
                         int32_t mask_is_prob, const void* w_packed, const float* scale, const float* bias, void* y, void* stream);
 
@@ -412,7 +422,9 @@ int32_t ctdet_dwconvT_bwd(const void* x, int32_t x_stride, const void* dz, int32
  * dcol_chunked (f16, Cin % 32 == 0): a pixel's dcol row is [Cin/32][9][32] instead of [9][Cin] -- the order the scatter
  * kernel consumes it in (one contiguous 576-byte run per 32-channel chunk); the producer gets it by permuting the rows of the
  * weight matrix of the d(columns) contraction.
- * mask_is_prob: channels 18..26 of om are sigmoid-ed masks (the reference's functional API) and dom carries d/d(mask). */
+ * mask_is_prob (the mask mode, ctdet_dcn_mask): PROB -- channels 18..26 of om are sigmoid-ed masks (the reference's functional
+ * API) and dom carries d/d(mask); NONE -- om holds the 18 offsets only (om_stride >= 18), dom gets d(offset) in channels 0..17
+ * and zeros in 18..dom_stride-1 (dom_stride >= 18), columns are bilinear(x) unmasked (deformable_im2col of DCNv1). */
 int32_t ctdet_dcn_cols(const void* x, int32_t x_stride, const float* om, int32_t om_stride, void* col, int32_t B,
                        int32_t H, int32_t W, int32_t Cin, int32_t mask_is_prob, int32_t dtype, void* stream);
 int32_t ctdet_dcn_col2im_coord(const void* dcol, const void* x, int32_t x_stride, const float* om, int32_t om_stride,
