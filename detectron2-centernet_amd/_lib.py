@@ -38,6 +38,7 @@ SIGNATURES = {
     "ctdet_dcnv2_offset_fwd": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_preprocess": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp]),
     "ctdet_head_fused_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "ctdet_head_fused_x3_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_dla_base_fwd": (_i32, [_vp] * 14),
     "ctdet_dla_base_x3_fwd": (_i32, [_vp] * 14),
     "ctdet_maxpool2x2": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -288,10 +288,8 @@ int32_t ctdet_preprocess(const void* img, int32_t img_dtype, void* out, int32_t 
                            out_stride, border, (hipStream_t)stream);
 }
 
-int32_t ctdet_head_fused_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* b1, void* stream) {
-  CTDET_CHECK(d && x && w1 && b1, "head_fused: null pointer");
-  HeadArgs a = {};
-  a.x = x; a.w1 = w1; a.b1 = b1;
+// the head descriptor -> HeadArgs (everything but the first conv's operands)
+static int head_args(const ctdet_head_desc* d, HeadArgs& a) {
   a.nheads = d->nheads; a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.in_stride = d->in_stride;
   a.clamp_lo = d->clamp_lo; a.clamp_hi = d->clamp_hi;
   CTDET_CHECK(d->nheads >= 1 && d->nheads <= 4, "head_fused: nheads=%d out of range", d->nheads);
@@ -300,7 +298,24 @@ int32_t ctdet_head_fused_fwd(const ctdet_head_desc* d, const void* x, const void
     a.w2[h] = d->w2[h]; a.b2[h] = (const float*)d->b2[h]; a.y[h] = (float*)d->y[h];
     a.y_stride[h] = d->y_stride[h]; a.cout[h] = d->cout[h]; a.act[h] = d->act[h];
   }
+  return 0;
+}
+
+int32_t ctdet_head_fused_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* b1, void* stream) {
+  CTDET_CHECK(d && x && w1 && b1, "head_fused: null pointer");
+  HeadArgs a = {};
+  a.x = x; a.w1 = w1; a.b1 = b1;
+  if (int rc = head_args(d, a)) return rc;
   return launch_head_fused(a, (hipStream_t)stream);
+}
+
+int32_t ctdet_head_fused_x3_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* s1, const float* b1,
+                                void* stream) {
+  CTDET_CHECK(d && x && w1 && s1 && b1, "head_fused_x3: null pointer");
+  HeadArgs a = {};
+  a.x = x; a.w1 = w1; a.s1 = s1; a.b1 = b1;
+  if (int rc = head_args(d, a)) return rc;
+  return launch_head_fused_x3(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_dla_base_fwd(const ctdet_dla_base_desc* d, const void* images, const void* w_stem, const float* scale_stem,

@@ -74,18 +74,20 @@ struct ConvArgs {
   float* cols_out;
 };
 
-// argument block of the fused CenterNet head kernel (conv_igemm.hip): per head 3x3 conv Cin->256 + bias + ReLU, then
-// 1x1 conv 256->cout + bias (+ sigmoid/clamp), the 256-channel hidden map staying in registers
+// argument block of the fused CenterNet head kernels (conv_igemm.hip): per head 3x3 conv Cin->256 + bias + ReLU, then
+// 1x1 conv 256->cout + bias (+ sigmoid/clamp), the 256-channel hidden map never stored.  f16: head_fused_kernel;
+// f16x3 (launch_head_fused_x3): the second layout of each field
 struct HeadArgs {
-  const void* x;          // f16 [B,H,W,in_stride]
-  const void* w1;         // f16 packed chunk-major [nheads*256][9*Cin]
+  const void* x;          // f16 [B,H,W,in_stride]                  | f32
+  const void* w1;         // f16 packed chunk-major [nheads*256][9*Cin] | korder 3 pair image [>= nheads*256][Cin/32*288] (f32 units)
   const float* b1;        // [nheads*256]
-  const void* w2[4];      // f16 [round_up(cout,16)][256]
-  const float* b2[4];     // f32 [round_up(cout,16)]
+  const void* w2[4];      // f16 [round_up(cout,16)][256]           | f16 [round_up(cout,16)][2][256]: {w_hi, w_lo} of the scaled row
+  const float* b2[4];     // f32 [round_up(cout,16)]                | f32 [2][round_up(cout,16)]: bias, inverse row scale
   float* y[4];            // f32 [B,H,W,y_stride]
   int y_stride[4], cout[4], act[4];
   int nheads, B, H, W, Cin, in_stride;
   float clamp_lo, clamp_hi;
+  const float* s1;        // -                                      | [nheads*256] inverse row scale of w1
 };
 
 // argument block of the fused DLA base kernel (dla_base.hip): normalisation + 7x7 stem + level0 + level1
@@ -147,4 +149,5 @@ int ctdet_device_cu_count();
 // launchers implemented in the .hip files (return 0 or negative errno)
 int launch_conv_f16(const ConvArgs& a, int out_dtype, bool deform, hipStream_t s);
 int launch_head_fused(const HeadArgs& a, hipStream_t s);
+int launch_head_fused_x3(const HeadArgs& a, hipStream_t s);
 int launch_conv_f32(const ConvArgs& a, bool deform, bool split, hipStream_t s);

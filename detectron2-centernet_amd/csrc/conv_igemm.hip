@@ -4,6 +4,7 @@
 // Kernels in this file (launch_conv_f16 picks one):
 //   conv3x3_halo_kernel   3x3/s1/p1, Cin % 32 == 0: input window of an 8x32 tile in LDS once per 32-channel chunk
 //   head_fused_kernel     CenterNet heads: 3x3 + ReLU + 1x1 per head, hidden map in registers
+//   head_fused_x3_kernel  the same in the f16x3 mode (pair-kernel K loop per 64-channel hidden slice)
 //   conv_igemm_uk_kernel  1x1 / strided / Root (multi-source) convs: uniform-K im2col-on-the-fly tiles
 //   conv_igemm_dma_kernel generic fallback (odd channel counts, input dilation for strided input gradients)
 //   conv_win_kernel, conv_smallc_kernel   the 3/16-channel DLA base layers
@@ -823,16 +824,18 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// korder 3: the pair kernel above spends a tenth tap of zeros on every 16-channel chunk (nine taps = four pairs and a half).
-// Here tap 8 of a chunk is paired with tap 8 of the NEXT chunk: two chunks = nine steps instead of ten (-10 % MFMAs and
-// operand reads).  Both windows of a chunk pair sit in the two halo buffers at once (A = even chunk in buffer 0, B = odd
-// chunk in buffer 1); weights: ops.PackedConv._pack_pairs, nine 128-byte {X, Y} steps per chunk pair.  Cin % 32 == 0.
-// ------------------------------------------------------------------------------------------
-// BC = 128 (round 4, CTDET_TUNE_PAIR2_128): one workgroup per CU, a wave then has the whole 512-register file -- 128 accumulators
-// (AGPRs) next to both operand sets -- and every pixel fragment read feeds twice the MFMAs.
-template <int BC, int WP, int WC_, int TW = 32>
-__global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kernel(const ConvArgs a) {
+// LDS bytes of pair2_kloop<BC, ...>: two halo buffers and a 3-stage {X, Y} weight ring
+template <int BC>
+constexpr int pair2_smem_bytes() {
+  return 2 * (10 * 32 * 64 + 4096) + 3 * 2 * (BC < 64 ? 64 : BC) * 64;
+}
+
+// K loop of conv3x3_halo_pair2_kernel for one (pixel tile, cout tile): on return acc[p][c] holds the raw sums (weight rows
+// still scaled) of the wave's TP pixel tiles x TC cout tiles, and no DMA is in flight; other waves may still read the LDS.
+// Reads a.x, a.w (rows n0 on), a.H, a.W, a.in_stride, a.Kpad and a.Cin.  Shared with head_fused_x3_kernel.
+template <int BC, int WP, int WC_, int TW>
+__device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b, int ty0, int tx0, int n0,
+                                            f32x4 (&acc)[256 / WP / 16][BC / WC_ / 16]) {
   // TW = 32: 8 x 32-pixel tiles; TW = 16: 16 x 16 (maps whose width is not a multiple of 32: the 16 x 16 level of DLA-34 at 512^2)
   constexpr int TH = 256 / TW, BP = TH * TW;
   constexpr int EN = TW / 16;           // 16-pixel tiles per tile row
@@ -846,20 +849,13 @@ __global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kerne
   constexpr int HMAIN = 10 * 32 * 64, HSIDE = 4096, HBUF = HMAIN + HSIDE;
   constexpr int WIMG = BCL * 64, WST = 2 * WIMG, NST = 3;
   static_assert(WP * WC_ == 4 && TP == EN * ROWS_W && (TH + 2 + RPR - 1) / RPR == 5, "wave layout");
+  static_assert(2 * HBUF + NST * WST == pair2_smem_bytes<BC>(), "LDS layout");
   static_assert(BC > 64 || 2 * HBUF + NST * WST <= 81920, "two workgroups per CU");
-  __shared__ __attribute__((aligned(16))) char smem[2 * HBUF + NST * WST];
   char* const ring = smem + 2 * HBUF;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave / WC_, wc = wave % WC_;
-  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
-  int m_tile, n_tile;
-  if (!tile_of_block(a.B * tiles_y * tiles_x, a.Cout_pad / BC, m_tile, n_tile)) return;
-  const int tx0 = (m_tile % tiles_x) * TW;
-  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
-  const int b = m_tile / (tiles_x * tiles_y);
-  const int n0 = n_tile * BC;
   const float* zero = (const float*)g_zero_page;
   asm volatile("" : "+v"(zero));
   const float* ximg = (const float*)a.x + (long)b * a.H * a.W * a.in_stride;
@@ -942,7 +938,6 @@ __global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kerne
   const int fr_off = l15 * 64 + ((kg ^ swz(l15)) << 4);
   const char* fragB = ring + (wc * 16 * TC) * 64 + fr_off;
 
-  f32x4 acc[TP][TC];
 #pragma unroll
   for (int p = 0; p < TP; ++p)
 #pragma unroll
@@ -1083,9 +1078,33 @@ __global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kerne
     kstep(kt + 7, pair, std::integral_constant<int, 7>{});
     kstep(kt + 8, pair, std::integral_constant<int, 8>{});
   }
+}
 
-  const int q = lane >> 4;
-  const int cb = n0 + wc * 16 * TC;
+// ------------------------------------------------------------------------------------------
+// korder 3: the pair kernel above spends a tenth tap of zeros on every 16-channel chunk (nine taps = four pairs and a half).
+// Here tap 8 of a chunk is paired with tap 8 of the NEXT chunk: two chunks = nine steps instead of ten (-10 % MFMAs and
+// operand reads).  Both windows of a chunk pair sit in the two halo buffers at once (A = even chunk in buffer 0, B = odd
+// chunk in buffer 1); weights: ops.PackedConv._pack_pairs, nine 128-byte {X, Y} steps per chunk pair.  Cin % 32 == 0.
+// ------------------------------------------------------------------------------------------
+// BC = 128 (round 4, CTDET_TUNE_PAIR2_128): one workgroup per CU, a wave then has the whole 512-register file -- 128 accumulators
+// (AGPRs) next to both operand sets -- and every pixel fragment read feeds twice the MFMAs.
+template <int BC, int WP, int WC_, int TW = 32>
+__global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kernel(const ConvArgs a) {
+  constexpr int TH = 256 / TW, EN = TW / 16, TP = 256 / WP / 16, TC = BC / WC_ / 16, ROWS_W = TH / WP;
+  __shared__ __attribute__((aligned(16))) char smem[pair2_smem_bytes<BC>()];
+  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
+  int m_tile, n_tile;
+  if (!tile_of_block(a.B * tiles_y * tiles_x, a.Cout_pad / BC, m_tile, n_tile)) return;
+  const int tx0 = (m_tile % tiles_x) * TW;
+  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
+  const int b = m_tile / (tiles_x * tiles_y);
+  const int n0 = n_tile * BC;
+  f32x4 acc[TP][TC];
+  pair2_kloop<BC, WP, WC_, TW>(a, smem, b, ty0, tx0, n0, acc);
+
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int row0 = (wave / WC_) * ROWS_W, l15 = lane & 15, q = lane >> 4;
+  const int cb = n0 + (wave % WC_) * 16 * TC;
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int y = ty0 + row0 + p / EN, x = tx0 + 16 * (p % EN) + l15;
@@ -1619,6 +1638,131 @@ int launch_head_fused(const HeadArgs& a, hipStream_t s) {
   const int nbx = a.B * (a.H / 8) * (a.W / 16);
   dim3 grid(8 * ((nbx + 7) / 8) * a.nheads);
   hipLaunchKernelGGL(head_fused_kernel, grid, dim3(256), 0, s, a);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// f16x3 form of the fused CenterNet head.  The unfused f16x3 path writes the f32 hidden maps of all heads (64 x 128^2 x 768
+// x 4 B = 3.2 GB per step) and reads them back in three 1x1 launches.  head_fused_kernel's "all 256 hidden channels of a
+// pixel in one wave" does not carry over: the f16x3 K loop (conv3x3_halo_pair2_kernel) already needs 224 registers for 64
+// accumulators.  Here a workgroup owns one pixel tile of the pair kernel (8x32, or 16x16) and one head, and walks the head's
+// four 64-channel hidden slices one after the other, each with pair2_kloop (korder 3 weights).  After a slice, a lane holds
+// 8 consecutive hidden channels of a pixel per cout-tile pair (cout_of), so h = relu(acc * s1 + b1), split in registers into
+// hi = f16(h) and lo = f16(h - hi), IS the B fragment of the 1x1; against W2 as {X = w_hi, Y = w_lo} (rows scaled into
+// [1024, 2048)) the 1x1 partial over the slice is X.H + Y.H + X.L, three MFMAs per 32 products as everywhere in the mode.
+// The partial sums go through the output map itself: slice 0 stores, slices 1..3 load, add and store, slice 3 then applies
+// the inverse row scale, b2 and the activation.  Every value is written and read back by the same lane, so the sum order
+// is fixed, ((p0 + p1) + p2) + p3, whatever the batch; no atomics, nothing to clear beforehand, and the traffic (80 KB per
+// tile for the 80-class map) stays in L2.
+// ------------------------------------------------------------------------------------------
+template <int TW>
+__global__ void __launch_bounds__(256, 2) head_fused_x3_kernel(const HeadArgs a) {
+  constexpr int HID = 256, BC = 64, WP = 4, NSL = HID / BC;
+  constexpr int TH = 256 / TW, EN = TW / 16, TP = 256 / WP / 16, TC = BC / 16, ROWS_W = TH / WP;
+  static_assert(TP == 4 && TC == 4, "four 16-pixel tiles x four 16-channel tiles per wave");
+  __shared__ __attribute__((aligned(16))) char smem[pair2_smem_bytes<BC>()];
+  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
+  int m_tile, head;
+  if (!tile_of_block(a.B * tiles_y * tiles_x, a.nheads, m_tile, head)) return;
+  const int tx0 = (m_tile % tiles_x) * TW;
+  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
+  const int b = m_tile / (tiles_x * tiles_y);
+  ConvArgs c = {};        // what pair2_kloop reads
+  c.x = a.x; c.w = a.w1; c.H = a.H; c.W = a.W; c.in_stride = a.in_stride; c.Cin = a.Cin; c.Kpad = a.Cin / 32 * 288;
+
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int row0 = wave * ROWS_W, l15 = lane & 15, q = lane >> 4;
+  const f16* w2 = (const f16*)a.w2[head];          // [round_up(cout,16)][2][256]: w_hi row, then w_lo row
+  const float* b2 = a.b2[head];                     // [2][round_up(cout,16)]: bias, then the inverse row scale
+  float* yh = a.y[head];
+  const int ystride = a.y_stride[head], cout = a.cout[head], act = a.act[head];
+  const int rows2 = (cout + 15) & ~15, ntile2 = rows2 >> 4, cw = (cout + 3) & ~3;
+  long mpix[TP];
+#pragma unroll
+  for (int p = 0; p < TP; ++p) mpix[p] = (long)(b * a.H + ty0 + row0 + p / EN) * a.W + tx0 + 16 * (p % EN) + l15;
+
+  for (int sl = 0; sl < NSL; ++sl) {
+    if (sl > 0) __syncthreads();                    // every wave is past the previous slice's LDS reads
+    const int n0 = head * HID + sl * BC;
+    f32x4 acc[TP][TC];
+    pair2_kloop<BC, WP, 1, TW>(c, smem, b, ty0, tx0, n0, acc);
+
+    // hidden = relu(acc * s1 + b1) as {hi, lo} B fragments: frag [p][hb] = channels n0 + hb*32 + q*8 .. +8 of pixel l15
+    f16x8 hf[TP][TC / 2], lf[TP][TC / 2];
+#pragma unroll
+    for (int hb = 0; hb < TC / 2; ++hb) {
+      const int c0 = n0 + hb * 32 + q * 8;
+      const f32x4 sa = *(const f32x4*)(a.s1 + c0), sb = *(const f32x4*)(a.s1 + c0 + 4);
+      const f32x4 ba = *(const f32x4*)(a.b1 + c0), bb = *(const f32x4*)(a.b1 + c0 + 4);
+#pragma unroll
+      for (int p = 0; p < TP; ++p) {
+        const f32x4 v0 = acc[p][2 * hb] * sa + ba, v1 = acc[p][2 * hb + 1] * sb + bb;
+        f16x8 hi, lo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float h = fmaxf(j < 4 ? v0[j] : v1[j - 4], 0.f);
+          hi[j] = (f16)h;
+          lo[j] = (f16)(h - (float)hi[j]);
+        }
+        hf[p][hb] = hi;
+        lf[p][hb] = lo;
+      }
+    }
+    // 1x1 partial over the slice, output tile ot (16 outputs): this lane gets outputs ot*16 + 4q .. +4 of pixel l15
+    for (int ot = 0; ot < ntile2; ++ot) {
+      f32x4 o[TP];
+#pragma unroll
+      for (int p = 0; p < TP; ++p) o[p] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      const f16* wrow = w2 + (long)(ot * 16 + l15) * (2 * HID) + sl * BC + q * 8;
+#pragma unroll
+      for (int hb = 0; hb < TC / 2; ++hb) {
+        const f16x8 X = *(const f16x8*)(wrow + hb * 32), Y = *(const f16x8*)(wrow + HID + hb * 32);
+#pragma unroll
+        for (int p = 0; p < TP; ++p) o[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, hf[p][hb], o[p], 0, 0, 0);
+#pragma unroll
+        for (int p = 0; p < TP; ++p) o[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Y, hf[p][hb], o[p], 0, 0, 0);
+#pragma unroll
+        for (int p = 0; p < TP; ++p) o[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, lf[p][hb], o[p], 0, 0, 0);
+      }
+      const int c0 = ot * 16 + 4 * q;
+      if (c0 < cw) {
+#pragma unroll
+        for (int p = 0; p < TP; ++p) {
+          float* yp = yh + mpix[p] * ystride + c0;
+          f32x4 v = o[p];
+          if (sl > 0) v = *(const f32x4*)yp + v;
+          if (sl == NSL - 1) {
+            v = v * *(const f32x4*)(b2 + rows2 + c0) + *(const f32x4*)(b2 + c0);
+            if (act == CTDET_ACT_RELU) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+            } else if (act == CTDET_ACT_SIGMOID_CLAMP) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(ctdet_sigmoid_exact(v[j]), a.clamp_lo), a.clamp_hi);
+            }
+          }
+          *(f32x4*)yp = v;
+        }
+      }
+    }
+  }
+}
+
+int launch_head_fused_x3(const HeadArgs& a, hipStream_t s) {
+  CTDET_CHECK(a.nheads >= 1 && a.nheads <= 4, "head_fused_x3: 1..4 heads");
+  CTDET_CHECK(a.Cin % 32 == 0 && ((a.H % 8 == 0 && a.W % 32 == 0) || (a.H % 16 == 0 && a.W % 16 == 0)) && a.in_stride % 4 == 0 &&
+                  (((size_t)a.x | (size_t)a.w1 | (size_t)a.s1 | (size_t)a.b1) & 15) == 0,
+              "head_fused_x3: needs Cin %% 32 == 0 and a map divisible by 8x32 or 16x16 (Cin=%d, %dx%d)", a.Cin, a.H, a.W);
+  for (int h = 0; h < a.nheads; ++h)
+    CTDET_CHECK(a.cout[h] >= 1 && a.cout[h] <= 256 && a.y_stride[h] % 4 == 0 && a.y_stride[h] >= ((a.cout[h] + 3) & ~3) &&
+                    ((((size_t)a.y[h]) | (size_t)a.w2[h] | (size_t)a.b2[h]) & 15) == 0,
+                "head_fused_x3: head %d: bad output (cout %d, stride %d)", h, a.cout[h], a.y_stride[h]);
+  const int TW = a.W % 32 == 0 ? 32 : 16;
+  const int nbx = a.B * (a.H / (256 / TW)) * (a.W / TW);
+  dim3 grid(8 * ((nbx + 7) / 8) * a.nheads);
+  if (TW == 32) hipLaunchKernelGGL(head_fused_x3_kernel<32>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(head_fused_x3_kernel<16>, grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }

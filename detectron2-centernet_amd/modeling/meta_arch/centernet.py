@@ -315,8 +315,9 @@ class CenterNet(nn.Module):
         ctx = self._ctx
         names = [h.lower() for h in self.heads]
         out = {}
-        fused = (self.head_conv == ops.PackedHeads.HID and ctx.compute == F16 and ops.HEADS_FUSED
-                 and y.shape[3] % 32 == 0 and y.shape[1] % 8 == 0 and y.shape[2] % 16 == 0 and len(names) <= 4
+        # (CTDET_NO_FUSED_HEADS=1 turns ops.HEADS_FUSED off for both precisions)
+        fused = (self.head_conv == ops.PackedHeads.HID and ctx.compute in (F16, F16X3) and ops.HEADS_FUSED
+                 and ops.heads_fused_ok(y, ctx.compute) and len(names) <= 4
                  and all(getattr(self, n)[2].kernel_size == (1, 1) for n in names))
         if fused:
             # 3x3 + ReLU + 1x1 of every head in one kernel: the 256-channel hidden maps never reach memory
@@ -324,11 +325,12 @@ class CenterNet(nn.Module):
             acts = [ACT_SIGMOID_CLAMP if (apply_sigmoid and n == "hm") else ACT_NONE for n in names]
             cache = self.__dict__.setdefault("_ctdet_packed", {})
             ver = tuple((t.data_ptr(), t._version) for fc in fcs for t in (fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias))
-            hit = cache.get(("heads_fused", tuple(acts)))
+            key = ("heads_fused", ctx.compute, tuple(acts))
+            hit = cache.get(key)
             if hit is None or hit[0] != ver:
                 ph = ops.PackedHeads([fc[0].weight for fc in fcs], [fc[0].bias for fc in fcs],
-                                     [fc[2].weight for fc in fcs], [fc[2].bias for fc in fcs], acts)
-                hit = cache[("heads_fused", tuple(acts))] = (ver, ph)
+                                     [fc[2].weight for fc in fcs], [fc[2].bias for fc in fcs], acts, compute=ctx.compute)
+                hit = cache[key] = (ver, ph)
             outs = ops.heads_fused(y, hit[1], clamp=SIGMOID_CLAMP)
             return dict(zip(names, outs))
         if self.head_conv > 0:

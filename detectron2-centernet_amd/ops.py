@@ -846,23 +846,49 @@ def dla_base_fused(images, mean, std, Hp, Wp, p, out=None, pooled=None):
 
 
 class PackedHeads:
-    """weights of the fused CenterNet heads (ctdet_head_fused_fwd): first convs [256, Cin, 3, 3] + bias per head, final
-    1x1 convs [cout, 256, 1, 1] + bias per head, acts per head."""
+    """weights of the fused CenterNet heads: first convs [256, Cin, 3, 3] + bias per head, final 1x1 convs [cout, 256, 1, 1]
+    + bias per head, acts per head.  compute F16: ctdet_head_fused_fwd (f16 activations).  F16X3: ctdet_head_fused_x3_fwd
+    (f32 activations) -- the first convs as the korder-3 pair image of the 3x3 halo kernels, the final convs split per row
+    into {w_hi, w_lo} after a power-of-two scaling into [1024, 2048) (as every f16x3 operand), b2 = [bias, inverse scale]."""
 
     HID = 256
 
-    def __init__(self, first_weights, first_biases, final_weights, final_biases, acts):
+    def __init__(self, first_weights, first_biases, final_weights, final_biases, acts, compute=F16):
         n = len(first_weights)
         assert 1 <= n <= 4 and all(w.shape[0] == self.HID and tuple(w.shape[2:]) == (3, 3) for w in first_weights)
         assert all(tuple(w.shape[1:]) == (self.HID, 1, 1) for w in final_weights)
+        assert compute in (F16, F16X3)
         dev = first_weights[0].device
-        self.n, self.Cin, self.acts = n, first_weights[0].shape[1], list(acts)
-        self.p1 = PackedConv(torch.cat([w.detach().float() for w in first_weights], 0).contiguous(), None, None, stride=1,
-                             pad=1, compute=F16)
-        assert self.p1.korder == 1 and self.p1.Kpad == 9 * self.Cin
-        self.b1 = torch.cat([b.detach().float() for b in first_biases]).contiguous()
+        self.n, self.Cin, self.acts, self.compute = n, first_weights[0].shape[1], list(acts), compute
+        w1 = torch.cat([w.detach().float() for w in first_weights], 0).contiguous()
+        b1 = torch.cat([b.detach().float() for b in first_biases]).contiguous()
         self.couts = [w.shape[0] for w in final_weights]
         self.w2, self.b2 = [], []
+        if compute == F16X3:
+            assert self.Cin % 32 == 0, "f16x3 fused heads: Cin % 32 == 0"
+            self.p1 = PackedConv(w1, None, b1, stride=1, pad=1, compute=F16X3)
+            self.w1, self.s1 = self.p1._x3_operand(3)
+            self.b1 = self.p1.bias
+            for w, b in zip(final_weights, final_biases):
+                c = w.shape[0]
+                rows = round_up(c, 16)
+                wp = torch.zeros(rows, self.HID, dtype=torch.float32, device=dev)
+                wp[:c] = w.detach().reshape(c, self.HID).float()
+                amax = wp.abs().amax(dim=1)
+                e = torch.floor(torch.log2(amax.clamp_min(1e-30)))
+                pw = torch.where(amax > 0, torch.exp2(10.0 - e), torch.ones_like(amax))
+                ws = wp * pw[:, None]
+                hi = ws.to(torch.float16)
+                lo = (ws - hi.float()).to(torch.float16)
+                self.w2.append(torch.stack([hi, lo], 1).contiguous())          # [rows, 2, 256]
+                bp = torch.zeros(2, rows, dtype=torch.float32, device=dev)
+                bp[0, :c] = b.detach().float()
+                bp[1] = 1.0 / pw
+                self.b2.append(bp)
+            return
+        self.p1 = PackedConv(w1, None, None, stride=1, pad=1, compute=F16)
+        assert self.p1.korder == 1 and self.p1.Kpad == 9 * self.Cin
+        self.b1 = b1
         for w, b in zip(final_weights, final_biases):
             c = w.shape[0]
             wp = torch.zeros(round_up(c, 16), self.HID, dtype=torch.float16, device=dev)
@@ -873,10 +899,26 @@ class PackedHeads:
             self.b2.append(bp)
 
 
+def heads_fused_ok(x, compute):
+    """may the fused head kernel of `compute` take the NHWC map x? (mirrors the checks of launch_head_fused /
+    launch_head_fused_x3; shapes and strides only, never the batch).  Under RANGE_CHECK the f16x3 heads stay unfused: the
+    fused kernel never materialises the hidden map the check reads."""
+    _, H, W, Cin = x.shape
+    if compute == F16:
+        return x.dtype == torch.float16 and Cin % 32 == 0 and H % 8 == 0 and W % 16 == 0
+    if compute == F16X3:
+        return (not RANGE_CHECK and x.dtype == torch.float32 and Cin % 32 == 0
+                and ((H % 8 == 0 and W % 32 == 0) or (H % 16 == 0 and W % 16 == 0))
+                and _nhwc_stride(x) % 4 == 0 and x.data_ptr() % 16 == 0)
+    return False
+
+
 def heads_fused(x, ph, clamp=(0.0, 1.0), outs=None):
-    """x f16 NHWC [B,H,W,Cin] -> list of f32 NHWC maps [B,H,W,round_up(cout,4)], one per head."""
+    """x NHWC [B,H,W,Cin] (f16 for an F16 pack, f32 for an F16X3 one) -> list of f32 NHWC maps [B,H,W,round_up(cout,4)],
+    one per head."""
     _require_cuda(x)
-    assert x.dtype == torch.float16 and x.shape[3] == ph.Cin
+    x3 = ph.compute == F16X3
+    assert x.dtype == (torch.float32 if x3 else torch.float16) and x.shape[3] == ph.Cin
     B, H, W, _ = x.shape
     if outs is None:
         outs = [torch.empty(B, H, W, round_up(c, 4), dtype=torch.float32, device=x.device) for c in ph.couts]
@@ -887,11 +929,14 @@ def heads_fused(x, ph, clamp=(0.0, 1.0), outs=None):
         d.y_stride[h], d.cout[h], d.act[h] = _nhwc_stride(outs[h]), ph.couts[h], ph.acts[h]
     d.clamp_lo, d.clamp_hi = clamp
     M = B * H * W
-    prof = _Prof(None, M, False, F32, name="head_fused_kernel<128x256,f16>",
-                 flops=sum(2.0 * M * PackedHeads.HID * (9 * ph.Cin + c) for c in ph.couts))
+    name = "head_fused_x3_kernel<256x256,f16x3>" if x3 else "head_fused_kernel<128x256,f16>"
+    prof = _Prof(None, M, False, F32, name=name, flops=sum(2.0 * M * PackedHeads.HID * (9 * ph.Cin + c) for c in ph.couts))
     for _ in range(prof.reps()):
-        rc = _lib.lib().ctdet_head_fused_fwd(C.byref(d), _ptr(x), _ptr(ph.p1.w), _ptr(ph.b1), _stream())
-    _lib.check(rc, "ctdet_head_fused_fwd")
+        if x3:
+            rc = _lib.lib().ctdet_head_fused_x3_fwd(C.byref(d), _ptr(x), _ptr(ph.w1), _ptr(ph.s1), _ptr(ph.b1), _stream())
+        else:
+            rc = _lib.lib().ctdet_head_fused_fwd(C.byref(d), _ptr(x), _ptr(ph.p1.w), _ptr(ph.b1), _stream())
+    _lib.check(rc, "ctdet_head_fused_x3_fwd" if x3 else "ctdet_head_fused_fwd")
     prof.done()
     return outs
 

@@ -159,6 +159,14 @@ typedef struct ctdet_head_desc {
   float clamp_lo, clamp_hi;
 } ctdet_head_desc;
 int32_t ctdet_head_fused_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* b1, void* stream);
+/* f16x3 form of ctdet_head_fused_fwd (same descriptor; every contraction as three f16 products, see ctdet_conv_desc).
+ * x: f32 NHWC (Cin % 32 == 0, in_stride % 4 == 0; H % 8 == 0 and W % 32 == 0, or H % 16 == 0 and W % 16 == 0);
+ * w1, s1: the nheads 3x3 weights concatenated along Cout as ctdet_pack_weights_x3 layout 3 (korder 3) and its inverse row
+ * scale [nheads*256]; b1 f32 [nheads*256]; w2[h]: f16 [round_up(cout,16)][2][256], per row {w_hi[256], w_lo[256]} of the row
+ * scaled by a power of two into [1024, 2048) (zero rows beyond cout); b2[h]: f32 [2][round_up(cout,16)], the bias then the
+ * inverse row scale; y[h] as for ctdet_head_fused_fwd.  Every pixel's result is independent of B. */
+int32_t ctdet_head_fused_x3_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* s1, const float* b1,
+                                void* stream);
 
 /* DLA base layers fused for inference: (x/255 - mean)/std (centernet.py:193-200) -> base_layer 7x7 3->16 -> level0 3x3
  * 16->16 -> level1 3x3 stride 2 16->32, each + folded BatchNorm + ReLU (dla.py:204-215, called at dla.py:230-233 for

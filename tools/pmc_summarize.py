@@ -65,6 +65,8 @@ def bench_name(mangled):
     if m:
         o = "f32" if ("float" in mangled or mangled.rstrip().endswith("fEv8ConvArgs")) else "f16"
         return f"conv3x3_halo_kernel<256x{m.group(1)},{o}>"
+    if "head_fused_x3_kernel" in mangled:
+        return "head_fused_x3_kernel<256x256,f16x3>"
     if "head_fused_kernel" in mangled:
         return "head_fused_kernel<128x256,f16>"
     if "dla_base_fused_kernel" in mangled:
