@@ -52,6 +52,9 @@ SIGNATURES = {
     "ctdet_pack_weights_x3": (_i32, [_vp, _vp, _vp] + [_i32] * 10 + [_vp]),
     "ctdet_pack_weights_x3_batch": (_i32, [_vp, _i32, _i32, _vp]),
     "ctdet_dwconvT_add": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ctdet_dwconv3x3_fwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ctdet_dwconv3x3_wgrad_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "ctdet_dwconv3x3_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_decode_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "ctdet_decode": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_postprocess": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),

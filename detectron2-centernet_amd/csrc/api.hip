@@ -28,6 +28,10 @@ int launch_finite_flag(const float*, long, int, int, int*, hipStream_t);
 int launch_pack_weights(const float*, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
 int launch_dwconvT_add(const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, int,
                        hipStream_t);
+int dwconv3x3_check(int, int, int, int, int, int, const int*, int);
+size_t dwconv3x3_wgrad_workspace_bytes(int, int, int, int, int);
+int launch_dwconv3x3(const void*, int, const float*, void*, int, int, int, int, int, int, int, int, hipStream_t);
+int launch_dwconv3x3_wgrad(const void*, int, const void*, int, float*, float*, float, int, int, int, int, int, int, hipStream_t);
 size_t decode_workspace_bytes(int B, int H, int W, int C, int K);
 int decode_status_words(int H, int W, int C, int K, long* ws_words, int* below_word);
 int launch_decode(const DecArgs&, hipStream_t);
@@ -425,6 +429,35 @@ int32_t ctdet_dwconvT_add(const void* x, const float* w, const void* skip, void*
   CTDET_CHECK(x && w && y, "dwconvT: null pointer");
   return launch_dwconvT_add(x, w, skip, y, dtype, B, H, W, C, f, in_stride, skip_stride, out_stride,
                             (hipStream_t)stream);
+}
+
+int32_t ctdet_dwconv3x3_fwd(const void* x, int32_t x_stride, const float* w, void* y, int32_t y_stride, int32_t B, int32_t H,
+                            int32_t W, int32_t C, int32_t stride, int32_t rot180, int32_t dtype, void* stream) {
+  CTDET_CHECK(x && w && y, "dwconv3x3: null pointer");
+  CTDET_CHECK(rot180 == 0 || rot180 == 1, "dwconv3x3: rot180 %d", rot180);
+  const int strides[2] = {x_stride, y_stride};
+  const int rc = dwconv3x3_check(dtype, B, H, W, C, stride, strides, 2);
+  if (rc) return rc;
+  return launch_dwconv3x3(x, x_stride, w, y, y_stride, B, H, W, C, stride, rot180, dtype, (hipStream_t)stream);
+}
+
+size_t ctdet_dwconv3x3_wgrad_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype) {
+  return dwconv3x3_wgrad_workspace_bytes(B, H, W, C, dtype);
+}
+
+int32_t ctdet_dwconv3x3_wgrad(const void* x, int32_t x_stride, const void* dy, int32_t dy_stride, float* workspace, float* dw,
+                              float scale, int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                              int32_t dtype, void* stream) {
+  CTDET_CHECK(x && dy && dw, "dwconv3x3_wgrad: null pointer");
+  CTDET_CHECK(accumulate == 0 || accumulate == 1, "dwconv3x3_wgrad: accumulate %d", accumulate);
+  const int strides[2] = {x_stride, dy_stride};
+  const int rc = dwconv3x3_check(dtype, B, H, W, C, stride, strides, 2);
+  if (rc) return rc;
+  CTDET_CHECK(stride == 1, "dwconv3x3_wgrad: stride %d: only the stride-1 backward is built", stride);
+  CTDET_CHECK(workspace || dwconv3x3_wgrad_workspace_bytes(B, H, W, C, dtype) == 0, "dwconv3x3_wgrad: null workspace");
+  CTDET_CHECK(((uintptr_t)dw & 3) == 0 && ((uintptr_t)workspace & 3) == 0, "dwconv3x3_wgrad: misaligned dw / workspace");
+  return launch_dwconv3x3_wgrad(x, x_stride, dy, dy_stride, workspace, dw, scale, accumulate, B, H, W, C, dtype,
+                                (hipStream_t)stream);
 }
 
 size_t ctdet_decode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t K) {

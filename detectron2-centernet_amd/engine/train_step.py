@@ -13,8 +13,8 @@ import torch
 
 from .. import ops
 from ..layers import hipnn
-from ..ops_train import (BNActFn, ConvFn, ConvTransposeFn, DCNFn, DeformConvFn, DwConvTAddFn, EseFn, FocalLossFn, FrozenConvFn,
-                         FrozenDCNFn, MaxPool3x3s2Fn, MaxPoolFn, RegL1Fn, SyncBNActFn, sync_bn_world)
+from ..ops_train import (BNActFn, ConvFn, ConvTransposeFn, DCNFn, DeformConvFn, DwConv3x3Fn, DwConvTAddFn, EseFn, FocalLossFn,
+                         FrozenConvFn, FrozenDCNFn, MaxPool3x3s2Fn, MaxPoolFn, RegL1Fn, SyncBNActFn, sync_bn_world)
 
 
 _COUNTERS = []
@@ -191,14 +191,22 @@ def resnet_features(backbone, x, ctx, want="res4"):
 
 # ---------------------------------------------------------------------------------------------- VoVNet configs
 def _frozen_seq(seq, x):
-    """a Sequential of (conv, FrozenBatchNorm2d, ReLU) triples (vovnet.py:120-163) as autograd nodes"""
+    """a Sequential of (conv, FrozenBatchNorm2d, ReLU) triples (vovnet.py:120-163) and (depthwise 3x3, 1x1, FrozenBatchNorm2d,
+    ReLU) quadruples (dw_conv3x3, vovnet.py:96-117: DwConv3x3Fn, then FrozenConvFn) as autograd nodes"""
     mods = list(seq)
-    for i in range(0, len(mods), 3):
+    i = 0
+    while i < len(mods):
+        dw = None
+        if isinstance(mods[i], torch.nn.Conv2d) and mods[i].groups > 1:
+            dw, i = mods[i], i + 1
         conv, norm = mods[i], mods[i + 1]
         if any(p.requires_grad for p in norm.parameters()):
             raise NotImplementedError("VoVNet training is built for MODEL.VOVNET.NORM = FrozenBN (the configs' value)")
+        if dw is not None:
+            x = DwConv3x3Fn.apply(x, dw.weight, dw.stride[0])
         scale, bias = hipnn.fold_bn(norm)
         x = FrozenConvFn.apply(x, conv.weight, scale, bias, None, conv.stride[0], conv.padding[0], True)
+        i += 3
     return x
 
 
@@ -227,8 +235,11 @@ def _ese(m, x, identity):
 
 
 def vovnet_osa(m, x):
-    """_OSA_module.forward (vovnet.py:250-273)"""
+    """_OSA_module.forward (vovnet.py:250-273); the depthwise modules reduce x first when its width is not the stage's (the
+    concat still starts with the un-reduced x)"""
     outs = [x]
+    if getattr(m, "isReduced", False):
+        x = _frozen_seq(m.conv_reduction, x)
     for layer in m.layers:
         x = _frozen_seq(layer, x)
         outs.append(x)

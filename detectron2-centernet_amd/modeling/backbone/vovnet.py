@@ -8,7 +8,11 @@ reference state dict loads key-for-key (`stem.stem_1/conv.weight`, `stage3.OSA3_
 FrozenBatchNorm + ReLU is one launch, the stage pooling `MaxPool2d(3, 2, ceil_mode=True)` is `maxpool3x3s2_ceil`, the
 eSE attention (global average pool -> 1x1 fc -> hard sigmoid -> channel scale, + the identity of the later blocks of a
 stage) is `global_avgpool` + a [B,1,1,C] 1x1 conv + `ese_scale`.
-Not built: the depthwise (`dw`) variants (no yaml of the CenterNet project selects them) and the FPN wrapper.
+The depthwise bodies (`V-19-slim-dw-eSE`, `V-19-dw-eSE`; `dw_conv3x3` :96-117) replace the stem's second and third 3x3 and
+every OSA layer by a depthwise 3x3 (`ops.dwconv3x3`) followed by a 1x1 + FrozenBatchNorm + ReLU (one launch), with no norm
+or activation in between; an OSA module whose input width differs from its stage width first reduces x with a 1x1 triple
+(`conv_reduction`), while the concat still starts with the un-reduced x.
+Not built: the FPN wrapper.
 """
 from collections import OrderedDict
 
@@ -23,6 +27,10 @@ from .backbone import Backbone
 from .build import BACKBONE_REGISTRY
 
 _STAGE_SPECS = {
+    "V-19-slim-dw-eSE": dict(stem=[64, 64, 64], stage_conv_ch=[64, 80, 96, 112], stage_out_ch=[112, 256, 384, 512],
+                             layer_per_block=3, block_per_stage=[1, 1, 1, 1], dw=True),
+    "V-19-dw-eSE": dict(stem=[64, 64, 64], stage_conv_ch=[128, 160, 192, 224], stage_out_ch=[256, 512, 768, 1024],
+                        layer_per_block=3, block_per_stage=[1, 1, 1, 1], dw=True),
     "V-19-slim-eSE": dict(stem=[64, 64, 128], stage_conv_ch=[64, 80, 96, 112], stage_out_ch=[112, 256, 384, 512],
                           layer_per_block=3, block_per_stage=[1, 1, 1, 1]),
     "V-19-eSE": dict(stem=[64, 64, 128], stage_conv_ch=[128, 160, 192, 224], stage_out_ch=[256, 512, 768, 1024],
@@ -43,11 +51,31 @@ def _conv_norm_relu(cin, cout, module_name, postfix, norm, k=3, stride=1):
             (f"{module_name}_{postfix}/relu", nn.ReLU(inplace=True))]
 
 
+def _dw_conv_pw(c, module_name, postfix, norm, stride=1):
+    """`dw_conv3x3` of the reference: (name/dw_conv3x3, name/pw_conv1x1, name/pw_norm, name/pw_relu) -- a depthwise 3x3, then a
+    1x1, a norm and a ReLU; no norm or activation between the two convs"""
+    return [(f"{module_name}_{postfix}/dw_conv3x3", nn.Conv2d(c, c, kernel_size=3, stride=stride, padding=1, groups=c, bias=False)),
+            (f"{module_name}_{postfix}/pw_conv1x1", nn.Conv2d(c, c, kernel_size=1, stride=1, padding=0, bias=False)),
+            (f"{module_name}_{postfix}/pw_norm", get_norm(norm, c)),
+            (f"{module_name}_{postfix}/pw_relu", nn.ReLU(inplace=True))]
+
+
+def _is_dw(m):
+    return isinstance(m, nn.Conv2d) and m.groups > 1
+
+
 def _run_seq(seq, x, ctx, cin_pad=None):
-    """a Sequential of (conv, norm, relu) triples on NHWC"""
+    """a Sequential of (conv, norm, relu) triples and (dw conv, pw conv, norm, relu) quadruples on NHWC"""
     mods = list(seq)
-    for i in range(0, len(mods), 3):
-        x = hipnn.conv_module(x, mods[i], mods[i + 1], ACT_RELU, ctx=ctx, cin_pad=cin_pad if i == 0 else None)
+    i = 0
+    while i < len(mods):
+        if _is_dw(mods[i]):
+            x = ops.dwconv3x3(x, mods[i].weight, mods[i].stride[0])
+            x = hipnn.conv_module(x, mods[i + 1], mods[i + 2], ACT_RELU, ctx=ctx)
+            i += 4
+        else:
+            x = hipnn.conv_module(x, mods[i], mods[i + 1], ACT_RELU, ctx=ctx, cin_pad=cin_pad if i == 0 else None)
+            i += 3
     return x
 
 
@@ -66,13 +94,21 @@ class eSEModule(nn.Module):
 
 
 class _OSA_module(nn.Module):
-    def __init__(self, in_ch, stage_ch, concat_ch, layer_per_block, module_name, norm, identity=False):
+    def __init__(self, in_ch, stage_ch, concat_ch, layer_per_block, module_name, norm, identity=False, depthwise=False):
         super().__init__()
         self.identity = identity
+        self.depthwise = depthwise
+        self.isReduced = depthwise and in_ch != stage_ch
+        if self.isReduced:
+            self.conv_reduction = nn.Sequential(OrderedDict(_conv_norm_relu(in_ch, stage_ch, f"{module_name}_reduction", "0",
+                                                                            norm, k=1)))
         self.layers = nn.ModuleList()
         c = in_ch
         for i in range(layer_per_block):
-            self.layers.append(nn.Sequential(OrderedDict(_conv_norm_relu(c, stage_ch, module_name, i, norm))))
+            if depthwise:
+                self.layers.append(nn.Sequential(OrderedDict(_dw_conv_pw(stage_ch, module_name, i, norm))))
+            else:
+                self.layers.append(nn.Sequential(OrderedDict(_conv_norm_relu(c, stage_ch, module_name, i, norm))))
             c = stage_ch
         self.concat = nn.Sequential(OrderedDict(_conv_norm_relu(in_ch + layer_per_block * stage_ch, concat_ch, module_name,
                                                                "concat", norm, k=1)))
@@ -80,6 +116,8 @@ class _OSA_module(nn.Module):
 
     def hip_forward(self, x, ctx):
         outs = [x]
+        if self.isReduced:
+            x = _run_seq(self.conv_reduction, x, ctx)
         for layer in self.layers:
             x = _run_seq(layer, x, ctx)
             outs.append(x)
@@ -94,15 +132,16 @@ class _OSA_module(nn.Module):
 
 
 class _OSA_stage(nn.Sequential):
-    def __init__(self, in_ch, stage_ch, concat_ch, block_per_stage, layer_per_block, stage_num, norm):
+    def __init__(self, in_ch, stage_ch, concat_ch, block_per_stage, layer_per_block, stage_num, norm, depthwise=False):
         super().__init__()
         if stage_num != 2:
             self.add_module("Pooling", nn.MaxPool2d(kernel_size=3, stride=2, ceil_mode=True))
         name = f"OSA{stage_num}_1"
-        self.add_module(name, _OSA_module(in_ch, stage_ch, concat_ch, layer_per_block, name, norm))
+        self.add_module(name, _OSA_module(in_ch, stage_ch, concat_ch, layer_per_block, name, norm, depthwise=depthwise))
         for i in range(block_per_stage - 1):
             name = f"OSA{stage_num}_{i + 2}"
-            self.add_module(name, _OSA_module(concat_ch, stage_ch, concat_ch, layer_per_block, name, norm, identity=True))
+            self.add_module(name, _OSA_module(concat_ch, stage_ch, concat_ch, layer_per_block, name, norm, identity=True,
+                                              depthwise=depthwise))
 
     def hip_forward(self, x, ctx):
         for m in self.children():
@@ -118,13 +157,19 @@ class VoVNet(Backbone):
         norm = cfg.MODEL.VOVNET.NORM
         body = cfg.MODEL.VOVNET.CONV_BODY
         if body not in _STAGE_SPECS:
-            raise NotImplementedError(f"VoVNet body '{body}': the eSE variants without depthwise convs are built")
+            raise NotImplementedError(f"VoVNet body '{body}': the bodies {sorted(_STAGE_SPECS)} are built")
         spec = _STAGE_SPECS[body]
         stem_ch = spec["stem"]
+        dw = spec.get("dw", False)
         self._out_features = list(out_features)
         stem = _conv_norm_relu(input_ch, stem_ch[0], "stem", "1", norm, stride=2)
-        stem += _conv_norm_relu(stem_ch[0], stem_ch[1], "stem", "2", norm, stride=1)
-        stem += _conv_norm_relu(stem_ch[1], stem_ch[2], "stem", "3", norm, stride=2)
+        if dw:      # the depthwise bodies keep one width through the stem (64, 64, 64)
+            assert stem_ch[0] == stem_ch[1] == stem_ch[2]
+            stem += _dw_conv_pw(stem_ch[1], "stem", "2", norm, stride=1)
+            stem += _dw_conv_pw(stem_ch[2], "stem", "3", norm, stride=2)
+        else:
+            stem += _conv_norm_relu(stem_ch[0], stem_ch[1], "stem", "2", norm, stride=1)
+            stem += _conv_norm_relu(stem_ch[1], stem_ch[2], "stem", "3", norm, stride=2)
         self.add_module("stem", nn.Sequential(OrderedDict(stem)))
         stride = 4
         self._out_feature_strides = {"stem": stride, "stage2": stride}
@@ -135,7 +180,7 @@ class VoVNet(Backbone):
             name = "stage%d" % (i + 2)
             self.stage_names.append(name)
             self.add_module(name, _OSA_stage(in_ch_list[i], spec["stage_conv_ch"][i], spec["stage_out_ch"][i],
-                                             spec["block_per_stage"][i], spec["layer_per_block"], i + 2, norm))
+                                             spec["block_per_stage"][i], spec["layer_per_block"], i + 2, norm, depthwise=dw))
             self._out_feature_channels[name] = spec["stage_out_ch"][i]
             if i != 0:
                 stride *= 2

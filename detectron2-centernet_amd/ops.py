@@ -1074,6 +1074,45 @@ def dwconvT_add(x, weight, f, skip=None, out=None, fresh_weight=False, prepared=
     return out
 
 
+def dw3_weight(weight, fresh=False):
+    """Conv2d(C, C, 3, groups=C) weight [C,1,3,3] -> f32 tap-major [9][C] (t = ky*3 + kx), the layout of ctdet_dwconv3x3_fwd;
+    cached on the tensor like _dw_weight.  fresh: re-derived from the live parameter (training: a captured step must not
+    replay with the copy of capture time)."""
+    Cc = weight.shape[0]
+    assert tuple(weight.shape) == (Cc, 1, 3, 3), f"depthwise 3x3 weight expected, got {tuple(weight.shape)}"
+    if fresh:
+        return weight.detach().reshape(Cc, 9).to(torch.float32).t().contiguous()
+    hit = getattr(weight, "_ctdet_dw3", None)
+    if hit is None or hit[0] != (weight.data_ptr(), weight._version):
+        hit = ((weight.data_ptr(), weight._version), weight.detach().reshape(Cc, 9).to(torch.float32).t().contiguous())
+        try:
+            weight._ctdet_dw3 = hit
+        except AttributeError:
+            pass
+    return hit[1]
+
+
+def dwconv3x3(x, weight, stride, out=None, rot180=False, prepared=None):
+    """Conv2d(C, C, 3, stride, padding=1, groups=C, bias=False)(x) on NHWC x (f16 or f32; may be a channel slice), weight
+    [C,1,3,3]; out: an NHWC tensor (or channel slice) of the output shape to write into.  rot180: the taps rotated by 180
+    degrees (with stride 1: the input gradient of the layer for x = dY).  prepared: the weight's [9][C] f32 form if the
+    caller already made it."""
+    _require_cuda(x, weight, out)
+    B, H, W, Cc = x.shape
+    w = prepared if prepared is not None else dw3_weight(weight)
+    assert w.shape == (9, Cc) and w.dtype == torch.float32 and w.is_contiguous()
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty(B, Ho, Wo, Cc, dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (B, Ho, Wo, Cc) and out.dtype == x.dtype
+    with prof_region(f"dwconv3x3<s{stride}>", flops=2.0 * 9 * B * Ho * Wo * Cc,
+                     nbytes=float(x.element_size() * (B * H * W + B * Ho * Wo) * Cc), info=f"{H}x{W} C={Cc}"):
+        rc = _lib.lib().ctdet_dwconv3x3_fwd(_ptr(x), _nhwc_stride(x), _ptr(w), _ptr(out), _nhwc_stride(out), B, H, W, Cc,
+                                            stride, int(rot180), dt_of(x), _stream())
+    _lib.check(rc, "ctdet_dwconv3x3_fwd")
+    return out
+
+
 class DecodeWorkspace:
     """candidate lists of ctdet_decode for a (B, H, W, C, K) problem"""
 

@@ -880,6 +880,64 @@ class DwConvTAddFn(torch.autograd.Function):
         return dx, dw * PARAM_GRAD_MULT, dz, None
 
 
+def dwconv3x3_wgrad(x, dy, stride=1, scale=None, into=None, workspace=None):
+    """weight gradient of a depthwise 3x3 conv (padding 1, stride 1): scale * dW, f32 [C,1,3,3] (OIHW), for y = dwconv(x, W); x,
+    dy NHWC [B,H,W,C], both f16 or both f32.  scale defaults to PARAM_GRAD_MULT.  into: a [C,1,3,3] f32 tensor (the
+    parameter's slot of the flat gradient buffer) the gradient is added to -- nothing is returned.  Deterministic: per-workgroup
+    partial sums in `workspace` (allocated here if not given; never cleared), summed in a fixed order."""
+    ops._require_cuda(x, dy, into, workspace)
+    B, H, W, Cc = x.shape
+    assert tuple(dy.shape) == (B, H, W, Cc) and dy.dtype == x.dtype, "dwconv3x3_wgrad: x and dy must match (stride 1)"
+    nbytes = _lib.lib().ctdet_dwconv3x3_wgrad_workspace_bytes(B, H, W, Cc, dt_of(x))
+    if workspace is None:
+        workspace = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=x.device)
+    assert workspace.dtype == torch.float32 and workspace.numel() * 4 >= nbytes
+    if into is not None:
+        assert into.dtype == torch.float32 and into.is_contiguous() and into.numel() == 9 * Cc
+        dw = into
+    else:
+        dw = torch.empty(Cc, 1, 3, 3, dtype=torch.float32, device=x.device)
+    sc = float(PARAM_GRAD_MULT if scale is None else scale)
+    with ops.prof_region("dwconv3x3_wgrad", flops=2.0 * 9 * B * H * W * Cc, nbytes=float(2 * x.element_size() * B * H * W * Cc),
+                         info=f"{H}x{W} C={Cc}"):
+        rc = _lib.lib().ctdet_dwconv3x3_wgrad(_ptr(x), _nhwc_stride(x), _ptr(dy), _nhwc_stride(dy), _ptr(workspace), _ptr(dw), sc,
+                                              int(into is not None), B, H, W, Cc, stride, dt_of(x), _stream())
+    _lib.check(rc, "ctdet_dwconv3x3_wgrad")
+    return None if into is not None else dw
+
+
+class DwConv3x3Fn(torch.autograd.Function):
+    """Conv2d(C, C, 3, stride, 1, groups=C, bias=False): the dw_conv3x3 of the depthwise VoVNet bodies (vovnet.py:96-117).
+    Forward: ctdet_dwconv3x3_fwd.  Backward (stride 1): dX = the same kernel on dY with the taps rotated by 180 degrees; dW
+    through the deterministic two-kernel weight gradient, straight into the parameter's slot of the flat gradient buffer when
+    it has one -- and not at all when the weight is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        ctx.stride = stride
+        ctx.wparam = weight
+        ctx.wk = ops.dw3_weight(weight, fresh=True)        # [9][C] f32: made once per step, used by both passes
+        ctx.save_for_backward(x)
+        return ops.dwconv3x3(x, weight, stride, prepared=ctx.wk)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        if ctx.stride != 1:
+            raise NotImplementedError("the backward of a stride-2 depthwise 3x3 conv is not built (only the frozen stem has one)")
+        dy = dy.contiguous().to(x.dtype)
+        dx = ops.dwconv3x3(dy, ctx.wparam, 1, rot180=True, prepared=ctx.wk) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            slot = grad_slot(ctx.wparam)
+            if slot is not None:
+                dwconv3x3_wgrad(x, dy, into=slot)
+                grad_done(ctx.wparam)
+            else:
+                dw = dwconv3x3_wgrad(x, dy)
+        return dx, dw, None
+
+
 def _dcn_backward(x, om, weight, dyp, mask_mode, comp, pgm, want_w=True):
     """DCN backward (3x3/s1/p1) for dY = dyp (channel-padded): (dx, dom, dW [Cout, Cin, 3, 3] or None without want_w).  The
     columns are materialised once (as the reference does for both directions, deform_conv_cuda.cu:874-917) so dW and

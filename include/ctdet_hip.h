@@ -422,6 +422,24 @@ int32_t ctdet_maxpool2x2_bwd(const void* x, int32_t x_stride, const void* dz, in
 int32_t ctdet_dwconvT_bwd(const void* x, int32_t x_stride, const void* dz, int32_t dz_stride, const float* w, void* dx,
                           int32_t dx_stride, float* dw, int32_t B, int32_t H, int32_t W, int32_t C, int32_t f,
                           int32_t dtype, void* stream);
+/* Depthwise 3x3 convolution, Conv2d(C, C, 3, stride, 1, groups=C, bias=False) -- the dw_conv3x3 layers of the depthwise VoVNet
+ * bodies (vovnet.py:96-117).  Activations NHWC, f16 (f32 accumulation) or f32 (dtype CTDET_DT_F16 / CTDET_DT_F32; the f16x3
+ * mode passes its f32 tensors as F32: there is no contraction to split); C % 8 (f16) / C % 4 (f32) == 0, C <= 256 vectors;
+ * pixel strides >= C and multiples of the same; every pointer 16-byte aligned.  Weights f32 tap-major [9][C], t = ky*3 + kx.
+ * The nine taps are summed in a fixed order (ky, then kx), so results do not change from run to run.
+ * ctdet_dwconv3x3_fwd: y [B,Ho,Wo,y_stride], Ho = (H-1)/stride + 1, stride 1 or 2.  rot180 = 1 reads the taps rotated by 180
+ *   degrees: with stride 1 that is the input gradient, dX = dwconv(dY, rot180(W)).  (No stride-2 backward is built: only the
+ *   stem, frozen in the configs, has a strided layer.)
+ * ctdet_dwconv3x3_wgrad: dw[c][0][ky][kx] (OIHW [C,1,3,3], f32) = scale * sum over n, y, x of dy[n,y,x,c] * x[n, y-1+ky, x-1+kx, c]
+ *   for a stride-1 layer (x and dy both [B,H,W,*]); accumulate = 1 adds into dw instead of overwriting it.  No atomics:
+ *   workgroups write f32 partial sums to their own slots of `workspace` (ctdet_dwconv3x3_wgrad_workspace_bytes; every slot
+ *   is written on every call, the caller never clears it), a second kernel sums the slots in a fixed order in f64. */
+int32_t ctdet_dwconv3x3_fwd(const void* x, int32_t x_stride, const float* w, void* y, int32_t y_stride, int32_t B, int32_t H,
+                            int32_t W, int32_t C, int32_t stride, int32_t rot180, int32_t dtype, void* stream);
+size_t ctdet_dwconv3x3_wgrad_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype);
+int32_t ctdet_dwconv3x3_wgrad(const void* x, int32_t x_stride, const void* dy, int32_t dy_stride, float* workspace, float* dw,
+                              float scale, int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                              int32_t dtype, void* stream);
 /* DCNv2 3x3/s1/p1 training pieces: columns [M][9*Cin] f16 (= modulated_deformable_im2col, kernel.cu:786-868) and the
  * backward through the sampler (col2im :871-949 + coordinate/mask gradients :952-1066): dcol [M][9*Cin] f16 ->
  * dx f32 dense [B*H*W][Cin] (+= atomics, zeroed by the caller), dom [M][dom_stride] f32 or (f16 data only) f16: offset and
