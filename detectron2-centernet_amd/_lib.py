@@ -29,6 +29,10 @@ SIGNATURES = {
     "ctdet_last_error": (C.c_char_p, []),
     "ctdet_abi_version": (_i32, []),
     "ctdet_conv_cout_tile": (_i32, [_i32]),
+    "ctdet_set_label_mode": (_i32, [_i32]),
+    "ctdet_last_kernel_label": (C.c_char_p, []),
+    "ctdet_conv_pair_supported": (_i32, [C.POINTER(ConvDesc), _vp]),
+    "ctdet_head_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_conv2d_fwd": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_conv1x1_cat_fwd": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_dcnv2_fwd": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,7 @@
 // C-ABI entry points of libctdet_hip.so (see include/ctdet_hip.h for the contract and the reference
 // interfaces each function replaces).  No torch types, no allocation, no synchronisation (except the
 // explicit diagnostic helper ctdet_decode_status).
-#include "common.h"
+#include "conv_common.h"
 #include "../../include/ctdet_hip.h"
 #include <stdarg.h>
 #include <stdio.h>
@@ -15,6 +15,16 @@ void ctdet_set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+thread_local int g_label_mode = 0;
+static thread_local char g_label[128] = "";
+bool ctdet_set_label(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_label, sizeof(g_label), fmt, ap);
+  va_end(ap);
+  return g_label_mode == 2;
 }
 
 // launchers from the kernel files
@@ -62,6 +72,8 @@ int launch_pack_weights_x3(const float*, void*, float*, int, int, int, int, int,
 int launch_pack_weights_x3_batch(const void*, int, int, hipStream_t);
 int launch_split_weights(const float*, void*, long, hipStream_t);
 bool dcn_offset_fused_ok(const ConvArgs& a);
+int conv_pair_korder(const ConvArgs& a);
+bool head_fused_x_ok(const HeadArgs& a, bool x3);
 bool dcn_split_window_ok(const ConvArgs& a);
 size_t chan_reduce_workspace_bytes(int C);
 int launch_bn_train_fwd(const f16*, int, const f16*, int, f16*, int, int, int, const float*, const float*, float, float,
@@ -148,18 +160,16 @@ extern "C" {
 const char* ctdet_last_error(void) { return g_err; }
 int32_t ctdet_set_tuning_flags(uint32_t flags) { g_tuning.store(flags, std::memory_order_relaxed); return 0; }
 uint32_t ctdet_get_tuning_flags(void) { return g_tuning.load(std::memory_order_relaxed); }
-int32_t ctdet_abi_version(void) { return 7; }
+int32_t ctdet_abi_version(void) { return 8; }
+int32_t ctdet_set_label_mode(int32_t mode) {
+  CTDET_CHECK(mode >= 0 && mode <= 2, "set_label_mode: mode %d (0 off, 1 record, 2 dry run)", mode);
+  g_label_mode = mode;
+  return 0;
+}
+const char* ctdet_last_kernel_label(void) { return g_label; }
 static_assert(CTDET_DCN_MASK_LOGIT == DCN_MASK_LOGIT && CTDET_DCN_MASK_PROB == DCN_MASK_PROB && CTDET_DCN_MASK_NONE == DCN_MASK_NONE,
               "mask modes of the ABI and of the kernels");
-int32_t ctdet_conv_cout_tile(int32_t cout) {
-  if (cout <= 16) return 16;
-  if (cout <= 32) return 32;
-  if (cout <= 64) return 64;
-  if (cout <= 128) return 128;          // = pick_bc (conv_common.h)
-  if (cout % 128 == 0) return 128;
-  if (cout % 64 == 0) return 64;
-  return 32;
-}
+int32_t ctdet_conv_cout_tile(int32_t cout) { return pick_bc(cout); }
 
 int32_t ctdet_conv2d_fwd(const ctdet_conv_desc* d, const void* x, const void* w_packed, const float* scale,
                          const float* bias, const void* residual, void* y, void* stream) {
@@ -175,6 +185,13 @@ int32_t ctdet_conv2d_fwd(const ctdet_conv_desc* d, const void* x, const void* w_
     return launch_conv_f32(a, false, d->compute_dtype == CTDET_DT_F16X3, (hipStream_t)stream);
   }
   CTDET_CHECK(false, "conv: bad compute dtype %d", d->compute_dtype);
+}
+
+int32_t ctdet_conv_pair_supported(const ctdet_conv_desc* d, const void* x) {
+  ConvArgs a;
+  if (fill_args(d, a) || d->compute_dtype != CTDET_DT_F16X3) return 0;
+  a.x = x;
+  return conv_pair_korder(a);
 }
 
 int32_t ctdet_conv1x1_cat_fwd(const ctdet_conv_desc* d, const void* const* xs, const int32_t* cins,
@@ -303,6 +320,13 @@ static int head_args(const ctdet_head_desc* d, HeadArgs& a) {
     a.y_stride[h] = d->y_stride[h]; a.cout[h] = d->cout[h]; a.act[h] = d->act[h];
   }
   return 0;
+}
+
+int32_t ctdet_head_fused_supported(int32_t compute_dtype, int32_t H, int32_t W, int32_t Cin, int32_t in_stride, const void* x) {
+  HeadArgs a = {};
+  a.x = x; a.H = H; a.W = W; a.Cin = Cin; a.in_stride = in_stride;
+  if (compute_dtype != CTDET_DT_F16 && compute_dtype != CTDET_DT_F16X3) return 0;
+  return head_fused_x_ok(a, compute_dtype == CTDET_DT_F16X3) ? 1 : 0;
 }
 
 int32_t ctdet_head_fused_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* b1, void* stream) {

@@ -31,6 +31,19 @@ void ctdet_set_error(const char* fmt, ...);
     }                                                                 \
   } while (0)
 
+// kernel labels (thread-local, ctdet_set_label_mode() / ctdet_last_kernel_label()): the launchers of the profiled conv
+// kernels say which instantiation they launch, on the line that launches it.  Mode 0: nothing is recorded (one thread-local
+// load and a branch per launch); 1: the label is formatted, then the kernel is launched; 2 (dry run): the label is formatted
+// and the launcher returns 0 instead of launching -- every check and the whole selection ran, nothing touched the device.
+extern thread_local int g_label_mode;
+bool ctdet_set_label(const char* fmt, ...);   // formats the label; true in the dry-run mode
+#define CTDET_KERNEL(...)                                             \
+  do {                                                                \
+    if (g_label_mode && ctdet_set_label(__VA_ARGS__)) return 0;       \
+  } while (0)
+// how a label names the output type of a kernel instantiation
+template <typename TOut> inline const char* out_name() { return sizeof(TOut) == 2 ? "f16" : "f32"; }
+
 enum { CTDET_F16 = 0, CTDET_F32 = 1, CTDET_U8 = 2, CTDET_F16X3 = 3 };
 enum { CTDET_ACT_NONE = 0, CTDET_ACT_RELU = 1, CTDET_ACT_SIGMOID_CLAMP = 2 };
 // DCN mask modes (ConvArgs::mask_is_prob and the DCN entry points' argument; CTDET_DCN_MASK_* in ctdet_hip.h)

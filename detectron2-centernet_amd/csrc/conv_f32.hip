@@ -1140,10 +1140,14 @@ __global__ void __launch_bounds__(256) conv_f32_win_kernel(const ConvArgs a) {
   }
 }
 
+// how a label names the arithmetic of an f32-tensor kernel: its SP instantiation contracts split f16 operands
+template <bool SP> static const char* sp_name() { return SP ? "f16x3" : "f32"; }
+
 template <int R, int CIN, int TC, int STRIDE, int TH, bool SP>
 static int launch_f32_win(const ConvArgs& a, hipStream_t s) {
   constexpr int TW = STRIDE == 1 ? 64 : 32;
   const int tiles = a.B * (a.Ho / TH) * (a.Wo / TW);
+  CTDET_KERNEL("conv_%s_win_kernel<%dx%d,Cin%d,Cout%d,s%d>", sp_name<SP>(), R, R, CIN, 16 * TC, STRIDE);
   // pad 0 (a pre-padded image: ops.preprocess border): the window never leaves the tensor -> no bounds checks
   if (a.pad == 0)
     hipLaunchKernelGGL((conv_f32_win_kernel<R, CIN, TC, STRIDE, TH, true, SP>), dim3(tiles), dim3(256), 0, s, a);
@@ -1218,6 +1222,7 @@ __global__ void __launch_bounds__(256) conv_direct_f32_kernel(const ConvArgs a) 
 int launch_halo_split(const ConvArgs& a, hipStream_t s);   // conv_igemm.hip
 int launch_halo_pair(const ConvArgs& a, hipStream_t s);    // conv_igemm.hip
 int launch_halo_pair2(const ConvArgs& a, hipStream_t s);   // conv_igemm.hip
+bool halo_pair_x_ok(const ConvArgs& a, int korder);        // conv_igemm.hip
 
 static bool aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
 
@@ -1238,6 +1243,7 @@ template <int BP, int BC, int WP, int WC_, bool SP>
 static int launch_f32_mfma(const ConvArgs& a, int kind, hipStream_t s) {   // kind: 0 generic, 1 uniform-K
   const int nbx = (a.M + BP - 1) / BP, nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL("conv_%s_%s_kernel<%dx%d>", sp_name<SP>(), kind == 1 ? "uk" : "mfma", BP, BC);
   if (kind == 1 && a.nsrc > 1)
     hipLaunchKernelGGL((conv_f32_uk_kernel<BP, BC, WP, WC_, true, SP>), grid, dim3(256), 0, s, a);
   else if (kind == 1)
@@ -1252,6 +1258,7 @@ template <int BP, int BC, int WP, int WC_, bool SP, bool NM>
 static int launch_f32_dcn(const ConvArgs& a, hipStream_t s) {
   const int nbx = (a.M + BP - 1) / BP, nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL("dcn_%s_mfma_kernel<%dx%d>", sp_name<SP>(), BP, BC);
   hipLaunchKernelGGL((dcn_f32_mfma_kernel<BP, BC, WP, WC_, SP, NM>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -1279,6 +1286,7 @@ static int launch_f32_deform(const ConvArgs& a, bool vec, int bc, hipStream_t s)
       // 64 couts per workgroup (128 would spill under two workgroups per CU); wider layers sample the window once per cout tile
       const int nbx = a.B * (a.H / 8) * (a.W / 16);
       dim3 grid(8 * ((nbx + 7) / 8) * (a.Cout_pad / 64));
+      CTDET_KERNEL("dcn_%s_window_kernel<8x16,%d>", sp_name<SP>(), a.Cout_pad);
       if (SP && !(ctdet_tuning_flags() & CTDET_TUNE_DCN_WINDOW_V1)) {
         // the sampling (conflict-laden LDS gathers, blend, split) is this kernel's larger half and is repeated for every cout
         // tile: the 128- and 256-cout layers use 128-cout tiles -- eight 16-pixel waves, one workgroup per CU, the same
@@ -1310,9 +1318,21 @@ static int launch_f32_deform(const ConvArgs& a, bool vec, int bc, hipStream_t s)
   }
   const int CP = (a.Cout + 3) & ~3;
   const long total = (long)a.M * CP;
+  CTDET_KERNEL("conv_direct_%s_kernel<dcn>", sp_name<SP>());
   hipLaunchKernelGGL((conv_direct_f32_kernel<true, SP, NM>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
+}
+
+// a narrow input on dense pixels: what the LDS-window kernels of the DLA base layers read
+static bool f32_narrow_input(const ConvArgs& a) { return (a.Cin == 4 || a.Cin == 8 || a.Cin == 16) && a.in_stride == a.Cin; }
+
+// Which pair-packed weight image would an f16x3 3x3 / s1 / p1 conv of these activations take (ctdet_conv_pair_supported)?
+// 0: none (tap-major weights: the window, halo-split or uniform-K kernels), else the korder to pack.  A narrow input on rows of
+// 64 pixels stays with the window branch below (level0 of DLA-34: 492 vs 825 us per 64 images), whose weights are tap-major.
+int conv_pair_korder(const ConvArgs& a) {
+  if ((ctdet_tuning_flags() & CTDET_TUNE_NO_HALO) || (f32_narrow_input(a) && a.W % 64 == 0)) return 0;
+  return halo_pair_x_ok(a, 3) ? 3 : halo_pair_x_ok(a, 2) ? 2 : 0;
 }
 
 template <bool SP>
@@ -1324,8 +1344,8 @@ static int launch_conv_f32_t(const ConvArgs& a, bool deform, hipStream_t s) {
   CTDET_CHECK(a.korder == 0 || (SP && (a.korder == 2 || a.korder == 3)), "conv(f32 / f16x3): korder %d", a.korder);
   const int bc = pick_bc(a.Cout);
   const bool vec = f32_vector_ok(a, bc) && (!deform || (a.Cin % 16 == 0 && a.nsrc <= 1));
-  if (vec && !deform && (a.Cin == 4 || a.Cin == 8 || a.Cin == 16) && a.in_dil == 1 && a.nsrc <= 1 && a.R == a.S && a.dil == 1 &&
-      a.in_stride == a.Cin && a.Cout_pad == bc && !a.res && a.Kpad == ((a.K + 15) & ~15)) {
+  if (vec && !deform && f32_narrow_input(a) && a.in_dil == 1 && a.nsrc <= 1 && a.R == a.S && a.dil == 1 &&
+      a.Cout_pad == bc && !a.res && a.Kpad == ((a.K + 15) & ~15)) {
     // the three narrow DLA base layers on tile-divisible maps
     if (a.R == 7 && a.Cin == 8 && bc == 16 && a.stride == 1 && a.Ho % 8 == 0 && a.Wo % 64 == 0 && (a.pad == 0 || a.pad == 3))
       return launch_f32_win<7, 8, 1, 1, 8, SP>(a, s);
@@ -1362,6 +1382,7 @@ static int launch_conv_f32_t(const ConvArgs& a, bool deform, hipStream_t s) {
   const int CP = (a.Cout + 3) & ~3;
   const long total = (long)a.M * CP;
   dim3 grid((unsigned)((total + 255) / 256));
+  CTDET_KERNEL("conv_direct_%s_kernel<conv>", sp_name<SP>());
   hipLaunchKernelGGL((conv_direct_f32_kernel<false, SP>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;

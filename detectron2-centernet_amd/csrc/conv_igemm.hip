@@ -534,6 +534,7 @@ template <int BC, int WP, int WC_, typename TOut, bool SP = false>
 static int launch_halo(const ConvArgs& a, hipStream_t s) {
   const int nbx = a.B * (a.H / 8) * (a.W / 32), nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL("conv3x3_halo_kernel<256x%d,%s>", BC, SP ? "f16x3" : out_name<TOut>());
   hipLaunchKernelGGL((conv3x3_halo_kernel<BC, WP, WC_, TOut, SP>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -1354,6 +1355,7 @@ template <int BC, int WP, int WC_>
 static int launch_halo_pair_t(const ConvArgs& a, hipStream_t s) {
   const int nbx = a.B * (a.H / 8) * (a.W / 32), nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL("conv3x3_halo_pair_kernel<256x%d,f16x3>", BC);
   hipLaunchKernelGGL((conv3x3_halo_pair_kernel<BC, WP, WC_>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -1363,6 +1365,7 @@ template <int BC, int WP, int WC_, int TW = 32>
 static int launch_halo_pair2_t(const ConvArgs& a, hipStream_t s) {
   const int nbx = a.B * (a.H / (256 / TW)) * (a.W / TW), nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL(TW == 32 ? "conv3x3_halo_pair2_kernel<256x%d,f16x3>" : "conv3x3_halo_pair2_kernel<16x16x%d,f16x3>", BC);
   hipLaunchKernelGGL((conv3x3_halo_pair2_kernel<BC, WP, WC_, TW>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -1372,17 +1375,24 @@ template <int BC, int WP, int WC_, typename TOut, int TW = 32>
 static int launch_halo_tap2(const ConvArgs& a, hipStream_t s) {
   const int nbx = a.B * (a.H / (256 / TW)) * (a.W / TW), nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL(TW == 32 ? "conv3x3_halo_tap2_kernel<256x%d,%s>" : "conv3x3_halo_tap2_kernel<16x16x%d,%s>", BC, out_name<TOut>());
   hipLaunchKernelGGL((conv3x3_halo_tap2_kernel<BC, WP, WC_, TOut, TW>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
+// the activation side of what the halo pair kernels need (f16x3, 3x3 / s1 / p1): korder 2 = Cin % 16 == 0 on 8x32-pixel tiles,
+// korder 3 = Cin % 32 == 0 on 8x32- or 16x16-pixel tiles.  The launchers below check it; conv_pair_korder (conv_f32.hip)
+// answers ctdet_conv_pair_supported with it before a pair image is packed.
+bool halo_pair_x_ok(const ConvArgs& a, int korder) {
+  const bool tiles = (a.H % 8 == 0 && a.W % 32 == 0) || (korder == 3 && a.H % 16 == 0 && a.W % 16 == 0);
+  return a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.in_dil == 1 && a.nsrc <= 1 &&
+         a.Cin % (korder == 3 ? 32 : 16) == 0 && tiles && a.Ho == a.H && a.Wo == a.W && a.in_stride % 4 == 0 && (((size_t)a.x) & 15) == 0;
+}
+
 // korder 3 (cross-chunk pair-packed split weights, Kpad = Cin / 32 * 288)
 int launch_halo_pair2(const ConvArgs& a, hipStream_t s) {
-  CTDET_CHECK(a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.in_dil == 1 && a.nsrc <= 1 &&
-                  a.Cin % 32 == 0 && a.Kpad == a.Cin / 32 * 288 && ((a.H % 8 == 0 && a.W % 32 == 0) || (a.H % 16 == 0 && a.W % 16 == 0)) &&
-                  a.Ho == a.H && a.Wo == a.W &&
-                  a.in_stride % 4 == 0 && (((size_t)a.x | (size_t)a.w) & 15) == 0,
+  CTDET_CHECK(halo_pair_x_ok(a, 3) && a.Kpad == a.Cin / 32 * 288 && (((size_t)a.w) & 15) == 0,
               "conv(f16x3, cross-chunk pair weights): needs 3x3/s1/p1, Cin %% 32 == 0 and a map divisible by 8x32 or 16x16 (Cin=%d, %dx%d, Kpad=%d)",
               a.Cin, a.H, a.W, a.Kpad);
   // a grid of 64-cout tiles that leaves CUs without a workgroup (the 512-channel level at batch 16: 16 pixel tiles x 8) runs on
@@ -1400,9 +1410,7 @@ int launch_halo_pair2(const ConvArgs& a, hipStream_t s) {
 
 // korder 2 (pair-packed split weights, Kpad = Cin / 16 * 160): only this kernel reads them
 int launch_halo_pair(const ConvArgs& a, hipStream_t s) {
-  CTDET_CHECK(a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.in_dil == 1 && a.nsrc <= 1 &&
-                  a.Cin % 16 == 0 && a.Kpad == a.Cin / 16 * 160 && a.H % 8 == 0 && a.W % 32 == 0 && a.Ho == a.H && a.Wo == a.W &&
-                  a.in_stride % 4 == 0 && (((size_t)a.x | (size_t)a.w) & 15) == 0,
+  CTDET_CHECK(halo_pair_x_ok(a, 2) && a.Kpad == a.Cin / 16 * 160 && (((size_t)a.w) & 15) == 0,
               "conv(f16x3, pair weights): needs 3x3/s1/p1, Cin %% 16 == 0 and a map divisible by 8x32 (Cin=%d, %dx%d, Kpad=%d)",
               a.Cin, a.H, a.W, a.Kpad);
   // 64-cout tiles also for the 128-cout layers: with 128 accumulators the two operand register sets do not fit
@@ -1627,9 +1635,16 @@ __global__ void __launch_bounds__(256, 2) head_fused_kernel(const HeadArgs a) {
   }
 }
 
+// the input map a fused head kernel takes (ctdet_head_fused_supported): f16 on 8x16-pixel tiles, f16x3 on 8x32 or 16x16
+bool head_fused_x_ok(const HeadArgs& a, bool x3) {
+  if (!x3) return a.Cin % 32 == 0 && a.H % 8 == 0 && a.W % 16 == 0 && a.in_stride % 8 == 0;
+  return a.Cin % 32 == 0 && ((a.H % 8 == 0 && a.W % 32 == 0) || (a.H % 16 == 0 && a.W % 16 == 0)) && a.in_stride % 4 == 0 &&
+         (((size_t)a.x) & 15) == 0;
+}
+
 int launch_head_fused(const HeadArgs& a, hipStream_t s) {
   CTDET_CHECK(a.nheads >= 1 && a.nheads <= 4, "head_fused: 1..4 heads");
-  CTDET_CHECK(a.Cin % 32 == 0 && a.H % 8 == 0 && a.W % 16 == 0 && a.in_stride % 8 == 0,
+  CTDET_CHECK(head_fused_x_ok(a, false),
               "head_fused: needs Cin %% 32 == 0 and a map divisible by 8x16 (Cin=%d, %dx%d)", a.Cin, a.H, a.W);
   for (int h = 0; h < a.nheads; ++h)
     CTDET_CHECK(a.cout[h] >= 1 && a.cout[h] <= 256 && a.y_stride[h] % 4 == 0 && a.y_stride[h] >= ((a.cout[h] + 3) & ~3) &&
@@ -1637,6 +1652,7 @@ int launch_head_fused(const HeadArgs& a, hipStream_t s) {
                 "head_fused: head %d: bad output (cout %d, stride %d)", h, a.cout[h], a.y_stride[h]);
   const int nbx = a.B * (a.H / 8) * (a.W / 16);
   dim3 grid(8 * ((nbx + 7) / 8) * a.nheads);
+  CTDET_KERNEL("head_fused_kernel<128x256,f16>");
   hipLaunchKernelGGL(head_fused_kernel, grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -1751,8 +1767,7 @@ __global__ void __launch_bounds__(256, 2) head_fused_x3_kernel(const HeadArgs a)
 
 int launch_head_fused_x3(const HeadArgs& a, hipStream_t s) {
   CTDET_CHECK(a.nheads >= 1 && a.nheads <= 4, "head_fused_x3: 1..4 heads");
-  CTDET_CHECK(a.Cin % 32 == 0 && ((a.H % 8 == 0 && a.W % 32 == 0) || (a.H % 16 == 0 && a.W % 16 == 0)) && a.in_stride % 4 == 0 &&
-                  (((size_t)a.x | (size_t)a.w1 | (size_t)a.s1 | (size_t)a.b1) & 15) == 0,
+  CTDET_CHECK(head_fused_x_ok(a, true) && (((size_t)a.w1 | (size_t)a.s1 | (size_t)a.b1) & 15) == 0,
               "head_fused_x3: needs Cin %% 32 == 0 and a map divisible by 8x32 or 16x16 (Cin=%d, %dx%d)", a.Cin, a.H, a.W);
   for (int h = 0; h < a.nheads; ++h)
     CTDET_CHECK(a.cout[h] >= 1 && a.cout[h] <= 256 && a.y_stride[h] % 4 == 0 && a.y_stride[h] >= ((a.cout[h] + 3) & ~3) &&
@@ -1761,6 +1776,7 @@ int launch_head_fused_x3(const HeadArgs& a, hipStream_t s) {
   const int TW = a.W % 32 == 0 ? 32 : 16;
   const int nbx = a.B * (a.H / (256 / TW)) * (a.W / TW);
   dim3 grid(8 * ((nbx + 7) / 8) * a.nheads);
+  CTDET_KERNEL(TW == 32 ? "head_fused_x3_kernel<256x256,f16x3>" : "head_fused_x3_kernel<16x16x256,f16x3>");
   if (TW == 32) hipLaunchKernelGGL(head_fused_x3_kernel<32>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(head_fused_x3_kernel<16>, grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
@@ -2602,15 +2618,19 @@ static int launch_dcn_window_t(const ConvArgs& a, hipStream_t s) {
   const bool mixed = (ctdet_tuning_flags() & CTDET_TUNE_DCN_MIXED) != 0;
   if (BC == 64 && !mixed && a.H % 8 == 0 && a.W % 16 == 0 && a.H <= 65534 && a.W <= 65534 &&
       !(ctdet_tuning_flags() & CTDET_TUNE_DCN_WINDOW_V1)) {
+    CTDET_KERNEL(a.w_off ? "dcn_window_rows_kernel<128x64,offset conv fused>" : "dcn_window_kernel<128x64,%s>", out_name<TOut>());
     if constexpr (NM) hipLaunchKernelGGL((dcn_window_rows_kernel<TOut, false, false, true>), grid, dim3(256), 0, s, a);
     else if (a.w_off) hipLaunchKernelGGL((dcn_window_rows_kernel<TOut, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((dcn_window_rows_kernel<TOut, false>), grid, dim3(256), 0, s, a);
     CTDET_LAUNCH_CHECK();
     return 0;
   }
-  if (mixed && a.H % 8 == 0 && a.W % 16 == 0 && a.H <= 4094 && a.W <= 4094)
+  // (<128x64,f16> alone names the row-step kernel above: the per-tap kernel on 64-cout tiles says so)
+  const bool tiled = a.H % 8 == 0 && a.W % 16 == 0, mixed_ok = mixed && tiled && a.H <= 4094 && a.W <= 4094;
+  CTDET_KERNEL("dcn_window_kernel<128x%d,%s%s>", BC, out_name<TOut>(), mixed_ok ? ",mixed" : !tiled ? ",edge" : BC == 64 ? ",per-tap" : "");
+  if (mixed_ok)
     hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), false, TOut, true, NM>), grid, dim3(256), 0, s, a);
-  else if (a.H % 8 == 0 && a.W % 16 == 0)
+  else if (tiled)
     hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), false, TOut, false, NM>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((dcn_window_kernel<BC, (BC > 64 ? 4 : 8), true, TOut, false, NM>), grid, dim3(256), 0, s, a);
@@ -2731,6 +2751,7 @@ static int launch_smallc(const ConvArgs& a, hipStream_t s) {
   const int nseg = a.B * a.Ho * (a.Wo / 64);
   int blocks = (nseg + 3) / 4;
   if (blocks > 256 * 8) blocks = 256 * 8;
+  CTDET_KERNEL("conv_smallc_kernel<Cout%d,K%d,%s>", 16 * TC, 32 * NK, out_name<TOut>());
   if (a.pad == 0)  // pre-padded input (zero frame in memory): every tap of every pixel is in bounds
     hipLaunchKernelGGL((conv_smallc_kernel<TC, NK, true, TOut>), dim3(blocks), dim3(256), 0, s, a);
   else
@@ -2829,6 +2850,7 @@ template <int R, int CIN, int TC, int STRIDE, typename TOut>
 static int launch_win(const ConvArgs& a, hipStream_t s) {
   constexpr int TH = STRIDE == 1 ? 16 : 8, TW = STRIDE == 1 ? 64 : 32;
   const int blocks = a.B * (a.Ho / TH) * (a.Wo / TW);
+  CTDET_KERNEL("conv_win_kernel<%dx%d,Cin%d,Cout%d,s%d,%s>", R, R, CIN, 16 * TC, STRIDE, out_name<TOut>());
   if (a.pad == 0)  // pre-padded input (zero frame in memory): every tap of every pixel is in bounds
     hipLaunchKernelGGL((conv_win_kernel<R, CIN, TC, STRIDE, true, TOut>), dim3(blocks), dim3(256), 0, s, a);
   else
@@ -2846,6 +2868,7 @@ template <int BP, int BC, int WP, int WC_, typename TOut>
 static int launch_dma(const ConvArgs& a, hipStream_t s) {
   const int nbx = (a.M + BP - 1) / BP, nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL("conv_igemm_dma_kernel<%dx%d,%s>", BP, BC, out_name<TOut>());
   hipLaunchKernelGGL((conv_igemm_dma_kernel<BP, BC, WP, WC_, TOut>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -2855,6 +2878,7 @@ template <int BP, int BC, int WP, int WC_, typename TOut>
 static int launch_uk(const ConvArgs& a, hipStream_t s) {
   const int nbx = (a.M + BP - 1) / BP, nby = a.Cout_pad / BC;
   dim3 grid(8 * ((nbx + 7) / 8) * nby);
+  CTDET_KERNEL("conv_igemm_uk_kernel<%dx%d,%s,%s>", BP, BC, a.nsrc > 1 ? "cat" : "conv", out_name<TOut>());
   if (a.nsrc > 1)
     hipLaunchKernelGGL((conv_igemm_uk_kernel<BP, BC, WP, WC_, true, TOut>), grid, dim3(256), 0, s, a);
   else

@@ -362,12 +362,12 @@ int launch_dla_base(const BaseArgs& a, hipStream_t s) {
   const int ncu = ctdet_device_cu_count();
   const long want = 2L * ncu;
   const unsigned blocks = (unsigned)(tiles < want ? tiles : want);
+  CTDET_CHECK(a.img_dtype == CTDET_U8 || a.img_dtype == CTDET_F32, "dla_base: image dtype %d (want u8 or f32)", a.img_dtype);
+  CTDET_KERNEL("dla_base_fused_kernel<u8|f32 -> 32ch,f16>");
   if (a.img_dtype == CTDET_U8)
     hipLaunchKernelGGL((dla_base_fused_kernel<uint8_t>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
-  else if (a.img_dtype == CTDET_F32)
-    hipLaunchKernelGGL((dla_base_fused_kernel<float>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
   else
-    CTDET_CHECK(false, "dla_base: image dtype %d (want u8 or f32)", a.img_dtype);
+    hipLaunchKernelGGL((dla_base_fused_kernel<float>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -708,12 +708,12 @@ int launch_dla_base_x3(const BaseArgs& a, hipStream_t s) {
   const long tiles = (long)a.B * (a.Hp / (2 * T1H)) * (a.Wp / (2 * T1W));
   if (tiles == 0) return 0;
   CTDET_CHECK(tiles < (1L << 31), "dla_base(f16x3): too many tiles");
+  CTDET_CHECK(a.img_dtype == CTDET_U8 || a.img_dtype == CTDET_F32, "dla_base(f16x3): image dtype %d (want u8 or f32)", a.img_dtype);
+  CTDET_KERNEL("dla_base_x3_kernel<u8|f32 -> 32ch,f16x3>");
   if (a.img_dtype == CTDET_U8)
     hipLaunchKernelGGL((dla_base_x3_kernel<uint8_t>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
-  else if (a.img_dtype == CTDET_F32)
-    hipLaunchKernelGGL((dla_base_x3_kernel<float>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
   else
-    CTDET_CHECK(false, "dla_base(f16x3): image dtype %d (want u8 or f32)", a.img_dtype);
+    hipLaunchKernelGGL((dla_base_x3_kernel<float>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
   CTDET_LAUNCH_CHECK();
   return 0;
 }

@@ -18,91 +18,18 @@ from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, DCN_MASK_LOGIT, DCN_MA
 _TORCH_DT = {F16: torch.float16, F32: torch.float32}
 
 # bench.py's roofline leg: when PROFILE_ON, every conv-shaped launch is bracketed by HIP events on the
-# launch stream and (kernel instantiation, algorithmic FLOPs, start, end, algorithmic bytes, info, repetitions) is
+# launch stream and (kernel label as the launcher gave it, algorithmic FLOPs, start, end, algorithmic bytes, info, repetitions) is
 # appended to PROFILE.
 PROFILE_ON = False
 PROFILE = []
 PROFILE_REP = 5   # each profiled launch is issued this many times back to back between one event pair
 
 
-def _kernel_name(p, M, deform, out_dt, x_shape=None, nsrc=1):
-    """mirrors the kernel selection of launch_conv_f16_t() in csrc/conv_igemm.hip"""
-    bc = _lib.lib().ctdet_conv_cout_tile(p.Cout_eff)
-    if p.compute == F16X3:       # the f32 kernels' split instantiations: same selection, tagged
-        H, W = (x_shape[1], x_shape[2]) if x_shape is not None else (0, 0)
-        if (not deform and p.R == 3 and p.S == 3 and p.stride == 1 and p.pad == 1 and p.dil == 1 and p.in_dil == 1 and nsrc <= 1
-                and p.Cin % 16 == 0 and p.Kpad == p.K and H and ((H % 8 == 0 and W % 32 == 0) or (H % 16 == 0 and W % 16 == 0 and (p.Cin // 16) % 2 == 0))
-                and bc in (32, 64, 128)
-                and not (_lib.lib().ctdet_get_tuning_flags() & _lib.TUNE_NO_HALO)):
-            bc = min(bc, 64)
-            return f"conv3x3_halo_pair{'2' if (p.Cin // 16) % 2 == 0 else ''}_kernel<256x{max(bc, 32)},f16x3>"
-        p32 = _F32View(p)
-        return _kernel_name(p32, M, deform, out_dt, x_shape, nsrc).replace("_f32_", "_f16x3_", 1)
-    if p.compute != F16:
-        big = ((M + 255) // 256) * (p.Cout_pad // bc) >= 512
-        if deform:
-            H, W = (x_shape[1], x_shape[2]) if x_shape is not None else (0, 0)
-            win = (p.R == 3 and p.stride == 1 and p.pad == 1 and p.dil == 1 and H and H % 8 == 0 and W % 16 == 0 and
-                   p.Kpad == p.K and p.Cout_pad % 64 == 0 and p.Cin % 16 == 0 and
-                   not (_lib.lib().ctdet_get_tuning_flags() & _lib.TUNE_NO_F32_DCN_WINDOW))
-            return f"dcn_f32_window_kernel<8x16,{p.Cout_pad}>" if win else f"dcn_f32_mfma_kernel<128x{bc}>"
-        bp = 256 if (big or bc == 16) else 128
-        H, W = (x_shape[1], x_shape[2]) if x_shape is not None else (0, 0)
-        if p.Cin in (4, 8, 16) and p.R == p.S and p.dil == 1 and nsrc <= 1 and H:
-            Ho, Wo = p.out_hw(H, W)
-            if ((p.R, p.Cin, bc, p.stride) in ((7, 4, 16, 1), (7, 8, 16, 1), (3, 16, 16, 1)) and Ho % 8 == 0 and Wo % 64 == 0) or \
-                    ((p.R, p.Cin, bc, p.stride) == (3, 16, 32, 2) and Ho % 4 == 0 and Wo % 32 == 0):
-                return f"conv_f32_win_kernel<{p.R}x{p.R},Cin{p.Cin},Cout{bc},s{p.stride}>"
-        uk = p.R * p.S <= 32 and p.in_dil == 1 and p.Kpad == p.K and p.Cin % 16 == 0
-        return f"conv_f32_{'uk' if uk else 'mfma'}_kernel<{bp}x{bc}>"
-    o = "f16" if out_dt == F16 else "f32"
-    if deform:
-        return f"dcn_window_kernel<128x{bc},{o}>"
-    H, W = (x_shape[1], x_shape[2]) if x_shape is not None else (0, 0)
-    big = ((M + 255) // 256) * (p.Cout_pad // bc) >= 512
-    bp = 256 if (big or bc == 16) else 128
-    if (p.R == 3 and p.S == 3 and p.stride == 1 and p.pad == 1 and p.dil == 1 and p.in_dil == 1 and nsrc <= 1 and p.korder == 1
-            and H and H % 16 == 0 and W % 16 == 0 and W % 32 != 0 and bc in (32, 64, 128) and p.Cin % 64 == 0 and p.Kpad == 9 * p.Cin
-            and not (_lib.lib().ctdet_get_tuning_flags() & (_lib.TUNE_NO_HALO_TAP2 | _lib.TUNE_NO_HALO))):
-        return f"conv3x3_halo_tap2_kernel<16x16x{min(bc, 64)},{o}>"
-    if (p.R == 3 and p.S == 3 and p.stride == 1 and p.pad == 1 and p.dil == 1 and p.in_dil == 1 and nsrc <= 1
-            and p.korder == 1 and H % 8 == 0 and W % 32 == 0 and bc in (32, 64, 128)):
-        if p.Cin % 64 == 0 and p.Kpad == 9 * p.Cin and not (_lib.lib().ctdet_get_tuning_flags() & _lib.TUNE_NO_HALO_TAP2):
-            return f"conv3x3_halo_tap2_kernel<256x{min(bc, 64)},{o}>"
-        small = not (_lib.lib().ctdet_get_tuning_flags() & _lib.TUNE_NO_SMALL_GRID_TILES)
-        if bc == 128 and small and (M // 256) * (p.Cout_pad // 128) < 512:
-            bc = 64                      # fewer workgroups than the chip holds: 64-cout tiles
-        return f"conv3x3_halo_kernel<256x{bc},{o}>"
-    Wo = (W + 2 * p.pad - p.dil * (p.S - 1) - 1) // p.stride + 1 if W else 0
-    if p.Cin in (8, 16) and p.korder == 0 and nsrc <= 1 and Wo and Wo % 64 == 0 and p.Cout_pad <= 32:
-        Ho = (H + 2 * p.pad - p.dil * (p.R - 1) - 1) // p.stride + 1
-        win = ((p.R, p.Cin, bc, p.stride) in ((7, 8, 16, 1), (3, 16, 16, 1)) and Ho % 16 == 0) or \
-              ((p.R, p.Cin, bc, p.stride) == (3, 16, 32, 2) and Ho % 8 == 0 and Wo % 32 == 0)
-        if win and p.R == p.S and p.dil == 1 and not (_lib.lib().ctdet_get_tuning_flags() & _lib.TUNE_NO_WIN):
-            return f"conv_win_kernel<{p.R}x{p.R},Cin{p.Cin},Cout{bc},s{p.stride},{o}>"
-        return f"conv_smallc_kernel<Cout{bc},K{p.Kpad},{o}>"
-    if p.Kpad == p.K and p.R * p.S <= 32 and p.in_dil == 1 and (p.korder == 1 or p.R * p.S == 1) and p.Cin % 32 == 0:
-        if (bc == 128 and not big and ((M + 127) // 128) * (p.Cout_pad // 128) < 512
-                and not (_lib.lib().ctdet_get_tuning_flags() & _lib.TUNE_NO_SMALL_GRID_TILES)):
-            bc = 64
-        return f"conv_igemm_uk_kernel<{bp}x{bc},{'cat' if nsrc > 1 else 'conv'},{o}>"
-    return f"conv_igemm_dma_kernel<{bp}x{bc},{o}>"
-
-
-class _F32View:
-    """a PackedConv seen as its F32 twin (kernel selection of the F16X3 mode mirrors the F32 one)"""
-
-    def __init__(self, p):
-        self.__dict__.update(p.__dict__)
-        self.compute = F32
-        self.out_hw = p.out_hw
-
-
 class _Prof:
-    def __init__(self, p, M, deform, out_dt, x_shape=None, nsrc=1, name=None, flops=None):
+    def __init__(self, p, M, deform, out_dt, nsrc=1, flops=None):
         self.on = PROFILE_ON
         if self.on:
-            self.name = name if name is not None else _kernel_name(p, M, deform, out_dt, x_shape, nsrc)
+            _lib.lib().ctdet_set_label_mode(1)      # the launcher names the kernel instantiation it launches: done() reads it
             self.flops = flops if flops is not None else 2.0 * M * p.Cout * p.R * p.S * p.Cin_real
             osz = 2 if out_dt == F16 else 4
             if p is not None:   # algorithmic bytes: input once + output once (+ offsets/masks for the deformable conv)
@@ -122,7 +49,9 @@ class _Prof:
         if self.on:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
-            PROFILE.append((self.name, self.flops, self.e0, e1, self.bytes, self.info, PROFILE_REP))
+            name = _lib.lib().ctdet_last_kernel_label().decode()
+            _lib.lib().ctdet_set_label_mode(0)
+            PROFILE.append((name, self.flops, self.e0, e1, self.bytes, self.info, PROFILE_REP))
 
 
 class prof_region:
@@ -524,21 +453,28 @@ class PackedConv:
         return img.reshape(rows, nch * 320).view(torch.float32), 2
 
     def pair_ok(self, x):
-        """may the halo pair kernel take this input? (mirrors launch_halo_pair in csrc/conv_igemm.hip)"""
-        # (a 16-channel input on a 64-divisible map is the LDS-window kernel's: level0 of DLA-34, 492 vs 825 us per 64 images)
-        tile32 = x.shape[1] % 8 == 0 and x.shape[2] % 32 == 0
-        tile16 = x.shape[1] % 16 == 0 and x.shape[2] % 16 == 0 and (self.Cin // 16) % 2 == 0     # (16x16 tiles: korder 3 only)
-        ok = ((self.w_pair is not None or self._wp_scaled is not None or self._pair_capable) and self.in_dil == 1 and (tile32 or tile16)
-              and _nhwc_stride(x) % 4 == 0 and x.data_ptr() % 16 == 0
-              and (self.Cin > 16 or x.shape[2] % 64 != 0 or _nhwc_stride(x) != self.Cin)
-              and not (_lib.lib().ctdet_get_tuning_flags() & _lib.TUNE_NO_HALO))
-        if ok and self.w_pair is None:
+        """may the halo pair kernel take this input?"""
+        B, H, W, _ = x.shape
+        out = torch.empty(0, *self.out_hw(H, W), self.Cout_eff, dtype=torch.float32, device=x.device)
+        d = self.desc(x[:0], out, ACT_NONE, None)
+        d.B = B
+        return self._pair_image(d, x)
+
+    def _pair_image(self, d, x):
+        """does the conv d of x run on a pair-packed image?  Which convs do is the library's rule (ctdet_conv_pair_supported:
+        tiles, alignment, the layers left to the LDS-window kernel, tuning flags); here only whether such an image exists or can
+        be made, and its packing on first use."""
+        if self.w_pair is None and self._wp_scaled is None and not self._pair_capable:
+            return False
+        korder = _lib.lib().ctdet_conv_pair_supported(C.byref(d), _ptr(x))
+        if korder and self.w_pair is None:
+            self.pair_korder = korder
             if self._x3_src is not None:
-                self.pair_korder = 3 if (self.Cin // 16) % 2 == 0 else 2
-                self.w_pair, self.scale_pair = self._x3_operand(self.pair_korder)
+                self.w_pair, self.scale_pair = self._x3_operand(korder)
             else:
-                (self.w_pair, self.pair_korder), self._wp_scaled = self._pack_pairs(self._wp_scaled), None
-        return ok
+                (self.w_pair, packed), self._wp_scaled = self._pack_pairs(self._wp_scaled), None
+                assert packed == korder, (packed, korder)
+        return bool(korder)
 
     def _pad_vec(self, v, fill, dev):
         if v is None:
@@ -576,7 +512,7 @@ class PackedConv:
         d.clamp_lo, d.clamp_hi = clamp
         d.korder = self.korder
         d.in_dil = self.in_dil
-        if allow_pair and self.pair_ok(x):
+        if allow_pair and self._pair_image(d, x):
             d.korder, d.Kpad, d.Cout_pad = self.pair_korder, self.w_pair.shape[1], self.w_pair.shape[0]
         return d
 
@@ -599,7 +535,7 @@ def conv2d(x, p, out=None, act=ACT_NONE, residual=None, out_dtype=None, clamp=(0
     if residual is not None:
         assert residual.dtype == out.dtype and residual.shape[:3] == out.shape[:3]
     d = p.desc(x, out, act, residual, clamp, allow_pair=True)
-    prof = _Prof(p, d.B * d.Ho * d.Wo, False, d.out_dtype, x.shape)
+    prof = _Prof(p, d.B * d.Ho * d.Wo, False, d.out_dtype)
     if d.korder >= 2:
         w, sc = p.w_pair, (p.scale_pair if p.scale_pair is not None else p.scale)
     else:
@@ -640,7 +576,7 @@ def conv1x1_cat(xs, p, out=None, act=ACT_NONE, residual=None, out_dtype=None):
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in xs])
     cin_a = (C.c_int32 * n)(*cins)
     str_a = (C.c_int32 * n)(*[_nhwc_stride(t) for t in xs])
-    prof = _Prof(p, B * H * W, False, d.out_dtype, xs[0].shape, len(xs))
+    prof = _Prof(p, B * H * W, False, d.out_dtype, len(xs))
     for _ in range(prof.reps()):
         rc = _lib.lib().ctdet_conv1x1_cat_fwd(C.byref(d), ptrs, cin_a, str_a, n, _ptr(p.w), _ptr(p.scale),
                                               _ptr(p.bias), _ptr(residual), _ptr(out), _stream())
@@ -681,7 +617,7 @@ def dcnv2(x, offset_mask, p, out=None, act=ACT_NONE, out_dtype=None, mask_is_pro
     cols = None
     if want_cols and p.compute == F16X3 and _lib.lib().ctdet_dcnv2_cols_supported(C.byref(d), _ptr(x), _ptr(out)):
         cols = torch.empty(x.shape[0], x.shape[1], x.shape[2], 9 * p.Cin, dtype=torch.float32, device=x.device)
-    prof = _Prof(p, d.B * d.Ho * d.Wo, True, d.out_dtype, x.shape)     # (after the allocation: a 600 MB hipMalloc is not kernel time)
+    prof = _Prof(p, d.B * d.Ho * d.Wo, True, d.out_dtype)     # (after the allocation: a 600 MB hipMalloc is not kernel time)
     if prof.on and cols is not None:
         prof.bytes += cols.numel() * 4
     for _ in range(prof.reps()):
@@ -723,8 +659,7 @@ def dcnv2_offset(x, p_off, p, out=None, act=ACT_NONE, out_dtype=None, om_out=Non
     out = _alloc_out(x, p, out, out_dtype)
     assert p_off.bias.shape[0] >= 28                     # Cout_eff floats: the kernel reads channels 0..27
     d = p.desc(x, out, act, None)
-    prof = _Prof(p, d.B * d.Ho * d.Wo, True, d.out_dtype, x.shape, name=f"dcn_window_rows_kernel<128x64,offset conv fused>",
-                 flops=2.0 * d.B * d.Ho * d.Wo * p.K * (p.Cout + 27))
+    prof = _Prof(p, d.B * d.Ho * d.Wo, True, d.out_dtype, flops=2.0 * d.B * d.Ho * d.Wo * p.K * (p.Cout + 27))
     if prof.on:
         prof.bytes -= d.B * d.Ho * d.Wo * 27 * 4      # no offset tensor is read
     for _ in range(prof.reps()):
@@ -826,7 +761,6 @@ def dla_base_fused(images, mean, std, Hp, Wp, p, out=None, pooled=None):
         d.pool_stride = _nhwc_stride(pooled)
     px = B * Hp * Wp
     prof = _Prof(None, px, False, F16X3 if x3 else F16,
-                 name="dla_base_x3_kernel<u8|f32 -> 32ch,f16x3>" if x3 else "dla_base_fused_kernel<u8|f32 -> 32ch,f16>",
                  flops=2.0 * (px * 16 * 147 + px * 16 * 144 + (px // 4) * 32 * 144))
     for _ in range(prof.reps()):
         if x3:
@@ -900,17 +834,13 @@ class PackedHeads:
 
 
 def heads_fused_ok(x, compute):
-    """may the fused head kernel of `compute` take the NHWC map x? (mirrors the checks of launch_head_fused /
-    launch_head_fused_x3; shapes and strides only, never the batch).  Under RANGE_CHECK the f16x3 heads stay unfused: the
-    fused kernel never materialises the hidden map the check reads."""
+    """may the fused head kernel of `compute` take the NHWC map x? (shapes, strides and alignment: the library's rule,
+    ctdet_head_fused_supported; never the batch).  Under RANGE_CHECK the f16x3 heads stay unfused: the fused kernel never
+    materialises the hidden map the check reads."""
+    if compute not in (F16, F16X3) or x.dtype != _TORCH_DT[F16 if compute == F16 else F32] or (compute == F16X3 and RANGE_CHECK):
+        return False
     _, H, W, Cin = x.shape
-    if compute == F16:
-        return x.dtype == torch.float16 and Cin % 32 == 0 and H % 8 == 0 and W % 16 == 0
-    if compute == F16X3:
-        return (not RANGE_CHECK and x.dtype == torch.float32 and Cin % 32 == 0
-                and ((H % 8 == 0 and W % 32 == 0) or (H % 16 == 0 and W % 16 == 0))
-                and _nhwc_stride(x) % 4 == 0 and x.data_ptr() % 16 == 0)
-    return False
+    return bool(_lib.lib().ctdet_head_fused_supported(compute, H, W, Cin, _nhwc_stride(x), _ptr(x)))
 
 
 def heads_fused(x, ph, clamp=(0.0, 1.0), outs=None):
@@ -929,8 +859,7 @@ def heads_fused(x, ph, clamp=(0.0, 1.0), outs=None):
         d.y_stride[h], d.cout[h], d.act[h] = _nhwc_stride(outs[h]), ph.couts[h], ph.acts[h]
     d.clamp_lo, d.clamp_hi = clamp
     M = B * H * W
-    name = "head_fused_x3_kernel<256x256,f16x3>" if x3 else "head_fused_kernel<128x256,f16>"
-    prof = _Prof(None, M, False, F32, name=name, flops=sum(2.0 * M * PackedHeads.HID * (9 * ph.Cin + c) for c in ph.couts))
+    prof = _Prof(None, M, False, F32, flops=sum(2.0 * M * PackedHeads.HID * (9 * ph.Cin + c) for c in ph.couts))
     for _ in range(prof.reps()):
         if x3:
             rc = _lib.lib().ctdet_head_fused_x3_fwd(C.byref(d), _ptr(x), _ptr(ph.w1), _ptr(ph.s1), _ptr(ph.b1), _stream())

@@ -75,6 +75,18 @@ int32_t ctdet_set_tuning_flags(uint32_t flags);
 uint32_t ctdet_get_tuning_flags(void);
 int32_t ctdet_conv_cout_tile(int32_t cout);
 
+/* Kernel labels.  Which kernel instantiation serves a call is decided in the launchers alone; a launcher of the conv-shaped
+ * entry points (ctdet_conv2d_fwd, ctdet_conv1x1_cat_fwd, ctdet_dcnv2_*_fwd, ctdet_head_fused*_fwd, ctdet_dla_base*_fwd) can say
+ * which one it launches.  Mode, per calling thread: 0 (default) nothing is recorded; 1 the label of every such launch is kept
+ * for ctdet_last_kernel_label(); 2 dry run: the call checks its arguments and selects exactly as a real call, keeps the label
+ * and returns 0 without launching (no pointer is dereferenced, no device is needed). */
+int32_t     ctdet_set_label_mode(int32_t mode);
+const char* ctdet_last_kernel_label(void);   /* label of this thread's last labelled launch, "" if none */
+
+/* Would ctdet_conv2d_fwd run this F16X3 3x3 / s1 / p1 conv (descriptor with korder 0) of the activations x on a pair-packed
+ * weight image?  0: no (pass the tap-major image), 2 / 3: yes, pack and pass the image of that korder. */
+int32_t ctdet_conv_pair_supported(const ctdet_conv_desc* d, const void* x);
+
 /* f32 packed conv weights (the compute_dtype F32 image, n floats, n % 4 == 0, 16-byte aligned) -> the F16X3 image of the
  * same size (see ctdet_conv_desc).  Replaces nothing in the reference (its convs are cuDNN fp32); it is the pack step of
  * the F16X3 compute mode. */
@@ -167,6 +179,9 @@ int32_t ctdet_head_fused_fwd(const ctdet_head_desc* d, const void* x, const void
  * inverse row scale; y[h] as for ctdet_head_fused_fwd.  Every pixel's result is independent of B. */
 int32_t ctdet_head_fused_x3_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* s1, const float* b1,
                                 void* stream);
+/* May the fused head kernel of compute_dtype (CTDET_DT_F16 / CTDET_DT_F16X3) take the NHWC map x [*,H,W,in_stride]?  The
+ * input-side conditions of the two entry points above (tile divisibility, Cin, pixel stride, alignment of x); 1 or 0. */
+int32_t ctdet_head_fused_supported(int32_t compute_dtype, int32_t H, int32_t W, int32_t Cin, int32_t in_stride, const void* x);
 
 /* DLA base layers fused for inference: (x/255 - mean)/std (centernet.py:193-200) -> base_layer 7x7 3->16 -> level0 3x3
  * 16->16 -> level1 3x3 stride 2 16->32, each + folded BatchNorm + ReLU (dla.py:204-215, called at dla.py:230-233 for

@@ -132,7 +132,7 @@ def test_mask_mode_in_header_and_bindings():
     assert (_lib.DCN_MASK_LOGIT, _lib.DCN_MASK_PROB, _lib.DCN_MASK_NONE) == (0, 1, 2)
     assert ops.DCN_MASK_NONE == modes["NONE"]
     l = _lib.lib()
-    assert l.ctdet_abi_version() == 7
+    assert l.ctdet_abi_version() == 8
     for name in ("ctdet_dcnv2_fwd", "ctdet_dcnv2_fwd_cols", "ctdet_dcn_cols", "ctdet_dcn_col2im_coord", "ctdet_dcn_col2im_fused"):
         assert name in _lib.SIGNATURES
     # an unknown mode is refused before any device work

@@ -90,7 +90,7 @@ def test_dwconv_abi_declared_and_validates_arguments():
     for name in ("ctdet_dwconv3x3_fwd", "ctdet_dwconv3x3_wgrad", "ctdet_dwconv3x3_wgrad_workspace_bytes"):
         assert name + "(" in header and name in _lib.SIGNATURES
     l = _lib.lib()
-    assert l.ctdet_abi_version() == 7
+    assert l.ctdet_abi_version() == 8
     F16, F32 = _lib.F16, _lib.F32
     p = 1 << 20           # any 16-byte-aligned address: every call below must be refused before it is used
     # stride outside {1, 2}

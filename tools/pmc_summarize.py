@@ -50,12 +50,14 @@ def bench_name(mangled):
     m = re.search(r"dcn_window_rows_kernel(?:I|<)(DF16_|f|_Float16|float)", mangled)
     if m:
         return f"dcn_window_kernel<128x64,{'f16' if m.group(1) in ('DF16_', '_Float16') else 'f32'}>"
-    m = re.search(r"dcn_window_kernelILi(\d+)ELi\d+ELb[01]E(DF16_|f)", mangled)
+    m = re.search(r"dcn_window_kernelILi(\d+)ELi\d+ELb([01])E(DF16_|f)Lb([01])E", mangled)     # <BC, waves, EDGE, TOut, MIXED, ..>
     if m:
-        return f"dcn_window_kernel<128x{m.group(1)},{'f16' if m.group(2) == 'DF16_' else 'f32'}>"
-    m = re.search(r"conv3x3_halo_pair2_kernel(?:ILi|<)(\d+)", mangled)
+        form = ",mixed" if m.group(4) == "1" else ",edge" if m.group(2) == "1" else ",per-tap" if m.group(1) == "64" else ""
+        return f"dcn_window_kernel<128x{m.group(1)},{'f16' if m.group(3) == 'DF16_' else 'f32'}{form}>"
+    m = re.search(r"conv3x3_halo_pair2_kernel(?:ILi(\d+)ELi\d+ELi\d+ELi(\d+)E|<(\d+), \d+, \d+, (\d+)>)", mangled)   # <BC, .., .., TW>
     if m:
-        return f"conv3x3_halo_pair2_kernel<256x{m.group(1)},f16x3>"
+        bc, tw = (m.group(1), m.group(2)) if m.group(1) else (m.group(3), m.group(4))
+        return f"conv3x3_halo_pair2_kernel<{'256' if tw == '32' else '16x16'}x{bc},f16x3>"
     m = re.search(r"conv3x3_halo_pair_kernel(?:ILi|<)(\d+)", mangled)
     if m:
         return f"conv3x3_halo_pair_kernel<256x{m.group(1)},f16x3>"
@@ -64,9 +66,12 @@ def bench_name(mangled):
     m = re.search(r"conv3x3_halo_kernel(?:ILi|<)(\d+)", mangled)
     if m:
         o = "f32" if ("float" in mangled or mangled.rstrip().endswith("fEv8ConvArgs")) else "f16"
+        if re.search(r"fLb1EE|float, true>", mangled):      # the SP instantiation: split f16 operands of f32 tensors
+            o = "f16x3"
         return f"conv3x3_halo_kernel<256x{m.group(1)},{o}>"
-    if "head_fused_x3_kernel" in mangled:
-        return "head_fused_x3_kernel<256x256,f16x3>"
+    m = re.search(r"head_fused_x3_kernel(?:ILi|<)(\d+)", mangled)      # <TW>
+    if m:
+        return f"head_fused_x3_kernel<{'256' if m.group(1) == '32' else '16x16'}x256,f16x3>"
     if "head_fused_kernel" in mangled:
         return "head_fused_kernel<128x256,f16>"
     if "dla_base_fused_kernel" in mangled:
