@@ -72,6 +72,8 @@ int launch_pack_weights_x3(const float*, void*, float*, int, int, int, int, int,
 int launch_pack_weights_x3_batch(const void*, int, int, hipStream_t);
 int launch_split_weights(const float*, void*, long, hipStream_t);
 bool dcn_offset_fused_ok(const ConvArgs& a);
+bool dcn_offset_fused_x3_ok(const ConvArgs& a);
+int launch_dcn_offset_x3(const ConvArgs& a, hipStream_t s);
 int conv_pair_korder(const ConvArgs& a);
 bool head_fused_x_ok(const HeadArgs& a, bool x3);
 bool dcn_split_window_ok(const ConvArgs& a);
@@ -280,8 +282,10 @@ int32_t ctdet_dcnv2_fwd_cols(const ctdet_conv_desc* d, const void* x, const floa
 
 int32_t ctdet_dcnv2_offset_supported(const ctdet_conv_desc* d) {
   ConvArgs a;
-  if (fill_args(d, a) || d->compute_dtype != CTDET_DT_F16) return 0;
+  if (fill_args(d, a)) return 0;
   a.y = nullptr;
+  if (d->compute_dtype == CTDET_DT_F16X3) return (d->out_dtype == CTDET_DT_F32 && dcn_offset_fused_x3_ok(a)) ? 1 : 0;
+  if (d->compute_dtype != CTDET_DT_F16) return 0;
   return dcn_offset_fused_ok(a) ? 1 : 0;
 }
 
@@ -293,7 +297,13 @@ int32_t ctdet_dcnv2_offset_fwd(const ctdet_conv_desc* d, const void* x, const vo
   if (rc) return rc;
   if (a.M == 0) return 0;
   CTDET_CHECK(x && w_off_packed && b_off && w_packed && y, "dcnv2_offset: null pointer");
-  CTDET_CHECK(d->compute_dtype == CTDET_DT_F16, "dcnv2_offset: f16 only");
+  if (d->compute_dtype == CTDET_DT_F16X3) {
+    CTDET_CHECK(d->out_dtype == CTDET_DT_F32 && !om_out, "dcnv2_offset(f16x3): f32 output, no om_out (inference form)");
+    a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;
+    a.w_off = w_off_packed; a.b_off = b_off; a.mask_is_prob = DCN_MASK_LOGIT;
+    return launch_dcn_offset_x3(a, (hipStream_t)stream);
+  }
+  CTDET_CHECK(d->compute_dtype == CTDET_DT_F16, "dcnv2_offset: f16 or f16x3");
   CTDET_CHECK(!om_out || (om_out_stride >= 28 && om_out_stride % 4 == 0 && ((size_t)om_out & 15) == 0),
               "dcnv2_offset: om_out needs a 16-byte aligned row of >= 28 floats (stride %d)", om_out_stride);
   a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;

@@ -750,8 +750,18 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
 // ------------------------------------------------------------------------------------------
 // COLS: the instantiation that also writes the sampled columns (training forward); a template parameter so that the inference
 // kernel's register allocation does not carry the pointer and index (with it the <2,64> form spilled 14 registers: +8 % time)
-template <int TP, int BC, bool COLS = false, bool NM = false>
+// FUS: the offset / mask conv (3x3/s1/p1, Cin -> 27 on a 32-cout tile; a.w_off = its korder-3 pair image, a.b_off = 32 biases then
+// 32 inverse row scales) is computed here first, for the tile's 128 pixels, and its output stays in LDS.  Per 16-channel chunk
+// the tile's 10x18-pixel halo comes in by LDS-DMA and is split ONCE, in place, into {hi[4], lo[4]} pieces (two such halos -- a
+// chunk pair -- in the sampling window's space) and the tap-pair steps of conv3x3_halo_pair2_kernel run from them: H / L
+// fragments by ds_read_b64 at shifted pixel addresses, no VALU; the X / Y weight images of the nine steps sit in the space of
+// the geometry tables and the ring (not live yet), re-filled by DMA a segment ahead.  Every sum is the same sequence of MFMA accumulations as in that kernel's 32-cout
+// form (its tiles alternate between the product orders X.H, Y.H, X.L and X.L, X.H, Y.H by image row), so the offsets are
+// bit-identical to the two-launch path wherever that path runs the pair kernel.  A far sample keeps its integer corner in the
+// window-code word (12 bits each: the map is at most 4094 pixels a side), since there is no offset tensor to re-read.
+template <int TP, int BC, bool COLS = false, bool NM = false, bool FUS = false>
 __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_split_window_kernel(const ConvArgs a) {
+  static_assert(!FUS || (TP == 2 && BC == 64 && !COLS && !NM), "the fused offset conv: inference form of the 64-cout DCNv2 tile");
   constexpr int TH = 8, TW = 16, BP = 128, MG = 4;
   constexpr int NT = 512 / TP;                                  // TP = 2: 4 waves of 32 pixels, TP = 1: 8 waves of 16
   static_assert(BC * 4 <= NT, "at most one weight piece per thread and tap (waves beyond BC / 16 fetch none)");
@@ -819,22 +829,218 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
       }
     }
   };
-  issue_window(0);
-  issue_w(0, 0, 0);
+  constexpr int OMS = 33;                                       // FUS: floats per pixel of the offset tile in LDS (odd: no bank conflicts)
+  float* const om_lds = (float*)geow;
+  if constexpr (FUS) {
+    // LDS of this phase: two split halos -- 10 x 18 pixels x 4 channel groups x {hi[4], lo[4]}, fetched as f32 and split in place
+    // -- in the window's space; behind it (geometry tables and ring, neither live yet) the X / Y weight images of a chunk
+    // pair's nine steps, 32 rows x 64 B each: steps 0..4 (segment A) and 5..8 (segment B)
+    constexpr int HPC = (TH + 2) * (TW + 2) * 4;                // 720 pieces of a halo
+    constexpr int H_LD = (HPC + NT - 1) / NT;                   // DMA rounds
+    constexpr int HB = H_LD * NT * 16;                          // 12288: the last round's tail lanes write behind the halo
+    constexpr int WSTEP = 2 * 32 * 64;                          // a step's X and Y images
+    static_assert(NT == 256 && 2 * HB <= WINB && 9 * WSTEP <= GEOW + GEOC + NST * STG, "LDS layout of the offset conv");
+    static_assert(BP * OMS * 4 <= GEOW, "the offset tile lives in the weight table's space");
+    static_assert(sizeof(smem) <= 81920, "two workgroups per CU");
+    char* const halo = win;
+    char* const wimg = geow;
+    int hofs[H_LD];
+#pragma unroll
+    for (int i = 0; i < H_LD; ++i) {
+      const int j = tid + NT * i;
+      const int hp = j >> 2, sl = j & 3;
+      const int hr = hp / (TW + 2), hc = hp - hr * (TW + 2);
+      const int y = ty0 - 1 + hr, x = tx0 - 1 + hc;
+      const bool ok = j < HPC && y >= 0 && y < a.H && x >= 0 && x < a.W;
+      hofs[i] = ok ? (y * a.W + x) * a.in_stride + (sl ^ swz(hc)) * 4 : -1;   // slot sl of pixel column hc holds group sl ^ swz(hc)
+    }
+    auto issue_halo = [&](int chunk, int hb) {
+#pragma unroll
+      for (int i = 0; i < H_LD; ++i) {
+        int o = hofs[i];
+        asm volatile("" : "+v"(o));
+        dma16(o >= 0 ? ximg + o + chunk * 16 : zero, halo + hb * HB + (wave * 64 + NT * i) * 16);
+      }
+    };
+    // the thread's own pieces of halo hb: 4 f32 -> {hi[4], lo[4]} f16, in place (conv3x3_halo_pair2_kernel's split)
+    auto convert = [&](int hb) {
+      char* base = halo + hb * HB + tid * 16;
+      f32x4 v[H_LD];
+#pragma unroll
+      for (int i = 0; i < H_LD; ++i) v[i] = *(const f32x4*)(base + i * NT * 16);
+#pragma unroll
+      for (int i = 0; i < H_LD; ++i) {
+        const f16x4 hi = __builtin_convertvector(v[i], f16x4);
+        f32x4 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = v[i][e] - (float)hi[e];
+        const f16x4 lo = __builtin_convertvector(r, f16x4);
+        *(f16x8*)(base + i * NT * 16) = __builtin_shufflevector(hi, lo, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+    };
+    // weights: thread = (image X / Y, LDS row, slot); LDS row (tile tt, row r) = cout_of<2>(tt, r / 4, r % 4), slot = k group ^ swz(row)
+    const int orow = a.Cin / 32 * 288;                          // floats per row of the pair image
+    const float* wsrc;
+    {
+      const int img = tid >> 7, lr = (tid >> 2) & 31, sl = tid & 3;
+      wsrc = (const float*)a.w_off + (long)cout_of<2>(lr >> 4, (lr & 15) >> 2, lr & 3) * orow + img * 16 + (sl ^ swz(lr)) * 4;
+    }
+    auto issue_wseg = [&](int pair, int s0, int s1) {           // steps s0 .. s1 - 1 of the pair into their slots
+      for (int s_ = s0; s_ < s1; ++s_) dma16(wsrc + (pair * 9 + s_) * 32, wimg + s_ * WSTEP + wave * 1024);
+    };
+    // wave = tile rows 2 * wave, 2 * wave + 1 (16 pixels each) x 32 couts; lane (l15, kg): pixel column l15, k group kg
+    const int l15 = lane & 15, kg = lane >> 4;
+    int pb[3];                                                  // piece of halo pixel (row 0, column l15 + S)
+#pragma unroll
+    for (int S_ = 0; S_ < 3; ++S_) pb[S_] = (l15 + S_) * 64 + ((kg ^ swz(l15 + S_)) << 4);
+    const char* wfrag = wimg + l15 * 64 + ((kg ^ swz(l15)) << 4);
+    // which product order the pair kernel gives the pixels of tile row r: its 8 x 32 tiles (W % 32 == 0) switch with every
+    // row, its 16 x 16 tiles with every second one
+    const bool w32 = a.W % 32 == 0;
+    const bool ordb[2] = {w32 ? false : (wave & 1) != 0, w32 ? true : (wave & 1) != 0};
+    typedef unsigned long long u64;
+    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) const volatile u64 lds_u64;
+    f32x4 oacc[2][2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) oacc[u][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // step S of a chunk pair (pair2_kloop): operands (halo, tap) = S < 4: (0, 2S), (0, 2S+1); S = 4: (0, 8), (1, 8); else (1, ..)
+    auto step = [&](auto sc) {
+      constexpr int S = decltype(sc)::value;
+      constexpr int B0 = S <= 4 ? 0 : 1, B1 = S < 4 ? 0 : 1;
+      constexpr int T0 = S < 4 ? 2 * S : (S == 4 ? 8 : 2 * (S - 5)), T1 = S < 4 ? 2 * S + 1 : (S == 4 ? 8 : 2 * (S - 5) + 1);
+      f16x8 xw[2], yw[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        xw[c] = *(const f16x8*)(wfrag + S * WSTEP + c * 1024);
+        yw[c] = *(const f16x8*)(wfrag + S * WSTEP + 2048 + c * 1024);
+      }
+      u64x2 hq[2], lq[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const char* s0 = halo + B0 * HB + (2 * wave + u + T0 / 3) * ((TW + 2) * 64) + pb[T0 % 3];
+        const char* s1 = halo + B1 * HB + (2 * wave + u + T1 / 3) * ((TW + 2) * 64) + pb[T1 % 3];
+        hq[u][0] = *(lds_u64*)s0; hq[u][1] = *(lds_u64*)s1;
+        lq[u][0] = *(lds_u64*)(s0 + 8); lq[u][1] = *(lds_u64*)(s1 + 8);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const f16x8 H = __builtin_bit_cast(f16x8, hq[u]), L = __builtin_bit_cast(f16x8, lq[u]);
+        if (ordb[u]) {
+#pragma unroll
+          for (int c = 0; c < 2; ++c) oacc[u][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xw[c], L, oacc[u][c], 0, 0, 0);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) oacc[u][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xw[c], H, oacc[u][c], 0, 0, 0);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) oacc[u][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(yw[c], H, oacc[u][c], 0, 0, 0);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 2; ++c) oacc[u][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xw[c], H, oacc[u][c], 0, 0, 0);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) oacc[u][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(yw[c], H, oacc[u][c], 0, 0, 0);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) oacc[u][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xw[c], L, oacc[u][c], 0, 0, 0);
+        }
+      }
+    };
+    const int npair = a.Cin / 32;
+    issue_halo(0, 0);
+    issue_halo(1, 1);
+    issue_wseg(0, 0, 9);
+    wait_vmcnt<0>();
+    convert(0);
+    convert(1);
+    __syncthreads();
+    for (int pair = 0; pair < npair; ++pair) {
+      const bool last = pair + 1 == npair;
+      step(std::integral_constant<int, 0>{});
+      step(std::integral_constant<int, 1>{});
+      step(std::integral_constant<int, 2>{});
+      step(std::integral_constant<int, 3>{});
+      if (pair > 0) {                                           // the odd chunk's halo and segment B, issued a pair ago
+        wait_vmcnt<0>();
+        convert(1);
+      }
+      __syncthreads();
+      step(std::integral_constant<int, 4>{});
+      __syncthreads();                                          // halo 0 and segment A are read
+      if (!last) {
+        issue_halo(2 * pair + 2, 0);
+        issue_wseg(pair + 1, 0, 5);
+      }
+      step(std::integral_constant<int, 5>{});
+      step(std::integral_constant<int, 6>{});
+      step(std::integral_constant<int, 7>{});
+      step(std::integral_constant<int, 8>{});
+      if (!last) {
+        wait_vmcnt<0>();
+        convert(0);
+      }
+      __syncthreads();                                          // halo 1 and segment B are read
+      if (!last) {
+        issue_halo(2 * pair + 3, 1);
+        issue_wseg(pair + 1, 5, 9);
+      }
+    }
+    // conv3x3_halo_pair2_kernel's epilogue: raw sum x inverse row scale + bias.  Finished (the asm pins it) before the DMAs
+    // below go out: the compiler's wait for these plain loads would otherwise wait for the DMAs as well
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int c0 = cout_of<2>(c, kg, 0);
+        f32x4 v = oacc[u][c];
+        const f32x4 sv = *(const f32x4*)(a.b_off + 32 + c0);
+        v = v * sv;
+        const f32x4 bv = *(const f32x4*)(a.b_off + c0);
+        v = v + bv;
+        asm volatile("" : "+v"(v));
+        oacc[u][c] = v;
+      }
+    // nothing of this phase is live in LDS any more: the sampler's first window and weights go out, the offset tile
+    // ([pixel][OMS]) takes the weight images' place
+    issue_window(0);
+    issue_w(0, 0, 0);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        float* dst = om_lds + ((2 * wave + u) * 16 + l15) * OMS + cout_of<2>(c, kg, 0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dst[e] = oacc[u][c][e];
+      }
+    __syncthreads();
+  } else {
+    issue_window(0);
+    issue_w(0, 0, 0);
+  }
 
   // ---- sampling geometry, once per (pixel, tap): thread = pixel gp, taps gh, gh + NT/128, ...
   {
     constexpr int GS = NT / 128;
+    constexpr int GN = (9 + GS - 1) / GS;
     const int gp = tid & 127, gh = tid >> 7;
     const int py = ty0 + (gp >> 4), pxx = tx0 + (gp & 15);
-    const float* omrow = a.om + ((long)(b * a.H + py) * a.W + pxx) * a.om_stride;
+    const float* omrow = FUS ? om_lds + gp * OMS : a.om + ((long)(b * a.H + py) * a.W + pxx) * a.om_stride;
+    float fdh[FUS ? GN : 1], fdw[FUS ? GN : 1], fmk[FUS ? GN : 1];
+    if constexpr (FUS) {                                        // the tables below overwrite the offset tile: read it first
 #pragma unroll
-    for (int i = 0; i < (9 + GS - 1) / GS; ++i) {
+      for (int i = 0; i < GN; ++i) {
+        const int t = GS * i + gh;
+        if (t < 9) { fdh[i] = omrow[2 * t]; fdw[i] = omrow[2 * t + 1]; fmk[i] = omrow[18 + t]; }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < GN; ++i) {
       const int t = GS * i + gh;
       if (t < 9) {
         const int tr = t / 3, ts = t - 3 * tr;
-        const float h_im = (float)(py - 1 + tr) + omrow[2 * t], w_im = (float)(pxx - 1 + ts) + omrow[2 * t + 1];
-        const float mraw = NM ? 1.f : omrow[18 + t];                                                  // NM: no mask channel
+        const float odh = FUS ? fdh[FUS ? i : 0] : omrow[2 * t], odw = FUS ? fdw[FUS ? i : 0] : omrow[2 * t + 1];
+        const float h_im = (float)(py - 1 + tr) + odh, w_im = (float)(pxx - 1 + ts) + odw;
+        const float mraw = NM ? 1.f : (FUS ? fmk[FUS ? i : 0] : omrow[18 + t]);                       // NM: no mask channel
         const bool valid = h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W;     // kernel.cu:852
         const float mk = valid ? ((NM || a.mask_is_prob) ? mraw : ctdet_sigmoid_exact(mraw)) : 0.f;   // invalid: contributes 0
         const float fh = floorf(h_im), fw = floorf(w_im);
@@ -845,8 +1051,11 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
         // image, where the window is zero-filled): the window read then IS the guarded read of kernel.cu:683-693
         const bool inside = wr >= 0 && wr + 1 < WR && wcn >= 0 && wcn + 1 < WCOLS;
         const bool oow = valid && !inside;
+        // FUS: a far sample carries (h_low + 1) << 16 | (w_low + 1) << 4 (both in 0 .. 4094; the low 16 bits stay a 16-byte
+        // aligned LDS offset for the window reads whose result the slow path replaces)
+        const unsigned farcode = FUS ? (0x80000000u | ((unsigned)(h_low + 1) << 16) | ((unsigned)(w_low + 1) << 4)) : 0x80000000u;
         // window byte offset of corner 1 for channel group 0, the row parity in bit 5 (group g sits at (g << 4) ^ (parity << 5))
-        const unsigned code = (valid && inside) ? ((unsigned)((wr * WCOLS + wcn) * 64) | ((unsigned)(wr & 1) << 5)) : (oow ? 0x80000000u : 0u);
+        const unsigned code = (valid && inside) ? ((unsigned)((wr * WCOLS + wcn) * 64) | ((unsigned)(wr & 1) << 5)) : (oow ? farcode : 0u);
         f32x4 gv;
         gv[0] = hh * hw * mk; gv[1] = hh * lw * mk; gv[2] = lh * hw * mk; gv[3] = lh * lw * mk;
         *(f32x4*)(geow + (t * BP + gp) * 16) = gv;
@@ -886,11 +1095,16 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
       if (any_far) {                                          // rare: the lanes concerned re-derive the sample from the offsets
         const bool out = code[p] >> 31;
         const int py = ty0 + prow, pxx = tx0 + (TP == 2 ? 8 * p : 0) + pcol, tr = t / 3, ts = t - 3 * (t / 3);
-        const float* omrow = a.om + ((long)(b * a.H + py) * a.W + pxx) * a.om_stride;
-        float dh, dw;
-        gload2_sync(omrow + 2 * t, dh, dw);                  // (asm loads: see gload2_sync)
-        const float h_im = (float)(py - 1 + tr) + dh, w_im = (float)(pxx - 1 + ts) + dw;
-        const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
+        int h_low, w_low;
+        if constexpr (FUS) {                                  // the corner the geometry stage left in the code word
+          h_low = (int)((code[p] >> 16) & 0xFFFu) - 1; w_low = (int)((code[p] >> 4) & 0xFFFu) - 1;
+        } else {
+          const float* omrow = a.om + ((long)(b * a.H + py) * a.W + pxx) * a.om_stride;
+          float dh, dw;
+          gload2_sync(omrow + 2 * t, dh, dw);                // (asm loads: see gload2_sync)
+          const float h_im = (float)(py - 1 + tr) + dh, w_im = (float)(pxx - 1 + ts) + dw;
+          h_low = (int)floorf(h_im); w_low = (int)floorf(w_im);
+        }
         const bool r0 = out && h_low >= 0, r1 = out && h_low + 1 <= a.H - 1, c0 = w_low >= 0, c1 = w_low + 1 <= a.W - 1;
         const long o0 = ((long)h_low * a.W + w_low) * a.in_stride, o2 = o0 + (long)a.W * a.in_stride;
         const float* base = ximg + chunk * 16 + q * 4;
@@ -1394,6 +1608,29 @@ bool dcn_split_window_ok(const ConvArgs& a) {
   return f32_vector_ok(a, bc) && a.Cin % 16 == 0 && a.nsrc <= 1 && a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 &&
          a.H % 8 == 0 && a.W % 16 == 0 && a.H <= 4094 && a.W <= 4094 && a.Kpad == a.K && a.Cout_pad % 64 == 0 && a.korder == 0 &&
          !(ctdet_tuning_flags() & (CTDET_TUNE_NO_F32_DCN_WINDOW | CTDET_TUNE_DCN_WINDOW_V1));
+}
+
+// may the f16x3 DCNv2 of these arguments compute its own offsets and mask (dcn_split_window_kernel<2, 64, ..., fused>)?  One
+// 64-cout tile covers Cout (two cout-tile workgroups per pixel tile would each repeat the offset conv) and the offset
+// conv's pair image pairs 16-channel chunks (Cin % 32 == 0).  Nothing here looks at the batch size.
+bool dcn_offset_fused_x3_ok(const ConvArgs& a) {
+  return dcn_split_window_ok(a) && a.Cin % 32 == 0 && a.Cout_pad == 64 && !a.res && !(ctdet_tuning_flags() & CTDET_TUNE_DCN_SPLIT_8W64);
+}
+
+// a.w_off: korder-3 pair image of the [27, Cin, 3, 3] offset / mask conv (32 rows x Cin / 32 * 288 f32 units), a.b_off: its 32
+// biases followed by its 32 inverse row scales
+int launch_dcn_offset_x3(const ConvArgs& a, hipStream_t s) {
+  CTDET_CHECK((long)a.B * a.H * a.W * a.in_stride < (1L << 31), "dcnv2_offset(f16x3): input too large for 32-bit element offsets");
+  CTDET_CHECK(dcn_offset_fused_x3_ok(a) && aligned16(a.w_off) && aligned16(a.b_off) && !a.cols_out && !a.om_out &&
+                  a.mask_is_prob == DCN_MASK_LOGIT,
+              "dcnv2_offset(f16x3): needs 3x3/s1/p1, Cin %% 32 == 0, a map divisible by 8x16, 64 packed couts and 16-byte aligned "
+              "operands (Cin=%d, %dx%d, Cout_pad=%d; ctdet_dcnv2_offset_supported)", a.Cin, a.H, a.W, a.Cout_pad);
+  const int nbx = a.B * (a.H / 8) * (a.W / 16);
+  dim3 grid(8 * ((nbx + 7) / 8));
+  CTDET_KERNEL("dcn_f16x3_window_kernel<8x16,64,offset conv fused>");
+  hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, false, false, true>), grid, dim3(256), 0, s, a);
+  CTDET_LAUNCH_CHECK();
+  return 0;
 }
 
 int launch_conv_f32(const ConvArgs& a, bool deform, bool split, hipStream_t s) {

@@ -170,7 +170,8 @@ class DCN(nn.Module):
         p = hipnn.packed(self, "dcn", ctx.compute, self.weight, bn, self.bias, self.stride, self.padding, self.dilation,
                          cout_align=64 if ctx.compute == F16 else None)
         com = self.conv_offset_mask
-        if ctx.compute == F16 and x.shape[3] % 32 == 0:
+        fused_x3 = ctx.compute == ops.F16X3 and ops.DCN_X3_FUSED and not ops.RANGE_CHECK
+        if (ctx.compute == F16 or fused_x3) and x.shape[3] % 32 == 0:
             # offset conv and deformable conv in one kernel where the geometry allows (64-cout layers on tile-divisible maps)
             p_off = hipnn.packed(com, "conv", ctx.compute, com.weight, None, com.bias, com.stride[0], com.padding[0], com.dilation[0])
             if ops.dcnv2_offset_supported(x, p_off, p):

@@ -633,15 +633,49 @@ def dcnv2(x, offset_mask, p, out=None, act=ACT_NONE, out_dtype=None, mask_is_pro
     return (out, cols) if want_cols else out
 
 
+# CTDET_NO_FUSED_DCN_X3=1: the f16x3 DCNv2 layers keep their offset / mask conv as a launch of its own (the A/B switch of the
+# fused form; CTDET_RANGE_CHECK=1 does the same, it has to see that conv's output)
+DCN_X3_FUSED = os.environ.get("CTDET_NO_FUSED_DCN_X3", "0") != "1"
+
+
+def _off_operands_x3(p_off):
+    """(korder-3 pair image, [32 biases, 32 inverse row scales]) of a packed f16x3 offset / mask conv for ctdet_dcnv2_offset_fwd,
+    or None when it has no such image: the same image, bias and scale conv2d() hands the pair kernel"""
+    if p_off.w_pair is None or p_off.pair_korder != 3:
+        if p_off._x3_src is not None and p_off._pair_capable and p_off.Cin % 32 == 0:
+            p_off.pair_korder = 3
+            p_off.w_pair, p_off.scale_pair = p_off._x3_operand(3)
+        elif p_off._wp_scaled is not None and p_off.w_pair is None and p_off.Cin % 32 == 0:
+            (p_off.w_pair, p_off.pair_korder), p_off._wp_scaled = p_off._pack_pairs(p_off._wp_scaled), None
+        else:
+            return None
+    sc = p_off.scale_pair if p_off.scale_pair is not None else p_off.scale
+    hit = p_off.__dict__.get("_off_bs")
+    if hit is None or hit[0] is not sc or hit[1] is not p_off.bias:
+        bs = torch.zeros(64, dtype=torch.float32, device=p_off.w_pair.device)
+        bs[:p_off.bias.shape[0]] = p_off.bias
+        bs[32:32 + sc.shape[0]] = sc
+        hit = p_off._off_bs = (sc, p_off.bias, bs)
+    return p_off.w_pair, hit[2]
+
+
 def dcnv2_offset_supported(x, p_off, p):
-    """may `dcnv2_offset` serve this layer? (f16, 3x3/s1/p1 both convs, at most 64 couts packed to 64 rows, map divisible by
-    the 8x16 tile, Cin % 32 == 0, 27 offset / mask channels packed chunk-major into 32 rows)"""
-    if p.compute != F16 or p_off.compute != F16 or p.Cout_pad != 64 or p_off.Cout != 27 or p_off.Cout_pad != 32:
+    """may `dcnv2_offset` serve this layer?  Both convs 3x3/s1/p1 on a map divisible by the 8x16 tile, Cin % 32 == 0, at most 64
+    couts packed to 64 rows, 27 offset / mask channels in 32 packed rows -- f16: chunk-major; f16x3: the korder-3 pair image
+    (f32 x of 16-byte aligned pixels).  The batch size plays no part."""
+    if p.compute not in (F16, F16X3) or p_off.compute != p.compute or p.Cout_pad != 64 or p_off.Cout != 27:
         return False
-    if (p_off.R, p_off.S, p_off.stride, p_off.pad, p_off.dil, p_off.korder, p_off.Kpad) != (3, 3, 1, 1, 1, 1, p.Kpad):
+    if (p_off.R, p_off.S, p_off.stride, p_off.pad, p_off.dil) != (3, 3, 1, 1, 1) or p_off.bias is None:
         return False
     B, H, W, _ = x.shape
-    out = torch.empty(0, H, W, round_up(p.Cout_eff, 8), dtype=torch.float16, device=x.device)
+    if p.compute == F16X3:
+        if dt_of(x) != F32 or x.data_ptr() % 16 or p.Cin % 32 or p_off.Cin != p.Cin or _off_operands_x3(p_off) is None:
+            return False
+        out = torch.empty(0, H, W, p.Cout_eff, dtype=torch.float32, device=x.device)
+    else:
+        if p_off.Cout_pad != 32 or (p_off.korder, p_off.Kpad) != (1, p.Kpad):
+            return False
+        out = torch.empty(0, H, W, round_up(p.Cout_eff, 8), dtype=torch.float16, device=x.device)
     d = p.desc(x[:0], out, ACT_NONE, None)
     d.B = B
     return bool(_lib.lib().ctdet_dcnv2_offset_supported(C.byref(d)))
@@ -649,10 +683,20 @@ def dcnv2_offset_supported(x, p_off, p):
 
 def dcnv2_offset(x, p_off, p, out=None, act=ACT_NONE, out_dtype=None, om_out=None):
     """act(dcn(x, conv_offset_mask(x))) in one kernel (ctdet_dcnv2_offset_fwd): p_off = the packed 3x3 offset / mask conv with
-    its bias, p = the packed deformable conv.  om_out (f32 [B,H,W,>=28]) receives the offsets / mask logits if given."""
+    its bias, p = the packed deformable conv.  om_out (f16 mode only; f32 [B,H,W,>=28]) receives the offsets / mask logits if given."""
     _require_cuda(x, out, om_out)
-    assert dt_of(x) == F16 and p.compute == F16 and p_off.bias is not None and p_off.scale is None
-    if out is None and p.Cout_eff % 8:
+    assert dt_of(x) == p.act_dt and p.compute in (F16, F16X3) and p_off.compute == p.compute and p_off.bias is not None
+    if p.compute == F16X3:
+        assert om_out is None, "dcnv2_offset (f16x3) keeps no offsets: the inference form"
+        ops_off = _off_operands_x3(p_off)
+        if ops_off is None:
+            raise ValueError("dcnv2_offset (f16x3): the offset conv has no korder-3 pair image (3x3/s1/p1, Cin % 32 == 0)")
+        w_off, b_off = ops_off
+        p._wp_scaled = None          # a deformable conv's weights: no pair image will be needed
+    else:
+        assert p_off.scale is None
+        w_off, b_off = p_off.w, p_off.bias
+    if out is None and p.compute == F16 and p.Cout_eff % 8:
         B, H, W, _ = x.shape
         dt = out_dtype if out_dtype is not None else torch.float16
         out = torch.empty(B, H, W, round_up(p.Cout_eff, 8), dtype=dt, device=x.device)[..., :p.Cout_eff]
@@ -663,11 +707,13 @@ def dcnv2_offset(x, p_off, p, out=None, act=ACT_NONE, out_dtype=None, om_out=Non
     if prof.on:
         prof.bytes -= d.B * d.Ho * d.Wo * 27 * 4      # no offset tensor is read
     for _ in range(prof.reps()):
-        rc = _lib.lib().ctdet_dcnv2_offset_fwd(C.byref(d), _ptr(x), _ptr(p_off.w), _ptr(p_off.bias), _ptr(om_out),
+        rc = _lib.lib().ctdet_dcnv2_offset_fwd(C.byref(d), _ptr(x), _ptr(w_off), _ptr(b_off), _ptr(om_out),
                                                _nhwc_stride(om_out) if om_out is not None else 0, _ptr(p.w), _ptr(p.scale),
                                                _ptr(p.bias), _ptr(out), _stream())
     _lib.check(rc, "ctdet_dcnv2_offset_fwd")
     prof.done()
+    if p.compute == F16X3:
+        _range_check(out, p, "dcnv2_offset")
     return out
 
 

@@ -140,7 +140,12 @@ int32_t ctdet_dcnv2_fwd_cols(const ctdet_conv_desc* d, const void* x, const floa
  * goes to memory unless om_out is given (f32 [M][om_out_stride], channels 0..27 written; a backward pass needs it).
  * w_off_packed: ctdet_pack_weights of the [27,Cin,3,3] weight with rows_pad 32, chunk-major; b_off: 28 f32 (27 used).
  * f16 compute, Cout <= 64 packed to 64 rows, maps divisible by 8x16, Cin % 32 == 0: ctdet_dcnv2_offset_supported(d) says
- * whether a descriptor qualifies (otherwise: ctdet_conv2d_fwd + ctdet_dcnv2_fwd). */
+ * whether a descriptor qualifies (otherwise: ctdet_conv2d_fwd + ctdet_dcnv2_fwd).
+ * CTDET_DT_F16X3 (f32 x and y, the DCN weights tap-major as for ctdet_dcnv2_fwd; same shape rules, 16-byte aligned x, pixel rows
+ * and operands; the batch size plays no part): w_off_packed is the korder-3 tap-pair image of the [27,Cin,3,3] weight
+ * (ctdet_pack_weights_x3 layout 3: 32 rows x Cin / 32 * 288 f32 units), b_off 64 f32: 32 biases, then the 32 inverse row
+ * scales of that image; om_out must be null (the inference form).  The offsets are computed by the MFMA sequence of the
+ * tap-pair conv kernel, so y equals ctdet_conv2d_fwd + ctdet_dcnv2_fwd bit for bit wherever that kernel serves the conv. */
 int32_t ctdet_dcnv2_offset_supported(const ctdet_conv_desc* d);
 int32_t ctdet_dcnv2_offset_fwd(const ctdet_conv_desc* d, const void* x, const void* w_off_packed, const float* b_off,
                                float* om_out, int32_t om_out_stride, const void* w_packed, const float* scale,
