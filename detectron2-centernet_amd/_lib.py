@@ -14,6 +14,9 @@ F16, F32, U8, F16X3 = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP = 0, 1, 2
 # mask mode of the DCN entry points (enum ctdet_dcn_mask; the argument named mask_is_prob): mask logits, probabilities, no mask
 DCN_MASK_LOGIT, DCN_MASK_PROB, DCN_MASK_NONE = 0, 1, 2
+# enum ctdet_sgd_clip / ctdet_grad_norm
+CLIP_NONE, CLIP_VALUE, CLIP_NORM = 0, 1, 2
+NORM_L1, NORM_L2, NORM_INF = 1, 2, 3
 
 
 class ConvDesc(C.Structure):
@@ -95,6 +98,10 @@ SIGNATURES = {
     "ctdet_dcn_col2im_fused": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_sgd_momentum": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32, _f32, _i32, _vp]),
     "ctdet_sgd_momentum_runs": (_i32, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _vp]),
+    "ctdet_grad_chunk_norms": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "ctdet_grad_clip_coefs": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "ctdet_sgd_momentum_runs_clip": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _i32, _f32, _vp,
+                                             _vp]),
     "ctdet_set_tuning_flags": (_i32, [C.c_uint32]),
     "ctdet_get_tuning_flags": (C.c_uint32, []),
     "ctdet_comm_unique_id": (_i32, [_vp]),

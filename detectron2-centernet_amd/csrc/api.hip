@@ -58,6 +58,13 @@ int launch_reg_l1(const float*, int, const uint8_t*, const int64_t*, const float
 int launch_sgd(float*, const float*, float*, long, const float*, float, float, int, hipStream_t);
 int launch_sgd_runs(float*, const float*, float*, long, const long*, const int*, const float*, const float*, int, float, int,
                     hipStream_t);
+int launch_sgd_runs_clip(float*, const float*, float*, long, const long*, const int*, const float*, const float*, int, float, int,
+                         int, int, float, const float*, hipStream_t);
+int launch_grad_chunk_norms(const float*, long, const long*, const int*, int, int, float*, hipStream_t);
+int launch_grad_clip_coefs(const float*, const int*, int, int, int, float, float*, float*, hipStream_t);
+static_assert(CTDET_CLIP_NONE == SGD_CLIP_NONE && CTDET_CLIP_VALUE == SGD_CLIP_VALUE && CTDET_CLIP_NORM == SGD_CLIP_NORM &&
+              CTDET_NORM_L1 == GRAD_NORM_L1 && CTDET_NORM_L2 == GRAD_NORM_L2 && CTDET_NORM_INF == GRAD_NORM_INF,
+              "clip / norm modes: header and kernels disagree");
 
 struct WgradArgs {
   const void* x; const void* dy; float* dw;
@@ -791,6 +798,39 @@ int32_t ctdet_sgd_momentum_runs(float* param, const float* grad, float* momentum
   CTDET_CHECK(param && grad && momentum_buf && run_end && run_lr_index && run_weight_decay && lr_table, "sgd_runs: null pointer");
   return launch_sgd_runs(param, grad, momentum_buf, (long)n, (const long*)run_end, run_lr_index, run_weight_decay, lr_table,
                          nruns, momentum, first_step, (hipStream_t)stream);
+}
+
+int32_t ctdet_grad_chunk_norms(const float* grad, int64_t n, const int64_t* chunk_start, const int32_t* chunk_len,
+                               int32_t nchunks, int32_t norm_type, float* partials, void* stream) {
+  CTDET_CHECK(grad && chunk_start && chunk_len && partials, "grad_chunk_norms: null pointer");
+  CTDET_CHECK(n >= 0 && nchunks >= 0, "grad_chunk_norms: n=%lld nchunks=%d", (long long)n, nchunks);
+  CTDET_CHECK(norm_type >= CTDET_NORM_L1 && norm_type <= CTDET_NORM_INF, "grad_chunk_norms: norm type %d", norm_type);
+  CTDET_CHECK(((uintptr_t)grad & 15) == 0, "grad_chunk_norms: grad must be 16-byte aligned");
+  return launch_grad_chunk_norms(grad, (long)n, (const long*)chunk_start, chunk_len, nchunks, norm_type, partials,
+                                 (hipStream_t)stream);
+}
+
+int32_t ctdet_grad_clip_coefs(const float* partials, const int32_t* param_chunk_end, int32_t nparams, int32_t nchunks,
+                              int32_t norm_type, float clip_value, float* norms, float* coefs, void* stream) {
+  CTDET_CHECK(partials && param_chunk_end && norms && coefs, "grad_clip_coefs: null pointer");
+  CTDET_CHECK(nparams >= 0 && nchunks >= 0, "grad_clip_coefs: nparams=%d nchunks=%d", nparams, nchunks);
+  CTDET_CHECK(norm_type >= CTDET_NORM_L1 && norm_type <= CTDET_NORM_INF, "grad_clip_coefs: norm type %d", norm_type);
+  CTDET_CHECK(clip_value > 0.f, "grad_clip_coefs: clip value %g", (double)clip_value);
+  return launch_grad_clip_coefs(partials, param_chunk_end, nparams, nchunks, norm_type, clip_value, norms, coefs,
+                                (hipStream_t)stream);
+}
+
+int32_t ctdet_sgd_momentum_runs_clip(float* param, const float* grad, float* momentum_buf, int64_t n, const int64_t* run_end,
+                                     const int32_t* run_lr_index, const float* run_weight_decay, const float* lr_table,
+                                     int32_t nruns, float momentum, int32_t first_step, int32_t nesterov, int32_t clip_type,
+                                     float clip_value, const float* coefs, void* stream) {
+  CTDET_CHECK(param && grad && momentum_buf && run_end && run_lr_index && run_weight_decay && lr_table,
+              "sgd_runs_clip: null pointer");
+  CTDET_CHECK(clip_type >= CTDET_CLIP_NONE && clip_type <= CTDET_CLIP_NORM, "sgd_runs_clip: clip type %d", clip_type);
+  CTDET_CHECK(clip_type == CTDET_CLIP_NONE || clip_value > 0.f, "sgd_runs_clip: clip value %g", (double)clip_value);
+  CTDET_CHECK(clip_type != CTDET_CLIP_NORM || coefs, "sgd_runs_clip: norm clipping needs coefs (one per run)");
+  return launch_sgd_runs_clip(param, grad, momentum_buf, (long)n, (const long*)run_end, run_lr_index, run_weight_decay, lr_table,
+                              nruns, momentum, first_step, nesterov, clip_type, clip_value, coefs, (hipStream_t)stream);
 }
 
 }  // extern "C"

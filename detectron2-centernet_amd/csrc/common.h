@@ -48,6 +48,9 @@ enum { CTDET_F16 = 0, CTDET_F32 = 1, CTDET_U8 = 2, CTDET_F16X3 = 3 };
 enum { CTDET_ACT_NONE = 0, CTDET_ACT_RELU = 1, CTDET_ACT_SIGMOID_CLAMP = 2 };
 // DCN mask modes (ConvArgs::mask_is_prob and the DCN entry points' argument; CTDET_DCN_MASK_* in ctdet_hip.h)
 enum { DCN_MASK_LOGIT = 0, DCN_MASK_PROB = 1, DCN_MASK_NONE = 2 };
+// gradient clipping of the flat SGD step (CTDET_CLIP_* / CTDET_NORM_* in ctdet_hip.h)
+enum { SGD_CLIP_NONE = 0, SGD_CLIP_VALUE = 1, SGD_CLIP_NORM = 2 };
+enum { GRAD_NORM_L1 = 1, GRAD_NORM_L2 = 2, GRAD_NORM_INF = 3 };
 // channels of an offset/mask row a DCN kernel reads: 18 offsets (+ 9 mask channels unless the mask is absent)
 __host__ __device__ inline int dcn_om_channels(int mask_mode) { return mask_mode == DCN_MASK_NONE ? 18 : 27; }
 

@@ -336,17 +336,27 @@ __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, const f
 // the same update over a flat buffer cut into `nruns` consecutive runs with their own (lr, weight decay): run r covers
 // [run_end[r-1], run_end[r]); lr = lr_table[run_lr_index[r]] is read from device memory.  One launch instead of one per run
 // (DLA-34: 109 runs, weights / norm / bias parameters alternate in backward order).
-__global__ void __launch_bounds__(256) sgd_runs_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       long n, const long* __restrict__ run_end,
-                                                       const int* __restrict__ run_lr_index, const float* __restrict__ run_wd,
-                                                       const float* __restrict__ lr_table, int nruns, float mom, int first) {
+//
+// CLIP / NEST select what detectron2/solver/build.py:19-58,134 adds to the step, in torch's order -- clip, weight decay,
+// momentum, Nesterov look-ahead:
+//   SGD_CLIP_VALUE  g = clamp(g, -clip_value, +clip_value)              (torch.nn.utils.clip_grad_value_, per parameter)
+//   SGD_CLIP_NORM   g = g * coefs[run], the runs being the parameters    (torch.nn.utils.clip_grad_norm_, per parameter)
+//   NEST            p -= lr * (g + mom * buf) instead of p -= lr * buf   (torch.optim.SGD(nesterov=True))
+// The clipped gradient lives in registers only: g is never written.  The instantiation <SGD_CLIP_NONE, false> is the
+// plain kernel, instruction for instruction.
+template <int CLIP, bool NEST>
+__device__ __forceinline__ void sgd_runs_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              long n, const long* __restrict__ run_end,
+                                              const int* __restrict__ run_lr_index, const float* __restrict__ run_wd,
+                                              const float* __restrict__ lr_table, int nruns, float mom, int first,
+                                              float clip_value, const float* __restrict__ coefs) {
   // A workgroup owns a contiguous range and a thread walks it in steps of 1024 elements, four at a time: a thread stays
   // inside one run for many iterations, so the run lookup (a binary search over dependent global loads) is rare.  With a
   // grid-wide stride every iteration landed in another run and searched again (204 us for 18.6 M parameters).
   const long per = (((n + gridDim.x - 1) / gridDim.x) + 1023) & ~1023L;
   const long beg = (long)blockIdx.x * per, end = beg + per < n ? beg + per : n;
   long cur_end = -1;
-  float lr = 0.f, wd = 0.f;
+  float lr = 0.f, wd = 0.f, cf = 1.f;
   auto lookup = [&](long i) {
     int lo = 0, hi = nruns - 1;
     while (lo < hi) {
@@ -356,6 +366,12 @@ __global__ void __launch_bounds__(256) sgd_runs_kernel(float* __restrict__ p, co
     cur_end = run_end[lo];
     lr = lr_table[run_lr_index[lo]];
     wd = run_wd[lo];
+    if constexpr (CLIP == SGD_CLIP_NORM) cf = coefs[lo];     // one run per parameter: the search that finds lr finds this
+  };
+  auto clipped = [&](float gi) {
+    if constexpr (CLIP == SGD_CLIP_VALUE) gi = gi > clip_value ? clip_value : (gi < -clip_value ? -clip_value : gi);  // NaN stays
+    if constexpr (CLIP == SGD_CLIP_NORM) gi = gi * cf;
+    return gi;
   };
   for (long i = beg + (long)threadIdx.x * 4; i < end; i += 1024) {
     if (i >= cur_end) lookup(i);
@@ -367,25 +383,44 @@ __global__ void __launch_bounds__(256) sgd_runs_kernel(float* __restrict__ p, co
       float bo[4], po[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        float gi = ge[k];
+        float gi = clipped(ge[k]);
         if (wd != 0.f) gi = gi + wd * pe[k];
         bo[k] = first ? gi : mom * me[k] + gi;
-        po[k] = pe[k] - lr * bo[k];
+        if constexpr (NEST) po[k] = pe[k] - lr * (gi + mom * bo[k]);
+        else po[k] = pe[k] - lr * bo[k];
       }
       *(float4*)(m + i) = make_float4(bo[0], bo[1], bo[2], bo[3]);
       *(float4*)(p + i) = make_float4(po[0], po[1], po[2], po[3]);
     } else {
       for (long j = i; j < i + 4 && j < end; ++j) {
         if (j >= cur_end) lookup(j);
-        float gi = g[j];
+        float gi = clipped(g[j]);
         const float pi = p[j];
         if (wd != 0.f) gi = gi + wd * pi;
         const float bi = first ? gi : mom * m[j] + gi;
         m[j] = bi;
-        p[j] = pi - lr * bi;
+        if constexpr (NEST) p[j] = pi - lr * (gi + mom * bi);
+        else p[j] = pi - lr * bi;
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(256) sgd_runs_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       long n, const long* __restrict__ run_end,
+                                                       const int* __restrict__ run_lr_index, const float* __restrict__ run_wd,
+                                                       const float* __restrict__ lr_table, int nruns, float mom, int first) {
+  sgd_runs_body<SGD_CLIP_NONE, false>(p, g, m, n, run_end, run_lr_index, run_wd, lr_table, nruns, mom, first, 0.f, nullptr);
+}
+
+template <int CLIP, bool NEST>
+__global__ void __launch_bounds__(256) sgd_runs_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, long n, const long* __restrict__ run_end,
+                                                            const int* __restrict__ run_lr_index,
+                                                            const float* __restrict__ run_wd, const float* __restrict__ lr_table,
+                                                            int nruns, float mom, int first, float clip_value,
+                                                            const float* __restrict__ coefs) {
+  sgd_runs_body<CLIP, NEST>(p, g, m, n, run_end, run_lr_index, run_wd, lr_table, nruns, mom, first, clip_value, coefs);
 }
 
 int launch_sgd_runs(float* p, const float* g, float* m, long n, const long* run_end, const int* run_lr_index,
@@ -395,6 +430,133 @@ int launch_sgd_runs(float* p, const float* g, float* m, long n, const long* run_
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(sgd_runs_kernel, dim3((unsigned)nb), dim3(256), 0, s, p, g, m, n, run_end, run_lr_index, run_wd, lr_table,
                      nruns, mom, first);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_sgd_runs_clip(float* p, const float* g, float* m, long n, const long* run_end, const int* run_lr_index,
+                         const float* run_wd, const float* lr_table, int nruns, float mom, int first, int nesterov, int clip_type,
+                         float clip_value, const float* coefs, hipStream_t s) {
+  if (n == 0 || nruns == 0) return 0;
+  if (clip_type == SGD_CLIP_NONE && !nesterov)
+    return launch_sgd_runs(p, g, m, n, run_end, run_lr_index, run_wd, lr_table, nruns, mom, first, s);
+  long nb = (n + 1023) / 1024;
+  if (nb > 2048) nb = 2048;
+#define SGD_CLIP_CASE(C, N)                                                                                               \
+  if (clip_type == C && (nesterov != 0) == N)                                                                             \
+    hipLaunchKernelGGL((sgd_runs_clip_kernel<C, N>), dim3((unsigned)nb), dim3(256), 0, s, p, g, m, n, run_end, run_lr_index, \
+                       run_wd, lr_table, nruns, mom, first, clip_value, coefs)
+  SGD_CLIP_CASE(SGD_CLIP_NONE, true);
+  SGD_CLIP_CASE(SGD_CLIP_VALUE, false);
+  SGD_CLIP_CASE(SGD_CLIP_VALUE, true);
+  SGD_CLIP_CASE(SGD_CLIP_NORM, false);
+  SGD_CLIP_CASE(SGD_CLIP_NORM, true);
+#undef SGD_CLIP_CASE
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-parameter gradient norms of the flat gradient buffer (clip_grad_norm_ called with one tensor at a time,
+// detectron2/solver/build.py:26-27,47-51): a segmented reduction over a few hundred segments of 1 .. 2.36 M elements.
+// The host cuts the buffer once into chunks of at most 4096 elements (solver/build.py: grad_chunks) that never cross a parameter boundary;
+// pass 1 writes one f32 partial per chunk (sum g^2, sum |g| or max |g|), pass 2 combines a parameter's partials and derives
+// torch's clip coefficient min(1, clip / (norm + 1e-6)).  Every sum has one fixed shape -- a thread's elements in address
+// order, a 64-lane butterfly, the four waves of the workgroup left to right; in pass 2 lane l takes partials l, l + 64, ..
+// in table order, then the same butterfly -- and nothing is accumulated with atomics, so the result is the same bits on
+// every run.
+// ------------------------------------------------------------------------------------------------
+template <int NT>
+__device__ __forceinline__ float norm_join(float a, float b) {
+  if constexpr (NT == GRAD_NORM_INF) return (b > a || b != b) ? b : a;   // a NaN on either side stays, as in torch's max
+  else return a + b;
+}
+template <int NT>
+__device__ __forceinline__ float norm_term(float acc, float x) {
+  if constexpr (NT == GRAD_NORM_L2) return acc + x * x;
+  else return norm_join<NT>(acc, fabsf(x));
+}
+template <int NT>
+__device__ __forceinline__ float norm_wave(float acc) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) acc = norm_join<NT>(acc, __shfl_xor(acc, o));
+  return acc;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(256) grad_chunk_norm_kernel(const float* __restrict__ g, long n,
+                                                              const long* __restrict__ chunk_start,
+                                                              const int* __restrict__ chunk_len, float* __restrict__ partials) {
+  // chunk starts are parameter offsets (any residue mod 4): the float4 grid is anchored at the 16-byte boundary below the
+  // start, and a group that hangs over either end of the chunk is read element by element
+  long s = chunk_start[blockIdx.x], e = s + chunk_len[blockIdx.x];
+  if (s < 0) s = 0;
+  if (e > n) e = n;      // a table that does not fit the buffer reads nothing outside it
+  float acc = 0.f;
+  for (long i = (s & ~3L) + (long)threadIdx.x * 4; i < e; i += 1024) {
+    if (i >= s && i + 4 <= e) {
+      const float4 v = *(const float4*)(g + i);
+      acc = norm_term<NT>(norm_term<NT>(norm_term<NT>(norm_term<NT>(acc, v.x), v.y), v.z), v.w);
+    } else {
+      for (long j = i < s ? s : i; j < i + 4 && j < e; ++j) acc = norm_term<NT>(acc, g[j]);
+    }
+  }
+  acc = norm_wave<NT>(acc);
+  __shared__ float wave_part[4];
+  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[blockIdx.x] = norm_join<NT>(norm_join<NT>(norm_join<NT>(wave_part[0], wave_part[1]), wave_part[2]), wave_part[3]);
+}
+
+// one wave per parameter: parameter q owns the chunks [param_chunk_end[q-1], param_chunk_end[q])
+template <int NT>
+__global__ void __launch_bounds__(256) grad_clip_coef_kernel(const float* __restrict__ partials,
+                                                             const int* __restrict__ param_chunk_end, int nparams, int nchunks,
+                                                             float clip_value, float* __restrict__ norms,
+                                                             float* __restrict__ coefs) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (q >= nparams) return;
+  int b = q ? param_chunk_end[q - 1] : 0, e = param_chunk_end[q];
+  if (b < 0) b = 0;
+  if (e > nchunks) e = nchunks;
+  float acc = 0.f;
+  for (int c = b + lane; c < e; c += 64) acc = norm_join<NT>(acc, partials[c]);
+  acc = norm_wave<NT>(acc);
+  if (lane == 0) {
+    const float norm = NT == GRAD_NORM_L2 ? sqrtf(acc) : acc;
+    norms[q] = norm;
+    const float c = clip_value / (norm + 1e-6f);
+    coefs[q] = c > 1.f ? 1.f : c;          // torch.clamp(c, max=1): a NaN norm gives a NaN coefficient
+  }
+}
+
+int launch_grad_chunk_norms(const float* g, long n, const long* chunk_start, const int* chunk_len, int nchunks, int norm_type,
+                            float* partials, hipStream_t s) {
+  if (nchunks == 0) return 0;
+  if (norm_type == GRAD_NORM_L2)
+    hipLaunchKernelGGL(grad_chunk_norm_kernel<GRAD_NORM_L2>, dim3(nchunks), dim3(256), 0, s, g, n, chunk_start, chunk_len, partials);
+  else if (norm_type == GRAD_NORM_L1)
+    hipLaunchKernelGGL(grad_chunk_norm_kernel<GRAD_NORM_L1>, dim3(nchunks), dim3(256), 0, s, g, n, chunk_start, chunk_len, partials);
+  else
+    hipLaunchKernelGGL(grad_chunk_norm_kernel<GRAD_NORM_INF>, dim3(nchunks), dim3(256), 0, s, g, n, chunk_start, chunk_len, partials);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_grad_clip_coefs(const float* partials, const int* param_chunk_end, int nparams, int nchunks, int norm_type,
+                           float clip_value, float* norms, float* coefs, hipStream_t s) {
+  if (nparams == 0) return 0;
+  const dim3 grid((nparams + 3) / 4);
+  if (norm_type == GRAD_NORM_L2)
+    hipLaunchKernelGGL(grad_clip_coef_kernel<GRAD_NORM_L2>, grid, dim3(256), 0, s, partials, param_chunk_end, nparams, nchunks,
+                       clip_value, norms, coefs);
+  else if (norm_type == GRAD_NORM_L1)
+    hipLaunchKernelGGL(grad_clip_coef_kernel<GRAD_NORM_L1>, grid, dim3(256), 0, s, partials, param_chunk_end, nparams, nchunks,
+                       clip_value, norms, coefs);
+  else
+    hipLaunchKernelGGL(grad_clip_coef_kernel<GRAD_NORM_INF>, grid, dim3(256), 0, s, partials, param_chunk_end, nparams, nchunks,
+                       clip_value, norms, coefs);
   CTDET_LAUNCH_CHECK();
   return 0;
 }

@@ -1222,3 +1222,44 @@ def sgd_momentum_runs_(param, grad, buf, run_end, run_lr_index, run_wd, lr_table
                                             _ptr(run_lr_index), _ptr(run_wd), _ptr(lr_table), run_end.numel(),
                                             float(momentum), int(bool(first_step)), _stream())
     _lib.check(rc, "ctdet_sgd_momentum_runs")
+
+
+def grad_chunk_norms_(grad, chunk_start, chunk_len, norm_type, partials):
+    """pass 1 of the per-parameter gradient norms: partials[c] = sum g^2 / sum |g| / max |g| (norm_type: _lib.NORM_*) over
+    chunk c of the flat gradient buffer (see ctdet_grad_chunk_norms)"""
+    _require_cuda(grad, chunk_start, chunk_len, partials)
+    assert grad.is_contiguous() and grad.dtype == torch.float32 and partials.dtype == torch.float32
+    assert chunk_start.dtype == torch.int64 and chunk_len.dtype == torch.int32
+    assert chunk_start.numel() == chunk_len.numel() == partials.numel()
+    rc = _lib.lib().ctdet_grad_chunk_norms(_ptr(grad), grad.numel(), _ptr(chunk_start), _ptr(chunk_len), chunk_start.numel(),
+                                           int(norm_type), _ptr(partials), _stream())
+    _lib.check(rc, "ctdet_grad_chunk_norms")
+
+
+def grad_clip_coefs_(partials, param_chunk_end, norm_type, clip_value, norms, coefs):
+    """pass 2: norms[q] from the partials of parameter q's chunks, coefs[q] = min(1, clip_value / (norms[q] + 1e-6))"""
+    _require_cuda(partials, param_chunk_end, norms, coefs)
+    assert param_chunk_end.dtype == torch.int32 and norms.dtype == coefs.dtype == torch.float32
+    assert param_chunk_end.numel() == norms.numel() == coefs.numel()
+    rc = _lib.lib().ctdet_grad_clip_coefs(_ptr(partials), _ptr(param_chunk_end), param_chunk_end.numel(), partials.numel(),
+                                          int(norm_type), float(clip_value), _ptr(norms), _ptr(coefs), _stream())
+    _lib.check(rc, "ctdet_grad_clip_coefs")
+
+
+def sgd_momentum_runs_clip_(param, grad, buf, run_end, run_lr_index, run_wd, lr_table, momentum, first_step, nesterov=False,
+                            clip_type=_lib.CLIP_NONE, clip_value=0.0, coefs=None):
+    """sgd_momentum_runs_ with per-parameter clipping (by value, or by the coefficients of grad_clip_coefs_: one run per
+    parameter then) and / or Nesterov momentum (see ctdet_sgd_momentum_runs_clip); `grad` is left as it is"""
+    _require_cuda(param, grad, buf, run_end, run_lr_index, run_wd, lr_table)
+    assert param.is_contiguous() and grad.is_contiguous() and buf.is_contiguous()
+    assert run_end.dtype == torch.int64 and run_lr_index.dtype == torch.int32
+    if clip_type == _lib.CLIP_NORM:
+        _require_cuda(coefs)
+        assert coefs.dtype == torch.float32 and coefs.numel() == run_end.numel()
+    else:
+        coefs = None
+    rc = _lib.lib().ctdet_sgd_momentum_runs_clip(_ptr(param), _ptr(grad), _ptr(buf), param.numel(), _ptr(run_end),
+                                                 _ptr(run_lr_index), _ptr(run_wd), _ptr(lr_table), run_end.numel(),
+                                                 float(momentum), int(bool(first_step)), int(bool(nesterov)), int(clip_type),
+                                                 float(clip_value), _ptr(coefs), _stream())
+    _lib.check(rc, "ctdet_sgd_momentum_runs_clip")

@@ -356,6 +356,34 @@ int32_t ctdet_sgd_momentum_runs(float* param, const float* grad, float* momentum
                                 const int32_t* run_lr_index, const float* run_weight_decay, const float* lr_table,
                                 int32_t nruns, float momentum, int32_t first_step, void* stream);
 
+/* Per-parameter gradient clipping and Nesterov momentum for the flat step (detectron2/solver/build.py:19-58,134: the
+ * clipper is called with ONE parameter at a time, then torch.optim.SGD(nesterov=...) runs).  Order per element: clip, weight
+ * decay, momentum, Nesterov look-ahead.  `grad` is only read: the clipped gradient exists in registers. */
+enum ctdet_sgd_clip { CTDET_CLIP_NONE = 0, CTDET_CLIP_VALUE = 1, CTDET_CLIP_NORM = 2 };
+enum ctdet_grad_norm { CTDET_NORM_L1 = 1, CTDET_NORM_L2 = 2, CTDET_NORM_INF = 3 };
+
+/* Pass 1 of the per-parameter norms: one f32 partial per chunk (sum g^2, sum |g| or max |g| by norm_type) of the flat
+ * gradient buffer.  Chunk c covers [chunk_start[c], chunk_start[c] + chunk_len[c]) (device i64 / i32 arrays) and lies inside
+ * one parameter; elements outside [0, n) are not read.  No atomics: the same input gives the same bits. */
+int32_t ctdet_grad_chunk_norms(const float* grad, int64_t n, const int64_t* chunk_start, const int32_t* chunk_len,
+                               int32_t nchunks, int32_t norm_type, float* partials, void* stream);
+
+/* Pass 2: parameter q owns the chunks [param_chunk_end[q-1], param_chunk_end[q]) (device i32 array, ascending, last ==
+ * nchunks); its partials are combined in a fixed order into norms[q], and coefs[q] = min(1, clip_value / (norms[q] + 1e-6))
+ * (torch.nn.utils.clip_grad_norm_). */
+int32_t ctdet_grad_clip_coefs(const float* partials, const int32_t* param_chunk_end, int32_t nparams, int32_t nchunks,
+                              int32_t norm_type, float clip_value, float* norms, float* coefs, void* stream);
+
+/* ctdet_sgd_momentum_runs with clip_type (ctdet_sgd_clip) and nesterov: CTDET_CLIP_VALUE clamps every gradient element to
+ * [-clip_value, clip_value]; CTDET_CLIP_NORM scales the gradient of run r by coefs[r] (device f32[nruns]) -- the caller passes
+ * one run per parameter, so that the search that finds a run's learning rate finds its coefficient; coefs is ignored
+ * otherwise.  nesterov: p -= lr * (g' + momentum * buf) with the updated buf.  CTDET_CLIP_NONE without nesterov is
+ * ctdet_sgd_momentum_runs itself. */
+int32_t ctdet_sgd_momentum_runs_clip(float* param, const float* grad, float* momentum_buf, int64_t n, const int64_t* run_end,
+                                     const int32_t* run_lr_index, const float* run_weight_decay, const float* lr_table,
+                                     int32_t nruns, float momentum, int32_t first_step, int32_t nesterov, int32_t clip_type,
+                                     float clip_value, const float* coefs, void* stream);
+
 /* ---- training-side entry points (f32 statistics and weight gradients; activations and activation gradients f16 --
  * the throughput mode -- or f32 -- the reference's precision -- selected by `dtype` (ctdet_dtype) / the descriptor's
  * compute_dtype).  Input gradients of plain convs are ctdet_conv2d_fwd calls with transposed/flipped weights (in_dil

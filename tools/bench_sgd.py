@@ -1,0 +1,132 @@
+#!/usr/bin/env python
+"""Dev tool: time the flat SGD update on DLA-34's parameter layout (about 18.6 M elements, 109 runs, ~300 parameters) for
+{plain, nesterov, value, norm-2, norm-1, norm-inf} -- 200 warm launches, 1000 timed, device events -- and print microseconds,
+achieved GB/s from the bytes a variant must move (the update: 3 reads + 2 writes of 4 B per element; the norm pass: one more
+read) and the share of the HBM bound.  The variants alternate over --rounds, so that a drift of the machine shows as spread
+inside a variant.  Not part of the product or of the tests.
+
+  --lib PATH     an additional "plain" case through another build of libctdet_hip.so (the plain case calls
+                 ctdet_sgd_momentum_runs alone, which every build of ABI 8 has): A/B of the plain path against a parent build
+  --train-step   instead: the f16x3 DLA-34 training step (16 x 512^2, engine/bench_train.py's step) with norm clipping off / on,
+                 a fresh trainer per leg, legs alternating"""
+import argparse
+import ctypes
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+from detectron2_centernet_amd import _lib, ops  # noqa: E402
+from detectron2_centernet_amd.solver.build import FlatSGD, param_groups  # noqa: E402
+
+HBM_PEAK = 8.0e12      # bytes / s (MI355X)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=1000)
+ap.add_argument("--warm", type=int, default=200)
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--lib", default=None)
+ap.add_argument("--train-step", action="store_true")
+ap.add_argument("--steps", type=int, default=40, help="--train-step: timed steps per leg")
+a = ap.parse_args()
+dev = torch.device("cuda:0")
+
+
+def timed(f, warm, reps):
+    for _ in range(warm):
+        f()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        f()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3      # us
+
+
+def train_step_legs():
+    from detectron2_centernet_amd.engine.bench_train import synthetic_batch
+    from detectron2_centernet_amd.engine.train_loop import SimpleTrainer
+
+    batch = synthetic_batch(16, 512, 0, dev)
+    for leg in range(2 * a.rounds):
+        on = leg % 2 == 1
+        model, cfg = bench.build_model("f16x3", dev, seed=1)
+        model.train()
+        cfg.SOLVER.IMS_PER_BATCH = 16
+        if on:
+            cfg.SOLVER.CLIP_GRADIENTS.ENABLED = True
+            cfg.SOLVER.CLIP_GRADIENTS.CLIP_TYPE, cfg.SOLVER.CLIP_GRADIENTS.CLIP_VALUE = "norm", 1.0
+        tr = SimpleTrainer(model, None, cfg)
+        ms = timed(lambda: tr.run_step_tensors(*batch), 8, a.steps) / 1e3
+        clipped = int((tr.optimizer.clip_coefs < 1).sum()) if on else 0
+        print(f"train step f16x3 16x512^2, norm clipping {'on ' if on else 'off'}: {ms:.3f} ms / step  ({tr.graph_state}"
+              f"{f', {clipped} parameters clipped in the last step' if on else ''})", flush=True)
+        del tr, model
+
+
+def main():
+    if a.train_step:
+        return train_step_legs()
+    model, cfg = bench.build_model("f16x3", dev, calibrate=False)
+    groups = param_groups(cfg, model)
+    variants = {"plain": (False, None), "nesterov": (True, None), "value": (False, ("value", 0.01)),
+                "norm-2": (False, ("norm", 1.0, 2.0)), "norm-1": (False, ("norm", 1.0, 1.0)),
+                "norm-inf": (False, ("norm", 1.0, float("inf")))}
+    opts = {k: FlatSGD(groups, 0.01, 0.9, nesterov=n, clip=c) for k, (n, c) in variants.items()}
+    n = opts["plain"].flat_param.numel()
+    g = torch.Generator().manual_seed(0)
+    # per-parameter scale alternating around the L2 clip value, so that about half the parameters clip
+    grad = torch.cat([torch.randn(k, generator=g) * ((0.25 if i % 2 else 4.0) / k ** 0.5)
+                      for i, (_, k) in enumerate(opts["plain"].offsets)]).to(dev)
+
+    def raw_plain(path):
+        h = ctypes.CDLL(path)
+        fn = h.ctdet_sgd_momentum_runs
+        fn.restype, fn.argtypes = _lib.SIGNATURES["ctdet_sgd_momentum_runs"]
+        o = opts["plain"]
+        args = [ctypes.c_void_p(t.data_ptr()) for t in (o.flat_param, grad, o.flat_mom)] + [n] + \
+               [ctypes.c_void_p(t.data_ptr()) for t in (o._run_end, o._run_lr_index, o._run_wd, o._lr_table)] + \
+               [o._run_end.numel(), 0.9, 0]
+
+        def f():
+            rc = fn(*args, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, rc
+        return f
+
+    def variant(o):
+        norm = o._clip_type == _lib.CLIP_NORM
+
+        def f():
+            if norm:
+                ops.grad_chunk_norms_(grad, o._chunk_start, o._chunk_len, o._norm_type, o._partials)
+                ops.grad_clip_coefs_(o._partials, o._param_chunk_end, o._norm_type, o._clip_value, o.grad_norms, o.clip_coefs)
+            ops.sgd_momentum_runs_clip_(o.flat_param, grad, o.flat_mom, o._run_end, o._run_lr_index, o._run_wd, o._lr_table,
+                                        0.9, False, o.nesterov, o._clip_type, o._clip_value, o.clip_coefs)
+        return f
+
+    def norm_pass(o):
+        def f():
+            ops.grad_chunk_norms_(grad, o._chunk_start, o._chunk_len, o._norm_type, o._partials)
+            ops.grad_clip_coefs_(o._partials, o._param_chunk_end, o._norm_type, o._clip_value, o.grad_norms, o.clip_coefs)
+        return f
+
+    cases = [("plain", raw_plain(_lib.LIB_PATH), 20)]
+    if a.lib:
+        cases.append((f"plain [{os.path.basename(os.path.dirname(a.lib)) or a.lib}]", raw_plain(a.lib), 20))
+    cases += [(k, variant(opts[k]), 24 if k.startswith("norm") else 20) for k in list(variants)[1:]]
+    cases.append(("norm-2 pass alone", norm_pass(opts["norm-2"]), 4))
+    print(f"{n} elements, {len(opts['plain'].runs)} runs, {len(groups)} parameters, {opts['norm-2']._chunk_start.numel()} chunks; "
+          f"{a.warm} warm + {a.reps} timed launches per case and round")
+    for r in range(a.rounds):
+        for name, f, bpe in cases:
+            us = timed(f, a.warm, a.reps)
+            by = bpe * n
+            print(f"round {r}  {name:28s} {us:8.2f} us  {by / us / 1e3:8.1f} GB/s  {by / HBM_PEAK * 1e6 / us * 100:5.1f} % of the "
+                  f"HBM bound ({by / 1e6:.0f} MB)", flush=True)
+
+
+main()
