@@ -26,7 +26,7 @@ class ConvDesc(C.Structure):
         "compute_dtype", "out_dtype", "act", "res_stride")] + [("clamp_lo", C.c_float), ("clamp_hi", C.c_float), ("korder", C.c_int32), ("in_dil", C.c_int32)]
 
 
-_vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
+_vp, _i32, _i64, _f32, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
 # name -> (restype, argtypes); must list every symbol declared in include/ctdet_hip.h
 SIGNATURES = {
     "ctdet_last_error": (C.c_char_p, []),
@@ -102,6 +102,9 @@ SIGNATURES = {
     "ctdet_grad_clip_coefs": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "ctdet_sgd_momentum_runs_clip": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _i32, _f32, _vp,
                                              _vp]),
+    "ctdet_adam_advance": (_i32, [_vp, _vp, _f64, _f64, _vp]),
+    "ctdet_adam_runs": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _f64, _f64, _i32, _i32, _i32,
+                               _f32, _vp, _vp]),
     "ctdet_set_tuning_flags": (_i32, [C.c_uint32]),
     "ctdet_get_tuning_flags": (C.c_uint32, []),
     "ctdet_comm_unique_id": (_i32, [_vp]),

@@ -62,6 +62,9 @@ int launch_sgd_runs_clip(float*, const float*, float*, long, const long*, const 
                          int, int, float, const float*, hipStream_t);
 int launch_grad_chunk_norms(const float*, long, const long*, const int*, int, int, float*, hipStream_t);
 int launch_grad_clip_coefs(const float*, const int*, int, int, int, float, float*, float*, hipStream_t);
+int launch_adam_advance(long long*, float*, double, double, hipStream_t);
+int launch_adam_runs(float*, const float*, float*, float*, float*, long, const long*, const int*, const float*, const float*, int,
+                     const float*, double, double, double, int, int, int, float, const float*, hipStream_t);
 static_assert(CTDET_CLIP_NONE == SGD_CLIP_NONE && CTDET_CLIP_VALUE == SGD_CLIP_VALUE && CTDET_CLIP_NORM == SGD_CLIP_NORM &&
               CTDET_NORM_L1 == GRAD_NORM_L1 && CTDET_NORM_L2 == GRAD_NORM_L2 && CTDET_NORM_INF == GRAD_NORM_INF,
               "clip / norm modes: header and kernels disagree");
@@ -832,5 +835,37 @@ int32_t ctdet_sgd_momentum_runs_clip(float* param, const float* grad, float* mom
   return launch_sgd_runs_clip(param, grad, momentum_buf, (long)n, (const long*)run_end, run_lr_index, run_weight_decay, lr_table,
                               nruns, momentum, first_step, nesterov, clip_type, clip_value, coefs, (hipStream_t)stream);
 }
+
+#define CTDET_ADAM_BETAS(what)                                                                                          \
+  CTDET_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, what ": betas (%g, %g) outside [0, 1)", beta1, beta2)
+
+int32_t ctdet_adam_advance(int64_t* step_dev, float* bias_dev, double beta1, double beta2, void* stream) {
+  CTDET_CHECK(step_dev && bias_dev, "adam_advance: null pointer");
+  CTDET_ADAM_BETAS("adam_advance");
+  return launch_adam_advance((long long*)step_dev, bias_dev, beta1, beta2, (hipStream_t)stream);
+}
+
+int32_t ctdet_adam_runs(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                        const int64_t* run_end, const int32_t* run_lr_index, const float* run_weight_decay,
+                        const float* lr_table, int32_t nruns, const float* bias_dev, double beta1, double beta2, double eps,
+                        int32_t decoupled, int32_t amsgrad, int32_t clip_type, float clip_value, const float* coefs,
+                        void* stream) {
+  CTDET_CHECK(param && grad && exp_avg && exp_avg_sq && run_end && run_lr_index && run_weight_decay && lr_table && bias_dev,
+              "adam_runs: null pointer");
+  CTDET_CHECK(!amsgrad || max_exp_avg_sq, "adam_runs: amsgrad needs max_exp_avg_sq");
+  CTDET_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
+                (amsgrad ? (uintptr_t)max_exp_avg_sq : 0)) & 15) == 0,
+              "adam_runs: param, grad and the moment buffers must be 16-byte aligned");
+  CTDET_CHECK(n >= 0 && nruns >= 0, "adam_runs: n=%lld nruns=%d", (long long)n, nruns);
+  CTDET_ADAM_BETAS("adam_runs");
+  CTDET_CHECK(eps > 0.0, "adam_runs: eps %g must be positive", eps);
+  CTDET_CHECK(clip_type >= CTDET_CLIP_NONE && clip_type <= CTDET_CLIP_NORM, "adam_runs: clip type %d", clip_type);
+  CTDET_CHECK(clip_type == CTDET_CLIP_NONE || clip_value > 0.f, "adam_runs: clip value %g", (double)clip_value);
+  CTDET_CHECK(clip_type != CTDET_CLIP_NORM || coefs, "adam_runs: norm clipping needs coefs (one per run)");
+  return launch_adam_runs(param, grad, exp_avg, exp_avg_sq, amsgrad ? max_exp_avg_sq : nullptr, (long)n, (const long*)run_end,
+                          run_lr_index, run_weight_decay, lr_table, nruns, bias_dev, beta1, beta2, eps, decoupled, amsgrad,
+                          clip_type, clip_value, coefs, (hipStream_t)stream);
+}
+#undef CTDET_ADAM_BETAS
 
 }  // extern "C"

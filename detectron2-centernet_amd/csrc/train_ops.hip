@@ -1,4 +1,4 @@
-// Training-side HBM-bound kernels: gaussian target splat, focal loss, masked L1 loss, SGD.
+// Training-side HBM-bound kernels: gaussian target splat, focal loss, masked L1 loss, SGD, Adam / AdamW.
 //   gaussian targets : detectron2/data/detection_utils.py:600-705 (gen_heatmap, gaussian_radius, gaussian2D,
 //                      draw_umich_gaussian) -- the reference runs this per image / per object in numpy on the
 //                      host inside model.forward (centernet.py:188); here one launch covers B x 128 objects.
@@ -567,6 +567,133 @@ int launch_sgd(float* p, const float* g, float* m, long n, const float* lr_dev, 
   long nb = (n + 255) / 256;
   if (nb > 8192) nb = 8192;
   hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)nb), dim3(256), 0, s, p, g, m, n, lr_dev, mom, wd, first);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Adam / AdamW (optionally AMSGrad) over the same flat buffer and run tables: torch.optim.Adam / AdamW, single-tensor
+// non-capturable path, in torch's order per element --
+//   g' = clip(g)                               as in sgd_runs_body: none | value | coefs[run]
+//   ADAM : g' += wd * p   (when wd != 0)       ADAMW: p *= 1 - lr * wd
+//   m = b1 * m + (1 - b1) * g'                 v = b2 * v + (1 - b2) * g'^2
+//   AMSGRAD: vmax = max(vmax, v), vh = vmax    else vh = v
+//   p -= (lr / (1 - b1^t)) * m / (sqrt(vh) / sqrt(1 - b2^t) + eps)
+// The step count t lives in device memory: the captured training step replays optimizer.step() without the host, so a host
+// counter would freeze the bias correction at the value of the capture.  adam_advance_kernel (one thread, first launch of
+// every step) increments it and writes bias[0] = 1 / (1 - b1^t), bias[1] = 1 / sqrt(1 - b2^t), computed in f64; the update
+// kernel reads the two once per thread.  Per element: one sqrt and one division, both correctly rounded (no fast-math).
+// ------------------------------------------------------------------------------------------------
+__global__ void adam_advance_kernel(long long* __restrict__ step, float* __restrict__ bias, double beta1, double beta2) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long long t = step[0] + 1;
+  step[0] = t;
+  bias[0] = (float)(1.0 / (1.0 - pow(beta1, (double)t)));
+  bias[1] = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)t)));
+}
+
+int launch_adam_advance(long long* step, float* bias, double beta1, double beta2, hipStream_t s) {
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, s, step, bias, beta1, beta2);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
+struct AdamScalars {
+  float b1, omb1, b2, omb2, eps, clip_value;
+};
+
+// The layout of sgd_runs_body: a workgroup owns a contiguous range, a thread walks it four elements at a time, the run lookup
+// happens when a thread leaves its run, element-wise at run ends.  Streams per element: p, g, m, v read and p, m, v written
+// (28 B), AMSGrad one more of each (36 B).
+template <int CLIP, bool DECOUPLED, bool AMSGRAD>
+__global__ void __launch_bounds__(256) adam_runs_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ vmax, long n,
+                                                        const long* __restrict__ run_end, const int* __restrict__ run_lr_index,
+                                                        const float* __restrict__ run_wd, const float* __restrict__ lr_table,
+                                                        int nruns, const float* __restrict__ bias, AdamScalars a,
+                                                        const float* __restrict__ coefs) {
+  const long per = (((n + gridDim.x - 1) / gridDim.x) + 1023) & ~1023L;
+  const long beg = (long)blockIdx.x * per, end = beg + per < n ? beg + per : n;
+  const float ibc1 = bias[0], ibc2s = bias[1];
+  long cur_end = -1;
+  float step = 0.f, wd = 0.f, keep = 1.f, cf = 1.f;
+  auto lookup = [&](long i) {
+    int lo = 0, hi = nruns - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (run_end[mid] > i) hi = mid; else lo = mid + 1;
+    }
+    cur_end = run_end[lo];
+    const float lr = lr_table[run_lr_index[lo]];
+    wd = run_wd[lo];
+    step = lr * ibc1;
+    if constexpr (DECOUPLED) keep = (float)(1.0 - (double)lr * (double)wd);   // torch: 1 - lr * weight_decay in f64, rounded once
+    if constexpr (CLIP == SGD_CLIP_NORM) cf = coefs[lo];
+  };
+  // one element: gi, pi, mi, vi, xi (the running maximum) in, the new values out
+  auto update = [&](float gi, float& pi, float& mi, float& vi, float& xi) {
+    if constexpr (CLIP == SGD_CLIP_VALUE) gi = gi > a.clip_value ? a.clip_value : (gi < -a.clip_value ? -a.clip_value : gi);  // NaN stays
+    if constexpr (CLIP == SGD_CLIP_NORM) gi = gi * cf;
+    if constexpr (DECOUPLED) pi = pi * keep;
+    else if (wd != 0.f) gi = gi + wd * pi;
+    mi = a.b1 * mi + a.omb1 * gi;
+    vi = a.b2 * vi + a.omb2 * gi * gi;
+    float vh = vi;
+    if constexpr (AMSGRAD) vh = xi = (vi > xi || vi != vi) ? vi : xi;        // torch.maximum: a NaN on either side stays
+    const float denom = sqrtf(vh) * ibc2s + a.eps;
+    pi = pi - step * (mi / denom);
+  };
+  for (long i = beg + (long)threadIdx.x * 4; i < end; i += 1024) {
+    if (i >= cur_end) lookup(i);
+    if (i + 4 <= cur_end && i + 4 <= end) {
+      const float4 gv = *(const float4*)(g + i), pv = *(const float4*)(p + i), mv = *(const float4*)(m + i),
+                   vv = *(const float4*)(v + i);
+      float4 xv = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (AMSGRAD) xv = *(const float4*)(vmax + i);
+      const float ge[4] = {gv.x, gv.y, gv.z, gv.w};
+      float pe[4] = {pv.x, pv.y, pv.z, pv.w}, me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w},
+            xe[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) update(ge[k], pe[k], me[k], ve[k], xe[k]);
+      *(float4*)(m + i) = make_float4(me[0], me[1], me[2], me[3]);
+      *(float4*)(v + i) = make_float4(ve[0], ve[1], ve[2], ve[3]);
+      if constexpr (AMSGRAD) *(float4*)(vmax + i) = make_float4(xe[0], xe[1], xe[2], xe[3]);
+      *(float4*)(p + i) = make_float4(pe[0], pe[1], pe[2], pe[3]);
+    } else {
+      for (long j = i; j < i + 4 && j < end; ++j) {
+        if (j >= cur_end) lookup(j);
+        float pi = p[j], mi = m[j], vi = v[j], xi = 0.f;
+        if constexpr (AMSGRAD) xi = vmax[j];
+        update(g[j], pi, mi, vi, xi);
+        m[j] = mi;
+        v[j] = vi;
+        if constexpr (AMSGRAD) vmax[j] = xi;
+        p[j] = pi;
+      }
+    }
+  }
+}
+
+int launch_adam_runs(float* p, const float* g, float* m, float* v, float* vmax, long n, const long* run_end,
+                     const int* run_lr_index, const float* run_wd, const float* lr_table, int nruns, const float* bias,
+                     double beta1, double beta2, double eps, int decoupled, int amsgrad, int clip_type, float clip_value,
+                     const float* coefs, hipStream_t s) {
+  if (n == 0 || nruns == 0) return 0;
+  long nb = (n + 1023) / 1024;
+  if (nb > 2048) nb = 2048;
+  // torch hands (1 - beta) to its kernels as an f64 scalar rounded to f32 once: 1.f - (float)beta2 would be 4.7e-5 off
+  const AdamScalars a = {(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, clip_value};
+#define ADAM_CASE(C, D, A)                                                                                             \
+  if (clip_type == C && (decoupled != 0) == D && (amsgrad != 0) == A)                                                  \
+    hipLaunchKernelGGL((adam_runs_kernel<C, D, A>), dim3((unsigned)nb), dim3(256), 0, s, p, g, m, v, vmax, n, run_end, \
+                       run_lr_index, run_wd, lr_table, nruns, bias, a, coefs)
+#define ADAM_CLIP_CASES(C) \
+  ADAM_CASE(C, false, false); ADAM_CASE(C, false, true); ADAM_CASE(C, true, false); ADAM_CASE(C, true, true)
+  ADAM_CLIP_CASES(SGD_CLIP_NONE);
+  ADAM_CLIP_CASES(SGD_CLIP_VALUE);
+  ADAM_CLIP_CASES(SGD_CLIP_NORM);
+#undef ADAM_CLIP_CASES
+#undef ADAM_CASE
   CTDET_LAUNCH_CHECK();
   return 0;
 }

@@ -2,7 +2,7 @@
 
 Reference: torch DistributedDataParallel wrapped around the model (detectron2/engine/defaults.py:279-285; NCCL).
 Here: one process per GPU, `torch.distributed` (backend "nccl" == RCCL on ROCm, "gloo" in the CPU tests); the
-gradients already live in one contiguous buffer in backward order (solver.FlatSGD), cut into a few large buckets
+gradients already live in one contiguous buffer in backward order (solver.FlatSGD / FlatAdam), cut into a few large buckets
 (default 32 MB: one node's xGMI mesh is point-to-point, large messages keep every link busy).  A bucket's
 all-reduce is launched from the autograd hook of the last parameter that becomes ready in it, so communication
 runs while earlier layers are still back-propagating.  Gradients are pre-divided by the world size on the producer

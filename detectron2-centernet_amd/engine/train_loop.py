@@ -129,7 +129,7 @@ class SimpleTrainer:
             self.optimizer.step()
         if train_step.STEP_CHECK == 2:
             self._log_step(9)
-        for p in self.optimizer.params:   # the captured SGD kernels wrote the parameters behind autograd's back
+        for p in self.optimizer.params:   # the captured update kernels (SGD / Adam) wrote the parameters behind autograd's back
             torch.autograd.graph.increment_version(p)
         self.scheduler.step()
         self.iter += 1

@@ -1263,3 +1263,40 @@ def sgd_momentum_runs_clip_(param, grad, buf, run_end, run_lr_index, run_wd, lr_
                                                  float(momentum), int(bool(first_step)), int(bool(nesterov)), int(clip_type),
                                                  float(clip_value), _ptr(coefs), _stream())
     _lib.check(rc, "ctdet_sgd_momentum_runs_clip")
+
+
+def adam_advance_(step_count, bias, beta1, beta2):
+    """the first launch of an Adam step: step_count[0] += 1 (i64, device) and bias = [1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t)]
+    (see ctdet_adam_advance) -- a kernel, so that a captured step keeps counting when it is replayed"""
+    _require_cuda(step_count, bias)
+    assert step_count.dtype == torch.int64 and step_count.numel() == 1
+    assert bias.dtype == torch.float32 and bias.numel() == 2 and bias.is_contiguous()
+    rc = _lib.lib().ctdet_adam_advance(_ptr(step_count), _ptr(bias), float(beta1), float(beta2), _stream())
+    _lib.check(rc, "ctdet_adam_advance")
+
+
+def adam_runs_(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, run_end, run_lr_index, run_wd, lr_table, bias, beta1, beta2,
+               eps, decoupled=False, amsgrad=False, clip_type=_lib.CLIP_NONE, clip_value=0.0, coefs=None):
+    """one launch of Adam (decoupled: AdamW; amsgrad: with the running maximum `max_exp_avg_sq`) over a flat buffer of
+    consecutive hyper-parameter runs, clipped like sgd_momentum_runs_clip_ (see ctdet_adam_runs); `grad` is left as it is,
+    `bias` is what adam_advance_ wrote"""
+    _require_cuda(param, grad, exp_avg, exp_avg_sq, run_end, run_lr_index, run_wd, lr_table, bias)
+    state = [param, grad, exp_avg, exp_avg_sq]
+    if amsgrad:
+        _require_cuda(max_exp_avg_sq)
+        state.append(max_exp_avg_sq)
+    else:
+        max_exp_avg_sq = None
+    assert all(t.is_contiguous() and t.dtype == torch.float32 and t.numel() == param.numel() for t in state)
+    assert run_end.dtype == torch.int64 and run_lr_index.dtype == torch.int32
+    assert bias.dtype == torch.float32 and bias.numel() == 2
+    if clip_type == _lib.CLIP_NORM:
+        _require_cuda(coefs)
+        assert coefs.dtype == torch.float32 and coefs.numel() == run_end.numel()
+    else:
+        coefs = None
+    rc = _lib.lib().ctdet_adam_runs(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(max_exp_avg_sq), param.numel(),
+                                    _ptr(run_end), _ptr(run_lr_index), _ptr(run_wd), _ptr(lr_table), run_end.numel(), _ptr(bias),
+                                    float(beta1), float(beta2), float(eps), int(bool(decoupled)), int(bool(amsgrad)),
+                                    int(clip_type), float(clip_value), _ptr(coefs), _stream())
+    _lib.check(rc, "ctdet_adam_runs")

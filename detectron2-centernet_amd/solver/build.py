@@ -1,4 +1,5 @@
-"""SGD with momentum over flat parameter / gradient / momentum buffers, updated by the HIP kernel `sgd_kernel`.
+"""SGD with momentum -- or Adam / AdamW (SOLVER.OPTIMIZER) -- over flat parameter / gradient / state buffers,
+updated by the HIP kernels `sgd_runs_kernel` / `adam_runs_kernel`.
 
 Hyper-parameter grouping follows detectron2/solver/build.py:93-137: norm-layer parameters use WEIGHT_DECAY_NORM,
 `bias` parameters use BASE_LR*BIAS_LR_FACTOR and WEIGHT_DECAY_BIAS, everything else BASE_LR / WEIGHT_DECAY;
@@ -80,17 +81,22 @@ def _check_clip(clip):
     return _lib.CLIP_NORM, value, norm
 
 
-class FlatSGD:
-    def __init__(self, groups, base_lr, momentum=0.9, device=None, nesterov=False, clip=None):
+class FlatOptimizer:
+    """What the flat optimizers share: the parameters re-pointed into ONE f32 buffer in reverse registration order, the
+    gradient buffer next to it, the runs of equal (lr factor, weight decay) with their device tables, the learning-rate table
+    the schedulers write, the chunk tables and results of per-parameter norm clipping, the zero arena of the weight-gradient
+    accumulators and the plan that re-packs the conv weights after a step.  A subclass adds its state buffers and the update."""
+
+    def __init__(self, groups, base_lr, device=None, clip=None, needs_hip=None):
         """groups: [(param, lr_factor, weight_decay)].  Parameters are re-pointed into one flat buffer.
-        clip: None, ("value", c) or ("norm", c, p) with p in 1, 2, inf -- each parameter clipped on its own (clip_from_cfg)."""
-        self.base_lr, self.momentum, self.nesterov = float(base_lr), float(momentum), bool(nesterov)
+        clip: None, ("value", c) or ("norm", c, p) with p in 1, 2, inf -- each parameter clipped on its own (clip_from_cfg).
+        needs_hip: the refusal for parameters that are not on a ROCm device (None: they are accepted); raised before any
+        parameter is touched"""
+        self.base_lr = float(base_lr)
         self._clip_type, self._clip_value, self._norm_type = _check_clip(clip)
         groups = list(groups)
-        if (self.nesterov or self._clip_type != _lib.CLIP_NONE) and groups and \
-                torch.device(device or groups[0][0].device).type != "cuda":
-            raise NotImplementedError("SOLVER.NESTEROV / SOLVER.CLIP_GRADIENTS live in the HIP update kernel: there is no CPU "
-                                      "implementation of them; the model's parameters must be on a ROCm device")
+        if needs_hip and groups and torch.device(device or groups[0][0].device).type != "cuda":
+            raise NotImplementedError(needs_hip)
         groups = list(reversed(groups))  # heads first: the order gradients become ready in backward
         # contiguous segments per (lr_factor, wd) would break the backward-order layout; instead keep the order and
         # record maximal runs of equal hyper-parameters (a handful for DLA-34: weights / norm+bias alternate per layer
@@ -101,7 +107,6 @@ class FlatSGD:
         total = sum(p.numel() for p in self.params)
         self.flat_param = torch.empty(total, dtype=torch.float32, device=device)
         self.flat_grad = torch.zeros(total, dtype=torch.float32, device=device)
-        self.flat_mom = torch.zeros(total, dtype=torch.float32, device=device)
         self.offsets, self.runs = [], []
         off = 0
         for p, lf, wd in groups:
@@ -138,7 +143,6 @@ class FlatSGD:
             self._partials = torch.zeros(len(starts), dtype=torch.float32, device=device)
             self.grad_norms = torch.zeros(len(self.params), dtype=torch.float32, device=device)
             self.clip_coefs = torch.ones(len(self.params), dtype=torch.float32, device=device)
-        self._first = True
         self.set_lr_factor(1.0)
         # zero-initialised scratch for the atomically accumulated weight gradients (ops_train.ZeroArena): a little larger
         # than the parameter count (channel padding), cleared together with the gradient buffer
@@ -169,6 +173,32 @@ class FlatSGD:
             if p.grad is None or p.grad.data_ptr() != self.flat_grad.data_ptr() + 4 * off:
                 p.grad = p._ctdet_flat_grad = self.flat_grad[off:off + n].view_as(p.data)
 
+    def _clip_coef_launches(self):
+        """norm clipping: the two launches of the per-parameter norms and coefficients, in front of the update"""
+        if self._clip_type == _lib.CLIP_NORM:
+            ops.grad_chunk_norms_(self.flat_grad, self._chunk_start, self._chunk_len, self._norm_type, self._partials)
+            ops.grad_clip_coefs_(self._partials, self._param_chunk_end, self._norm_type, self._clip_value,
+                                 self.grad_norms, self.clip_coefs)
+
+    def _after_update(self):
+        for p in self.params:  # raw-pointer update: tell autograd / the packed-weight caches the values changed
+            torch.autograd.graph.increment_version(p)
+        if self._packs is not None:   # the f16 operands of every conv weight the last step used, in one launch
+            self._packs.run()
+
+
+class FlatSGD(FlatOptimizer):
+    def __init__(self, groups, base_lr, momentum=0.9, device=None, nesterov=False, clip=None):
+        """groups, clip: see FlatOptimizer"""
+        self.momentum, self.nesterov = float(momentum), bool(nesterov)
+        needs_hip = None
+        if self.nesterov or (clip is not None and _check_clip(clip)[0] != _lib.CLIP_NONE):
+            needs_hip = ("SOLVER.NESTEROV / SOLVER.CLIP_GRADIENTS live in the HIP update kernel: there is no CPU "
+                         "implementation of them; the model's parameters must be on a ROCm device")
+        super().__init__(groups, base_lr, device, clip, needs_hip)
+        self.flat_mom = torch.zeros_like(self.flat_param)
+        self._first = True
+
     def step(self):
         """launches only (the step is captured into the training graph): the plain update is one kernel; Nesterov and value
         clipping are variants of it; norm clipping puts the two kernels of the per-parameter norms in front.  `flat_grad` is
@@ -177,18 +207,12 @@ class FlatSGD:
             ops.sgd_momentum_runs_(self.flat_param, self.flat_grad, self.flat_mom, self._run_end, self._run_lr_index,
                                    self._run_wd, self._lr_table, self.momentum, self._first)
         else:
-            if self._clip_type == _lib.CLIP_NORM:
-                ops.grad_chunk_norms_(self.flat_grad, self._chunk_start, self._chunk_len, self._norm_type, self._partials)
-                ops.grad_clip_coefs_(self._partials, self._param_chunk_end, self._norm_type, self._clip_value,
-                                     self.grad_norms, self.clip_coefs)
+            self._clip_coef_launches()
             ops.sgd_momentum_runs_clip_(self.flat_param, self.flat_grad, self.flat_mom, self._run_end, self._run_lr_index,
                                         self._run_wd, self._lr_table, self.momentum, self._first, self.nesterov,
                                         self._clip_type, self._clip_value, self.clip_coefs)
         self._first = False
-        for p in self.params:  # raw-pointer update: tell autograd / the packed-weight caches the values changed
-            torch.autograd.graph.increment_version(p)
-        if self._packs is not None:   # the f16 operands of every conv weight the last step used, in one launch
-            self._packs.run()
+        self._after_update()
 
     def state_dict(self):
         return {"momentum": self.flat_mom.clone(), "first": self._first}
@@ -204,6 +228,9 @@ class FlatSGD:
             return
         if "state" not in sd or "param_groups" not in sd:
             raise KeyError("optimizer state: neither FlatSGD's {'momentum', 'first'} nor a torch.optim.SGD state dict")
+        if any("exp_avg" in st for st in sd["state"].values()):
+            raise KeyError("optimizer state: FlatSGD expects 'momentum_buffer' entries (torch.optim.SGD), this one holds "
+                           "'exp_avg' (torch.optim.Adam / AdamW: SOLVER.OPTIMIZER)")
         order = [i for g in sd["param_groups"] for i in g["params"]]
         if len(order) != len(self.params):
             raise ValueError(f"optimizer state holds {len(order)} parameters, the model has {len(self.params)} trainable ones")
@@ -223,9 +250,132 @@ class FlatSGD:
         self._first = loaded == 0
 
 
+def adam_state_from_torch(sd, numels, amsgrad=False):
+    """A `torch.optim.Adam` / `AdamW` state dict ({"state": {i: {"step", "exp_avg", "exp_avg_sq"[, "max_exp_avg_sq"]}},
+    "param_groups": [{"params": [indices], ...}]}, one group per parameter in module order, as FlatSGD.load_state_dict assumes
+    for SGD) -> FlatAdam's own {"exp_avg", "exp_avg_sq", ["max_exp_avg_sq"], "step"}: flat f32 CPU buffers in the order of
+    `numels`, the element counts of FlatAdam's parameters -- the REVERSED module order.  A pure function (no device).
+    `step` (an int or a tensor) must be the same for every parameter that has a state, since the flat step keeps one count;
+    a parameter without a state (torch creates it at the parameter's first gradient) gets zeros."""
+    if "state" not in sd or "param_groups" not in sd:
+        raise KeyError("optimizer state: neither FlatAdam's {'exp_avg', 'exp_avg_sq', 'step'} nor a torch.optim.Adam / AdamW "
+                       "state dict")
+    order = [i for g in sd["param_groups"] for i in g["params"]]
+    numels = list(numels)
+    if len(order) != len(numels):
+        raise ValueError(f"optimizer state holds {len(order)} parameters, the model has {len(numels)} trainable ones")
+    names = ["exp_avg", "exp_avg_sq"] + (["max_exp_avg_sq"] if amsgrad else [])
+    pieces, steps = {k: [] for k in names}, set()
+    for k in reversed(range(len(order))):           # module index k sits at position len - 1 - k of the flat buffer
+        st, n = sd["state"].get(order[k], {}), numels[len(order) - 1 - k]
+        if st:
+            missing = [key for key in names + ["step"] if key not in st]
+            if missing:
+                raise KeyError(f"optimizer state of parameter {order[k]}: FlatAdam expects {names + ['step']} "
+                               f"(torch.optim.Adam / AdamW{', amsgrad=True' if amsgrad else ''}), {missing} missing; it holds "
+                               f"{sorted(st)}")
+            steps.add(int(st["step"]))
+        for key in names:
+            buf = st.get(key) if st else None
+            if buf is None:
+                buf = torch.zeros(n)
+            if buf.numel() != n:
+                raise ValueError(f"{key} {order[k]}: {buf.numel()} elements, parameter has {n}")
+            pieces[key].append(buf.detach().reshape(-1).to("cpu", torch.float32))
+    if len(steps) > 1:
+        raise ValueError(f"optimizer state: per-parameter step counts {sorted(steps)}; the flat Adam step keeps one count for "
+                         "all parameters")
+    out = {key: torch.cat(v) if v else torch.zeros(0) for key, v in pieces.items()}
+    out["step"] = steps.pop() if steps else 0
+    return out
+
+
+def _check_adam(betas, eps):
+    """torch.optim.Adam's own refusals, in its words"""
+    betas = tuple(float(b) for b in betas)
+    if len(betas) != 2:
+        raise ValueError(f"SOLVER.ADAM.BETAS must hold two values, got {betas}")
+    if not float(eps) > 0.0:           # torch's words; torch lets eps == 0 through, the entry point does not
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    for i, b in enumerate(betas):
+        if not 0.0 <= b < 1.0:
+            raise ValueError(f"Invalid beta parameter at index {i}: {b}")
+    return betas, float(eps)
+
+
+class FlatAdam(FlatOptimizer):
+    """torch.optim.Adam (decoupled=False: weight decay added to the gradient) / AdamW (decoupled=True: p *= 1 - lr * wd),
+    optionally AMSGrad, single-tensor order, over the flat buffers: `exp_avg`, `exp_avg_sq`, `max_exp_avg_sq` (None without
+    amsgrad) and ONE step count for all parameters, `step_count`, which lives on the device -- the single-GPU training graph
+    replays step() without the host, so the kernels advance it.  A parameter whose gradient is zero is still
+    stepped (weight decay, decaying moments): the flat buffer has no "grad is None", as in FlatSGD.  SOLVER.MOMENTUM is not
+    read.  There is no CPU implementation."""
+
+    def __init__(self, groups, base_lr, betas=(0.9, 0.999), eps=1e-8, decoupled=False, amsgrad=False, clip=None, device=None):
+        """groups, clip: see FlatOptimizer"""
+        self.betas, self.eps = _check_adam(betas, eps)
+        self.decoupled, self.amsgrad = bool(decoupled), bool(amsgrad)
+        super().__init__(groups, base_lr, device, clip,
+                         needs_hip="SOLVER.OPTIMIZER ADAM / ADAMW live in the HIP update kernel: there is no CPU implementation "
+                                   "of them; the model's parameters must be on a ROCm device")
+        self.exp_avg = self.flat_mom = torch.zeros_like(self.flat_param)     # flat_mom: the name engine/bench_train.py reads
+        self.exp_avg_sq = torch.zeros_like(self.flat_param)
+        self.max_exp_avg_sq = torch.zeros_like(self.flat_param) if self.amsgrad else None
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=self.flat_param.device)
+        self._bias = torch.ones(2, dtype=torch.float32, device=self.flat_param.device)   # written by every step's first launch
+
+    def step(self):
+        """launches only: the step count and bias corrections (one thread), [the two kernels of the per-parameter norms],
+        the update.  `flat_grad` is read, never written"""
+        ops.adam_advance_(self.step_count, self._bias, *self.betas)
+        self._clip_coef_launches()
+        ops.adam_runs_(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq, self._run_end,
+                       self._run_lr_index, self._run_wd, self._lr_table, self._bias, self.betas[0], self.betas[1], self.eps,
+                       self.decoupled, self.amsgrad, self._clip_type, self._clip_value, self.clip_coefs)
+        self._after_update()
+
+    def _state_names(self):
+        return ["exp_avg", "exp_avg_sq"] + (["max_exp_avg_sq"] if self.amsgrad else [])
+
+    def state_dict(self):
+        """reading the step count waits for the device"""
+        sd = {k: getattr(self, k).clone() for k in self._state_names()}
+        sd["step"] = int(self.step_count.item())
+        return sd
+
+    def load_state_dict(self, sd):
+        """this optimizer's own state, or a `torch.optim.Adam` / `AdamW` state dict (adam_state_from_torch)"""
+        if "momentum" in sd or any("momentum_buffer" in st for st in sd.get("state", {}).values()):
+            raise KeyError(f"optimizer state: FlatAdam expects {self._state_names() + ['step']} or a torch.optim.Adam / AdamW "
+                           "state dict, this one is an SGD state (momentum)")
+        if "exp_avg" not in sd:
+            sd = adam_state_from_torch(sd, [n for _, n in self.offsets], self.amsgrad)
+        missing = [k for k in self._state_names() + ["step"] if k not in sd]
+        if missing:
+            raise KeyError(f"optimizer state: FlatAdam expects {self._state_names() + ['step']}, {missing} missing")
+        for k in self._state_names():
+            getattr(self, k).copy_(sd[k])
+        self.step_count.fill_(int(sd["step"]))
+
+
+OPTIMIZERS = ("SGD", "ADAM", "ADAMW")
+
+
 def build_optimizer(cfg, model):
-    """solver/build.py:93-137: torch.optim.SGD(momentum, nesterov) behind maybe_add_gradient_clipping.  What the kernels do
-    not implement is refused instead of being silently dropped: a NORM_TYPE other than 1, 2, inf, and either option for
-    parameters that are not on a ROCm device."""
-    return FlatSGD(param_groups(cfg, model), cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM,
-                   nesterov=cfg.SOLVER.get("NESTEROV", False), clip=clip_from_cfg(cfg))
+    """solver/build.py:93-137: torch.optim.SGD(momentum, nesterov) behind maybe_add_gradient_clipping; with SOLVER.OPTIMIZER
+    ADAM / ADAMW (keys the reference does not have) torch.optim.Adam / AdamW(SOLVER.ADAM.BETAS, EPS, AMSGRAD) behind the same
+    clipping.  What the kernels do not implement is refused instead of being silently dropped: a NORM_TYPE other than 1, 2,
+    inf, either SGD option or Adam for parameters that are not on a ROCm device, and NESTEROV with Adam (SOLVER.MOMENTUM is
+    simply not read there: beta1 takes its place)."""
+    name = cfg.SOLVER.get("OPTIMIZER", "SGD")
+    if name not in OPTIMIZERS:
+        raise ValueError(f"SOLVER.OPTIMIZER: {name!r} is not one of {', '.join(OPTIMIZERS)}")
+    if name == "SGD":
+        return FlatSGD(param_groups(cfg, model), cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM,
+                       nesterov=cfg.SOLVER.get("NESTEROV", False), clip=clip_from_cfg(cfg))
+    if cfg.SOLVER.get("NESTEROV", False):
+        raise ValueError(f"SOLVER.NESTEROV: True has no meaning for SOLVER.OPTIMIZER: {name} (Nesterov momentum is an option "
+                         "of SGD)")
+    adam = cfg.SOLVER.ADAM
+    return FlatAdam(param_groups(cfg, model), cfg.SOLVER.BASE_LR, betas=adam.BETAS, eps=adam.EPS, decoupled=name == "ADAMW",
+                    amsgrad=adam.AMSGRAD, clip=clip_from_cfg(cfg))

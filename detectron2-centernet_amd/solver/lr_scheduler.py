@@ -27,7 +27,7 @@ def warmup_cosine_factor(it, max_iters, warmup_factor, warmup_iters, warmup_meth
 
 
 class WarmupMultiStepLR:
-    """scheduler over a FlatSGD: `step()` advances one iteration and writes the new learning rates."""
+    """scheduler over a flat optimizer (FlatSGD / FlatAdam): `step()` advances one iteration and writes the new learning rates."""
 
     def __init__(self, optimizer, milestones, gamma=0.1, warmup_factor=0.001, warmup_iters=1000, warmup_method="linear",
                  last_epoch=-1):
@@ -55,7 +55,7 @@ class WarmupMultiStepLR:
 
 
 class WarmupCosineLR(WarmupMultiStepLR):
-    """lr_scheduler.py:52-87 over a FlatSGD (MAX_ITER iterations)"""
+    """lr_scheduler.py:52-87 over a flat optimizer (MAX_ITER iterations)"""
 
     def __init__(self, optimizer, max_iters, warmup_factor=0.001, warmup_iters=1000, warmup_method="linear", last_epoch=-1):
         self.optimizer, self.max_iters = optimizer, max_iters

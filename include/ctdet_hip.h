@@ -384,6 +384,24 @@ int32_t ctdet_sgd_momentum_runs_clip(float* param, const float* grad, float* mom
                                      int32_t nruns, float momentum, int32_t first_step, int32_t nesterov, int32_t clip_type,
                                      float clip_value, const float* coefs, void* stream);
 
+/* torch.optim.Adam / AdamW (optionally AMSGrad) over the same flat buffer and run tables, single-tensor order per element:
+ *   g' = clip(g) as above;  Adam: g' += wd*p (wd != 0), AdamW (decoupled): p *= 1 - lr*wd;
+ *   m = b1*m + (1-b1)*g';  v = b2*v + (1-b2)*g'^2;  amsgrad: vmax = max(vmax, v), vh = vmax, else vh = v;
+ *   p -= (lr / (1-b1^t)) * m / (sqrt(vh) / sqrt(1-b2^t) + eps)
+ * The step count t is a device counter, so that a captured step keeps counting when it is replayed: the first call below
+ * increments step_dev[0] (i64) and writes bias_dev[0] = 1/(1-b1^t), bias_dev[1] = 1/sqrt(1-b2^t) (f64 arithmetic, stored
+ * f32) from one thread; the second reads bias_dev.  betas in [0, 1). */
+int32_t ctdet_adam_advance(int64_t* step_dev, float* bias_dev, double beta1, double beta2, void* stream);
+
+/* param, grad, exp_avg, exp_avg_sq and (amsgrad) max_exp_avg_sq: f32[n], 16-byte aligned; max_exp_avg_sq may be NULL
+ * without amsgrad.  Runs, lr_table, clip_type / clip_value / coefs as in ctdet_sgd_momentum_runs_clip; `grad` is only read.
+ * A zero gradient still steps its element (weight decay): the flat buffer has no "grad is None". */
+int32_t ctdet_adam_runs(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                        const int64_t* run_end, const int32_t* run_lr_index, const float* run_weight_decay,
+                        const float* lr_table, int32_t nruns, const float* bias_dev, double beta1, double beta2, double eps,
+                        int32_t decoupled, int32_t amsgrad, int32_t clip_type, float clip_value, const float* coefs,
+                        void* stream);
+
 /* ---- training-side entry points (f32 statistics and weight gradients; activations and activation gradients f16 --
  * the throughput mode -- or f32 -- the reference's precision -- selected by `dtype` (ctdet_dtype) / the descriptor's
  * compute_dtype).  Input gradients of plain convs are ctdet_conv2d_fwd calls with transposed/flipped weights (in_dil
