@@ -44,10 +44,13 @@ SIGNATURES = {
     "ctdet_dcnv2_fwd_cols": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_dcnv2_offset_fwd": (_i32, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_preprocess": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "ctdet_preprocess_mirror": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ctdet_head_fused_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "ctdet_head_fused_x3_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_dla_base_fwd": (_i32, [_vp] * 14),
     "ctdet_dla_base_x3_fwd": (_i32, [_vp] * 14),
+    "ctdet_dla_base_mirror_fwd": (_i32, [_vp, _i32] + [_vp] * 13),
+    "ctdet_dla_base_x3_mirror_fwd": (_i32, [_vp, _i32] + [_vp] * 13),
     "ctdet_maxpool2x2": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_maxpool3x3s2": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_maxpool3x3s2_ceil": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
@@ -64,6 +67,7 @@ SIGNATURES = {
     "ctdet_dwconv3x3_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_decode_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "ctdet_decode": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctdet_decode_flip": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_postprocess": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_decode_status": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ctdet_gaussian_targets": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -29,7 +29,7 @@ bool ctdet_set_label(const char* fmt, ...) {
 
 // launchers from the kernel files
 int launch_preprocess(const void*, int, void*, int, int, int, int, int, int, long, const float*, const float*, int, int,
-                      hipStream_t);
+                      int mirror_from, hipStream_t);
 int launch_maxpool2x2(const void*, void*, int, int, int, int, int, int, int, hipStream_t);
 int launch_maxpool3x3s2(const void*, void*, int, int, int, int, int, int, int, int, hipStream_t);
 int launch_global_avgpool(const void*, int, int, int, int, int, float*, hipStream_t);
@@ -44,7 +44,7 @@ int launch_dwconv3x3(const void*, int, const float*, void*, int, int, int, int, 
 int launch_dwconv3x3_wgrad(const void*, int, const void*, int, float*, float*, float, int, int, int, int, int, int, hipStream_t);
 size_t decode_workspace_bytes(int B, int H, int W, int C, int K);
 int decode_status_words(int H, int W, int C, int K, long* ws_words, int* below_word);
-int launch_decode(const DecArgs&, hipStream_t);
+int launch_decode(const DecArgs&, bool flip, hipStream_t);
 int launch_postprocess(const float*, const float*, const int*, int, int, int, float, const float*, float*, float*, int*,
                        int*, hipStream_t);
 int launch_gaussian_radius(const int*, int, double*, int*, hipStream_t);
@@ -326,7 +326,16 @@ int32_t ctdet_preprocess(const void* img, int32_t img_dtype, void* out, int32_t 
                          const float* std3, int32_t out_stride, int32_t border, void* stream) {
   CTDET_CHECK(img && out && mean3 && std3, "preprocess: null pointer");
   return launch_preprocess(img, img_dtype, out, out_dtype, B, H, W, Hp, Wp, (long)img_batch_stride, mean3, std3,
-                           out_stride, border, (hipStream_t)stream);
+                           out_stride, border, -1, (hipStream_t)stream);
+}
+
+int32_t ctdet_preprocess_mirror(const void* img, int32_t img_dtype, void* out, int32_t out_dtype, int32_t B, int32_t H,
+                                int32_t W, int32_t Hp, int32_t Wp, int64_t img_batch_stride, const float* mean3,
+                                const float* std3, int32_t out_stride, int32_t border, int32_t mirror_from, void* stream) {
+  CTDET_CHECK(img && out && mean3 && std3, "preprocess: null pointer");
+  CTDET_CHECK(mirror_from >= 0 && mirror_from <= B, "preprocess: mirror_from=%d outside [0, B=%d]", mirror_from, B);
+  return launch_preprocess(img, img_dtype, out, out_dtype, B, H, W, Hp, Wp, (long)img_batch_stride, mean3, std3,
+                           out_stride, border, mirror_from, (hipStream_t)stream);
 }
 
 // the head descriptor -> HeadArgs (everything but the first conv's operands)
@@ -366,10 +375,12 @@ int32_t ctdet_head_fused_x3_fwd(const ctdet_head_desc* d, const void* x, const v
   return launch_head_fused_x3(a, (hipStream_t)stream);
 }
 
-int32_t ctdet_dla_base_fwd(const ctdet_dla_base_desc* d, const void* images, const void* w_stem, const float* scale_stem,
-                           const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
-                           const void* w_l1, const float* scale_l1, const float* bias_l1, void* out, void* pooled,
-                           void* stream) {
+// mirror_from < 0: the plain kernels; otherwise output images [mirror_from, B) are computed from the mirrored network input
+// of source images [0, B - mirror_from)
+static int32_t dla_base_entry(const ctdet_dla_base_desc* d, int mirror_from, const void* images, const void* w_stem,
+                              const float* scale_stem, const float* bias_stem, const void* w_l0, const float* scale_l0,
+                              const float* bias_l0, const void* w_l1, const float* scale_l1, const float* bias_l1,
+                              void* out, void* pooled, void* stream) {
   CTDET_CHECK(d && images && w_stem && scale_stem && bias_stem && w_l0 && scale_l0 && bias_l0 && w_l1 && scale_l1 && bias_l1 &&
               out, "dla_base: null pointer");
   BaseArgs a = {};
@@ -381,13 +392,32 @@ int32_t ctdet_dla_base_fwd(const ctdet_dla_base_desc* d, const void* images, con
   a.w2 = w_l1; a.s2 = scale_l1; a.b2 = bias_l1;
   a.y = out; a.out_stride = d->out_stride;
   a.pool = pooled; a.pool_stride = d->pool_stride;
+  a.mirror_from = mirror_from;
   return launch_dla_base(a, (hipStream_t)stream);
 }
 
-int32_t ctdet_dla_base_x3_fwd(const ctdet_dla_base_desc* d, const void* images, const void* w_stem, const float* scale_stem,
-                              const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
-                              const void* w_l1, const float* scale_l1, const float* bias_l1, float* out, float* pooled,
-                              void* stream) {
+int32_t ctdet_dla_base_fwd(const ctdet_dla_base_desc* d, const void* images, const void* w_stem, const float* scale_stem,
+                           const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
+                           const void* w_l1, const float* scale_l1, const float* bias_l1, void* out, void* pooled,
+                           void* stream) {
+  return dla_base_entry(d, -1, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1, bias_l1, out,
+                        pooled, stream);
+}
+
+int32_t ctdet_dla_base_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirror_from, const void* images, const void* w_stem,
+                                  const float* scale_stem, const float* bias_stem, const void* w_l0, const float* scale_l0,
+                                  const float* bias_l0, const void* w_l1, const float* scale_l1, const float* bias_l1,
+                                  void* out, void* pooled, void* stream) {
+  CTDET_CHECK(d && mirror_from >= 0 && mirror_from <= d->B, "dla_base: mirror_from=%d outside [0, B=%d]", mirror_from,
+              d ? d->B : 0);
+  return dla_base_entry(d, mirror_from, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1,
+                        bias_l1, out, pooled, stream);
+}
+
+static int32_t dla_base_x3_entry(const ctdet_dla_base_desc* d, int mirror_from, const void* images, const void* w_stem,
+                                 const float* scale_stem, const float* bias_stem, const void* w_l0, const float* scale_l0,
+                                 const float* bias_l0, const void* w_l1, const float* scale_l1, const float* bias_l1,
+                                 float* out, float* pooled, void* stream) {
   CTDET_CHECK(d && images && w_stem && scale_stem && bias_stem && w_l0 && scale_l0 && bias_l0 && w_l1 && scale_l1 && bias_l1 &&
               out, "dla_base(f16x3): null pointer");
   BaseArgs a = {};
@@ -399,7 +429,26 @@ int32_t ctdet_dla_base_x3_fwd(const ctdet_dla_base_desc* d, const void* images, 
   a.w2 = w_l1; a.s2 = scale_l1; a.b2 = bias_l1;
   a.y = out; a.out_stride = d->out_stride;
   a.pool = pooled; a.pool_stride = d->pool_stride;
+  a.mirror_from = mirror_from;
   return launch_dla_base_x3(a, (hipStream_t)stream);
+}
+
+int32_t ctdet_dla_base_x3_fwd(const ctdet_dla_base_desc* d, const void* images, const void* w_stem, const float* scale_stem,
+                              const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
+                              const void* w_l1, const float* scale_l1, const float* bias_l1, float* out, float* pooled,
+                              void* stream) {
+  return dla_base_x3_entry(d, -1, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1, bias_l1,
+                           out, pooled, stream);
+}
+
+int32_t ctdet_dla_base_x3_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirror_from, const void* images,
+                                     const void* w_stem, const float* scale_stem, const float* bias_stem, const void* w_l0,
+                                     const float* scale_l0, const float* bias_l0, const void* w_l1, const float* scale_l1,
+                                     const float* bias_l1, float* out, float* pooled, void* stream) {
+  CTDET_CHECK(d && mirror_from >= 0 && mirror_from <= d->B, "dla_base(f16x3): mirror_from=%d outside [0, B=%d]", mirror_from,
+              d ? d->B : 0);
+  return dla_base_x3_entry(d, mirror_from, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1,
+                           bias_l1, out, pooled, stream);
 }
 
 int32_t ctdet_maxpool2x2(const void* x, void* y, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -508,10 +557,10 @@ size_t ctdet_decode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, 
   return decode_workspace_bytes(B, H, W, C, K);
 }
 
-int32_t ctdet_decode(const float* heat, int32_t heat_stride, const float* wh, int32_t wh_stride, const float* reg,
-                     int32_t reg_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, float down_ratio,
-                     float heat_floor, void* workspace, float* boxes, float* scores, int32_t* classes, int32_t* inds,
-                     void* stream) {
+static int32_t decode_entry(bool flip, const float* heat, int32_t heat_stride, const float* wh, int32_t wh_stride,
+                            const float* reg, int32_t reg_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K,
+                            float down_ratio, float heat_floor, void* workspace, float* boxes, float* scores,
+                            int32_t* classes, int32_t* inds, void* stream) {
   CTDET_CHECK(heat && wh && workspace && boxes && scores && classes, "decode: null pointer");
   CTDET_CHECK(B >= 0 && H > 0 && W > 0, "decode: bad shape B=%d H=%d W=%d", B, H, W);
   CTDET_CHECK(heat_floor >= 0.f && heat_floor < 1.f, "decode: heat_floor %g outside [0, 1)", (double)heat_floor);
@@ -520,7 +569,23 @@ int32_t ctdet_decode(const float* heat, int32_t heat_stride, const float* wh, in
   a.B = B; a.H = H; a.W = W; a.C = C; a.K = K; a.down_ratio = down_ratio;
   memcpy(&a.floor_bits, &heat_floor, 4);
   a.ws = (uint32_t*)workspace; a.boxes = boxes; a.scores = scores; a.classes = classes; a.inds = inds;
-  return launch_decode(a, (hipStream_t)stream);
+  return launch_decode(a, flip, (hipStream_t)stream);
+}
+
+int32_t ctdet_decode(const float* heat, int32_t heat_stride, const float* wh, int32_t wh_stride, const float* reg,
+                     int32_t reg_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, float down_ratio,
+                     float heat_floor, void* workspace, float* boxes, float* scores, int32_t* classes, int32_t* inds,
+                     void* stream) {
+  return decode_entry(false, heat, heat_stride, wh, wh_stride, reg, reg_stride, B, H, W, C, K, down_ratio, heat_floor,
+                      workspace, boxes, scores, classes, inds, stream);
+}
+
+int32_t ctdet_decode_flip(const float* heat, int32_t heat_stride, const float* wh, int32_t wh_stride, const float* reg,
+                          int32_t reg_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, float down_ratio,
+                          float heat_floor, void* workspace, float* boxes, float* scores, int32_t* classes, int32_t* inds,
+                          void* stream) {
+  return decode_entry(true, heat, heat_stride, wh, wh_stride, reg, reg_stride, B, H, W, C, K, down_ratio, heat_floor,
+                      workspace, boxes, scores, classes, inds, stream);
 }
 
 int32_t ctdet_postprocess(const float* boxes, const float* scores, const int32_t* classes, int32_t B, int32_t K,

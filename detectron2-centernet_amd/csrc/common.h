@@ -122,6 +122,10 @@ struct BaseArgs {
   int out_stride;
   void* pool;             // optional f16 [B,Hp/4,Wp/4,pool_stride]: 2x2 max-pool of y
   int pool_stride;
+  // flip test: < 0 = none (the plain kernels).  Otherwise output images [mirror_from, B) are computed from the horizontally
+  // mirrored network input of SOURCE images [0, B - mirror_from): input column x reads image column Wp-1-x (zero where that
+  // is >= W, so the zero padding sits on the left); output images below mirror_from read their own source image, plain
+  int mirror_from;
 };
 int launch_dla_base(const BaseArgs& a, hipStream_t s);
 int launch_dla_base_x3(const BaseArgs& a, hipStream_t s);   // f16x3: w* = ctdet_pack_weights_x3 layout 0 images, y / pool f32

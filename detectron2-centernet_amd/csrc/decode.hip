@@ -25,6 +25,15 @@
 // has fewer than K peaks above the floor, takes the floor peaks of lowest flat index straight from the map -- the same
 // entries in the same order the canonical rule selects.  A positive value below the floor breaks the caller's promise
 // and is reported through the status word (ctdet_decode_status: -EINVAL).
+//
+// Flip test (the FLIP instantiations, ctdet_decode_flip): heat / wh / reg hold 2B images, image b + B being the network's
+// answer to the horizontally mirrored input of image b.  The map that is decoded is
+//   hm = (hm[b] + mirror(hm[b + B])) * 0.5f,  wh = (wh[b] + mirror(wh[b + B])) * 0.5f,  reg = reg[b]
+// (one f32 add, one multiply, in that order; mirror: x <-> W-1-x).  The merged heat map is never stored: the tile loader
+// reads both halves -- the mirrored one as the same 16-byte channel vectors, pixel x of the tile from pixel W-1-x of the
+// row, so a wave still covers whole contiguous pixel rows (C * 4 bytes each), only in descending pixel order -- and puts
+// the merged value into LDS; the few direct reads of dec_final_kernel (fill path) merge the same way, and wh is merged
+// at the K gathered positions.  Both inputs are >= the clamp floor, so is their mean: the floor promise carries over.
 #include "common.h"
 
 #define DEC_CAP 2048            // max uncertain candidates carried to the final sort
@@ -168,6 +177,12 @@ __device__ __forceinline__ bool dec_selected(const DecSel& r, uint32_t bits, uin
   return (dec_key(bits, canon) & r.care) >= r.want;
 }
 
+// one value of the mirror-merged map: the mean of the heat map (hb) and the mirrored second half (hb2)
+__device__ __forceinline__ float dec_heat_flip(const float* hb, const float* hb2, int W, int stride, int pix, int cls) {
+  const int x = pix % W;
+  return (hb[(long)pix * stride + cls] + hb2[(long)(pix - x + (W - 1 - x)) * stride + cls]) * 0.5f;
+}
+
 // geometry of the tile pass: TW = 16 columns, TH rows and CW channels per workgroup.  One thread owns one (tile column
 // incl. halo, 4-channel vector): 18 * CW/4 <= DEC_TNT, and both LDS images -- the (TH+2) x 18 x CW f32 tile and, after
 // the peak test, the compact peak list (u32 score bits + u16 position per possible peak) -- fit DEC_LDS_TILE
@@ -191,7 +206,7 @@ __global__ void __launch_bounds__(256) dec_init_kernel(DecArgs a, long ws_words)
   if (threadIdx.x < DEC_ST_WORDS) ws[threadIdx.x] = 0;
 }
 
-template <int TH>
+template <int TH, bool FLIP>
 __global__ void __launch_bounds__(DEC_TNT, 4) dec_tile_kernel(DecArgs a, int CW, int tiles_x, int tiles_y, long ws_words, int cap) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   uint32_t* lh = (uint32_t*)dsm;                    // DEC_HIST words
@@ -205,6 +220,7 @@ __global__ void __launch_bounds__(DEC_TNT, 4) dec_tile_kernel(DecArgs a, int CW,
   constexpr int PW = DEC_TW + 2;
   const int HW = a.H * a.W;
   const float* hb = a.heat + (long)b * HW * a.heat_stride;
+  const float* hb2 = FLIP ? a.heat + (long)(b + a.B) * HW * a.heat_stride : nullptr;     // the mirrored pass of image b
   const bool vec = (a.heat_stride & 3) == 0;
   const int t = threadIdx.x, lane = t & 63;
   // this thread's column of the tile (px = 0 and 17 are the halo columns) and its 4 channels
@@ -230,6 +246,26 @@ __global__ void __launch_bounds__(DEC_TNT, 4) dec_tile_kernel(DecArgs a, int CW,
           for (int e = 0; e < 4; ++e) if (c + e < a.C) v[r][e] = src[e];
         }
       }
+    }
+    if constexpr (FLIP) {
+      // column x of the merged map needs column W-1-x of the mirrored pass: the same channel vector of another pixel of
+      // the row.  Positions that stay -1 (outside the image, channels >= C) are -1 in both: (-1 + -1) * 0.5 = -1
+      f32x4 m[TH + 2];
+#pragma unroll
+      for (int r = 0; r < TH + 2; ++r) {
+        const int y = y0 + r - 1;
+        m[r] = (f32x4){-1.f, -1.f, -1.f, -1.f};
+        if (col_ok && y >= 0 && y < a.H) {
+          const float* src = hb2 + (long)(y * a.W + (a.W - 1 - x)) * a.heat_stride + c;
+          if (vec && c + 4 <= a.C) m[r] = *(const f32x4*)src;
+          else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (c + e < a.C) m[r][e] = src[e];
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < TH + 2; ++r) v[r] = (v[r] + m[r]) * 0.5f;
     }
 #pragma unroll
     for (int r = 0; r < TH + 2; ++r) *(f32x4*)(tile + (long)(r * PW + px) * CW + cv * 4) = v[r];
@@ -326,6 +362,7 @@ __global__ void __launch_bounds__(DEC_TNT, 4) dec_tile_kernel(DecArgs a, int CW,
 }
 
 // one workgroup per image: exact top K of the candidate list, bitonic sort (descending) of the finalists, boxes
+template <bool FLIP>
 __global__ void __launch_bounds__(1024) dec_final_kernel(DecArgs a, long ws_words, int cap) {
   __shared__ uint64_t keys[DEC_NCAND];
   __shared__ uint32_t lh[DEC_HIST];
@@ -382,20 +419,23 @@ __global__ void __launch_bounds__(1024) dec_final_kernel(DecArgs a, long ws_word
   if (n < (uint32_t)a.K) {
     __shared__ uint32_t sh_got, wcnt[16];
     const float* hb = a.heat + (long)b * HW * a.heat_stride;
+    const float* hb2 = FLIP ? a.heat + (long)(b + a.B) * HW * a.heat_stride : nullptr;   // the mirrored pass of image b
     const uint32_t total = (uint32_t)a.C * (uint32_t)HW, need = (uint32_t)a.K - n;
     const int lane = t & 63, wv = t >> 6;
     // value at canon position c and whether it is a 3x3 peak (positive, equal to the window maximum)
     auto probe = [&](uint32_t c, float& v) -> bool {
       const int cls = (int)(c / (uint32_t)HW), pix = (int)(c % (uint32_t)HW);
       const int x = pix % a.W, y = pix / a.W;
-      v = hb[(long)pix * a.heat_stride + cls];
+      if constexpr (FLIP) v = dec_heat_flip(hb, hb2, a.W, a.heat_stride, pix, cls);
+      else v = hb[(long)pix * a.heat_stride + cls];
       if (!(v > 0.f)) return false;
       bool peak = true;
       for (int dy = -1; dy <= 1; ++dy)
         for (int dx = -1; dx <= 1; ++dx) {
           const int yy = y + dy, xx = x + dx;
           if (yy < 0 || yy >= a.H || xx < 0 || xx >= a.W) continue;
-          peak &= hb[(long)(yy * a.W + xx) * a.heat_stride + cls] <= v;
+          if constexpr (FLIP) peak &= dec_heat_flip(hb, hb2, a.W, a.heat_stride, yy * a.W + xx, cls) <= v;
+          else peak &= hb[(long)(yy * a.W + xx) * a.heat_stride + cls] <= v;
         }
       return peak;
     };
@@ -408,6 +448,7 @@ __global__ void __launch_bounds__(1024) dec_final_kernel(DecArgs a, long ws_word
         if (c < total) {
           const int cls = (int)(c / (uint32_t)HW), pix = (int)(c % (uint32_t)HW);
           float v = hb[(long)pix * a.heat_stride + cls];
+          if constexpr (FLIP) v = dec_heat_flip(hb, hb2, a.W, a.heat_stride, pix, cls);
           if (__float_as_uint(v) == a.floor_bits) on = probe(c, v);
         }
         const unsigned long long m = __ballot(on);
@@ -460,7 +501,14 @@ __global__ void __launch_bounds__(1024) dec_final_kernel(DecArgs a, long ws_word
     float xs = (float)x, ys = (float)y;
     if (a.reg) { xs = xs + a.reg[pix * a.reg_stride]; ys = ys + a.reg[pix * a.reg_stride + 1]; }
     else { xs += 0.5f; ys += 0.5f; }
-    const float w = a.wh[pix * a.wh_stride], h = a.wh[pix * a.wh_stride + 1];
+    const float w0 = a.wh[pix * a.wh_stride], h0 = a.wh[pix * a.wh_stride + 1];
+    float wm = w0, hm = h0;
+    if constexpr (FLIP) {     // size map: mean with the mirrored pass; the offsets above are the plain pass's alone
+      const long mpix = (long)(b + a.B) * HW + (ind - x) + (a.W - 1 - x);
+      wm = (w0 + a.wh[mpix * a.wh_stride]) * 0.5f;
+      hm = (h0 + a.wh[mpix * a.wh_stride + 1]) * 0.5f;
+    }
+    const float w = wm, h = hm;
     const long o = (long)b * a.K + k;
     a.boxes[o * 4 + 0] = (xs - w / 2) * a.down_ratio;
     a.boxes[o * 4 + 1] = (ys - h / 2) * a.down_ratio;
@@ -539,7 +587,8 @@ int decode_status_words(int H, int W, int C, int K, long* ws_words, int* below_w
   return ST_OVERFLOW;
 }
 
-int launch_decode(const DecArgs& a, hipStream_t s) {
+// flip: heat / wh / reg hold 2 * a.B images and the mirror-merged maps are decoded (see the head of this file)
+int launch_decode(const DecArgs& a, bool flip, hipStream_t s) {
   CTDET_CHECK(a.C >= 1 && a.heat_stride >= a.C, "decode: C=%d / heat_stride=%d invalid", a.C, a.heat_stride);
   CTDET_CHECK(a.K >= 1 && a.K <= 1024 && a.K - 1 + DEC_CAP <= DEC_NCAND, "decode: K=%d out of range", a.K);
   CTDET_CHECK((long)a.C * a.H * a.W < (1L << 24), "decode: C*H*W too large for the 24-bit index field");
@@ -554,13 +603,23 @@ int launch_decode(const DecArgs& a, hipStream_t s) {
   CTDET_CHECK((DEC_TW + 2) * (g.CW / 4) <= DEC_TNT && g.CW <= 112, "decode: tile geometry");
   hipLaunchKernelGGL(dec_init_kernel, dim3(a.B), dim3(256), 0, s, a, words);
   const dim3 grid(g.tiles_x * g.tiles_y * g.cchunks, a.B);
-  switch (g.TH) {
-    case 8: hipLaunchKernelGGL(dec_tile_kernel<8>, grid, dim3(DEC_TNT), lds, s, a, g.CW, g.tiles_x, g.tiles_y, words, (int)cap); break;
-    case 4: hipLaunchKernelGGL(dec_tile_kernel<4>, grid, dim3(DEC_TNT), lds, s, a, g.CW, g.tiles_x, g.tiles_y, words, (int)cap); break;
-    case 2: hipLaunchKernelGGL(dec_tile_kernel<2>, grid, dim3(DEC_TNT), lds, s, a, g.CW, g.tiles_x, g.tiles_y, words, (int)cap); break;
-    default: hipLaunchKernelGGL(dec_tile_kernel<1>, grid, dim3(DEC_TNT), lds, s, a, g.CW, g.tiles_x, g.tiles_y, words, (int)cap); break;
-  }
-  hipLaunchKernelGGL(dec_final_kernel, dim3(a.B), dim3(1024), 0, s, a, words, (int)cap);
+#define DEC_TILE(TH_, FLIP_)                                                                                          \
+  hipLaunchKernelGGL((dec_tile_kernel<TH_, FLIP_>), grid, dim3(DEC_TNT), lds, s, a, g.CW, g.tiles_x, g.tiles_y, words, \
+                     (int)cap)
+#define DEC_RUN(FLIP_)                                                                                       \
+  do {                                                                                                       \
+    switch (g.TH) {                                                                                          \
+      case 8: DEC_TILE(8, FLIP_); break;                                                                     \
+      case 4: DEC_TILE(4, FLIP_); break;                                                                     \
+      case 2: DEC_TILE(2, FLIP_); break;                                                                     \
+      default: DEC_TILE(1, FLIP_); break;                                                                    \
+    }                                                                                                        \
+    hipLaunchKernelGGL((dec_final_kernel<FLIP_>), dim3(a.B), dim3(1024), 0, s, a, words, (int)cap);          \
+  } while (0)
+  if (flip) DEC_RUN(true);
+  else DEC_RUN(false);
+#undef DEC_RUN
+#undef DEC_TILE
   CTDET_LAUNCH_CHECK();
   return 0;
 }

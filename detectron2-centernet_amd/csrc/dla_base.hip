@@ -18,6 +18,12 @@
 //   level1  same, stride 2, two cout tiles paired so a lane stores 8 consecutive couts (16 bytes).
 // Regions are walked as flat runs of 16 pixels (pixel index / region width by constant division), so odd region widths
 // waste only the tail of the last tile.
+//
+// Flip test (the MIRROR instantiations, BaseArgs::mirror_from >= 0): output images b >= mirror_from are computed from the
+// horizontally mirrored network input of source image b - mirror_from -- the input window's column X of the Hp x Wp frame
+// reads image column Wp-1-X, zero where that is >= W (the mirror of the right-hand zero padding sits on the left).  The
+// caller's image batch is read in place, twice; no mirrored copy of it exists.  Interior windows of byte images keep their
+// dword loads: the same four bytes of a plane row, taken in reverse order when they are converted.
 #include "common.h"
 #include <type_traits>
 
@@ -63,7 +69,7 @@ __device__ __forceinline__ unsigned load_u32_unaligned(const void* p) {
 }
 }  // namespace
 
-template <typename TIn>
+template <typename TIn, bool MIRROR>
 __global__ void __launch_bounds__(256, 2) dla_base_fused_kernel(const BaseArgs a, int ntiles) {
   __shared__ __attribute__((aligned(16))) char inb[(NIN + IN_PAD) * 8];   // [pixel][4 ch] normalised input window
   __shared__ __attribute__((aligned(16))) char stb[2 * STP];              // [plane][pixel][8 ch] stem outputs
@@ -135,6 +141,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_fused_kernel(const BaseArgs a
   unsigned raw[IN_ROUNDS * raw1C];
   unsigned okmask = 0;
   bool raw_fast = false;
+  bool raw_mir = false;          // MIRROR: the fetched window belongs to a mirrored output image
   auto tile_origin = [&](int tile, int& ox, int& oy, int& b) {
     ox = (tile % tiles_x) * T1W;
     oy = ((tile / tiles_x) % tiles_y) * T1H;
@@ -143,17 +150,26 @@ __global__ void __launch_bounds__(256, 2) dla_base_fused_kernel(const BaseArgs a
   auto fetch = [&](int tile) {
     int ox, oy, b;
     tile_origin(tile, ox, oy, b);
-    const TIn* img = (const TIn*)a.img + (long)b * a.img_batch_stride;
+    int sb = b;                  // source image
+    if constexpr (MIRROR) {
+      raw_mir = b >= a.mirror_from;
+      if (raw_mir) sb = b - a.mirror_from;
+    }
+    const TIn* img = (const TIn*)a.img + (long)sb * a.img_batch_stride;
     const int y0 = 2 * oy - 5, x0 = 2 * ox - 5;
+    // mirrored: window column wc is image column xm0 - wc; a dword of the fast path then holds window columns 4g+3 .. 4g
+    const int xm0 = a.Wp - 1 - x0;
     // every byte the fast path touches lies inside the image rows (it reads 3 bytes past the window's last column)
-    raw_fast = BYTES && y0 >= 0 && y0 + INH <= a.H && x0 >= 0 && x0 + 4 * FAST_PER_ROW <= a.W;
+    raw_fast = BYTES && y0 >= 0 && y0 + INH <= a.H &&
+               (raw_mir ? xm0 < a.W && xm0 - 4 * FAST_PER_ROW + 1 >= 0 : x0 >= 0 && x0 + 4 * FAST_PER_ROW <= a.W);
     if (raw_fast) {
+      const int xf = raw_mir ? xm0 - 3 : x0, gs = raw_mir ? -4 : 4;
 #pragma unroll
       for (int i = 0; i < FAST_ROUNDS; ++i) {
         const int e = min(tid + 256 * i, FAST_N - 1);
         const int c = e / (INH * FAST_PER_ROW), rem = e - c * (INH * FAST_PER_ROW);
         const int wr = rem / FAST_PER_ROW, g = rem - wr * FAST_PER_ROW;
-        raw[i] = load_u32_unaligned((const char*)img + c * plane + (long)(y0 + wr) * a.W + x0 + 4 * g);
+        raw[i] = load_u32_unaligned((const char*)img + c * plane + (long)(y0 + wr) * a.W + xf + gs * g);
       }
     } else {
       okmask = 0;
@@ -161,7 +177,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_fused_kernel(const BaseArgs a
       for (int i = 0; i < IN_ROUNDS; ++i) {
         const int pid = tid + 256 * i;
         const int wr = pid / INW, wc = pid - wr * INW;
-        const int Y = y0 + wr, X = x0 + wc;
+        const int Y = y0 + wr, X = raw_mir ? xm0 - wc : x0 + wc;
         const bool ok = pid < NIN && Y >= 0 && Y < a.H && X >= 0 && X < a.W;
         const int Yc = Y < 0 ? 0 : (Y >= a.H ? a.H - 1 : Y), Xc = X < 0 ? 0 : (X >= a.W ? a.W - 1 : X);
         const TIn* p = img + (long)Yc * a.W + Xc;
@@ -186,7 +202,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_fused_kernel(const BaseArgs a
         const int npx = e < FAST_N ? (g == FAST_PER_ROW - 1 ? INW - 4 * (FAST_PER_ROW - 1) : 4) : 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-          if (k < npx) *(f16*)(dst + k * 8) = lut[c * 256 + ((raw[i] >> (8 * k)) & 255u)];
+          if (k < npx) *(f16*)(dst + k * 8) = lut[c * 256 + ((raw[i] >> (8 * (raw_mir ? 3 - k : k))) & 255u)];
       }
     } else {
 #pragma unroll
@@ -363,11 +379,21 @@ int launch_dla_base(const BaseArgs& a, hipStream_t s) {
   const long want = 2L * ncu;
   const unsigned blocks = (unsigned)(tiles < want ? tiles : want);
   CTDET_CHECK(a.img_dtype == CTDET_U8 || a.img_dtype == CTDET_F32, "dla_base: image dtype %d (want u8 or f32)", a.img_dtype);
+  CTDET_CHECK(a.mirror_from <= a.B, "dla_base: mirror_from=%d outside [0, B=%d]", a.mirror_from, a.B);
+  if (a.mirror_from >= 0) {
+    CTDET_KERNEL("dla_base_fused_kernel<u8|f32 -> 32ch,f16,mirror>");
+    if (a.img_dtype == CTDET_U8)
+      hipLaunchKernelGGL((dla_base_fused_kernel<uint8_t, true>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
+    else
+      hipLaunchKernelGGL((dla_base_fused_kernel<float, true>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
+    CTDET_LAUNCH_CHECK();
+    return 0;
+  }
   CTDET_KERNEL("dla_base_fused_kernel<u8|f32 -> 32ch,f16>");
   if (a.img_dtype == CTDET_U8)
-    hipLaunchKernelGGL((dla_base_fused_kernel<uint8_t>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
+    hipLaunchKernelGGL((dla_base_fused_kernel<uint8_t, false>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
   else
-    hipLaunchKernelGGL((dla_base_fused_kernel<float>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
+    hipLaunchKernelGGL((dla_base_fused_kernel<float, false>), dim3(blocks), dim3(256), 0, s, a, (int)tiles);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -461,7 +487,7 @@ __device__ __forceinline__ f32x4 x3_mma(const f16x8 w, const f16x8 h, f32x4 acc)
 #endif
 }
 
-template <typename TIn>
+template <typename TIn, bool MIRROR>
 __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, int ntiles) {
   __shared__ __attribute__((aligned(16))) char stb[4 * X3_STP];    // [plane][pixel]{hi[4], lo[4]} stem outputs
   __shared__ __attribute__((aligned(16))) char l0b[4 * X3_L0P];    // the input window, then the level0 outputs
@@ -486,9 +512,12 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
   // ---- input window: rows 2oy-5 .. 2oy+19, columns 2ox-5 .. 2ox+35 of the image; zero outside it (also inside the padded
   // map: the reference pads the NORMALISED batch with zeros, centernet.py:193-200 + ImageList) ----
   {
-    const TIn* img = (const TIn*)a.img + (long)b * a.img_batch_stride;
+    // MIRROR, output image b >= mirror_from: source image b - mirror_from, window column wx = image column ixm - wx
+    bool mir = false;
+    if constexpr (MIRROR) mir = b >= a.mirror_from;
+    const TIn* img = (const TIn*)a.img + (long)(mir ? b - a.mirror_from : b) * a.img_batch_stride;
     const long plane = (long)a.H * a.W;
-    const int iy0 = 2 * oy - 5, ix0 = 2 * ox - 5;
+    const int iy0 = 2 * oy - 5, ix0 = 2 * ox - 5, ixm = a.Wp - 1 - ix0;
     float* lut = (float*)stb;
     constexpr int ROUNDS = (NIN + 255) / 256;
     // tap column 7 (zero weights) of the window's last row reads the pixels behind it: finite values wanted
@@ -501,7 +530,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
       for (int i = 0; i < ROUNDS; ++i) {
         const int p = tid + 256 * i;
         const int wy = p / INW, wx = p - wy * INW;
-        const int y = iy0 + wy, x = ix0 + wx;
+        const int y = iy0 + wy, x = mir ? ixm - wx : ix0 + wx;
         rawpx[i] = 0xffffffffu;
         if (p < NIN && y >= 0 && y < a.H && x >= 0 && x < a.W) {
           const TIn* s = img + (long)y * a.W + x;
@@ -528,7 +557,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
         const int p = tid + 256 * i;
         if (p < NIN) {
           const int wy = p / INW, wx = p - wy * INW;
-          const int y = iy0 + wy, x = ix0 + wx;
+          const int y = iy0 + wy, x = mir ? ixm - wx : ix0 + wx;
           f32x4 v = {0.f, 0.f, 0.f, 0.f};
           if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
             const TIn* s = img + (long)y * a.W + x;
@@ -709,11 +738,21 @@ int launch_dla_base_x3(const BaseArgs& a, hipStream_t s) {
   if (tiles == 0) return 0;
   CTDET_CHECK(tiles < (1L << 31), "dla_base(f16x3): too many tiles");
   CTDET_CHECK(a.img_dtype == CTDET_U8 || a.img_dtype == CTDET_F32, "dla_base(f16x3): image dtype %d (want u8 or f32)", a.img_dtype);
+  CTDET_CHECK(a.mirror_from <= a.B, "dla_base(f16x3): mirror_from=%d outside [0, B=%d]", a.mirror_from, a.B);
+  if (a.mirror_from >= 0) {
+    CTDET_KERNEL("dla_base_x3_kernel<u8|f32 -> 32ch,f16x3,mirror>");
+    if (a.img_dtype == CTDET_U8)
+      hipLaunchKernelGGL((dla_base_x3_kernel<uint8_t, true>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
+    else
+      hipLaunchKernelGGL((dla_base_x3_kernel<float, true>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
+    CTDET_LAUNCH_CHECK();
+    return 0;
+  }
   CTDET_KERNEL("dla_base_x3_kernel<u8|f32 -> 32ch,f16x3>");
   if (a.img_dtype == CTDET_U8)
-    hipLaunchKernelGGL((dla_base_x3_kernel<uint8_t>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
+    hipLaunchKernelGGL((dla_base_x3_kernel<uint8_t, false>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
   else
-    hipLaunchKernelGGL((dla_base_x3_kernel<float>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
+    hipLaunchKernelGGL((dla_base_x3_kernel<float, false>), dim3((unsigned)tiles), dim3(256), 0, s, a, (int)tiles);
   CTDET_LAUNCH_CHECK();
   return 0;
 }

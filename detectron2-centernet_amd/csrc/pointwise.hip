@@ -1,16 +1,19 @@
 // HBM-bound helper kernels of the DLA-34 forward path (NHWC, 16-byte vector accesses).
 //   preprocess   : CenterNet.preprocess_image  (detectron2/modeling/meta_arch/centernet.py:173-185)
 //                  x/255, (x-mean)/std, zero pad to size_divisibility, CHW -> NHWC(8 ch, 3 used)
+//                  MIRROR (flip test, ctdet_preprocess_mirror): output image b >= mirror_from is the horizontal mirror of
+//                  the padded network input of source image b - mirror_from -- column x holds source column Wp-1-x, zero
+//                  where that is >= W, so the zero padding sits on the left
 //   maxpool2x2   : Tree.downsample = nn.MaxPool2d(stride)   (detectron2/modeling/backbone/dla.py:128-129,139)
 //   dwconvT_add  : IDAUp `up_i` depthwise ConvTranspose2d(k=2f, s=f, p=f/2, groups=C) fused with the
 //                  `layers[i] + layers[i-1]` that feeds `node_i`  (dla.py:162-177)
 #include "common.h"
 
-template <typename TIn, typename TOut>
+template <typename TIn, typename TOut, bool MIRROR = false>
 __global__ void __launch_bounds__(256) preprocess_kernel(const TIn* __restrict__ img, TOut* __restrict__ out, int B,
                                                          int H, int W, int Hp, int Wp, long img_batch_stride,
                                                          float m0, float m1, float m2, float s0, float s1, float s2,
-                                                         int out_stride, int border) {
+                                                         int out_stride, int border, int mirror_from = 0) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const long total = (long)B * Hp * Wp;
   if (idx >= total) return;
@@ -19,8 +22,12 @@ __global__ void __launch_bounds__(256) preprocess_kernel(const TIn* __restrict__
   const int hy = (int)(t % Hp);
   const int b = (int)(t / Hp);
   float v[3] = {0.f, 0.f, 0.f};
-  if (hy < H && wx < W) {
-    const TIn* p = img + (long)b * img_batch_stride + (long)hy * W + wx;
+  int sb = b, sx = wx;      // source image and column
+  if constexpr (MIRROR) {
+    if (b >= mirror_from) { sb = b - mirror_from; sx = Wp - 1 - wx; }
+  }
+  if (hy < H && sx < W) {
+    const TIn* p = img + (long)sb * img_batch_stride + (long)hy * W + sx;
     const long plane = (long)H * W;
     // same operation order as the reference: (x / 255 - mean) / std, fp32
     v[0] = ((float)p[0] / 255.f - m0) / s0;
@@ -277,17 +284,28 @@ __global__ void __launch_bounds__(256) dwconvT_add_rows_kernel(const T* __restri
 
 static inline unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
 
+// mirror_from < 0: the plain kernel; otherwise output images [mirror_from, B) are mirrored copies of source images
+// [0, B - mirror_from)
 int launch_preprocess(const void* img, int img_dtype, void* out, int out_dtype, int B, int H, int W, int Hp, int Wp,
                       long img_batch_stride, const float* mean, const float* stdv, int out_stride, int border,
-                      hipStream_t s) {
+                      int mirror_from, hipStream_t s) {
   CTDET_CHECK((out_stride >= 8 && out_stride % 8 == 0) || (out_stride == 4 && out_dtype == CTDET_F32),
               "preprocess: out_stride=%d must be a multiple of 8 (or 4 for f32 output)", out_stride);
   CTDET_CHECK(Hp >= H && Wp >= W && border >= 0, "preprocess: padded size smaller than image");
+  CTDET_CHECK(mirror_from <= B, "preprocess: mirror_from=%d outside [0, B=%d]", mirror_from, B);
   const long total = (long)B * Hp * Wp;
   if (total == 0) return 0;
-#define PP(TI, TO)                                                                                               \
-  hipLaunchKernelGGL((preprocess_kernel<TI, TO>), dim3(nblk(total)), dim3(256), 0, s, (const TI*)img, (TO*)out, \
-                     B, H, W, Hp, Wp, img_batch_stride, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], out_stride, border)
+#define PP(TI, TO)                                                                                                       \
+  do {                                                                                                                   \
+    if (mirror_from < 0)                                                                                                 \
+      hipLaunchKernelGGL((preprocess_kernel<TI, TO>), dim3(nblk(total)), dim3(256), 0, s, (const TI*)img, (TO*)out, B,  \
+                         H, W, Hp, Wp, img_batch_stride, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2],           \
+                         out_stride, border, 0);                                                                        \
+    else                                                                                                                 \
+      hipLaunchKernelGGL((preprocess_kernel<TI, TO, true>), dim3(nblk(total)), dim3(256), 0, s, (const TI*)img,         \
+                         (TO*)out, B, H, W, Hp, Wp, img_batch_stride, mean[0], mean[1], mean[2], stdv[0], stdv[1],       \
+                         stdv[2], out_stride, border, mirror_from);                                                     \
+  } while (0)
   if (img_dtype == CTDET_U8 && out_dtype == CTDET_F16) PP(uint8_t, f16);
   else if (img_dtype == CTDET_U8 && out_dtype == CTDET_F32) PP(uint8_t, float);
   else if (img_dtype == CTDET_F32 && out_dtype == CTDET_F16) PP(float, f16);

@@ -2,7 +2,11 @@
 `convert_inputs` (host: normalise + pad + stack) -> `inference` (the network: {images, im_info} -> {hm after sigmoid+clamp,
 wh, reg}) -> `convert_outputs` (decode + per-image filtering + detector_postprocess).  The reference traces `inference` to
 ONNX/TensorRT; here the same three stages run on the HIP kernels, so a serving stack built around that contract can call
-them unchanged.  Tensors are logical NCHW like the reference's (views of the NHWC device buffers)."""
+them unchanged.  Tensors are logical NCHW like the reference's (views of the NHWC device buffers).
+
+flip=True serves CenterNet's flip test (modeling/test_time_augmentation.py) through the same three stages: `convert_inputs`
+appends the mirrored network input of image b at b + B, `inference` runs the 2B images, `convert_outputs` decodes the
+mirror-merged maps -- B results, equal to CenterNetWithTTA's."""
 import torch
 
 from ..layers import hipnn
@@ -10,14 +14,14 @@ from ..modeling.postprocessing import detector_postprocess
 
 
 class CenterNetModel:
-    def __init__(self, cfg, torch_model):
+    def __init__(self, cfg, torch_model, flip=False):
         from ..modeling.meta_arch.centernet import CenterNet
         assert isinstance(torch_model, CenterNet)
-        self._cfg, self._wrapped_model = cfg, torch_model
+        self._cfg, self._wrapped_model, self._flip = cfg, torch_model, bool(flip)
         torch_model.eval()
 
     def convert_inputs(self, batched_inputs):
-        images, _ = self._wrapped_model.preprocess_image(batched_inputs)
+        images, _ = self._wrapped_model.preprocess_image(batched_inputs, flip=self._flip)
         return {"images": images.tensor, "im_info": torch.tensor(images.image_sizes), "_nhwc": getattr(images, "nhwc", None)}
 
     @torch.no_grad()
@@ -31,7 +35,7 @@ class CenterNetModel:
 
     def convert_outputs(self, batched_inputs, inputs, results):
         sizes = [tuple(int(v) for v in s) for s in inputs["im_info"]]
-        per_image = self._wrapped_model.inference(results, sizes)
+        per_image = self._wrapped_model.inference(results, sizes, flip=self._flip)
         out = []
         for r, inp, size in zip(per_image, batched_inputs, sizes):
             out.append({"instances": detector_postprocess(r, inp.get("height", size[0]), inp.get("width", size[1]))})

@@ -233,12 +233,12 @@ class DLA(Backbone):
             self.__dict__[key] = hit
         return hit[1]
 
-    def base_level1(self, images, mean, std, Hp, Wp, out=None, pooled=None, x3=False):
+    def base_level1(self, images, mean, std, Hp, Wp, out=None, pooled=None, x3=False, mirror=False):
         """images: [B,3,H,W] uint8/f32 device batch (not normalised) -> level1 output [B,Hp/2,Wp/2,32] NHWC (f16; f32 with
         x3: f16x3 arithmetic), computed by the fused base kernel (normalisation, base_layer, level0, level1); level 0 is never
         materialised.  pooled: optional [B,Hp/4,Wp/4,32] buffer for the 2x2 max-pool of the output (level2's down-sampled
-        input)."""
-        return ops.dla_base_fused(images, mean, std, Hp, Wp, self._packed_base(x3), out=out, pooled=pooled)
+        input).  mirror: ops.dla_base_fused's flip-test forms ("both": 2B output images, plain then mirrored)."""
+        return ops.dla_base_fused(images, mean, std, Hp, Wp, self._packed_base(x3), out=out, pooled=pooled, mirror=mirror)
 
     def hip_forward_level1(self, x, ctx, pooled=None):
         """the six level outputs given level1's (level 0 is None); pooled: MaxPool2d(2) of x when already computed"""

@@ -58,8 +58,9 @@ MAX_ENGINES = 16   # captured eval graphs kept per model (least recently used go
 SIGMOID_CLAMP = (ops.SIGMOID_CLAMP_FLOOR, 1.0 - ops.SIGMOID_CLAMP_FLOOR)
 
 
-def _engine_key(fused_base, B, H, W, Hp, Wp, img_dtype):
-    return (B, Hp, Wp, img_dtype) if fused_base else (B, H, W, Hp, Wp, img_dtype)
+def _engine_key(fused_base, B, H, W, Hp, Wp, img_dtype, flip=False):
+    key = (B, Hp, Wp, img_dtype) if fused_base else (B, H, W, Hp, Wp, img_dtype)
+    return key + ("flip",) if flip else key      # a plain and a flip-test engine of one shape live side by side
 
 
 class _EvalEngine:
@@ -67,29 +68,40 @@ class _EvalEngine:
 
     The model is held through a weak reference (model -> _engines -> engine -> model would be a cycle that only the
     cyclic collector frees -- possibly in the middle of a later stream capture, which aborts the process): an engine
-    dropped from the model's cache dies right there, by reference count, outside any capture."""
+    dropped from the model's cache dies right there, by reference count, outside any capture.
 
-    def __init__(self, model, B, H, W, Hp, Wp, img_dtype, use_graph=True):
+    flip: CenterNet's flip test (TEST.AUG.FLIP) in the same one graph.  The network runs on 2B images -- the B inputs and
+    the horizontal mirrors of their NETWORK INPUT, i.e. of the normalised tensor after right/bottom zero padding: mirrored
+    image b has column x equal to column Wp-1-x of the plain one, its zero padding on the left, so every output map is the
+    exact mirror (x <-> W_out-1-x) of what the mirrored scene gives, for sizes that are multiples of 32 or not.  The mirrored
+    half is produced by the kernels that read the images (fused DLA base / preprocess), never as a copy of the batch.  The
+    decode merges inside its one pass over the maps: hm = (hm[b] + mirror(hm[b+B])) * 0.5 on the sigmoid-and-clamped maps,
+    wh = (wh[b] + mirror(wh[b+B])) * 0.5, reg = reg[b]; peak NMS, top-K, decode and everything after run once, on B images
+    (img_params, _post() and the handles are those of a plain engine; the finite flag covers both halves)."""
+
+    def __init__(self, model, B, H, W, Hp, Wp, img_dtype, use_graph=True, flip=False):
         import weakref
         self._model = weakref.ref(model)
         dev = model.device
-        self.B, self.img_dtype = B, img_dtype
+        self.B, self.img_dtype, self.flip = B, img_dtype, bool(flip)
+        NB = 2 * B if flip else B            # images the network runs on
+        self._mirror = "both" if flip else False
         self.img_params = torch.zeros(B, 4, dtype=torch.float32, device=dev)
         # DLA-34: normalisation + base_layer + level0 + level1 run as one kernel straight from the image batch
         self.fused_base = model.backbone_type == "dla34" and model.backbone.images_fusable(model._ctx, Hp, Wp)
         # the base kernel runs outside the captured graph and reads the caller's image batch in place, whatever its
         # unpadded size: the graph only depends on the padded size
-        self.key = _engine_key(self.fused_base, B, H, W, Hp, Wp, img_dtype)
+        self.key = _engine_key(self.fused_base, B, H, W, Hp, Wp, img_dtype, flip)
         self.images = torch.zeros(B, 3, H, W, dtype=img_dtype, device=dev)
         # otherwise: normalised input with a 3-pixel zero frame (the 7x7 stem's padding), cleared once, interior rewritten
         # per call
         self.border = int(getattr(model.backbone, "stem_border", 3))      # VoVNet's 3x3 stem pads in the kernel: 0
         # f32 tensors (f32 / f16x3 modes), DLA-34: 4-channel pixels (3 used) halve the 7x7 stem's K
         xch = 4 if (model._ctx.dtype == torch.float32 and model.backbone_type == "dla34") else 8
-        self.xpad = None if self.fused_base else torch.zeros(B, Hp + 2 * self.border, Wp + 2 * self.border, xch,
+        self.xpad = None if self.fused_base else torch.zeros(NB, Hp + 2 * self.border, Wp + 2 * self.border, xch,
                                                              dtype=model._ctx.dtype, device=dev)
-        self.l1 = torch.empty(B, Hp // 2, Wp // 2, 32, dtype=model._ctx.dtype, device=dev) if self.fused_base else None
-        self.l1p = torch.empty(B, Hp // 4, Wp // 4, 32, dtype=model._ctx.dtype, device=dev) if self.fused_base else None
+        self.l1 = torch.empty(NB, Hp // 2, Wp // 2, 32, dtype=model._ctx.dtype, device=dev) if self.fused_base else None
+        self.l1p = torch.empty(NB, Hp // 4, Wp // 4, 32, dtype=model._ctx.dtype, device=dev) if self.fused_base else None
         self.graph = None
         self.Hp, self.Wp = Hp, Wp
         if self.fused_base:
@@ -135,18 +147,21 @@ class _EvalEngine:
     def _base(self, images):
         m = self.model
         m.backbone.base.base_level1(images, m._mean_host, m._std_host, self.Hp, self.Wp, out=self.l1, pooled=self.l1p,
-                                    x3=m._ctx.compute == ops.F16X3)
+                                    x3=m._ctx.compute == ops.F16X3, mirror=self._mirror)
 
     def _run(self):
         m = self.model
         if self.fused_base:
             self.out = m._network_outputs(None, apply_sigmoid=True, level1=(self.l1, self.l1p))
         else:
-            x = ops.preprocess(self.images, m._mean_host, m._std_host, self.Hp, self.Wp, out=self.xpad, border=self.border)
+            x = ops.preprocess(self.images, m._mean_host, m._std_host, self.Hp, self.Wp, out=self.xpad, border=self.border,
+                               mirror=self._mirror)
             self.out = m._network_outputs(x, apply_sigmoid=True, prepadded=self.border > 0)
         hm, wh, reg = self.out
         # the head kernel's epilogue has just clamped hm to [1e-4, 1 - 1e-4]: the decode may skip the floor plateau
-        self.dec = ops.decode(hm, wh, reg, m.topk_candidates, m.backbone.down_ratio, heat_floor=ops.SIGMOID_CLAMP_FLOOR)
+        # (flip: the mean of two clamped values respects the floor too)
+        self.dec = ops.decode(hm, wh, reg, m.topk_candidates, m.backbone.down_ratio, heat_floor=ops.SIGMOID_CLAMP_FLOOR,
+                              flip=self.flip)
         # one flag per step, computed inside the captured part: are the size / offset maps finite?  They carry no clamp, so an
         # activation that left the f16 range on its way through an f16x3 (or f16) layer -- hi = f16(x) is inf beyond 65504 --
         # or any other blow-up of a diverged network ends up here as inf / NaN (the heat map would hide it: its epilogue
@@ -294,11 +309,11 @@ class CenterNet(nn.Module):
             self._engines = {}
         return super().train(mode)
 
-    def _engine(self, B, H, W, Hp, Wp, img_dtype):
+    def _engine(self, B, H, W, Hp, Wp, img_dtype, flip=False):
         """the captured engine of this input geometry (least recently used ones beyond MAX_ENGINES are destroyed here, before
-        a new one is built, i.e. never inside a stream capture)"""
+        a new one is built, i.e. never inside a stream capture); flip: the flip-test engine (see _EvalEngine)"""
         fused = self.backbone_type == "dla34" and self.backbone.images_fusable(self._ctx, Hp, Wp)
-        key = _engine_key(fused, B, H, W, Hp, Wp, img_dtype)
+        key = _engine_key(fused, B, H, W, Hp, Wp, img_dtype, flip)
         eng = self._engines.get(key)
         if eng is not None:
             self._engines[key] = self._engines.pop(key)      # most recently used last
@@ -306,7 +321,8 @@ class CenterNet(nn.Module):
         while len(self._engines) >= MAX_ENGINES:
             old = self._engines.pop(next(iter(self._engines)))
             del old
-        eng = self._engines[key] = _EvalEngine(self, B, H, W, Hp, Wp, img_dtype, self.use_hip_graph and not ops.RANGE_CHECK)
+        eng = self._engines[key] = _EvalEngine(self, B, H, W, Hp, Wp, img_dtype, self.use_hip_graph and not ops.RANGE_CHECK,
+                                               flip=flip)
         return eng
 
     # ------------------------------------------------------------------ network (NHWC, HIP kernels)
@@ -400,7 +416,8 @@ class CenterNet(nn.Module):
             return self._forward_train(batched_inputs)
         return self._forward_eval(batched_inputs)
 
-    def _forward_eval(self, batched_inputs):
+    def _forward_eval(self, batched_inputs, flip=False):
+        """flip: CenterNet's flip test (modeling/test_time_augmentation.py: CenterNetWithTTA) -- same I/O, the flip engine"""
         dev = self.device
         if dev.type != "cuda":
             raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
@@ -410,16 +427,16 @@ class CenterNet(nn.Module):
         same = all(s == sizes[0] for s in sizes) and all(im.dtype == imgs[0].dtype for im in imgs)
         Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
         if not same:
-            return self._forward_eval_ragged(batched_inputs, imgs, sizes, Hp, Wp)
+            return self._forward_eval_ragged(batched_inputs, imgs, sizes, Hp, Wp, flip)
         H, W = sizes[0]
         img_dtype = torch.uint8 if imgs[0].dtype == torch.uint8 else torch.float32
-        eng = self._engine(B, H, W, Hp, Wp, img_dtype)
+        eng = self._engine(B, H, W, Hp, Wp, img_dtype, flip)
         stage = eng.staging(H, W)
         for b, im in enumerate(imgs):
             stage[b].copy_(im if im.dtype == img_dtype else im.to(img_dtype), non_blocking=True)
         return self._finish_eval(eng, batched_inputs, sizes)
 
-    def forward_async(self, batched_inputs):
+    def forward_async(self, batched_inputs, flip=False):
         """eval forward of a `list[dict]` batch without waiting for it: returns a handle whose `.result()` is what
         `forward` returns.  Same-size images go through the captured engine (one step in flight is safe: the engine's
         post-processing writes fresh tensors per step); ragged batches run eagerly and come back already finished."""
@@ -427,22 +444,22 @@ class CenterNet(nn.Module):
         imgs = [x["image"] for x in batched_inputs]
         sizes = [tuple(im.shape[-2:]) for im in imgs]
         if not (all(s == sizes[0] for s in sizes) and all(im.dtype == imgs[0].dtype for im in imgs)):
-            return _Done(self._forward_eval(batched_inputs))
+            return _Done(self._forward_eval(batched_inputs, flip))
         Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
         H, W = sizes[0]
         img_dtype = torch.uint8 if imgs[0].dtype == torch.uint8 else torch.float32
-        eng = self._engine(len(imgs), H, W, Hp, Wp, img_dtype)
+        eng = self._engine(len(imgs), H, W, Hp, Wp, img_dtype, flip)
         stage = eng.staging(H, W)
         for b, im in enumerate(imgs):
             stage[b].copy_(im if im.dtype == img_dtype else im.to(img_dtype), non_blocking=True)
         return self._launch_eval(eng, batched_inputs, sizes)
 
-    def infer_batch_tensor(self, images, out_sizes=None):
+    def infer_batch_tensor(self, images, out_sizes=None, flip=False):
         """Fast path for an already-batched device tensor [B,3,H,W] (uint8 or float32, 0..255): the DLA base kernel reads
         it in place (other backbones: one staging copy), then one graph replay.  Returns the same list of {"instances": Instances} as forward()."""
-        return self.infer_batch_tensor_async(images, out_sizes).result()
+        return self.infer_batch_tensor_async(images, out_sizes, flip).result()
 
-    def infer_batch_tensor_async(self, images, out_sizes=None):
+    def infer_batch_tensor_async(self, images, out_sizes=None, flip=False):
         """Enqueue one eval step (base kernel on `images` / input copy, graph replay, snapshot of the outputs, async read-back of the
         per-image detection counts) and return a handle; `handle.result()` waits for that step only and builds the
         Instances.  A serving loop keeps one step in flight (`h2 = async(next); h1.result()`), so the host work of
@@ -450,7 +467,7 @@ class CenterNet(nn.Module):
         B, _, H, W = images.shape
         Hp, Wp = ImageList.padded_size([(H, W)], self.size_divisibility)
         img_dtype = torch.uint8 if images.dtype == torch.uint8 else torch.float32
-        eng = self._engine(B, H, W, Hp, Wp, img_dtype)
+        eng = self._engine(B, H, W, Hp, Wp, img_dtype, flip)
         if images.dtype != img_dtype or not images.is_contiguous():
             images = images.to(img_dtype).contiguous()
         inputs = [{} if out_sizes is None else {"height": out_sizes[b][0], "width": out_sizes[b][1]} for b in range(B)]
@@ -470,18 +487,20 @@ class CenterNet(nn.Module):
         boxes, scores, classes, counts = eng(images)   # fresh tensors per step (the engine's post-processing allocates them)
         return _EvalHandle(boxes, scores, classes, counts, out_sizes)
 
-    def _forward_eval_ragged(self, batched_inputs, imgs, sizes, Hp, Wp):
-        """images of different sizes: per-image preprocess launches into the zero-padded batch, eager launches."""
+    def _forward_eval_ragged(self, batched_inputs, imgs, sizes, Hp, Wp, flip=False):
+        """images of different sizes: per-image preprocess launches into the zero-padded batch, eager launches.
+        flip: the flip test on 2B network inputs, each image's mirrored padded input behind the B plain ones."""
         dev, B = self.device, len(imgs)
-        x = torch.zeros(B, Hp, Wp, 8, dtype=self._ctx.dtype, device=dev)
+        x = torch.zeros(2 * B if flip else B, Hp, Wp, 8, dtype=self._ctx.dtype, device=dev)
         for b, im in enumerate(imgs):
             im = im.to(dev)
-            im = im if im.dtype == torch.uint8 else im.float()
-            ops.preprocess(im.unsqueeze(0).contiguous(), self._mean_host, self._std_host, Hp, Wp, out=x[b:b + 1],
-                           partial=True)
+            im = (im if im.dtype == torch.uint8 else im.float()).unsqueeze(0).contiguous()
+            ops.preprocess(im, self._mean_host, self._std_host, Hp, Wp, out=x[b:b + 1], partial=True)
+            if flip:
+                ops.preprocess(im, self._mean_host, self._std_host, Hp, Wp, out=x[B + b:B + b + 1], partial=True, mirror=True)
         hm, wh, reg = self._network_outputs(x, apply_sigmoid=True)
         boxes, scores, classes, _ = ops.decode(hm, wh, reg, self.topk_candidates, self.backbone.down_ratio,
-                                               heat_floor=ops.SIGMOID_CLAMP_FLOOR)
+                                               heat_floor=ops.SIGMOID_CLAMP_FLOOR, flip=flip)
         params = torch.empty(B, 4, dtype=torch.float32)
         out_sizes = []
         for b, (inp, size) in enumerate(zip(batched_inputs, sizes)):
@@ -501,18 +520,22 @@ class CenterNet(nn.Module):
             results.append({"instances": r})
         return results
 
-    def preprocess_image(self, batched_inputs):
+    def preprocess_image(self, batched_inputs, flip=False):
         """centernet.py:173-189.  Returns (ImageList of the normalised, padded batch as a logical-NCHW view of the
-        NHWC device buffer, list of per-image target dicts when training)."""
+        NHWC device buffer, list of per-image target dicts when training).  flip (eval only): the batch holds 2B images,
+        the mirrored network input of image b at b + B (image_sizes stays the B sizes)."""
         dev = self.device
         imgs = [x["image"].to(dev) for x in batched_inputs]
         sizes = [tuple(im.shape[-2:]) for im in imgs]
+        B = len(imgs)
+        assert not (flip and self.training), "the flip test is an inference-time augmentation"
         Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
-        x = torch.zeros(len(imgs), Hp, Wp, 8, dtype=self._ctx.dtype, device=dev)
+        x = torch.zeros(2 * B if flip else B, Hp, Wp, 8, dtype=self._ctx.dtype, device=dev)
         for b, im in enumerate(imgs):
-            im = im if im.dtype == torch.uint8 else im.float()
-            ops.preprocess(im.unsqueeze(0).contiguous(), self._mean_host, self._std_host, Hp, Wp, out=x[b:b + 1],
-                           partial=True)
+            im = (im if im.dtype == torch.uint8 else im.float()).unsqueeze(0).contiguous()
+            ops.preprocess(im, self._mean_host, self._std_host, Hp, Wp, out=x[b:b + 1], partial=True)
+            if flip:
+                ops.preprocess(im, self._mean_host, self._std_host, Hp, Wp, out=x[B + b:B + b + 1], partial=True, mirror=True)
         images = ImageList(x[..., :3].permute(0, 3, 1, 2), sizes)
         images.nhwc = x
         if not self.training:
@@ -575,13 +598,14 @@ class CenterNet(nn.Module):
         from ...engine.train_step import centernet_train_forward
         return centernet_train_forward(self, batched_inputs)
 
-    def inference(self, outputs, image_sizes):
-        """centernet.py:214-234: outputs dict of logical-NCHW hm (after sigmoid+clamp) / wh / reg."""
+    def inference(self, outputs, image_sizes, flip=False):
+        """centernet.py:214-234: outputs dict of logical-NCHW hm (after sigmoid+clamp) / wh / reg.  flip: the maps hold 2B
+        images (plain, then mirrored passes) and are merged by the flip-test decode; image_sizes are the B sizes."""
         hm = outputs["hm"].permute(0, 2, 3, 1).float().contiguous()
         wh = outputs["wh"].permute(0, 2, 3, 1).float().contiguous()
         reg = outputs["reg"].permute(0, 2, 3, 1).float().contiguous()
-        boxes, scores, classes, _ = ops.decode(hm, wh, reg, self.topk_candidates, self.backbone.down_ratio)
-        B = hm.shape[0]
+        boxes, scores, classes, _ = ops.decode(hm, wh, reg, self.topk_candidates, self.backbone.down_ratio, flip=flip)
+        B = hm.shape[0] // 2 if flip else hm.shape[0]
         params = torch.tensor([[1.0, 1.0, float(s[1]), float(s[0])] for s in image_sizes], dtype=torch.float32)
         params[:, 2:] = 1e30  # no clipping here: detector_postprocess does it (:169)
         max_det = min(self.max_detections_per_image, self.topk_candidates)

@@ -717,13 +717,24 @@ def dcnv2_offset(x, p_off, p, out=None, act=ACT_NONE, out_dtype=None, om_out=Non
     return out
 
 
-def preprocess(images, mean, std, Hp, Wp, out_dtype=torch.float16, out=None, partial=False, border=0):
+def _mirror_from(mirror, B):
+    """(output images, mirror_from) of the flip-test forms: False = plain, True = every image mirrored, "both" = 2B output
+    images, the plain B first, then their mirrors"""
+    assert mirror in (False, True, "both"), mirror
+    return (2 * B, B) if mirror == "both" else (B, 0 if mirror else None)
+
+
+def preprocess(images, mean, std, Hp, Wp, out_dtype=torch.float16, out=None, partial=False, border=0, mirror=False):
     """images: [B,3,H,W] uint8/float32 CHW on device -> normalised NHWC [B,Hp,Wp,8] (3 channels used).
     `out` may be a batch-slice of a larger padded buffer (ragged batches: one call per image).
-    border > 0: `out` is a caller-owned [B,Hp+2b,Wp+2b,8] buffer whose zero frame was cleared once."""
+    border > 0: `out` is a caller-owned [B,Hp+2b,Wp+2b,8] buffer whose zero frame was cleared once.
+    mirror (flip test): True = the horizontal mirror of the NETWORK INPUT -- the normalised tensor after right/bottom zero
+    padding: column x holds source column Wp-1-x, zero where that is >= W, so the padding sits on the left; "both" = 2B
+    output images, the plain ones then their mirrors, from the same B images."""
     _require_cuda(images)
     B, Cc, H, W = images.shape
     assert Cc == 3 and images.stride(3) == 1 and images.stride(2) == W and images.stride(1) == H * W
+    B, mfrom = _mirror_from(mirror, B)
     if out is None:
         if border:
             out = torch.zeros(B, Hp + 2 * border, Wp + 2 * border, 8, dtype=out_dtype, device=images.device)
@@ -733,8 +744,13 @@ def preprocess(images, mean, std, Hp, Wp, out_dtype=torch.float16, out=None, par
     assert tuple(out.shape[1:3]) == (Hp + 2 * border, Wp + 2 * border)
     m = (C.c_float * 3)(*[float(v) for v in mean])
     s = (C.c_float * 3)(*[float(v) for v in std])
-    rc = _lib.lib().ctdet_preprocess(_ptr(images), dt_of(images), _ptr(out), dt_of(out), B, H, W, Hp, Wp,
-                                     images.stride(0), m, s, _nhwc_stride(out), int(border), _stream())
+    assert out.shape[0] == B
+    if mfrom is None:
+        rc = _lib.lib().ctdet_preprocess(_ptr(images), dt_of(images), _ptr(out), dt_of(out), B, H, W, Hp, Wp,
+                                         images.stride(0), m, s, _nhwc_stride(out), int(border), _stream())
+    else:
+        rc = _lib.lib().ctdet_preprocess_mirror(_ptr(images), dt_of(images), _ptr(out), dt_of(out), B, H, W, Hp, Wp,
+                                                images.stride(0), m, s, _nhwc_stride(out), int(border), mfrom, _stream())
     _lib.check(rc, "ctdet_preprocess")
     return out
 
@@ -783,14 +799,17 @@ def dla_base_fused_ok(Hp, Wp):
     return BASE_FUSED and Hp % 16 == 0 and Wp % 32 == 0
 
 
-def dla_base_fused(images, mean, std, Hp, Wp, p, out=None, pooled=None):
+def dla_base_fused(images, mean, std, Hp, Wp, p, out=None, pooled=None, mirror=False):
     """images [B,3,H,W] uint8/f32 on device -> level1 output of DLA (NHWC [B,Hp/2,Wp/2,32]; f16, or f32 when p is a
     PackedDlaBaseX3: f16x3 arithmetic) in one launch: normalisation, 7x7 stem, level0, level1 (stride 2), BatchNorm folded,
     ReLU after each.  pooled: optional [B,Hp/4,Wp/4,>=32] buffer of the output's dtype that receives MaxPool2d(2) of the
-    output (what level2's Tree starts with)."""
+    output (what level2's Tree starts with).
+    mirror (flip test, see preprocess): True = computed from the mirrored network input, which makes the output the plain
+    output mirrored; "both" = 2B output images, plain then mirrored, the B images read in place twice."""
     _require_cuda(images, out, pooled)
     B, Cc, H, W = images.shape
     assert Cc == 3 and images.stride(3) == 1 and images.stride(2) == W and images.stride(1) == H * W
+    B, mfrom = _mirror_from(mirror, B)
     x3 = getattr(p, "x3", False)
     odt = torch.float32 if x3 else torch.float16
     if out is None:
@@ -808,15 +827,17 @@ def dla_base_fused(images, mean, std, Hp, Wp, p, out=None, pooled=None):
     px = B * Hp * Wp
     prof = _Prof(None, px, False, F16X3 if x3 else F16,
                  flops=2.0 * (px * 16 * 147 + px * 16 * 144 + (px // 4) * 32 * 144))
+    L = _lib.lib()
+    if x3:
+        operands = (_ptr(images), _ptr(p.p0.w), _ptr(p.p0.scale), _ptr(p.p0.bias), _ptr(p.p1.w), _ptr(p.p1.scale),
+                    _ptr(p.p1.bias), _ptr(p.p2.w), _ptr(p.p2.scale), _ptr(p.p2.bias), _ptr(out), _ptr(pooled), _stream())
+        fn = L.ctdet_dla_base_x3_fwd if mfrom is None else L.ctdet_dla_base_x3_mirror_fwd
+    else:
+        operands = (_ptr(images), _ptr(p.w0), _ptr(p.s0), _ptr(p.b0), _ptr(p.p1.w), _ptr(p.p1.scale), _ptr(p.p1.bias),
+                    _ptr(p.p2.w), _ptr(p.p2.scale), _ptr(p.p2.bias), _ptr(out), _ptr(pooled), _stream())
+        fn = L.ctdet_dla_base_fwd if mfrom is None else L.ctdet_dla_base_mirror_fwd
     for _ in range(prof.reps()):
-        if x3:
-            rc = _lib.lib().ctdet_dla_base_x3_fwd(C.byref(d), _ptr(images), _ptr(p.p0.w), _ptr(p.p0.scale), _ptr(p.p0.bias),
-                                                  _ptr(p.p1.w), _ptr(p.p1.scale), _ptr(p.p1.bias), _ptr(p.p2.w),
-                                                  _ptr(p.p2.scale), _ptr(p.p2.bias), _ptr(out), _ptr(pooled), _stream())
-        else:
-            rc = _lib.lib().ctdet_dla_base_fwd(C.byref(d), _ptr(images), _ptr(p.w0), _ptr(p.s0), _ptr(p.b0), _ptr(p.p1.w),
-                                               _ptr(p.p1.scale), _ptr(p.p1.bias), _ptr(p.p2.w), _ptr(p.p2.scale),
-                                               _ptr(p.p2.bias), _ptr(out), _ptr(pooled), _stream())
+        rc = fn(C.byref(d), *operands) if mfrom is None else fn(C.byref(d), mfrom, *operands)
     _lib.check(rc, "ctdet_dla_base_fwd")
     if prof.on:
         prof.bytes = images.numel() * images.element_size() + (px // 4) * 32 * out.element_size() * (1.25 if pooled is not None else 1.0)
@@ -1100,15 +1121,22 @@ class DecodeWorkspace:
 SIGMOID_CLAMP_FLOOR = 1e-4     # `_sigmoid`'s lower clamp (centernet.py:13-15); the head kernels' epilogue writes exactly this f32
 
 
-def decode(heat, wh, reg, K, down_ratio, workspace=None, check_status=False, heat_floor=0.0):
+def decode(heat, wh, reg, K, down_ratio, workspace=None, check_status=False, heat_floor=0.0, flip=False):
     """Batched ctdet_decode. heat f32 NHWC [B,H,W,C] (may be the channel slice [..., :C] of a wider buffer: padded head
     outputs are decoded in place); wh/reg f32 NHWC (2 channels, may be slices).  heat_floor: a lower bound of the positive
     heat values the caller vouches for (SIGMOID_CLAMP_FLOOR for a clamped map; same results, the background plateau is
     skipped).
+    flip (flip test): heat / wh / reg hold 2B images, image b + B being the network's maps for the horizontally mirrored
+    input of image b; decoded are hm = (hm[b] + mirror(hm[b+B])) * 0.5, wh = (wh[b] + mirror(wh[b+B])) * 0.5 and reg = reg[b]
+    (mirror: x <-> W-1-x; one f32 add and one multiply in that order), merged inside the decode's one pass over the maps.
     Returns boxes [B,K,4], scores [B,K], classes [B,K] (int32), inds [B,K] (int32)."""
     _require_cuda(heat, wh, reg)
     assert heat.dtype == torch.float32
     B, H, W, Cc = heat.shape
+    if flip:
+        assert B % 2 == 0 and wh.shape[0] == B and (reg is None or reg.shape[0] == B), "flip decode: 2B images, plain half first"
+        assert heat.stride(0) == H * W * heat.stride(2) and wh.stride(0) == H * W * wh.stride(2), "flip decode: dense batches"
+        B //= 2
     if workspace is None or workspace.key != (B, H, W, Cc, K):
         workspace = DecodeWorkspace(B, H, W, Cc, K, heat.device)
     dev = heat.device
@@ -1117,9 +1145,10 @@ def decode(heat, wh, reg, K, down_ratio, workspace=None, check_status=False, hea
     classes = torch.empty(B, K, dtype=torch.int32, device=dev)
     inds = torch.empty(B, K, dtype=torch.int32, device=dev)
     with prof_region("decode", nbytes=float(B * H * W * Cc * 4), info=f"{B}x{H}x{W}x{Cc} K={K}"):
-        rc = _lib.lib().ctdet_decode(_ptr(heat), _nhwc_stride(heat), _ptr(wh), _nhwc_stride(wh), _ptr(reg),
-                                     _nhwc_stride(reg) if reg is not None else 0, B, H, W, Cc, K, float(down_ratio),
-                                     float(heat_floor), _ptr(workspace.buf), _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(inds), _stream())
+        fn = _lib.lib().ctdet_decode_flip if flip else _lib.lib().ctdet_decode
+        rc = fn(_ptr(heat), _nhwc_stride(heat), _ptr(wh), _nhwc_stride(wh), _ptr(reg),
+                _nhwc_stride(reg) if reg is not None else 0, B, H, W, Cc, K, float(down_ratio),
+                float(heat_floor), _ptr(workspace.buf), _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(inds), _stream())
     _lib.check(rc, "ctdet_decode")
     if check_status:
         _lib.check(_lib.lib().ctdet_decode_status(_ptr(workspace.buf), B, H, W, Cc, K, _stream()), "ctdet_decode_status")

@@ -160,6 +160,15 @@ int32_t ctdet_dcnv2_offset_fwd(const ctdet_conv_desc* d, const void* x, const vo
 int32_t ctdet_preprocess(const void* img, int32_t img_dtype, void* out, int32_t out_dtype, int32_t B, int32_t H,
                          int32_t W, int32_t Hp, int32_t Wp, int64_t img_batch_stride, const float* mean3,
                          const float* std3, int32_t out_stride, int32_t border, void* stream);
+/* Flip test-time augmentation: ctdet_preprocess whose output images b >= mirror_from (0 <= mirror_from <= B, B = output
+ * images) are the horizontal mirror of the NETWORK INPUT of source image b - mirror_from: the normalised tensor after the
+ * right/bottom zero padding, so column x holds source column Wp-1-x and reads as zero where that is >= W (the padding
+ * sits on the left).  Output images below mirror_from are plain copies of their own source image.  img holds
+ * max(mirror_from, B - mirror_from) images: mirror_from = 0 mirrors a batch, mirror_from = B/2 writes the plain and the
+ * mirrored half of a flip-test batch from the same B/2 images. */
+int32_t ctdet_preprocess_mirror(const void* img, int32_t img_dtype, void* out, int32_t out_dtype, int32_t B, int32_t H,
+                                int32_t W, int32_t Hp, int32_t Wp, int64_t img_batch_stride, const float* mean3,
+                                const float* std3, int32_t out_stride, int32_t border, int32_t mirror_from, void* stream);
 
 /* Fused CenterNet head (detectron2/modeling/meta_arch/centernet.py:115-121,151-154): for every head h
  *   y[h] = act_h( W2_h * relu(conv3x3_p1(x, W1_h) + b1_h) + b2_h ),   hidden width 256,
@@ -218,6 +227,21 @@ int32_t ctdet_dla_base_x3_fwd(const ctdet_dla_base_desc* d, const void* images, 
                               const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
                               const void* w_l1, const float* scale_l1, const float* bias_l1, float* out, float* pooled,
                               void* stream);
+/* Flip test-time augmentation: the two fused base kernels with a `mirror_from` batch index next to the descriptor
+ * (0 <= mirror_from <= d->B, d->B = OUTPUT images; anything else is rejected).  Output images b >= mirror_from are computed
+ * from the horizontally mirrored network input of source image b - mirror_from -- input column x of the Hp x Wp frame reads
+ * image column Wp-1-x, zero where that is >= W -- so they equal the plain output mirrored (x <-> Wp/2-1-x) bit for bit;
+ * output images below mirror_from are the plain ones.  `images` holds max(mirror_from, d->B - mirror_from) images and is read
+ * in place (mirror_from = d->B / 2: the same images twice, no mirrored copy of the batch).  Everything else as for
+ * ctdet_dla_base_fwd / ctdet_dla_base_x3_fwd. */
+int32_t ctdet_dla_base_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirror_from, const void* images, const void* w_stem,
+                                  const float* scale_stem, const float* bias_stem, const void* w_l0, const float* scale_l0,
+                                  const float* bias_l0, const void* w_l1, const float* scale_l1, const float* bias_l1,
+                                  void* out, void* pooled, void* stream);
+int32_t ctdet_dla_base_x3_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirror_from, const void* images,
+                                     const void* w_stem, const float* scale_stem, const float* bias_stem, const void* w_l0,
+                                     const float* scale_l0, const float* bias_l0, const void* w_l1, const float* scale_l1,
+                                     const float* bias_l1, float* out, float* pooled, void* stream);
 
 /* nn.MaxPool2d(2, stride=2) on NHWC (dla.py:128-129). */
 int32_t ctdet_maxpool2x2(const void* x, void* y, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -303,6 +327,17 @@ int32_t ctdet_decode(const float* heat, int32_t heat_stride, const float* wh, in
                      int32_t reg_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, float down_ratio,
                      float heat_floor, void* workspace, float* boxes, float* scores, int32_t* classes, int32_t* inds,
                      void* stream);
+/* Flip-test decode: the arguments of ctdet_decode with B the OUTPUT batch; heat, wh and reg hold 2B images, the plain
+ * passes first, image b + B being the network's maps for the horizontally mirrored input of image b.  Decoded are
+ *   hm = (hm[b] + mirror(hm[b+B])) * 0.5f,   wh = (wh[b] + mirror(wh[b+B])) * 0.5f,   reg = reg[b]
+ * (mirror: x <-> W-1-x; one f32 add and one multiply, in that order -- bit for bit what ctdet_decode returns for maps merged
+ * that way beforehand).  The merged heat map is never written: both halves are read in the one pass over the heat map, wh is
+ * merged at the K gathered positions.  A mean of two values >= heat_floor is >= heat_floor, so the promise carries over.
+ * Workspace (ctdet_decode_workspace_bytes), status words and ctdet_decode_status as for ctdet_decode at batch B. */
+int32_t ctdet_decode_flip(const float* heat, int32_t heat_stride, const float* wh, int32_t wh_stride, const float* reg,
+                          int32_t reg_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, float down_ratio,
+                          float heat_floor, void* workspace, float* boxes, float* scores, int32_t* classes, int32_t* inds,
+                          void* stream);
 /* CenterNet.inference_single_image (centernet.py:251-261) + detector_postprocess
  * (detectron2/modeling/postprocessing.py:11-72, structures/boxes.py:184-213,271-278) for a whole batch:
  * keep k < max_det with score > score_thresh, scale boxes by (scale_x, scale_y), clip to (out_w, out_h), drop
