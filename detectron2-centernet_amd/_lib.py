@@ -109,6 +109,12 @@ SIGNATURES = {
     "ctdet_adam_advance": (_i32, [_vp, _vp, _f64, _f64, _vp]),
     "ctdet_adam_runs": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _f64, _f64, _i32, _i32, _i32,
                                _f32, _vp, _vp]),
+    "ctdet_cocoeval_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "ctdet_cocoeval_iou": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "ctdet_cocoeval_match": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _i32,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctdet_cocoeval_accumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp,
+                                         _vp, _vp, _vp, _vp]),
     "ctdet_set_tuning_flags": (_i32, [C.c_uint32]),
     "ctdet_get_tuning_flags": (C.c_uint32, []),
     "ctdet_comm_unique_id": (_i32, [_vp]),

@@ -1,7 +1,24 @@
 """Hand-off of the decoded detections to COCO evaluation: the wire format of
 detectron2/evaluation/coco_evaluation.py:321-382 (`instances_to_coco_json`: XYWH boxes, one dict per detection) and the
-category-id remapping of `COCOEvaluator._eval_predictions` (:147-163).  Scoring itself (pycocotools) is out of scope."""
+category-id remapping of `COCOEvaluator._eval_predictions` (:147-163).  Scoring itself is in cocoeval.py / coco_evaluation.py."""
 import torch
+
+
+def coco_records(boxes, scores, classes, image_ids, reverse_id_mapping=None):
+    """host boxes f32 [n,4] XYXY, scores [n], classes [n] and one image id per detection -> the COCO results list: XYWH in
+    f32 (BoxMode.XYXY_ABS -> XYWH_ABS, structures/boxes.py:100-103), contiguous class indices mapped back to dataset category
+    ids when the mapping is given.  Shared by `instances_to_coco_json` (per image) and `COCOEvaluator` (whole dataset)."""
+    boxes = torch.as_tensor(boxes).detach().float().cpu().reshape(-1, 4).clone()
+    boxes[:, 2] -= boxes[:, 0]
+    boxes[:, 3] -= boxes[:, 1]
+    boxes = boxes.tolist()
+    scores = torch.as_tensor(scores).detach().cpu().tolist()
+    classes = torch.as_tensor(classes).detach().cpu().tolist()
+    if reverse_id_mapping is not None:
+        for c in classes:
+            assert c in reverse_id_mapping, f"A prediction has category_id={c}, which is not available in the dataset."
+        classes = [reverse_id_mapping[c] for c in classes]
+    return [{"image_id": image_ids[k], "category_id": classes[k], "bbox": boxes[k], "score": scores[k]} for k in range(len(scores))]
 
 
 def instances_to_coco_json(instances, img_id):
@@ -9,13 +26,7 @@ def instances_to_coco_json(instances, img_id):
     n = len(instances) if instances.has("scores") else 0
     if n == 0:
         return []
-    boxes = instances.pred_boxes.tensor.detach().float().cpu().clone()
-    boxes[:, 2] -= boxes[:, 0]          # BoxMode.XYXY_ABS -> XYWH_ABS (structures/boxes.py:100-103)
-    boxes[:, 3] -= boxes[:, 1]
-    boxes = boxes.tolist()
-    scores = instances.scores.detach().cpu().tolist()
-    classes = instances.pred_classes.detach().cpu().tolist()
-    return [{"image_id": img_id, "category_id": classes[k], "bbox": boxes[k], "score": scores[k]} for k in range(n)]
+    return coco_records(instances.pred_boxes.tensor, instances.scores, instances.pred_classes, [img_id] * n)
 
 
 def results_to_coco_json(outputs, image_ids, dataset_id_to_contiguous_id=None):

@@ -8,7 +8,8 @@ the device, between two HIP events on the launch stream, instead of by stalling 
 the `DatasetEvaluator` protocol (reset / process / evaluate), the warm-up rule (the first min(5, len - 1) batches are not
 timed) and the two log lines ("Total inference time", "Total inference pure compute time", evaluator.py:163-174).
 `COCOResultsWriter` collects the detections in the COCO results wire format (coco_evaluation.py:109-126, 321-382), gathers
-them on the main process and writes the json there; scoring with pycocotools is out of scope (absent here)."""
+them on the main process and writes the json there; it does not score.  Box AP is `COCOEvaluator`'s (coco_evaluation.py),
+scored on the device by the HIP matcher and PR kernels (cocoeval.py; pycocotools is absent here)."""
 import datetime
 import json
 import logging

@@ -583,6 +583,45 @@ int32_t ctdet_allreduce_bucket(void* comm, float* buf, int64_t count, void* stre
 int32_t ctdet_bcast(void* comm, float* buf, int64_t count, int32_t root, void* stream);
 int32_t ctdet_comm_destroy(void* comm);
 
+/* ---- COCO box-AP scoring ("bbox" task, useCats = 1) ---------------------------------------------------------------
+ * The native op pair of the reference's scorer (detectron2/layers/csrc/cocoeval/cocoeval.cpp: COCOevalEvaluateImages,
+ * COCOevalAccumulate, bound in vision.cpp), over the detections of a whole dataset in device memory.  The result is pinned to
+ * that code bit for bit (tp / (tp + fp), no np.spacing); DESIGN.md 7.7 holds the definition.  All arithmetic is f64; the
+ * two orders (cell major / category major, score descending) equal stable sorts.  These calls use a device radix sort and are
+ * not meant to be captured into a graph.
+ *
+ * ctdet_cocoeval_iou (test hook): dt f64 [D,4] and gt f64 [G,4] XYWH, gt_crowd u8 [G] -> iou f64 [D,G]:
+ *   w = min(dx+dw, gx+gw) - max(dx, gx), h likewise; 0 if w <= 0 or h <= 0, else w*h / (crowd ? dw*dh : dw*dh + gw*gh - w*h).
+ *
+ * ctdet_cocoeval_match: detections concatenated over the dataset -- boxes f32 [N,4] XYXY (width and height are taken in f32,
+ *   then widened), scores f32 [N], classes i32 [N] in [0,K), image i32 [N] = index into the sorted image-id list in [0,I);
+ *   ground truth sorted by (image, category) with CSR offsets gt_off i32 [I*K+1] into gt_boxes f64 [NG,4] XYWH, gt_area f64 [NG]
+ *   (the annotation's area), gt_crowd u8 [NG]; iou_thrs f64 [T], area_rngs f64 [A,2], A*T <= 64, I*K < 2^26 (one workgroup per cell); max_det = the largest maxDet.
+ *   Outputs: order i32 [N] (input index of every position of order 1: cell major, score descending, stable), rank i32 [N]
+ *   (position within its cell, by position of order 1), flags u8 [N, A*T] by position of order 1, written for rank < max_det
+ *   (bit 0 matched, bit 1 ignored), npig i32 [K,A] (non-ignored ground truths), status i32 [1] (1: an image or class index was
+ *   out of range; such detections take no part).
+ * ctdet_cocoeval_accumulate: from those, scores and classes as given to match, rec_thrs f64 [R], max_dets i32 [M] (device
+ *   memory) and the max_det given to match -- a maxDet above it acts as max_det, as in the reference, whose cells were cut to
+ *   max_det by the matching step: precision f64 [T,R,K,A,M], scores_out f64 [T,R,K,A,M], recall f64 [T,K,A,M], every element written (-1 where a
+ *   (category, area range) has no valid ground truth).
+ * One workspace serves both calls: ctdet_cocoeval_workspace_bytes(N, NG, I, K, A, T) bytes (0: arguments out of range),
+ *   256-byte aligned:  2 * 8N (keys) + 2 * 4N (values, order 2) + 4 (max(I*K, K) + 2) (offsets) + NG*A*T (taken flags of
+ *   cells too large for LDS) + 16N + 16 MiB (bound of the sort's temporary storage, checked at the call), each rounded up to
+ *   256 bytes. */
+size_t ctdet_cocoeval_workspace_bytes(int64_t N, int64_t NG, int32_t I, int32_t K, int32_t A, int32_t T);
+int32_t ctdet_cocoeval_iou(const double* dt, int32_t D, const double* gt, const uint8_t* gt_crowd, int32_t G, double* iou,
+                           void* stream);
+int32_t ctdet_cocoeval_match(const float* boxes, const float* scores, const int32_t* classes, const int32_t* image, int64_t N,
+                             const double* gt_boxes, const double* gt_area, const uint8_t* gt_crowd, const int32_t* gt_off,
+                             int64_t NG, int32_t I, int32_t K, const double* iou_thrs, int32_t T, const double* area_rngs,
+                             int32_t A, int32_t max_det, void* workspace, int32_t* order, int32_t* rank, uint8_t* flags,
+                             int32_t* npig, int32_t* status, void* stream);
+int32_t ctdet_cocoeval_accumulate(const float* scores, const int32_t* classes, const int32_t* order, const int32_t* rank,
+                                  const uint8_t* flags, const int32_t* npig, int64_t N, int32_t K, int32_t A, int32_t T,
+                                  const double* rec_thrs, int32_t R, const int32_t* max_dets, int32_t M, int32_t max_det,
+                                  void* workspace, double* precision, double* scores_out, double* recall, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
