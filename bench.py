@@ -2,7 +2,12 @@
 """Benchmark of the CenterNet DLA-34 hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--task infer|train] [--batch B] [--precision f16x3|f16|f32]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the model, warms up, times the K steps, writes
+the outputs of the last one if --dump-outputs is given and prints the result line.  Everything else described below (the
+roofline, the CPU baselines, `accuracy`, the sub-records of the other precisions and of training) is measured only with
+--full, after the timed steps of the headline, and is added to the same line.
 
 N = 1 workload (BASELINE.json configs[1]): DLA-34 CenterNet inference, batch 64, 512x512 synthetic uint8
 images resident in HBM; one step = the whole eval forward of the meta-architecture (preprocess, backbone, heads,
@@ -13,7 +18,8 @@ is bracketed by barrier + torch.cuda.synchronize and the maximum over ranks is r
 
 Prints ONE JSON line (rank 0).  The headline (`value`, `dtype`) is the mode that meets north_star's parity bar at the
 highest rate: f16x3 -- f32 tensors, every product as three f16 products on the f16 matrix pipe (heat map within 1e-5 of
-the fp32 oracle).  With it: the roofline of the dominant kernel (measured live with HIP events around every launch in an
+the fp32 oracle).  With --full, next to it:
+the roofline of the dominant kernel (measured live with HIP events around every launch in an
 instrumented eager pass, plus the decode's HBM rate), the CPU baseline (the oracle's port of the reference arithmetic
 timed on this host's cores, bounded sample), `accuracy` (heat-map error and top-K agreement against the fp32 oracle on
 the CPU sample), the sub-records `f16` (f16 storage: the fastest mode, whose error exceeds the 1e-3 bar -- reported, not
@@ -580,7 +586,7 @@ def infer_record(precision, state, images, steps, warmup, dist, backend, device,
     return rec, model, cfg
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -592,6 +598,10 @@ def main():
                     help="headline mode (default f16x3: the fastest mode inside north_star's 1e-3 parity bar)")
     ap.add_argument("--config", default="dla34", choices=["dla34", "r50"],
                     help="dla34: BASELINE.json configs[1] (+[2]); r50: configs[4], ResNet-50 CenterNet 800x800 bs 8 per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure everything else: roofline, CPU baselines, accuracy "
+                         "against the oracle, the other precisions and the training sub-records (off by default; the --no-* "
+                         "options below drop single legs of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-f32", action="store_true", help="skip the f32 sub-records (inference and training)")
@@ -601,9 +611,16 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the headline's last timed step returned (rank 0) as DIR/<name>.npy: the detections "
                          "(boxes, scores, classes, detections_per_image) for --task infer, the losses for --task train")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
+    if not args.full:      # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_roofline = args.no_f32 = args.no_f16 = args.no_train = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)

@@ -414,3 +414,19 @@ def test_bench_dump_outputs_writes_the_step_results(tmp_path):
     assert hm.dtype == np.float64 and hm.shape == () and float(hm) == 1.25
     with pytest.raises(SystemExit):
         bench.dump_outputs({"big": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)}, str(tmp_path / "big"))
+
+
+def test_bench_plain_run_measures_the_headline_alone():
+    """bench.py without --full switches every leg beside the headline off, whatever else is given; with --full the legs run
+    and the --no-* options drop single ones"""
+    import bench
+
+    legs = ("no_cpu_baseline", "no_roofline", "no_f32", "no_f16", "no_train")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    assert (plain.gpus, plain.steps, plain.warmup, plain.task, plain.precision, plain.dump_outputs) == (1, 7, 2, "infer", "f16x3", None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    assert (full.gpus, full.steps, full.warmup, full.task, full.precision, full.dump_outputs) == (1, 7, 2, "infer", "f16x3", None)
+    part = bench.parse_args(["--full", "--no-train", "--no-f32"])
+    assert [getattr(part, k) for k in legs] == [False, False, True, False, True]

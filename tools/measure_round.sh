@@ -8,10 +8,10 @@ ROOT=$(pwd)
 M=$ROOT/gpurun_out/m
 mkdir -p $M
 if [ "$1" = "1" ]; then
-  python bench.py > $M/bench_default.json 2> $M/bench_default.err
+  python bench.py --full > $M/bench_default.json 2> $M/bench_default.err
   cd /tmp && export TMPDIR=/tmp
   for P in f16x3 f32 f16; do
-    rocprofv3 --kernel-trace --stats --output-format csv -d $M/prof_infer_$P -o t -- python3 $ROOT/bench.py --precision $P --steps 20 --warmup 5 --no-cpu-baseline --no-train --no-f32 --no-f16 > $M/bench_infer_${P}_under_rocprof.json 2> $M/prof_infer_$P.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $M/prof_infer_$P -o t -- python3 $ROOT/bench.py --precision $P --steps 20 --warmup 5 --full --no-cpu-baseline --no-train --no-f32 --no-f16 > $M/bench_infer_${P}_under_rocprof.json 2> $M/prof_infer_$P.err
   done
 elif [ "$1" = "2" ]; then
   cd /tmp && export TMPDIR=/tmp
@@ -24,7 +24,7 @@ else
   python tools/layer_table.py 64 f16x3 > $M/layer_table_f16x3.txt 2>&1
   python tools/layer_table.py 64 f16 > $M/layer_table_f16.txt 2>&1
   python tools/bench_decode.py > $M/decode.txt 2>&1
-  python bench.py --config r50 --no-cpu-baseline > $M/bench_r50.json 2> $M/bench_r50.err
-  python bench.py --gpus 2 --no-cpu-baseline --no-roofline > $M/bench_gpus2_rehearsal.json 2> $M/bench_gpus2_rehearsal.err
+  python bench.py --config r50 --full --no-cpu-baseline > $M/bench_r50.json 2> $M/bench_r50.err
+  python bench.py --gpus 2 --full --no-cpu-baseline --no-roofline > $M/bench_gpus2_rehearsal.json 2> $M/bench_gpus2_rehearsal.err
 fi
 ls $M

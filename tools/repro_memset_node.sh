@@ -7,7 +7,7 @@ R=${1:-3}
 mkdir -p gpurun_out/repro
 for flags in 4096 0; do
   for i in $(seq 1 $R); do
-    CTDET_TUNE_FLAGS=$flags timeout -k 10 200 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --no-f16 --no-roofline \
+    CTDET_TUNE_FLAGS=$flags timeout -k 10 200 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline --no-f32 --no-f16 --no-roofline \
       > gpurun_out/repro/f${flags}_$i.json 2> gpurun_out/repro/f${flags}_$i.err
     echo "CTDET_TUNE_FLAGS=$flags run $i rc=$? $(python - <<PY
 import json
