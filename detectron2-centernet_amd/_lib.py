@@ -47,6 +47,7 @@ SIGNATURES = {
     "ctdet_preprocess_mirror": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ctdet_head_fused_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "ctdet_head_fused_x3_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctdet_head_sparse_x3_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp]),
     "ctdet_dla_base_fwd": (_i32, [_vp] * 14),
     "ctdet_dla_base_x3_fwd": (_i32, [_vp] * 14),
     "ctdet_dla_base_mirror_fwd": (_i32, [_vp, _i32] + [_vp] * 13),

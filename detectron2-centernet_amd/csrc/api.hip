@@ -375,6 +375,18 @@ int32_t ctdet_head_fused_x3_fwd(const ctdet_head_desc* d, const void* x, const v
   return launch_head_fused_x3(a, (hipStream_t)stream);
 }
 
+int32_t ctdet_head_sparse_x3_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* s1, const float* b1,
+                                 const int32_t* inds, int32_t K, float down_ratio, int32_t flip, float* whreg, float* boxes,
+                                 void* stream) {
+  CTDET_CHECK(d && x && w1 && s1 && b1 && inds && whreg && boxes, "head_sparse_x3: null pointer");
+  CTDET_CHECK(d->nheads == 2 && d->w2[0] && d->w2[1] && d->b2[0] && d->b2[1], "head_sparse_x3: a two-head (wh, reg) pack");
+  HeadArgs a = {};
+  a.x = x; a.w1 = w1; a.s1 = s1; a.b1 = b1;
+  a.nheads = 2; a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.in_stride = d->in_stride;
+  for (int h = 0; h < 2; ++h) { a.w2[h] = d->w2[h]; a.b2[h] = (const float*)d->b2[h]; a.cout[h] = d->cout[h]; }
+  return launch_head_sparse_x3(a, inds, whreg, boxes, K, down_ratio, flip != 0, (hipStream_t)stream);
+}
+
 // mirror_from < 0: the plain kernels; otherwise output images [mirror_from, B) are computed from the mirrored network input
 // of source images [0, B - mirror_from)
 static int32_t dla_base_entry(const ctdet_dla_base_desc* d, int mirror_from, const void* images, const void* w_stem,
@@ -561,7 +573,9 @@ static int32_t decode_entry(bool flip, const float* heat, int32_t heat_stride, c
                             const float* reg, int32_t reg_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K,
                             float down_ratio, float heat_floor, void* workspace, float* boxes, float* scores,
                             int32_t* classes, int32_t* inds, void* stream) {
-  CTDET_CHECK(heat && wh && workspace && boxes && scores && classes, "decode: null pointer");
+  CTDET_CHECK(heat && workspace && scores && classes, "decode: null pointer");
+  // wh == NULL: scores, classes and inds only (the boxes come from ctdet_head_sparse_x3_fwd, which needs the inds)
+  CTDET_CHECK(wh ? boxes != nullptr : (inds != nullptr && !reg), "decode: %s", wh ? "null boxes" : "without wh: inds required, reg must be null");
   CTDET_CHECK(B >= 0 && H > 0 && W > 0, "decode: bad shape B=%d H=%d W=%d", B, H, W);
   CTDET_CHECK(heat_floor >= 0.f && heat_floor < 1.f, "decode: heat_floor %g outside [0, 1)", (double)heat_floor);
   DecArgs a;

@@ -138,7 +138,7 @@ struct DecArgs {
   float down_ratio;
   uint32_t floor_bits;                      // bits of the promised lower bound of the heat values (0 = none)
   uint32_t* ws;
-  float* boxes; float* scores; int* classes; int* inds;
+  float* boxes; float* scores; int* classes; int* inds;   // wh == nullptr: no boxes (launch_head_sparse_x3 writes them), inds required
 };
 
 __device__ __forceinline__ float ctdet_sigmoid(float v) { return 1.0f / (1.0f + __expf(-v)); }
@@ -170,4 +170,8 @@ int ctdet_device_cu_count();
 int launch_conv_f16(const ConvArgs& a, int out_dtype, bool deform, hipStream_t s);
 int launch_head_fused(const HeadArgs& a, hipStream_t s);
 int launch_head_fused_x3(const HeadArgs& a, hipStream_t s);
+// the wh / reg heads (a two-head f16x3 pack; a.y unused) at the pixels inds[B,K] of a.x, and the decode's boxes from them;
+// flip: a.x holds 2 * a.B images, wh is the mean with the mirrored pixel of image b + a.B
+int launch_head_sparse_x3(const HeadArgs& a, const int* inds, float* whreg, float* boxes, int K, float down_ratio, bool flip,
+                          hipStream_t s);
 int launch_conv_f32(const ConvArgs& a, bool deform, bool split, hipStream_t s);

@@ -1783,6 +1783,242 @@ int launch_head_fused_x3(const HeadArgs& a, hipStream_t s) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Sparse f16x3 heads: the size (wh) and offset (reg) heads at the K decoded peaks of every image instead of at every pixel.
+// The decode reads wh / reg at inds[b, k] only (K = 100 of 128^2 pixels), so head_fused_x3_kernel runs for hm alone and this
+// kernel does the other two heads' 64 -> 256 3x3, ReLU and 256 -> 2 1x1 for B*K pixels, then assembles the boxes with
+// dec_final_kernel's expressions.  Same arithmetic as the dense kernel: the 3x3 patch of a peak is split once into
+// {hi, lo}, every 32 products are X.H + Y.H + X.L on the f16 matrix pipe against the korder-3 pair image of w1 (f32
+// accumulation, in the dense kernel's order for the pixel: the results equal the dense maps' bit for bit), h = relu(acc * s1 +
+// b1) is split again and meets {w_hi, w_lo} of the scaled 1x1 rows.
+// A workgroup owns two 16-entry MFMA column tiles.  Plain: 32 peaks.  FLIP: 16 peaks, tile 0 = the peaks in image b, tile 1 =
+// their mirrored pixels (x -> W-1-x) in image b + B; wh = (w0 + wm) * 0.5f, reg from tile 0 alone (tile 1's reg is computed
+// and dropped).  Phase 1 gathers the patches into LDS in B-fragment order, [tile][K step][entry][kg] x 16 bytes = {operand 0:
+// 4 channels, operand 1: 4 channels} of a step of the pair image (zeros outside the map).  Phase 2: wave w owns hidden
+// channels [64w, 64w + 64) of both heads -- per head four 16-row weight tiles whose rows are picked so that a lane ends up
+// with 8 consecutive hidden channels of its entry (rows 8(i/4) + (i%4) and + 4 of a 32-channel block), i.e. with the B
+// fragment of the 1x1 in registers, as in the dense kernel; weight fragments come straight from L2, once per workgroup.
+// The four waves' 1x1 partials (the dense kernel's four slices) are summed through LDS in the dense order ((p0 + p1) + p2) + p3.
+// ------------------------------------------------------------------------------------------
+struct HeadSparseArgs {
+  const float* x;           // f32 [NB,H,W,in_stride], 64 channels (NB = 2B under flip)
+  const void* w1;           // korder-3 pair image of the two heads' first convs, rows [0,256) wh, [256,512) reg; 576 f32 units per row
+  const float *s1, *b1;     // [512]
+  const void* w2[2];        // f16 [16][2][256]
+  const float* b2[2];       // f32 [2][16]
+  const int* inds;          // [B,K]
+  float* whreg;             // [B,K,4] (w, h, off_x, off_y)
+  float* boxes;             // [B,K,4]
+  int B, K, H, W, in_stride;
+  float down_ratio;
+};
+
+template <bool FLIP>
+__global__ void __launch_bounds__(256, 2) head_sparse_x3_kernel(const HeadSparseArgs a) {
+  constexpr int CIN = 64, HID = 256, NSTEP = CIN / 32 * 9, KROW = CIN / 32 * 288;   // K steps; f32 units per packed row
+  constexpr int PPW = FLIP ? 16 : 32;                                               // peaks per workgroup
+  constexpr int FRAG = NSTEP * 1024;                                                // bytes of one tile's fragments (hi or lo)
+  __shared__ __attribute__((aligned(16))) char sH[2 * FRAG];
+  __shared__ __attribute__((aligned(16))) char sL[2 * FRAG];
+  __shared__ int s_ind[32];
+  __shared__ float s_part[4][2][32][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, q = lane >> 4;
+  const int P = a.B * a.K, HW = a.H * a.W;
+  const int p0 = blockIdx.x * PPW;
+
+  if (tid < 32) {
+    const int p = p0 + (FLIP ? (tid & 15) : tid);
+    int ind = -1;
+    if (p < P) ind = min(max(a.inds[p], 0), HW - 1);
+    s_ind[tid] = ind;
+  }
+  __syncthreads();
+
+  // ---- phase 1: patches -> {hi, lo} B fragments ----
+  for (int it = tid; it < 32 * 9 * 16; it += 256) {
+    const int kg = it & 3, c = (it >> 2) & 3, T = (it >> 4) % 9, e = (it >> 4) / 9;
+    const int ind = s_ind[e];
+    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (ind >= 0) {
+      const int p = p0 + (FLIP ? (e & 15) : e);
+      int b = p / a.K, px = ind % a.W;
+      const int py = ind / a.W;
+      if (FLIP && e >= 16) { b += a.B; px = a.W - 1 - px; }
+      const int yy = py + T / 3 - 1, xx = px + T % 3 - 1;
+      if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W)
+        v = *(const f32x4*)(a.x + ((long)b * HW + (long)yy * a.W + xx) * a.in_stride + c * 16 + kg * 4);
+    }
+    const f16x4 hi = __builtin_convertvector(v, f16x4);
+    f32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = v[j] - (float)hi[j];
+    const f16x4 lo = __builtin_convertvector(r, f16x4);
+    // (tap T, chunk c) -> step and operand of the pair image: chunk pair c / 2, A = even chunk, B = odd chunk
+    const int ab = c & 1;
+    const int S = T == 8 ? 4 : (ab ? 5 : 0) + (T >> 1), op = T == 8 ? ab : (T & 1);
+    const int off = (((e >> 4) * NSTEP + (c >> 1) * 9 + S) * 16 + (e & 15)) * 64 + kg * 16 + op * 8;
+    *(f16x4*)(sH + off) = hi;
+    *(f16x4*)(sL + off) = lo;
+  }
+  __syncthreads();
+
+  // ---- phase 2: 3x3 on the wave's 64 hidden channels of each head, then its slice of the 1x1 ----
+  const char* fragH = sH + l15 * 64 + q * 16;
+  const char* fragL = sL + l15 * 64 + q * 16;
+  // is entry l15 of tile t in the second pair of its wave's pixel tiles in head_fused_x3_kernel?  8 x 32 tiles (W % 32 == 0):
+  // a wave has two rows, tile = 2 * (y % 2) + x / 16; 16 x 16 tiles: four rows, tile = y % 4
+  bool late[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int y = max(s_ind[t * 16 + l15], 0) / a.W;
+    late[t] = a.W % 32 == 0 ? (y & 1) != 0 : (y & 3) >= 2;
+  }
+#pragma unroll 1
+  for (int h = 0; h < 2; ++h) {
+    const int cbase = h * HID + wave * 64;
+    // weight rows of tile (hb, half): hidden channel cbase + hb*32 + 8*(l15/4) + 4*half + l15%4
+    const char* wrow = (const char*)a.w1 + ((long)(cbase + 8 * (l15 >> 2) + (l15 & 3)) * KROW) * 4 + q * 16;
+    // the dense kernel adds a step's three products as X.H, Y.H, X.L for the first two pixel tiles of a wave and as X.L, X.H,
+    // Y.H for the other two (pair2_kloop's slot plan).  Both orders are accumulated here and every entry takes the one its
+    // pixel has in the dense kernel: wh / reg come out bit-identical to the dense maps at the same pixels
+    f32x4 acc[2][2][2], acb[2][2][2];     // [hb][half][entry tile]: order X.H, Y.H, X.L / order X.L, X.H, Y.H
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i >> 2][(i >> 1) & 1][i & 1] = acb[i >> 2][(i >> 1) & 1][i & 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 6
+    for (int st = 0; st < NSTEP; ++st) {
+      f16x8 H[2], L[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        H[t] = *(const f16x8*)(fragH + t * FRAG + st * 1024);
+        L[t] = *(const f16x8*)(fragL + t * FRAG + st * 1024);
+      }
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const char* wp = wrow + ((long)(hb * 32 + half * 4) * KROW) * 4 + st * 128;
+          const f16x8 X = *(const f16x8*)wp, Y = *(const f16x8*)(wp + 64);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            acc[hb][half][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, H[t], acc[hb][half][t], 0, 0, 0);
+            acb[hb][half][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, L[t], acb[hb][half][t], 0, 0, 0);
+          }
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            acc[hb][half][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Y, H[t], acc[hb][half][t], 0, 0, 0);
+            acb[hb][half][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, H[t], acb[hb][half][t], 0, 0, 0);
+          }
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            acc[hb][half][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, L[t], acc[hb][half][t], 0, 0, 0);
+            acb[hb][half][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Y, H[t], acb[hb][half][t], 0, 0, 0);
+          }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (late[i & 1]) acc[i >> 2][(i >> 1) & 1][i & 1] = acb[i >> 2][(i >> 1) & 1][i & 1];
+    // hidden = relu(acc * s1 + b1) as {hi, lo}: this lane has channels cbase + hb*32 + 8q .. +8 of entry l15; 1x1 partial
+    const f16* w2 = (const f16*)a.w2[h];
+    f32x4 o[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      const int c0 = cbase + hb * 32 + q * 8;
+      const f32x4 sa = *(const f32x4*)(a.s1 + c0), sb = *(const f32x4*)(a.s1 + c0 + 4);
+      const f32x4 ba = *(const f32x4*)(a.b1 + c0), bb = *(const f32x4*)(a.b1 + c0 + 4);
+      const f16* w2row = w2 + (long)l15 * (2 * HID) + wave * 64 + hb * 32 + q * 8;
+      const f16x8 X = *(const f16x8*)w2row, Y = *(const f16x8*)(w2row + HID);
+      f16x8 hf[2], lf[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const f32x4 v0 = acc[hb][0][t] * sa + ba, v1 = acc[hb][1][t] * sb + bb;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float hv = fmaxf(j < 4 ? v0[j] : v1[j - 4], 0.f);
+          hf[t][j] = (f16)hv;
+          lf[t][j] = (f16)(hv - (float)hf[t][j]);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, hf[t], o[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Y, hf[t], o[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, lf[t], o[t], 0, 0, 0);
+    }
+    if (q == 0) {           // outputs 0, 1 of the head for entry l15 of each tile
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        s_part[wave][h][t * 16 + l15][0] = o[t][0];
+        s_part[wave][h][t * 16 + l15][1] = o[t][1];
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- epilogue: sum the slices, inverse row scale + bias, flip merge, boxes (dec_final_kernel's expressions) ----
+  if (tid < PPW && p0 + tid < P) {
+    const int ind = s_ind[tid];
+    float val[2][2][2];     // [entry tile][head][output]
+#pragma unroll
+    for (int t = 0; t < (FLIP ? 2 : 1); ++t)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int e = FLIP ? t * 16 + tid : tid;
+          float v = s_part[0][h][e][j];
+          v = v + s_part[1][h][e][j];
+          v = v + s_part[2][h][e][j];
+          v = v + s_part[3][h][e][j];
+          val[t][h][j] = v * a.b2[h][16 + j] + a.b2[h][j];
+        }
+    const int x = ind % a.W, y = ind / a.W;
+    float xs = (float)x, ys = (float)y;
+    xs = xs + val[0][1][0]; ys = ys + val[0][1][1];
+    const float w0 = val[0][0][0], h0 = val[0][0][1];
+    float wm = w0, hm = h0;
+    if constexpr (FLIP) {
+      wm = (w0 + val[1][0][0]) * 0.5f;
+      hm = (h0 + val[1][0][1]) * 0.5f;
+    }
+    const float w = wm, h = hm;
+    const long o = p0 + tid;
+    *(f32x4*)(a.whreg + o * 4) = (f32x4){w, h, val[0][1][0], val[0][1][1]};
+    f32x4 box;
+    box[0] = (xs - w / 2) * a.down_ratio;
+    box[1] = (ys - h / 2) * a.down_ratio;
+    box[2] = (xs + w / 2) * a.down_ratio;
+    box[3] = (ys + h / 2) * a.down_ratio;
+    *(f32x4*)(a.boxes + o * 4) = box;
+  }
+}
+
+int launch_head_sparse_x3(const HeadArgs& h, const int* inds, float* whreg, float* boxes, int K, float down_ratio, bool flip,
+                          hipStream_t s) {
+  CTDET_CHECK(h.nheads == 2 && h.cout[0] == 2 && h.cout[1] == 2, "head_sparse_x3: a pack of the wh and reg heads (2 + 2 outputs)");
+  CTDET_CHECK(h.Cin == 64 && h.in_stride % 4 == 0 && h.in_stride >= 64 && (((size_t)h.x) & 15) == 0,
+              "head_sparse_x3: needs a 64-channel f32 map, 16-byte aligned (Cin=%d, stride %d)", h.Cin, h.in_stride);
+  CTDET_CHECK(((((size_t)h.w1) | (size_t)h.s1 | (size_t)h.b1 | (size_t)h.w2[0] | (size_t)h.w2[1] | (size_t)h.b2[0] |
+                (size_t)h.b2[1] | (size_t)whreg | (size_t)boxes) & 15) == 0, "head_sparse_x3: misaligned operand");
+  CTDET_CHECK(h.B >= 0 && K >= 1 && h.H >= 1 && h.W >= 1 && (long)h.B * K < (1L << 28) &&
+                  (long)h.B * (flip ? 2 : 1) * h.H * h.W * h.in_stride < (1L << 40),
+              "head_sparse_x3: bad shape B=%d K=%d %dx%d", h.B, K, h.H, h.W);
+  if (h.B == 0) return 0;
+  HeadSparseArgs a = {};
+  a.x = (const float*)h.x; a.w1 = h.w1; a.s1 = h.s1; a.b1 = h.b1;
+  for (int i = 0; i < 2; ++i) { a.w2[i] = h.w2[i]; a.b2[i] = h.b2[i]; }
+  a.inds = inds; a.whreg = whreg; a.boxes = boxes;
+  a.B = h.B; a.K = K; a.H = h.H; a.W = h.W; a.in_stride = h.in_stride; a.down_ratio = down_ratio;
+  const int P = h.B * K, ppw = flip ? 16 : 32;
+  CTDET_KERNEL(flip ? "head_sparse_x3_kernel<16 peaks x 2,f16x3,flip>" : "head_sparse_x3_kernel<32 peaks,f16x3>");
+  if (flip) hipLaunchKernelGGL(head_sparse_x3_kernel<true>, dim3((P + ppw - 1) / ppw), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(head_sparse_x3_kernel<false>, dim3((P + ppw - 1) / ppw), dim3(256), 0, s, a);
+  CTDET_LAUNCH_CHECK();
+  return 0;
+}
+
 static bool halo16_ok(const ConvArgs& a) {
   return a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.in_dil == 1 && a.nsrc <= 1 &&
          a.korder == 1 && a.Cin % 32 == 0 && a.Kpad == a.K && a.H % 16 == 0 && a.W % 16 == 0 && a.W % 32 != 0 && a.Ho == a.H &&

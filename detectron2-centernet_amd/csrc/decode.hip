@@ -496,24 +496,26 @@ __global__ void __launch_bounds__(1024) dec_final_kernel(DecArgs a, long ws_word
       ind = (int)(canon % HW);
       if ((uint32_t)k - n < nfloor) score = __uint_as_float(a.floor_bits);
     }
-    const int x = ind % a.W, y = ind / a.W;
-    const long pix = (long)b * HW + ind;
-    float xs = (float)x, ys = (float)y;
-    if (a.reg) { xs = xs + a.reg[pix * a.reg_stride]; ys = ys + a.reg[pix * a.reg_stride + 1]; }
-    else { xs += 0.5f; ys += 0.5f; }
-    const float w0 = a.wh[pix * a.wh_stride], h0 = a.wh[pix * a.wh_stride + 1];
-    float wm = w0, hm = h0;
-    if constexpr (FLIP) {     // size map: mean with the mirrored pass; the offsets above are the plain pass's alone
-      const long mpix = (long)(b + a.B) * HW + (ind - x) + (a.W - 1 - x);
-      wm = (w0 + a.wh[mpix * a.wh_stride]) * 0.5f;
-      hm = (h0 + a.wh[mpix * a.wh_stride + 1]) * 0.5f;
-    }
-    const float w = wm, h = hm;
     const long o = (long)b * a.K + k;
-    a.boxes[o * 4 + 0] = (xs - w / 2) * a.down_ratio;
-    a.boxes[o * 4 + 1] = (ys - h / 2) * a.down_ratio;
-    a.boxes[o * 4 + 2] = (xs + w / 2) * a.down_ratio;
-    a.boxes[o * 4 + 3] = (ys + h / 2) * a.down_ratio;
+    if (a.wh) {               // (no size map: the boxes are the sparse head kernel's, from inds)
+      const int x = ind % a.W, y = ind / a.W;
+      const long pix = (long)b * HW + ind;
+      float xs = (float)x, ys = (float)y;
+      if (a.reg) { xs = xs + a.reg[pix * a.reg_stride]; ys = ys + a.reg[pix * a.reg_stride + 1]; }
+      else { xs += 0.5f; ys += 0.5f; }
+      const float w0 = a.wh[pix * a.wh_stride], h0 = a.wh[pix * a.wh_stride + 1];
+      float wm = w0, hm = h0;
+      if constexpr (FLIP) {     // size map: mean with the mirrored pass; the offsets above are the plain pass's alone
+        const long mpix = (long)(b + a.B) * HW + (ind - x) + (a.W - 1 - x);
+        wm = (w0 + a.wh[mpix * a.wh_stride]) * 0.5f;
+        hm = (h0 + a.wh[mpix * a.wh_stride + 1]) * 0.5f;
+      }
+      const float w = wm, h = hm;
+      a.boxes[o * 4 + 0] = (xs - w / 2) * a.down_ratio;
+      a.boxes[o * 4 + 1] = (ys - h / 2) * a.down_ratio;
+      a.boxes[o * 4 + 2] = (xs + w / 2) * a.down_ratio;
+      a.boxes[o * 4 + 3] = (ys + h / 2) * a.down_ratio;
+    }
     a.scores[o] = score;
     a.classes[o] = cls;
     if (a.inds) a.inds[o] = ind;

@@ -149,15 +149,46 @@ class _EvalEngine:
         m.backbone.base.base_level1(images, m._mean_host, m._std_host, self.Hp, self.Wp, out=self.l1, pooled=self.l1p,
                                     x3=m._ctx.compute == ops.F16X3, mirror=self._mirror)
 
+    @property
+    def out(self):
+        """(hm, wh, reg) of the last step as dense NHWC maps.  A sparse step (see _run) made hm only: wh and reg are then
+        computed here, on first access after the step, by the dense fused kernel from the step's retained head input --
+        eagerly, outside the graph -- and kept until the next step."""
+        if self._out is None:
+            m = self.model
+            z = ops.heads_fused(self._y, m._packed_heads(["wh", "reg"], True), clamp=SIGMOID_CLAMP)
+            self._out = (self._hm, z[0][..., :2], z[1][..., :2])
+        return self._out
+
+    def _run_sparse(self, y):
+        """f16x3 step whose wh / reg heads run at the decoded peaks only: dense hm head (a third of the three-head grid),
+        map-free decode, then ops.heads_sparse on the decode's inds, which also assembles the boxes."""
+        m = self.model
+        K, dr = m.topk_candidates, m.backbone.down_ratio
+        self._y, self._out = y, None
+        self._hm = m._hm_view(m._head_outputs(y, True, only=("hm",))["hm"])
+        _, scores, classes, inds = ops.decode(self._hm, None, None, K, dr, heat_floor=ops.SIGMOID_CLAMP_FLOOR, flip=self.flip)
+        self.whreg, boxes = ops.heads_sparse(y, m._packed_heads(["wh", "reg"], True), inds, dr, flip=self.flip)
+        self.dec = (boxes, scores, classes, inds)
+        # the flag covers the peaks' wh / reg (both halves under flip: the mean of a non-finite value is non-finite) and the
+        # heads' input y, which is what the dense wh / reg maps used to reflect away from the peaks
+        self.finite = ops.finite_flag(self.whreg.view(self.B, K, 1, 4), y).bool()
+
     def _run(self):
         m = self.model
         if self.fused_base:
-            self.out = m._network_outputs(None, apply_sigmoid=True, level1=(self.l1, self.l1p))
+            x, prepadded, level1 = None, False, (self.l1, self.l1p)
         else:
             x = ops.preprocess(self.images, m._mean_host, m._std_host, self.Hp, self.Wp, out=self.xpad, border=self.border,
                                mirror=self._mirror)
-            self.out = m._network_outputs(x, apply_sigmoid=True, prepadded=self.border > 0)
-        hm, wh, reg = self.out
+            prepadded, level1 = self.border > 0, None
+        y = m._features(x, prepadded, level1)
+        self.sparse = m._sparse_heads_ok(y)
+        if self.sparse:
+            return self._run_sparse(y)
+        z = m._head_outputs(y, True)
+        self._out = (m._hm_view(z["hm"]), z["wh"][..., :2], z["reg"][..., :2])
+        hm, wh, reg = self._out
         # the head kernel's epilogue has just clamped hm to [1e-4, 1 - 1e-4]: the decode may skip the floor plateau
         # (flip: the mean of two clamped values respects the floor too)
         self.dec = ops.decode(hm, wh, reg, m.topk_candidates, m.backbone.down_ratio, heat_floor=ops.SIGMOID_CLAMP_FLOOR,
@@ -184,6 +215,8 @@ class _EvalEngine:
             self._base(self.images if images is None else images)
         elif images is not None:
             self.images.copy_(images, non_blocking=True)
+        if self.sparse:
+            self._out = None              # the dense wh / reg of the previous step
         if self.graph is not None:
             self.graph.replay()
         else:
@@ -326,28 +359,50 @@ class CenterNet(nn.Module):
         return eng
 
     # ------------------------------------------------------------------ network (NHWC, HIP kernels)
-    def _head_outputs(self, y, apply_sigmoid):
-        """y NHWC [B,h,w,64] -> dict head -> f32 NHWC buffer (channels padded to a multiple of 4)."""
+    def _heads_fusable(self, y):
+        # (CTDET_NO_FUSED_HEADS=1 turns ops.HEADS_FUSED off for both precisions)
+        ctx, names = self._ctx, [h.lower() for h in self.heads]
+        return (self.head_conv == ops.PackedHeads.HID and ctx.compute in (F16, F16X3) and ops.HEADS_FUSED
+                and ops.heads_fused_ok(y, ctx.compute) and len(names) <= 4
+                and all(getattr(self, n)[2].kernel_size == (1, 1) for n in names))
+
+    def _packed_heads(self, names, apply_sigmoid):
+        """the fused-head pack of the heads `names` (all of them, or a subset: hm alone / (wh, reg) of the sparse eval step)"""
+        ctx = self._ctx
+        fcs = [getattr(self, n) for n in names]
+        acts = [ACT_SIGMOID_CLAMP if (apply_sigmoid and n == "hm") else ACT_NONE for n in names]
+        cache = self.__dict__.setdefault("_ctdet_packed", {})
+        ver = tuple((t.data_ptr(), t._version) for fc in fcs for t in (fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias))
+        key = ("heads_fused", ctx.compute, tuple(names), tuple(acts))
+        hit = cache.get(key)
+        if hit is None or hit[0] != ver:
+            ph = ops.PackedHeads([fc[0].weight for fc in fcs], [fc[0].bias for fc in fcs],
+                                 [fc[2].weight for fc in fcs], [fc[2].bias for fc in fcs], acts, compute=ctx.compute)
+            hit = cache[key] = (ver, ph)
+        return hit[1]
+
+    def _sparse_heads_ok(self, y):
+        """may the eval step compute wh / reg at the decoded peaks only (ops.heads_sparse)?  f16x3 with the fused heads, heads
+        exactly hm / wh / reg (2 + 2 outputs, 1x1 final convs) on a 64-channel map, and K < h*w: with K >= h*w the decode pads
+        its list with non-peak pixels and nothing is saved."""
+        names = sorted(h.lower() for h in self.heads)
+        return (ops.HEADS_SPARSE and self._ctx.compute == F16X3 and names == ["hm", "reg", "wh"] and self._heads_fusable(y)
+                and y.shape[3] == 64 and self.wh[2].out_channels == 2 and self.reg[2].out_channels == 2
+                and self.topk_candidates < y.shape[1] * y.shape[2])
+
+    def _head_outputs(self, y, apply_sigmoid, only=None):
+        """y NHWC [B,h,w,64] -> dict head -> f32 NHWC buffer (channels padded to a multiple of 4).  only: a subset of the heads
+        (fused path of the sparse eval step)."""
         ctx = self._ctx
         names = [h.lower() for h in self.heads]
         out = {}
-        # (CTDET_NO_FUSED_HEADS=1 turns ops.HEADS_FUSED off for both precisions)
-        fused = (self.head_conv == ops.PackedHeads.HID and ctx.compute in (F16, F16X3) and ops.HEADS_FUSED
-                 and ops.heads_fused_ok(y, ctx.compute) and len(names) <= 4
-                 and all(getattr(self, n)[2].kernel_size == (1, 1) for n in names))
+        fused = self._heads_fusable(y)
+        assert only is None or fused
         if fused:
             # 3x3 + ReLU + 1x1 of every head in one kernel: the 256-channel hidden maps never reach memory
-            fcs = [getattr(self, n) for n in names]
-            acts = [ACT_SIGMOID_CLAMP if (apply_sigmoid and n == "hm") else ACT_NONE for n in names]
-            cache = self.__dict__.setdefault("_ctdet_packed", {})
-            ver = tuple((t.data_ptr(), t._version) for fc in fcs for t in (fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias))
-            key = ("heads_fused", ctx.compute, tuple(acts))
-            hit = cache.get(key)
-            if hit is None or hit[0] != ver:
-                ph = ops.PackedHeads([fc[0].weight for fc in fcs], [fc[0].bias for fc in fcs],
-                                     [fc[2].weight for fc in fcs], [fc[2].bias for fc in fcs], acts, compute=ctx.compute)
-                hit = cache[key] = (ver, ph)
-            outs = ops.heads_fused(y, hit[1], clamp=SIGMOID_CLAMP)
+            if only is not None:
+                names = [n for n in names if n in only]
+            outs = ops.heads_fused(y, self._packed_heads(names, apply_sigmoid), clamp=SIGMOID_CLAMP)
             return dict(zip(names, outs))
         if self.head_conv > 0:
             convs = [getattr(self, n)[0] for n in names]
@@ -398,17 +453,21 @@ class CenterNet(nn.Module):
                 y = y[..., :up.out_channels]
         return y
 
-    def _network_outputs(self, x_nhwc, apply_sigmoid, prepadded=False, level1=None):
+    def _features(self, x_nhwc, prepadded=False, level1=None):
+        """the NHWC map the heads read"""
         if self.backbone_type in ("resnet", "vovnet"):
-            y = self._deconv_forward(self.backbone.hip_forward(x_nhwc, self._ctx, prepadded)[self.deconv_feature])
-        else:
-            y = self.backbone.hip_forward(x_nhwc, self._ctx, prepadded, level1=level1)[-1]
-        z = self._head_outputs(y, apply_sigmoid)
-        hm = z["hm"]
+            return self._deconv_forward(self.backbone.hip_forward(x_nhwc, self._ctx, prepadded)[self.deconv_feature])
+        return self.backbone.hip_forward(x_nhwc, self._ctx, prepadded, level1=level1)[-1]
+
+    def _hm_view(self, hm):
         assert hm.shape[3] == self.num_classes or hm.shape[3] == ops.round_up(self.num_classes, 4)
         # class counts that are not multiples of 4: the padded buffer stays, consumers get the channel-slice view (the
         # decode and the loss kernels take a pixel stride)
-        return hm[..., :self.num_classes] if hm.shape[3] != self.num_classes else hm, z["wh"][..., :2], z["reg"][..., :2]
+        return hm[..., :self.num_classes] if hm.shape[3] != self.num_classes else hm
+
+    def _network_outputs(self, x_nhwc, apply_sigmoid, prepadded=False, level1=None):
+        z = self._head_outputs(self._features(x_nhwc, prepadded, level1), apply_sigmoid)
+        return self._hm_view(z["hm"]), z["wh"][..., :2], z["reg"][..., :2]
 
     # ------------------------------------------------------------------ reference API
     def forward(self, batched_inputs):

@@ -927,6 +927,9 @@ def heads_fused(x, ph, clamp=(0.0, 1.0), outs=None):
     d.clamp_lo, d.clamp_hi = clamp
     M = B * H * W
     prof = _Prof(None, M, False, F32, flops=sum(2.0 * M * PackedHeads.HID * (9 * ph.Cin + c) for c in ph.couts))
+    if prof.on:
+        prof.bytes = float(M * 4 * (ph.Cin + sum(round_up(c, 4) for c in ph.couts))) if x3 else prof.bytes
+        prof.info = f"M={M} {ph.Cin}->{PackedHeads.HID}->{','.join(str(c) for c in ph.couts)}"
     for _ in range(prof.reps()):
         if x3:
             rc = _lib.lib().ctdet_head_fused_x3_fwd(C.byref(d), _ptr(x), _ptr(ph.w1), _ptr(ph.s1), _ptr(ph.b1), _stream())
@@ -935,6 +938,41 @@ def heads_fused(x, ph, clamp=(0.0, 1.0), outs=None):
     _lib.check(rc, "ctdet_head_fused_x3_fwd" if x3 else "ctdet_head_fused_fwd")
     prof.done()
     return outs
+
+
+# CTDET_NO_SPARSE_HEADS=1: the f16x3 eval step computes the wh / reg heads densely again (the launches before heads_sparse existed)
+HEADS_SPARSE = os.environ.get("CTDET_NO_SPARSE_HEADS", "0") != "1"
+
+
+def heads_sparse(y, ph, inds, down_ratio, flip=False):
+    """the wh / reg heads at the decoded peaks only, and the decode's boxes from them.  y f32 NHWC [NB,H,W,64] (the heads' input;
+    NB = 2B under flip), ph an F16X3 PackedHeads of exactly (wh, reg), inds i32 [B,K] from decode(...).  flip: wh is the mean
+    with the mirrored pixel of image b + B, reg image b's (decode's flip rule).  Returns (whreg [B,K,4] = (w, h, off_x, off_y),
+    boxes [B,K,4])."""
+    _require_cuda(y, inds)
+    assert ph.compute == F16X3 and ph.n == 2 and ph.couts == [2, 2], "heads_sparse: a pack of the wh and reg heads"
+    assert y.dtype == torch.float32 and y.shape[3] == ph.Cin and inds.dtype == torch.int32 and inds.is_contiguous()
+    assert ph.w1.shape[0] >= 2 * PackedHeads.HID and ph.w1.shape[1] == ph.Cin // 32 * 288 and ph.Cin == 64
+    NB, H, W, _ = y.shape
+    B, K = inds.shape
+    assert NB == (2 * B if flip else B) and y.stride(0) == H * W * y.stride(2) and y.stride(1) == W * y.stride(2)
+    whreg = torch.empty(B, K, 4, dtype=torch.float32, device=y.device)
+    boxes = torch.empty(B, K, 4, dtype=torch.float32, device=y.device)
+    d = HeadDesc()
+    d.nheads, d.B, d.H, d.W, d.Cin, d.in_stride = 2, B, H, W, ph.Cin, _nhwc_stride(y)
+    for h in range(2):
+        d.w2[h], d.b2[h], d.cout[h] = ph.w2[h].data_ptr(), ph.b2[h].data_ptr(), ph.couts[h]
+    M = (2 if flip else 1) * B * K
+    prof = _Prof(None, M, False, F32, flops=2.0 * M * PackedHeads.HID * (9 * ph.Cin + 2) * 2)
+    if prof.on:      # algorithmic bytes: the patches once, the two heads' weights once
+        prof.bytes = float(M * 9 * ph.Cin * 4 + ph.w1.numel() * 4)
+        prof.info = f"peaks={M} {ph.Cin}->{PackedHeads.HID}->2,2 at inds" + (" flip" if flip else "")
+    for _ in range(prof.reps()):
+        rc = _lib.lib().ctdet_head_sparse_x3_fwd(C.byref(d), _ptr(y), _ptr(ph.w1), _ptr(ph.s1), _ptr(ph.b1), _ptr(inds), K,
+                                                 float(down_ratio), int(bool(flip)), _ptr(whreg), _ptr(boxes), _stream())
+    _lib.check(rc, "ctdet_head_sparse_x3_fwd")
+    prof.done()
+    return whreg, boxes
 
 
 def maxpool3x3s2(x, out=None):
@@ -975,7 +1013,8 @@ def finite_flag(*tensors):
     for t in tensors:
         assert t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1
         B, H, W, Cc = t.shape
-        _lib.check(_lib.lib().ctdet_finite_flag(_ptr(t), B * H * W, Cc, _nhwc_stride(t), _ptr(flag), _stream()), "ctdet_finite_flag")
+        with prof_region("finite_flag", nbytes=float(t.numel() * 4), info="x".join(str(n) for n in t.shape)):
+            _lib.check(_lib.lib().ctdet_finite_flag(_ptr(t), B * H * W, Cc, _nhwc_stride(t), _ptr(flag), _stream()), "ctdet_finite_flag")
     return flag
 
 
@@ -1129,13 +1168,18 @@ def decode(heat, wh, reg, K, down_ratio, workspace=None, check_status=False, hea
     flip (flip test): heat / wh / reg hold 2B images, image b + B being the network's maps for the horizontally mirrored
     input of image b; decoded are hm = (hm[b] + mirror(hm[b+B])) * 0.5, wh = (wh[b] + mirror(wh[b+B])) * 0.5 and reg = reg[b]
     (mirror: x <-> W-1-x; one f32 add and one multiply in that order), merged inside the decode's one pass over the maps.
+    wh = reg = None: the map-free mode -- scores, classes and inds as always, `boxes` comes back unwritten, for
+    heads_sparse(..., inds) to supply.
     Returns boxes [B,K,4], scores [B,K], classes [B,K] (int32), inds [B,K] (int32)."""
     _require_cuda(heat, wh, reg)
     assert heat.dtype == torch.float32
     B, H, W, Cc = heat.shape
+    assert wh is not None or reg is None, "decode: reg without wh"
     if flip:
-        assert B % 2 == 0 and wh.shape[0] == B and (reg is None or reg.shape[0] == B), "flip decode: 2B images, plain half first"
-        assert heat.stride(0) == H * W * heat.stride(2) and wh.stride(0) == H * W * wh.stride(2), "flip decode: dense batches"
+        assert B % 2 == 0 and (wh is None or wh.shape[0] == B) and (reg is None or reg.shape[0] == B), \
+            "flip decode: 2B images, plain half first"
+        assert heat.stride(0) == H * W * heat.stride(2) and (wh is None or wh.stride(0) == H * W * wh.stride(2)), \
+            "flip decode: dense batches"
         B //= 2
     if workspace is None or workspace.key != (B, H, W, Cc, K):
         workspace = DecodeWorkspace(B, H, W, Cc, K, heat.device)
@@ -1146,7 +1190,7 @@ def decode(heat, wh, reg, K, down_ratio, workspace=None, check_status=False, hea
     inds = torch.empty(B, K, dtype=torch.int32, device=dev)
     with prof_region("decode", nbytes=float(B * H * W * Cc * 4), info=f"{B}x{H}x{W}x{Cc} K={K}"):
         fn = _lib.lib().ctdet_decode_flip if flip else _lib.lib().ctdet_decode
-        rc = fn(_ptr(heat), _nhwc_stride(heat), _ptr(wh), _nhwc_stride(wh), _ptr(reg),
+        rc = fn(_ptr(heat), _nhwc_stride(heat), _ptr(wh), _nhwc_stride(wh) if wh is not None else 0, _ptr(reg),
                 _nhwc_stride(reg) if reg is not None else 0, B, H, W, Cc, K, float(down_ratio),
                 float(heat_floor), _ptr(workspace.buf), _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(inds), _stream())
     _lib.check(rc, "ctdet_decode")

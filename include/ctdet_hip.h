@@ -193,6 +193,17 @@ int32_t ctdet_head_fused_fwd(const ctdet_head_desc* d, const void* x, const void
  * inverse row scale; y[h] as for ctdet_head_fused_fwd.  Every pixel's result is independent of B. */
 int32_t ctdet_head_fused_x3_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* s1, const float* b1,
                                 void* stream);
+/* The size (wh) and offset (reg) heads of ctdet_head_fused_x3_fwd at the decoded peaks only, and the decode's boxes from them
+ * (an addition within ABI 8).  d: nheads = 2 with cout = {2, 2}, head 0 = wh, head 1 = reg, w2 / b2 as above (y, y_stride, act
+ * and the clamp are not read); x: f32 NHWC, Cin = 64, any H, W; w1, s1, b1: the two heads' rows of the same korder-3 pack.
+ * inds i32 [B,K]: the pixel y*W+x of every peak, as ctdet_decode returns them (clamped into the map).  flip = 0: x holds B
+ * images.  flip != 0: x holds 2B images (d->B is still the output batch) and wh is (wh[b, y, x] + wh[b+B, y, W-1-x]) * 0.5f,
+ * reg is image b's, as in ctdet_decode_flip.  Writes whreg f32 [B,K,4] = (w, h, off_x, off_y) and boxes f32 [B,K,4], the
+ * latter by ctdet_decode's expressions.  Products and their order of accumulation are those of ctdet_head_fused_x3_fwd for
+ * the same pixel (on a map that entry point takes): whreg equals its maps at inds, and the boxes ctdet_decode's, bit for bit. */
+int32_t ctdet_head_sparse_x3_fwd(const ctdet_head_desc* d, const void* x, const void* w1, const float* s1, const float* b1,
+                                 const int32_t* inds, int32_t K, float down_ratio, int32_t flip, float* whreg, float* boxes,
+                                 void* stream);
 /* May the fused head kernel of compute_dtype (CTDET_DT_F16 / CTDET_DT_F16X3) take the NHWC map x [*,H,W,in_stride]?  The
  * input-side conditions of the two entry points above (tile divisibility, Cin, pixel stride, alignment of x); 1 or 0. */
 int32_t ctdet_head_fused_supported(int32_t compute_dtype, int32_t H, int32_t W, int32_t Cin, int32_t in_stride, const void* x);
@@ -316,7 +327,8 @@ int32_t ctdet_dwconvT_add(const void* x, const float* w, const void* skip, void*
 /* Batched ctdet_decode (centernet.py:399-458): heat f32 NHWC [B,H,W,heat_stride] (already sigmoid+clamp; the first C
  * channels are classes, any C >= 1), wh/reg f32 with pixel strides; outputs boxes [B,K,4] f32, scores [B,K] f32, classes
  * [B,K] i32, inds [B,K] i32 (spatial index y*W+x; may be NULL).  Order: score desc, ties by c*H*W+y*W+x asc.  reg may
- * be NULL.  The heat map is read once; workspace: ctdet_decode_workspace_bytes of the same B, H, W, C, K.
+ * be NULL.  wh may be NULL (then reg must be NULL and inds must not be): scores, classes and inds are written as always and
+ * boxes is left untouched, for ctdet_head_sparse_x3_fwd to fill.  The heat map is read once; workspace: ctdet_decode_workspace_bytes of the same B, H, W, C, K.
  * heat_floor: a lower bound the caller promises for every positive heat value -- 1e-4f for the map `_sigmoid` clamps
  * (centernet.py:13-15) -- or 0 for none.  Results are the same either way; with the bound, the plateau a trained
  * network's background forms exactly on the clamp is skipped by the selection passes and only consulted (lowest flat index
