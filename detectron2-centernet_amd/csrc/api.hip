@@ -27,103 +27,15 @@ bool ctdet_set_label(const char* fmt, ...) {
   return g_label_mode == 2;
 }
 
-// launchers from the kernel files
-int launch_preprocess(const void*, int, void*, int, int, int, int, int, int, long, const float*, const float*, int, int,
-                      int mirror_from, hipStream_t);
-int launch_maxpool2x2(const void*, void*, int, int, int, int, int, int, int, hipStream_t);
-int launch_maxpool3x3s2(const void*, void*, int, int, int, int, int, int, int, int, hipStream_t);
-int launch_global_avgpool(const void*, int, int, int, int, int, float*, hipStream_t);
-int launch_ese_scale(const void*, int, const float*, const void*, int, void*, int, int, int, int, int, hipStream_t);
-int launch_finite_flag(const float*, long, int, int, int*, hipStream_t);
-int launch_pack_weights(const float*, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
-int launch_dwconvT_add(const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, int,
-                       hipStream_t);
-int dwconv3x3_check(int, int, int, int, int, int, const int*, int);
-size_t dwconv3x3_wgrad_workspace_bytes(int, int, int, int, int);
-int launch_dwconv3x3(const void*, int, const float*, void*, int, int, int, int, int, int, int, int, hipStream_t);
-int launch_dwconv3x3_wgrad(const void*, int, const void*, int, float*, float*, float, int, int, int, int, int, int, hipStream_t);
-size_t decode_workspace_bytes(int B, int H, int W, int C, int K);
-int decode_status_words(int H, int W, int C, int K, long* ws_words, int* below_word);
-int launch_decode(const DecArgs&, bool flip, hipStream_t);
-int launch_postprocess(const float*, const float*, const int*, int, int, int, float, const float*, float*, float*, int*,
-                       int*, hipStream_t);
-int launch_gaussian_radius(const int*, int, double*, int*, hipStream_t);
-int launch_gaussian_targets(const float*, const int64_t*, const int*, int, int, int, int, int, float*, float*, float*,
-                            int64_t*, uint8_t*, hipStream_t);
-size_t focal_workspace_bytes(long numel);
-int launch_focal_loss(const float*, const float*, const float*, int, int, int, int, float, void*, float*, float*, float*,
-                      hipStream_t);
-int launch_reg_l1(const float*, int, const uint8_t*, const int64_t*, const float*, int, int, int, float, float*, float*,
-                  int, hipStream_t);
-int launch_sgd(float*, const float*, float*, long, const float*, float, float, int, hipStream_t);
-int launch_sgd_runs(float*, const float*, float*, long, const long*, const int*, const float*, const float*, int, float, int,
-                    hipStream_t);
-int launch_sgd_runs_clip(float*, const float*, float*, long, const long*, const int*, const float*, const float*, int, float, int,
-                         int, int, float, const float*, hipStream_t);
-int launch_grad_chunk_norms(const float*, long, const long*, const int*, int, int, float*, hipStream_t);
-int launch_grad_clip_coefs(const float*, const int*, int, int, int, float, float*, float*, hipStream_t);
-int launch_adam_advance(long long*, float*, double, double, hipStream_t);
-int launch_adam_runs(float*, const float*, float*, float*, float*, long, const long*, const int*, const float*, const float*, int,
-                     const float*, double, double, double, int, int, int, float, const float*, hipStream_t);
+static_assert(CTDET_DT_F16 == CTDET_F16 && CTDET_DT_F32 == CTDET_F32 && CTDET_DT_U8 == CTDET_U8 && CTDET_DT_F16X3 == CTDET_F16X3,
+              "dtypes: header and kernels disagree");
 static_assert(CTDET_CLIP_NONE == SGD_CLIP_NONE && CTDET_CLIP_VALUE == SGD_CLIP_VALUE && CTDET_CLIP_NORM == SGD_CLIP_NORM &&
               CTDET_NORM_L1 == GRAD_NORM_L1 && CTDET_NORM_L2 == GRAD_NORM_L2 && CTDET_NORM_INF == GRAD_NORM_INF,
               "clip / norm modes: header and kernels disagree");
-
-struct WgradArgs {
-  const void* x; const void* dy; float* dw;
-  int B, H, W, Cin, in_stride, Cout, Ho, Wo, dy_stride, R, S, stride, pad, dil, K, M, msplit;
-  float scale;
-  int lw, lh;
-  int perm_rs, perm_cin, cin_real, cout_real;
-};
-int launch_grad_scatter_oihw(const void* const*, void* const*, const int*, const int*, const int*, const int*, int, hipStream_t);
-int launch_pack_weights_batch(const void*, int, int, hipStream_t);
-int launch_pack_weights_x3(const float*, void*, float*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-int launch_pack_weights_x3_batch(const void*, int, int, hipStream_t);
-int launch_split_weights(const float*, void*, long, hipStream_t);
-bool dcn_offset_fused_ok(const ConvArgs& a);
-bool dcn_offset_fused_x3_ok(const ConvArgs& a);
-int launch_dcn_offset_x3(const ConvArgs& a, hipStream_t s);
-int conv_pair_korder(const ConvArgs& a);
-bool head_fused_x_ok(const HeadArgs& a, bool x3);
-bool dcn_split_window_ok(const ConvArgs& a);
-size_t chan_reduce_workspace_bytes(int C);
-int launch_bn_train_fwd(const f16*, int, const f16*, int, f16*, int, int, int, const float*, const float*, float, float,
-                        float*, float*, float*, float*, float*, float*, void*, int, hipStream_t);
-int launch_bn_train_bwd(const f16*, int, const f16*, int, const f16*, int, const float*, const float*, const float*, int,
-                        int, int, f16*, int, f16*, int, float*, float*, float, void*, hipStream_t);
-int launch_conv_wgrad(const WgradArgs&, hipStream_t);
-int launch_conv_wgrad_f32(const WgradArgs&, hipStream_t);
-int launch_conv_wgrad_x3(const WgradArgs&, hipStream_t);
-int launch_bn_train_fwd_f32(const float*, int, const float*, int, float*, int, int, int, const float*, const float*, float,
-                            float, float*, float*, float*, float*, float*, float*, void*, int, hipStream_t);
-int launch_bn_train_bwd_f32(const float*, int, const float*, int, const float*, int, const float*, const float*, const float*,
-                            int, int, int, float*, int, float*, int, float*, float*, float, void*, hipStream_t);
-int launch_bn_local_stats(const void*, int, int, int, int, int, double*, void*, int, hipStream_t);
-int launch_bn_sync_fwd(const void*, int, const void*, int, void*, int, int, int, const double*, int, const float*, const float*,
-                       float, float, float*, float*, float*, float*, float*, float*, int, int, hipStream_t);
-int launch_bn_local_grad_sums(const void*, int, const void*, int, const void*, int, const float*, const float*, int, int, int, int,
-                              int, double*, float*, float*, float, void*, int, hipStream_t);
-int launch_bn_sync_bwd(const void*, int, const void*, int, const void*, int, const float*, const float*, const float*,
-                       const double*, const double*, int, int, int, int, void*, int, void*, int, int, hipStream_t);
-int launch_maxpool2x2_bwd_f32(const float*, int, const float*, int, float*, int, int, int, int, int, hipStream_t);
-int launch_maxpool3x3s2_bwd(const void*, int, const void*, int, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
-int launch_ese_dot(const void*, int, const void*, int, int, int, int, int, float*, hipStream_t);
-int launch_ese_bwd(const void*, int, const float*, const float*, void*, int, int, int, int, int, hipStream_t);
-int launch_dwconvT_bwd_f32(const float*, int, const float*, int, const float*, float*, int, float*, int, int, int, int, int,
-                           hipStream_t);
-int launch_dcn_cols_f32(const float*, int, const float*, int, float*, int, int, int, int, int, hipStream_t);
-int launch_dcn_col2im_coord_f32(const float*, const float*, int, const float*, int, float*, float*, int, int, int, int, int, int,
-                                int, int, hipStream_t);
-int launch_dcn_col2im_fused(const float*, int, int, const void*, const float*, const float*, int, const float*, int, float*, float*, int,
-                            int, int, int, int, int, hipStream_t);
-int launch_maxpool2x2_bwd(const f16*, int, const f16*, int, f16*, int, int, int, int, int, hipStream_t);
-int launch_depth_to_space2(const void*, int, void*, int, int, int, int, int, int, int, int, hipStream_t);
-int launch_dwconvT_bwd(const f16*, int, const f16*, int, const float*, f16*, int, float*, int, int, int, int, int,
-                       hipStream_t);
-int launch_dcn_cols(const f16*, int, const float*, int, f16*, int, int, int, int, int, hipStream_t);
-int launch_dcn_col2im_coord(const f16*, const f16*, int, const float*, int, float*, void*, int, int, int, int, int, int, int, int,
-                            hipStream_t);
+static_assert(CTDET_DCN_MASK_LOGIT == DCN_MASK_LOGIT && CTDET_DCN_MASK_PROB == DCN_MASK_PROB && CTDET_DCN_MASK_NONE == DCN_MASK_NONE,
+              "mask modes of the ABI and of the kernels");
+#define CTDET_DCN_MASK_MODE(what, mode) \
+  CTDET_CHECK((mode) >= CTDET_DCN_MASK_LOGIT && (mode) <= CTDET_DCN_MASK_NONE, what ": mask mode %d", mode)
 
 static int fill_args(const ctdet_conv_desc* d, ConvArgs& a) {
   CTDET_CHECK(d != nullptr, "conv: null descriptor");
@@ -149,6 +61,17 @@ static int fill_args(const ctdet_conv_desc* d, ConvArgs& a) {
               "conv: korder=%d invalid for Cin=%d", d->korder, d->Cin);
   CTDET_CHECK((long)d->B * d->Ho * d->Wo < (1L << 31), "conv: too many output pixels");
   return 0;
+}
+
+// the tail of the conv-shaped forward entry points: f16 tensors go to conv_igemm.hip, f32 tensors (f32 or f16x3 arithmetic)
+// to conv_f32.hip, which writes f32 only
+static int conv_dispatch(const char* op, const ctdet_conv_desc* d, const ConvArgs& a, bool deform, void* stream) {
+  if (d->compute_dtype == CTDET_DT_F16) return launch_conv_f16(a, d->out_dtype, deform, (hipStream_t)stream);
+  if (d->compute_dtype == CTDET_DT_F32 || d->compute_dtype == CTDET_DT_F16X3) {
+    CTDET_CHECK(d->out_dtype == CTDET_DT_F32, "%s(f32 / f16x3): output must be f32", op);
+    return launch_conv_f32(a, deform, d->compute_dtype == CTDET_DT_F16X3, (hipStream_t)stream);
+  }
+  CTDET_CHECK(false, "%s: bad compute dtype %d", op, d->compute_dtype);
 }
 
 static std::atomic<unsigned> g_tuning{0};
@@ -179,8 +102,6 @@ int32_t ctdet_set_label_mode(int32_t mode) {
   return 0;
 }
 const char* ctdet_last_kernel_label(void) { return g_label; }
-static_assert(CTDET_DCN_MASK_LOGIT == DCN_MASK_LOGIT && CTDET_DCN_MASK_PROB == DCN_MASK_PROB && CTDET_DCN_MASK_NONE == DCN_MASK_NONE,
-              "mask modes of the ABI and of the kernels");
 int32_t ctdet_conv_cout_tile(int32_t cout) { return pick_bc(cout); }
 
 int32_t ctdet_conv2d_fwd(const ctdet_conv_desc* d, const void* x, const void* w_packed, const float* scale,
@@ -191,12 +112,7 @@ int32_t ctdet_conv2d_fwd(const ctdet_conv_desc* d, const void* x, const void* w_
   if (a.M == 0) return 0;
   CTDET_CHECK(x && w_packed && y, "conv: null pointer");
   a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = residual; a.y = y;
-  if (d->compute_dtype == CTDET_DT_F16) return launch_conv_f16(a, d->out_dtype, false, (hipStream_t)stream);
-  if (d->compute_dtype == CTDET_DT_F32 || d->compute_dtype == CTDET_DT_F16X3) {
-    CTDET_CHECK(d->out_dtype == CTDET_DT_F32, "conv(f32 / f16x3): output must be f32");
-    return launch_conv_f32(a, false, d->compute_dtype == CTDET_DT_F16X3, (hipStream_t)stream);
-  }
-  CTDET_CHECK(false, "conv: bad compute dtype %d", d->compute_dtype);
+  return conv_dispatch("conv", d, a, false, stream);
 }
 
 int32_t ctdet_conv_pair_supported(const ctdet_conv_desc* d, const void* x) {
@@ -234,12 +150,7 @@ int32_t ctdet_conv1x1_cat_fwd(const ctdet_conv_desc* d, const void* const* xs, c
   a.nsrc = nsrc < 2 ? 2 : nsrc;  // always take the multi-source path (a single source is sources {0, 0-length})
   if (nsrc == 1) { a.nsrc = 1; a.in_stride = strides[0]; }
   a.x = xs[0]; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = residual; a.y = y;
-  if (d->compute_dtype == CTDET_DT_F16) return launch_conv_f16(a, d->out_dtype, false, (hipStream_t)stream);
-  if (d->compute_dtype == CTDET_DT_F32 || d->compute_dtype == CTDET_DT_F16X3) {
-    CTDET_CHECK(d->out_dtype == CTDET_DT_F32, "conv1x1_cat(f32 / f16x3): output must be f32");
-    return launch_conv_f32(a, false, d->compute_dtype == CTDET_DT_F16X3, (hipStream_t)stream);
-  }
-  CTDET_CHECK(false, "conv1x1_cat: bad compute dtype %d", d->compute_dtype);
+  return conv_dispatch("conv1x1_cat", d, a, false, stream);
 }
 
 int32_t ctdet_dcnv2_fwd(const ctdet_conv_desc* d, const void* x, const float* offset_mask, int32_t om_stride,
@@ -249,18 +160,13 @@ int32_t ctdet_dcnv2_fwd(const ctdet_conv_desc* d, const void* x, const float* of
   if (rc) return rc;
   if (a.M == 0) return 0;
   CTDET_CHECK(x && w_packed && y && offset_mask, "dcnv2: null pointer");
-  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcnv2: mask mode %d", mask_is_prob);
+  CTDET_DCN_MASK_MODE("dcnv2", mask_is_prob);
   CTDET_CHECK(om_stride >= (mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3) * d->R * d->S, "dcnv2: om_stride=%d < %d*R*S", om_stride,
               mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3);
   // korder 0: tap-major weights -> gather-from-global kernel; korder 1: chunk-major -> LDS-window kernel
   a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;
   a.om = offset_mask; a.om_stride = om_stride; a.mask_is_prob = mask_is_prob;
-  if (d->compute_dtype == CTDET_DT_F16) return launch_conv_f16(a, d->out_dtype, true, (hipStream_t)stream);
-  if (d->compute_dtype == CTDET_DT_F32 || d->compute_dtype == CTDET_DT_F16X3) {
-    CTDET_CHECK(d->out_dtype == CTDET_DT_F32, "dcnv2(f32 / f16x3): output must be f32");
-    return launch_conv_f32(a, true, d->compute_dtype == CTDET_DT_F16X3, (hipStream_t)stream);
-  }
-  CTDET_CHECK(false, "dcnv2: bad compute dtype %d", d->compute_dtype);
+  return conv_dispatch("dcnv2", d, a, true, stream);
 }
 
 int32_t ctdet_dcnv2_cols_supported(const ctdet_conv_desc* d, const void* x, const void* y) {
@@ -278,7 +184,7 @@ int32_t ctdet_dcnv2_fwd_cols(const ctdet_conv_desc* d, const void* x, const floa
   if (rc) return rc;
   if (a.M == 0) return 0;
   CTDET_CHECK(x && w_packed && y && offset_mask && cols_out, "dcnv2_fwd_cols: null pointer");
-  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcnv2: mask mode %d", mask_is_prob);
+  CTDET_DCN_MASK_MODE("dcnv2", mask_is_prob);
   CTDET_CHECK(om_stride >= (mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3) * d->R * d->S, "dcnv2: om_stride=%d < %d*R*S", om_stride,
               mask_is_prob == CTDET_DCN_MASK_NONE ? 2 : 3);
   CTDET_CHECK(d->compute_dtype == CTDET_DT_F16X3 && d->out_dtype == CTDET_DT_F32 && (((size_t)cols_out) & 15) == 0,
@@ -307,17 +213,17 @@ int32_t ctdet_dcnv2_offset_fwd(const ctdet_conv_desc* d, const void* x, const vo
   if (rc) return rc;
   if (a.M == 0) return 0;
   CTDET_CHECK(x && w_off_packed && b_off && w_packed && y, "dcnv2_offset: null pointer");
+  a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;
+  a.w_off = w_off_packed; a.b_off = b_off;
   if (d->compute_dtype == CTDET_DT_F16X3) {
     CTDET_CHECK(d->out_dtype == CTDET_DT_F32 && !om_out, "dcnv2_offset(f16x3): f32 output, no om_out (inference form)");
-    a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;
-    a.w_off = w_off_packed; a.b_off = b_off; a.mask_is_prob = DCN_MASK_LOGIT;
+    a.mask_is_prob = DCN_MASK_LOGIT;
     return launch_dcn_offset_x3(a, (hipStream_t)stream);
   }
   CTDET_CHECK(d->compute_dtype == CTDET_DT_F16, "dcnv2_offset: f16 or f16x3");
   CTDET_CHECK(!om_out || (om_out_stride >= 28 && om_out_stride % 4 == 0 && ((size_t)om_out & 15) == 0),
               "dcnv2_offset: om_out needs a 16-byte aligned row of >= 28 floats (stride %d)", om_out_stride);
-  a.x = x; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = nullptr; a.y = y;
-  a.w_off = w_off_packed; a.b_off = b_off; a.om_out = om_out; a.om_out_stride = om_out_stride;
+  a.om_out = om_out; a.om_out_stride = om_out_stride;
   return launch_conv_f16(a, d->out_dtype, true, (hipStream_t)stream);
 }
 
@@ -387,14 +293,16 @@ int32_t ctdet_head_sparse_x3_fwd(const ctdet_head_desc* d, const void* x, const 
   return launch_head_sparse_x3(a, inds, whreg, boxes, K, down_ratio, flip != 0, (hipStream_t)stream);
 }
 
+// launch: launch_dla_base (f16) or launch_dla_base_x3 (f16x3: out / pooled f32), `what` its name in messages.
 // mirror_from < 0: the plain kernels; otherwise output images [mirror_from, B) are computed from the mirrored network input
 // of source images [0, B - mirror_from)
-static int32_t dla_base_entry(const ctdet_dla_base_desc* d, int mirror_from, const void* images, const void* w_stem,
-                              const float* scale_stem, const float* bias_stem, const void* w_l0, const float* scale_l0,
-                              const float* bias_l0, const void* w_l1, const float* scale_l1, const float* bias_l1,
-                              void* out, void* pooled, void* stream) {
+static int32_t dla_base_entry(int (*launch)(const BaseArgs&, hipStream_t), const char* what, const ctdet_dla_base_desc* d,
+                              int mirror_from, const void* images, const void* w_stem, const float* scale_stem,
+                              const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
+                              const void* w_l1, const float* scale_l1, const float* bias_l1, void* out, void* pooled,
+                              void* stream) {
   CTDET_CHECK(d && images && w_stem && scale_stem && bias_stem && w_l0 && scale_l0 && bias_l0 && w_l1 && scale_l1 && bias_l1 &&
-              out, "dla_base: null pointer");
+              out, "%s: null pointer", what);
   BaseArgs a = {};
   a.img = images; a.img_dtype = d->img_dtype; a.img_batch_stride = (long)d->img_batch_stride;
   a.B = d->B; a.H = d->H; a.W = d->W; a.Hp = d->Hp; a.Wp = d->Wp;
@@ -405,15 +313,15 @@ static int32_t dla_base_entry(const ctdet_dla_base_desc* d, int mirror_from, con
   a.y = out; a.out_stride = d->out_stride;
   a.pool = pooled; a.pool_stride = d->pool_stride;
   a.mirror_from = mirror_from;
-  return launch_dla_base(a, (hipStream_t)stream);
+  return launch(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_dla_base_fwd(const ctdet_dla_base_desc* d, const void* images, const void* w_stem, const float* scale_stem,
                            const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
                            const void* w_l1, const float* scale_l1, const float* bias_l1, void* out, void* pooled,
                            void* stream) {
-  return dla_base_entry(d, -1, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1, bias_l1, out,
-                        pooled, stream);
+  return dla_base_entry(launch_dla_base, "dla_base", d, -1, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1,
+                        scale_l1, bias_l1, out, pooled, stream);
 }
 
 int32_t ctdet_dla_base_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirror_from, const void* images, const void* w_stem,
@@ -422,35 +330,16 @@ int32_t ctdet_dla_base_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirror_f
                                   void* out, void* pooled, void* stream) {
   CTDET_CHECK(d && mirror_from >= 0 && mirror_from <= d->B, "dla_base: mirror_from=%d outside [0, B=%d]", mirror_from,
               d ? d->B : 0);
-  return dla_base_entry(d, mirror_from, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1,
-                        bias_l1, out, pooled, stream);
-}
-
-static int32_t dla_base_x3_entry(const ctdet_dla_base_desc* d, int mirror_from, const void* images, const void* w_stem,
-                                 const float* scale_stem, const float* bias_stem, const void* w_l0, const float* scale_l0,
-                                 const float* bias_l0, const void* w_l1, const float* scale_l1, const float* bias_l1,
-                                 float* out, float* pooled, void* stream) {
-  CTDET_CHECK(d && images && w_stem && scale_stem && bias_stem && w_l0 && scale_l0 && bias_l0 && w_l1 && scale_l1 && bias_l1 &&
-              out, "dla_base(f16x3): null pointer");
-  BaseArgs a = {};
-  a.img = images; a.img_dtype = d->img_dtype; a.img_batch_stride = (long)d->img_batch_stride;
-  a.B = d->B; a.H = d->H; a.W = d->W; a.Hp = d->Hp; a.Wp = d->Wp;
-  for (int i = 0; i < 3; ++i) { a.mean[i] = d->mean[i]; a.stdv[i] = d->std[i]; }
-  a.w0 = w_stem; a.s0 = scale_stem; a.b0 = bias_stem;
-  a.w1 = w_l0; a.s1 = scale_l0; a.b1 = bias_l0;
-  a.w2 = w_l1; a.s2 = scale_l1; a.b2 = bias_l1;
-  a.y = out; a.out_stride = d->out_stride;
-  a.pool = pooled; a.pool_stride = d->pool_stride;
-  a.mirror_from = mirror_from;
-  return launch_dla_base_x3(a, (hipStream_t)stream);
+  return dla_base_entry(launch_dla_base, "dla_base", d, mirror_from, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0,
+                        bias_l0, w_l1, scale_l1, bias_l1, out, pooled, stream);
 }
 
 int32_t ctdet_dla_base_x3_fwd(const ctdet_dla_base_desc* d, const void* images, const void* w_stem, const float* scale_stem,
                               const float* bias_stem, const void* w_l0, const float* scale_l0, const float* bias_l0,
                               const void* w_l1, const float* scale_l1, const float* bias_l1, float* out, float* pooled,
                               void* stream) {
-  return dla_base_x3_entry(d, -1, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1, bias_l1,
-                           out, pooled, stream);
+  return dla_base_entry(launch_dla_base_x3, "dla_base(f16x3)", d, -1, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0,
+                        bias_l0, w_l1, scale_l1, bias_l1, out, pooled, stream);
 }
 
 int32_t ctdet_dla_base_x3_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirror_from, const void* images,
@@ -459,8 +348,8 @@ int32_t ctdet_dla_base_x3_mirror_fwd(const ctdet_dla_base_desc* d, int32_t mirro
                                      const float* bias_l1, float* out, float* pooled, void* stream) {
   CTDET_CHECK(d && mirror_from >= 0 && mirror_from <= d->B, "dla_base(f16x3): mirror_from=%d outside [0, B=%d]", mirror_from,
               d ? d->B : 0);
-  return dla_base_x3_entry(d, mirror_from, images, w_stem, scale_stem, bias_stem, w_l0, scale_l0, bias_l0, w_l1, scale_l1,
-                           bias_l1, out, pooled, stream);
+  return dla_base_entry(launch_dla_base_x3, "dla_base(f16x3)", d, mirror_from, images, w_stem, scale_stem, bias_stem, w_l0,
+                        scale_l0, bias_l0, w_l1, scale_l1, bias_l1, out, pooled, stream);
 }
 
 int32_t ctdet_maxpool2x2(const void* x, void* y, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -673,13 +562,12 @@ int32_t ctdet_bn_train_fwd(const void* y, int32_t y_stride, const void* res, int
                            void* stream) {
   CTDET_CHECK(y && z && gamma && beta && save_mean && save_invstd && scale && shift && workspace, "bn_train_fwd: null pointer");
   CTDET_CHECK(M > 0, "bn_train_fwd: empty batch");
-  if (dtype == CTDET_DT_F32)
-    return launch_bn_train_fwd_f32((const float*)y, y_stride, (const float*)res, res_stride, (float*)z, z_stride, M, C, gamma,
-                                   beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, scale, shift,
-                                   workspace, relu, (hipStream_t)stream);
-  return launch_bn_train_fwd((const f16*)y, y_stride, (const f16*)res, res_stride, (f16*)z, z_stride, M, C, gamma, beta,
-                             eps, momentum, running_mean, running_var, save_mean, save_invstd, scale, shift, workspace,
-                             relu, (hipStream_t)stream);
+  BnArgs a = {};
+  a.dtype = dtype; a.M = M; a.C = C; a.relu = relu;
+  a.y = y; a.y_stride = y_stride; a.res = res; a.res_stride = res_stride; a.z_out = z; a.z_stride = z_stride;
+  a.gamma = gamma; a.beta = beta; a.eps = eps; a.momentum = momentum; a.running_mean = running_mean; a.running_var = running_var;
+  a.save_mean = save_mean; a.save_invstd = save_invstd; a.save_scale = scale; a.save_shift = shift; a.workspace = workspace;
+  return launch_bn_train_fwd(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_bn_train_bwd(const void* dz, int32_t dz_stride, const void* z, int32_t z_stride, const void* y,
@@ -689,13 +577,12 @@ int32_t ctdet_bn_train_bwd(const void* dz, int32_t dz_stride, const void* z, int
   CTDET_CHECK(dz && dy && dgamma && dbeta && workspace, "bn_train_bwd: null pointer");
   CTDET_CHECK(!relu || z, "bn_train_bwd: relu backward needs z");
   CTDET_CHECK(!y || (mean && invstd && scale), "bn_train_bwd: statistics missing");
-  if (dtype == CTDET_DT_F32)
-    return launch_bn_train_bwd_f32((const float*)dz, dz_stride, (const float*)z, z_stride, (const float*)y, y_stride, mean,
-                                   invstd, scale, M, C, relu, (float*)dy, dy_stride, (float*)dres, dres_stride, dgamma,
-                                   dbeta, grad_mult, workspace, (hipStream_t)stream);
-  return launch_bn_train_bwd((const f16*)dz, dz_stride, (const f16*)z, z_stride, (const f16*)y, y_stride, mean, invstd,
-                             scale, M, C, relu, (f16*)dy, dy_stride, (f16*)dres, dres_stride, dgamma, dbeta, grad_mult,
-                             workspace, (hipStream_t)stream);
+  BnArgs a = {};
+  a.dtype = dtype; a.M = M; a.C = C; a.relu = relu;
+  a.dz = dz; a.dz_stride = dz_stride; a.z = z; a.z_stride = z_stride; a.y = y; a.y_stride = y_stride;
+  a.mean = mean; a.invstd = invstd; a.scale = scale; a.dy = dy; a.dy_stride = dy_stride; a.dres = dres; a.dres_stride = dres_stride;
+  a.dgamma = dgamma; a.dbeta = dbeta; a.grad_mult = grad_mult; a.workspace = workspace;
+  return launch_bn_train_bwd(a, (hipStream_t)stream);
 }
 
 static const int SYNC_BN_MAX_WORLD = 4096;
@@ -706,7 +593,10 @@ int32_t ctdet_bn_local_stats(const void* y, int32_t y_stride, int32_t M, int32_t
   CTDET_CHECK(y && stats && workspace, "bn_local_stats: null pointer");
   CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD && rank >= 0 && rank < world, "bn_local_stats: rank %d of world %d",
               rank, world);
-  return launch_bn_local_stats(y, y_stride, M, C, rank, world, stats, workspace, dtype == CTDET_DT_F32, (hipStream_t)stream);
+  BnArgs a = {};
+  a.dtype = dtype; a.M = M; a.C = C; a.y = y; a.y_stride = y_stride;
+  a.rank = rank; a.world = world; a.slots = stats; a.workspace = workspace;
+  return launch_bn_local_stats(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_bn_sync_fwd(const void* y, int32_t y_stride, const void* res, int32_t res_stride, void* z, int32_t z_stride,
@@ -717,9 +607,13 @@ int32_t ctdet_bn_sync_fwd(const void* y, int32_t y_stride, const void* res, int3
   CTDET_CHECK(!running_mean == !running_var, "bn_sync_fwd: running_mean and running_var go together");
   CTDET_CHECK(M > 0, "bn_sync_fwd: empty batch");
   CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD, "bn_sync_fwd: world %d", world);
-  return launch_bn_sync_fwd(y, y_stride, res, res_stride, z, z_stride, M, C, stats, world, gamma, beta, eps, momentum,
-                            running_mean, running_var, save_mean, save_invstd, scale, shift, relu, dtype == CTDET_DT_F32,
-                            (hipStream_t)stream);
+  BnArgs a = {};
+  a.dtype = dtype; a.M = M; a.C = C; a.relu = relu;
+  a.y = y; a.y_stride = y_stride; a.res = res; a.res_stride = res_stride; a.z_out = z; a.z_stride = z_stride;
+  a.stats = stats; a.world = world;
+  a.gamma = gamma; a.beta = beta; a.eps = eps; a.momentum = momentum; a.running_mean = running_mean; a.running_var = running_var;
+  a.save_mean = save_mean; a.save_invstd = save_invstd; a.save_scale = scale; a.save_shift = shift;
+  return launch_bn_sync_fwd(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_bn_local_grad_sums(const void* dz, int32_t dz_stride, const void* z, int32_t z_stride, const void* y,
@@ -732,8 +626,12 @@ int32_t ctdet_bn_local_grad_sums(const void* dz, int32_t dz_stride, const void* 
   CTDET_CHECK(M > 0, "bn_local_grad_sums: empty batch on rank %d", rank);
   CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD && rank >= 0 && rank < world,
               "bn_local_grad_sums: rank %d of world %d", rank, world);
-  return launch_bn_local_grad_sums(dz, dz_stride, z, z_stride, y, y_stride, mean, invstd, M, C, relu, rank, world, sums, dgamma,
-                                   dbeta, grad_mult, workspace, dtype == CTDET_DT_F32, (hipStream_t)stream);
+  BnArgs a = {};
+  a.dtype = dtype; a.M = M; a.C = C; a.relu = relu;
+  a.dz = dz; a.dz_stride = dz_stride; a.z = z; a.z_stride = z_stride; a.y = y; a.y_stride = y_stride;
+  a.mean = mean; a.invstd = invstd; a.rank = rank; a.world = world; a.slots = sums;
+  a.dgamma = dgamma; a.dbeta = dbeta; a.grad_mult = grad_mult; a.workspace = workspace;
+  return launch_bn_local_grad_sums(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_bn_sync_bwd(const void* dz, int32_t dz_stride, const void* z, int32_t z_stride, const void* y, int32_t y_stride,
@@ -744,8 +642,12 @@ int32_t ctdet_bn_sync_bwd(const void* dz, int32_t dz_stride, const void* z, int3
   CTDET_CHECK(!relu || z, "bn_sync_bwd: relu backward needs z");
   CTDET_CHECK(M > 0, "bn_sync_bwd: empty batch");
   CTDET_CHECK(world >= 1 && world <= SYNC_BN_MAX_WORLD, "bn_sync_bwd: world %d", world);
-  return launch_bn_sync_bwd(dz, dz_stride, z, z_stride, y, y_stride, mean, invstd, scale, stats, sums, world, M, C, relu, dy,
-                            dy_stride, dres, dres_stride, dtype == CTDET_DT_F32, (hipStream_t)stream);
+  BnArgs a = {};
+  a.dtype = dtype; a.M = M; a.C = C; a.relu = relu;
+  a.dz = dz; a.dz_stride = dz_stride; a.z = z; a.z_stride = z_stride; a.y = y; a.y_stride = y_stride;
+  a.mean = mean; a.invstd = invstd; a.scale = scale; a.stats = stats; a.sums = sums; a.world = world;
+  a.dy = dy; a.dy_stride = dy_stride; a.dres = dres; a.dres_stride = dres_stride;
+  return launch_bn_sync_bwd(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_conv_wgrad(const ctdet_conv_desc* d, const void* x, const void* dy, float* dw, float scale, void* stream) {
@@ -780,7 +682,6 @@ int32_t ctdet_grad_scatter_oihw(const void* const* src, void* const* dst, const 
 int32_t ctdet_depth_to_space2(const void* src, int32_t src_stride, void* dst, int32_t dst_stride, int32_t B, int32_t H,
                               int32_t W, int32_t C, int32_t Hs, int32_t Ws, int32_t dtype, void* stream) {
   CTDET_CHECK(src && dst, "depth_to_space2: null pointer");
-  CTDET_CHECK(dtype == CTDET_DT_F16 || dtype == CTDET_DT_F32, "depth_to_space2: bad dtype %d", dtype);
   return launch_depth_to_space2(src, src_stride, dst, dst_stride, B, H, W, C, Hs, Ws, dtype, (hipStream_t)stream);
 }
 
@@ -815,57 +716,51 @@ int32_t ctdet_ese_bwd(const void* dy, int32_t dy_stride, const float* gate, cons
 int32_t ctdet_maxpool2x2_bwd(const void* x, int32_t x_stride, const void* dz, int32_t dz_stride, void* dx,
                              int32_t dx_stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream) {
   CTDET_CHECK(x && dz && dx, "maxpool2x2_bwd: null pointer");
-  if (dtype == CTDET_DT_F32)
-    return launch_maxpool2x2_bwd_f32((const float*)x, x_stride, (const float*)dz, dz_stride, (float*)dx, dx_stride, B, H, W, C,
-                                     (hipStream_t)stream);
-  return launch_maxpool2x2_bwd((const f16*)x, x_stride, (const f16*)dz, dz_stride, (f16*)dx, dx_stride, B, H, W, C,
-                               (hipStream_t)stream);
+  return launch_maxpool2x2_bwd(x, x_stride, dz, dz_stride, dx, dx_stride, dtype, B, H, W, C, (hipStream_t)stream);
 }
 
 int32_t ctdet_dwconvT_bwd(const void* x, int32_t x_stride, const void* dz, int32_t dz_stride, const float* w, void* dx,
                           int32_t dx_stride, float* dw, int32_t B, int32_t H, int32_t W, int32_t C, int32_t f,
                           int32_t dtype, void* stream) {
   CTDET_CHECK(x && dz && w && dx && dw, "dwconvT_bwd: null pointer");
-  if (dtype == CTDET_DT_F32)
-    return launch_dwconvT_bwd_f32((const float*)x, x_stride, (const float*)dz, dz_stride, w, (float*)dx, dx_stride, dw, B, H,
-                                  W, C, f, (hipStream_t)stream);
-  return launch_dwconvT_bwd((const f16*)x, x_stride, (const f16*)dz, dz_stride, w, (f16*)dx, dx_stride, dw, B, H, W, C, f,
-                            (hipStream_t)stream);
+  return launch_dwconvT_bwd(x, x_stride, dz, dz_stride, w, dx, dx_stride, dw, dtype, B, H, W, C, f, (hipStream_t)stream);
 }
 
 int32_t ctdet_dcn_cols(const void* x, int32_t x_stride, const float* om, int32_t om_stride, void* col, int32_t B,
                        int32_t H, int32_t W, int32_t Cin, int32_t mask_is_prob, int32_t dtype, void* stream) {
   CTDET_CHECK(x && om && col, "dcn_cols: null pointer");
-  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcn_cols: mask mode %d", mask_is_prob);
-  if (dtype == CTDET_DT_F32)
-    return launch_dcn_cols_f32((const float*)x, x_stride, om, om_stride, (float*)col, B, H, W, Cin, mask_is_prob,
-                               (hipStream_t)stream);
-  return launch_dcn_cols((const f16*)x, x_stride, om, om_stride, (f16*)col, B, H, W, Cin, mask_is_prob, (hipStream_t)stream);
+  CTDET_DCN_MASK_MODE("dcn_cols", mask_is_prob);
+  DcnBwdArgs a = {};
+  a.dtype = dtype; a.x = x; a.x_stride = x_stride; a.om = om; a.om_stride = om_stride; a.col = col;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.mask_mode = mask_is_prob;
+  return launch_dcn_cols(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_dcn_col2im_coord(const void* dcol, const void* x, int32_t x_stride, const float* om, int32_t om_stride,
                                float* dx, void* dom, int32_t dom_stride, int32_t dom_dtype, int32_t B, int32_t H, int32_t W,
                                int32_t Cin, int32_t mask_is_prob, int32_t dcol_chunked, int32_t dtype, void* stream) {
   CTDET_CHECK(dcol && x && om && dx && dom, "dcn_col2im_coord: null pointer");
-  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcn_col2im_coord: mask mode %d",
-              mask_is_prob);
+  CTDET_DCN_MASK_MODE("dcn_col2im_coord", mask_is_prob);
   CTDET_CHECK(dom_dtype == CTDET_DT_F32 || (dom_dtype == CTDET_DT_F16 && dtype == CTDET_DT_F16),
               "dcn_col2im_coord: dom dtype %d with data dtype %d", dom_dtype, dtype);
-  if (dtype == CTDET_DT_F32 || dtype == CTDET_DT_F16X3)
-    return launch_dcn_col2im_coord_f32((const float*)dcol, (const float*)x, x_stride, om, om_stride, dx, (float*)dom, dom_stride,
-                                       B, H, W, Cin, mask_is_prob, dcol_chunked, dtype == CTDET_DT_F16X3, (hipStream_t)stream);
-  return launch_dcn_col2im_coord((const f16*)dcol, (const f16*)x, x_stride, om, om_stride, dx, dom, dom_stride,
-                                 dom_dtype == CTDET_DT_F16, B, H, W, Cin, mask_is_prob, dcol_chunked, (hipStream_t)stream);
+  DcnBwdArgs a = {};
+  a.dtype = dtype; a.x = x; a.x_stride = x_stride; a.om = om; a.om_stride = om_stride;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.mask_mode = mask_is_prob;
+  a.dcol = dcol; a.dcol_chunked = dcol_chunked; a.dx = dx; a.dom = dom; a.dom_stride = dom_stride; a.dom_dtype = dom_dtype;
+  return launch_dcn_col2im_coord(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_dcn_col2im_fused(const float* dy, int32_t dy_stride, int32_t K, const void* w_packed, const float* w_scale,
                                const float* x, int32_t x_stride, const float* om, int32_t om_stride, float* dx, float* dom,
                                int32_t dom_stride, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t mask_is_prob, void* stream) {
   CTDET_CHECK(dy && w_packed && w_scale && x && om && dx && dom, "dcn_col2im_fused: null pointer");
-  CTDET_CHECK(mask_is_prob >= CTDET_DCN_MASK_LOGIT && mask_is_prob <= CTDET_DCN_MASK_NONE, "dcn_col2im_fused: mask mode %d",
-              mask_is_prob);
-  return launch_dcn_col2im_fused(dy, dy_stride, K, w_packed, w_scale, x, x_stride, om, om_stride, dx, dom, dom_stride, B, H, W, Cin,
-                                 mask_is_prob, (hipStream_t)stream);
+  CTDET_DCN_MASK_MODE("dcn_col2im_fused", mask_is_prob);
+  DcnBwdArgs a = {};
+  a.dtype = CTDET_F32; a.x = x; a.x_stride = x_stride; a.om = om; a.om_stride = om_stride;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.mask_mode = mask_is_prob;
+  a.dy = dy; a.dy_stride = dy_stride; a.K = K; a.wpk = w_packed; a.wscale = w_scale;
+  a.dx = dx; a.dom = dom; a.dom_stride = dom_stride; a.dom_dtype = CTDET_F32;
+  return launch_dcn_col2im_fused(a, (hipStream_t)stream);
 }
 
 int32_t ctdet_sgd_momentum(float* param, const float* grad, float* momentum_buf, int64_t n, const float* lr_dev,
@@ -946,5 +841,6 @@ int32_t ctdet_adam_runs(float* param, const float* grad, float* exp_avg, float* 
                           clip_type, clip_value, coefs, (hipStream_t)stream);
 }
 #undef CTDET_ADAM_BETAS
+#undef CTDET_DCN_MASK_MODE
 
 }  // extern "C"

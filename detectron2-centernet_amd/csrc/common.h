@@ -127,8 +127,6 @@ struct BaseArgs {
   // is >= W, so the zero padding sits on the left); output images below mirror_from read their own source image, plain
   int mirror_from;
 };
-int launch_dla_base(const BaseArgs& a, hipStream_t s);
-int launch_dla_base_x3(const BaseArgs& a, hipStream_t s);   // f16x3: w* = ctdet_pack_weights_x3 layout 0 images, y / pool f32
 
 // argument block of the batched decode (decode.hip)
 struct DecArgs {
@@ -139,6 +137,63 @@ struct DecArgs {
   uint32_t floor_bits;                      // bits of the promised lower bound of the heat values (0 = none)
   uint32_t* ws;
   float* boxes; float* scores; int* classes; int* inds;   // wh == nullptr: no boxes (launch_head_sparse_x3 writes them), inds required
+};
+
+// argument block of the conv weight-gradient launchers (train_bwd.hip; also the kernels' own argument):
+// dW[n][k] += sum_m dY[m][n] * im2col(x)[m][k]
+struct WgradArgs {
+  const void* x; const void* dy; float* dw;   // x, dy: f16 (f16 mode) or f32 (f16x3 mode: split into hi + lo f16 halves on the way to LDS)
+  int B, H, W, Cin, in_stride, Cout, Ho, Wo, dy_stride, R, S, stride, pad, dil, K, M, msplit;
+  float scale;   // multiplier applied to every partial sum before it is added to dw
+  int lw, lh;    // log2(Wo), log2(Ho) when both are powers of two, else -1
+  // output layout: perm_rs == 0: dw[n][k], k = tap*Cin + c (tap-major).  perm_rs > 0: the parameter's own OIHW layout,
+  // dw[(n*cin_real + c)*perm_rs + tap] with k = tap*perm_cin + c, channels c >= cin_real (input padding)
+  // and rows n >= cout_real (output-channel padding of dy) dropped -- the kernel then accumulates straight into the
+  // optimizer's gradient buffer
+  int perm_rs, perm_cin, cin_real, cout_real;
+};
+
+// argument block of the six BatchNorm launchers (train_bwd.hip).  Tensors are [M][*_stride] pixel rows of C channels, all of
+// element type `dtype`; per-channel vectors are f32 [C].  A field a launcher does not use is zero.
+struct BnArgs {
+  int dtype;                 // CTDET_F16 / CTDET_F32
+  int M, C, relu;
+  const void* y;    int y_stride;      // the conv output BatchNorm normalises
+  const void* res;  int res_stride;    // forward: residual added before the ReLU, or null
+  void* z_out;                         // forward: the result, pixel stride z_stride
+  const void* z;    int z_stride;      // backward: the forward's result (read where relu is set)
+  const void* dz;   int dz_stride;     // backward: gradient of z
+  void* dy;         int dy_stride;     // backward: gradient of y
+  void* dres;       int dres_stride;   // backward: gradient of the residual, or null
+  const float *gamma, *beta;
+  float eps, momentum;
+  float *running_mean, *running_var;   // updated in place, or null
+  float *save_mean, *save_invstd, *save_scale, *save_shift;   // forward: batch statistics and the folded affine, written
+  const float *mean, *invstd, *scale;  // backward: what the forward saved
+  float *dgamma, *dbeta;
+  float grad_mult;                     // multiplier of dgamma / dbeta
+  void* workspace;                     // chan_reduce_workspace_bytes(C)
+  // SyncBatchNorm: rank-slot buffers, f64 [world][K][C]
+  int rank, world;
+  double* slots;                       // bn_local_stats / bn_local_grad_sums: this rank's slot written, the others zeroed
+  const double *stats, *sums;          // the all-reduced buffers of the two
+};
+
+// argument block of the DCNv2 backward launchers (train_bwd.hip): dcn_cols, dcn_col2im_coord, dcn_col2im_fused
+struct DcnBwdArgs {
+  int dtype;                 // element type of x, col and dcol: CTDET_F16, CTDET_F32 or CTDET_F16X3 (f32 tensors; col2im_coord
+                             // then takes the LDS-window scatter where the shape allows).  col2im_fused: f32 only, unused
+  const void* x;    int x_stride;      // [B,H,W,x_stride] input of the layer
+  const float* om;  int om_stride;     // [M, om_stride] offsets (+ mask channels, see mask_mode)
+  int B, H, W, Cin, mask_mode;         // DCN_MASK_*
+  void* col;                           // dcn_cols: [M][9*Cin] sampled columns (written)
+  const void* dcol; int dcol_chunked;  // col2im_coord: d(columns), rows [tap][Cin] or chunked [Cin/32][tap][32]
+  float* dx;                           // [M][Cin] f32, accumulated into
+  void* dom; int dom_stride, dom_dtype;   // d(offset / mask) rows: CTDET_F32, or CTDET_F16 with f16 tensors
+  // col2im_fused: the d(columns) GEMM runs in the scatter kernel.  dy f32 [M][dy_stride] with K channels (multiple of 32;
+  // channels beyond the layer's couts zero), wpk / wscale from ctdet_pack_weights_x3 (layout 5, transposed 3)
+  const float* dy;  int dy_stride, K;
+  const void* wpk;  const float* wscale;
 };
 
 __device__ __forceinline__ float ctdet_sigmoid(float v) { return 1.0f / (1.0f + __expf(-v)); }
@@ -166,12 +221,131 @@ unsigned ctdet_tuning_flags();
 // number of CUs of the CURRENT device (cached per device ordinal, not per process)
 int ctdet_device_cu_count();
 
-// launchers implemented in the .hip files (return 0 or negative errno)
+// Everything one .hip file defines and another calls (api.hip, mostly), declared here and nowhere else.  Launchers return 0 or
+// a negative errno; tensors whose element type varies are `const void*` with an `int dtype` (CTDET_F16 / CTDET_F32 / ...), and
+// a dtype a launcher does not serve is rejected with -22, never run as another one.
+
+// conv_igemm.hip
 int launch_conv_f16(const ConvArgs& a, int out_dtype, bool deform, hipStream_t s);
+bool halo_pair_x_ok(const ConvArgs& a, int korder);          // activation side of what the f16x3 halo pair kernels need
+int launch_halo_pair(const ConvArgs& a, hipStream_t s);      // korder 2 pair image
+int launch_halo_pair2(const ConvArgs& a, hipStream_t s);     // korder 3 (cross-chunk) pair image
+int launch_halo_split(const ConvArgs& a, hipStream_t s);     // tap-major split weights; 1 if the shape does not qualify
+bool head_fused_x_ok(const HeadArgs& a, bool x3);            // may these activations take the fused head kernel?
 int launch_head_fused(const HeadArgs& a, hipStream_t s);
 int launch_head_fused_x3(const HeadArgs& a, hipStream_t s);
 // the wh / reg heads (a two-head f16x3 pack; a.y unused) at the pixels inds[B,K] of a.x, and the decode's boxes from them;
 // flip: a.x holds 2 * a.B images, wh is the mean with the mirrored pixel of image b + a.B
 int launch_head_sparse_x3(const HeadArgs& a, const int* inds, float* whreg, float* boxes, int K, float down_ratio, bool flip,
                           hipStream_t s);
-int launch_conv_f32(const ConvArgs& a, bool deform, bool split, hipStream_t s);
+bool dcn_offset_fused_ok(const ConvArgs& a);                 // geometry the f16 row-step kernel (fused offset conv) serves
+// f16 `columns` of the DCNv2 backward from the sampling kernel's LDS window (launch_dcn_cols decides when)
+int launch_dcn_cols_window(const DcnBwdArgs& a, hipStream_t s);
+
+// conv_f32.hip
+int launch_conv_f32(const ConvArgs& a, bool deform, bool split, hipStream_t s);   // split: the f16x3 mode
+int conv_pair_korder(const ConvArgs& a);                     // korder of the pair image an f16x3 3x3 conv would take, 0: none
+bool dcn_split_window_ok(const ConvArgs& a);                 // LDS-window kernel that can also write ConvArgs::cols_out?
+bool dcn_offset_fused_x3_ok(const ConvArgs& a);              // may the f16x3 DCNv2 compute its own offsets and mask?
+int launch_dcn_offset_x3(const ConvArgs& a, hipStream_t s);
+int launch_split_weights(const float* src, void* dst, long n, hipStream_t s);
+
+// dla_base.hip
+int launch_dla_base(const BaseArgs& a, hipStream_t s);
+int launch_dla_base_x3(const BaseArgs& a, hipStream_t s);   // f16x3: w* = ctdet_pack_weights_x3 layout 0 images, y / pool f32
+
+// pointwise.hip
+// mirror_from < 0: the plain kernel; otherwise output images [mirror_from, B) are mirrored copies of source images [0, B - mirror_from)
+int launch_preprocess(const void* img, int img_dtype, void* out, int out_dtype, int B, int H, int W, int Hp, int Wp,
+                      long img_batch_stride, const float* mean, const float* stdv, int out_stride, int border,
+                      int mirror_from, hipStream_t s);
+int launch_maxpool2x2(const void* x, void* y, int dtype, int B, int H, int W, int C, int in_stride, int out_stride,
+                      hipStream_t s);
+int launch_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, int C, int in_stride, int out_stride,
+                        int ceil_nopad, hipStream_t s);
+int launch_finite_flag(const float* x, long M, int C, int stride, int* flag, hipStream_t s);
+int launch_global_avgpool(const void* x, int dtype, int B, int HW, int C, int stride, float* out, hipStream_t s);
+int launch_ese_scale(const void* x, int x_stride, const float* sc, const void* idn, int idn_stride, void* y, int y_stride,
+                     int dtype, int B, int HW, int C, hipStream_t s);
+int launch_pack_weights(const float* w, void* out, int O, int I, int R, int S, int chans_pad, int rows_pad, int Kpad,
+                        int korder, int transposed, hipStream_t s);
+int launch_pack_weights_batch(const void* table_dev, int n, int total_blocks, hipStream_t s);   // table: ctdet_pack_desc[n]
+int launch_pack_weights_x3(const float* w, void* out, float* scale_out, int O, int I, int R, int S, int chans_pad, int rows_pad,
+                           int Kpad, int layout, int transposed, int scale_n, hipStream_t s);
+int launch_pack_weights_x3_batch(const void* table_dev, int n, int total_blocks, hipStream_t s);   // table: ctdet_pack3_desc[n]
+int launch_dwconvT_add(const void* x, const float* w, const void* skip, void* y, int dtype, int B, int H, int W, int C,
+                       int f, int in_stride, int skip_stride, int out_stride, hipStream_t s);
+
+// dwconv.hip
+// shape / dtype checks shared by the entry points (api.hip validates pointers first)
+int dwconv3x3_check(int dtype, int B, int H, int W, int C, int stride, const int* strides, int nstrides);
+size_t dwconv3x3_wgrad_workspace_bytes(int B, int H, int W, int C, int dtype);
+int launch_dwconv3x3(const void* x, int x_stride, const float* w, void* y, int y_stride, int B, int H, int W, int C, int stride,
+                     int rot180, int dtype, hipStream_t s);
+int launch_dwconv3x3_wgrad(const void* x, int x_stride, const void* dy, int dy_stride, float* ws, float* dw, float scale,
+                           int accumulate, int B, int H, int W, int C, int dtype, hipStream_t s);
+
+// decode.hip
+size_t decode_workspace_bytes(int B, int H, int W, int C, int K);
+// words of one image's workspace and the index of its below-the-floor word; returns the index of the overflow word
+int decode_status_words(int H, int W, int C, int K, long* ws_words, int* below_word);
+int launch_decode(const DecArgs& a, bool flip, hipStream_t s);
+int launch_postprocess(const float* boxes, const float* scores, const int* classes, int B, int K, int max_det,
+                       float thresh, const float* img_params, float* out_boxes, float* out_scores, int* out_classes,
+                       int* counts, hipStream_t s);
+
+// train_ops.hip
+int launch_gaussian_radius(const int* hw, int n, double* out_r, int* out_i, hipStream_t s);
+int launch_gaussian_targets(const float* boxes, const int64_t* classes, const int* counts, int B, int Nmax, int H,
+                            int W, int C, float* hm, float* wh, float* reg, int64_t* ind, uint8_t* reg_mask,
+                            hipStream_t s);
+size_t focal_workspace_bytes(long numel);
+int launch_focal_loss(const float* logits, const float* gt, const float* alpha, int B, int H, int W, int C,
+                      float grad_scale, void* workspace, float* loss, float* stats, float* grad, hipStream_t s);
+int launch_reg_l1(const float* pred, int pred_stride, const uint8_t* mask, const int64_t* ind, const float* target,
+                  int B, int N, int HW, float grad_scale, float* loss, float* grad, int grad_stride, hipStream_t s);
+int launch_sgd(float* p, const float* g, float* m, long n, const float* lr_dev, float mom, float wd, int first,
+               hipStream_t s);
+int launch_sgd_runs(float* p, const float* g, float* m, long n, const long* run_end, const int* run_lr_index,
+                    const float* run_wd, const float* lr_table, int nruns, float mom, int first, hipStream_t s);
+int launch_sgd_runs_clip(float* p, const float* g, float* m, long n, const long* run_end, const int* run_lr_index,
+                         const float* run_wd, const float* lr_table, int nruns, float mom, int first, int nesterov, int clip_type,
+                         float clip_value, const float* coefs, hipStream_t s);
+int launch_grad_chunk_norms(const float* g, long n, const long* chunk_start, const int* chunk_len, int nchunks, int norm_type,
+                            float* partials, hipStream_t s);
+int launch_grad_clip_coefs(const float* partials, const int* param_chunk_end, int nparams, int nchunks, int norm_type,
+                           float clip_value, float* norms, float* coefs, hipStream_t s);
+int launch_adam_advance(long long* step, float* bias, double beta1, double beta2, hipStream_t s);
+int launch_adam_runs(float* p, const float* g, float* m, float* v, float* vmax, long n, const long* run_end,
+                     const int* run_lr_index, const float* run_wd, const float* lr_table, int nruns, const float* bias,
+                     double beta1, double beta2, double eps, int decoupled, int amsgrad, int clip_type, float clip_value,
+                     const float* coefs, hipStream_t s);
+
+// train_bwd.hip
+size_t chan_reduce_workspace_bytes(int C);                   // BnArgs::workspace
+int launch_bn_train_fwd(const BnArgs& a, hipStream_t s);
+int launch_bn_train_bwd(const BnArgs& a, hipStream_t s);
+int launch_bn_local_stats(const BnArgs& a, hipStream_t s);       // SyncBN forward, before the all-reduce of a.slots
+int launch_bn_sync_fwd(const BnArgs& a, hipStream_t s);          // ... and after it (a.stats)
+int launch_bn_local_grad_sums(const BnArgs& a, hipStream_t s);   // SyncBN backward, before the all-reduce of a.slots
+int launch_bn_sync_bwd(const BnArgs& a, hipStream_t s);          // ... and after it (a.stats, a.sums)
+int launch_conv_wgrad(const WgradArgs& a, hipStream_t s);        // f16 tensors
+int launch_conv_wgrad_x3(const WgradArgs& a, hipStream_t s);     // f32 tensors, split f16 products
+int launch_conv_wgrad_f32(const WgradArgs& a, hipStream_t s);    // f32 tensors, f32 FMAs
+int launch_grad_scatter_oihw(const void* const* src, void* const* dst, const int* cout, const int* cin_real, const int* cin_k,
+                             const int* taps, int n, hipStream_t s);
+int launch_depth_to_space2(const void* src, int src_stride, void* dst, int dst_stride, int B, int H, int W, int C, int Hs, int Ws,
+                           int dtype, hipStream_t s);
+int launch_maxpool2x2_bwd(const void* x, int x_stride, const void* dz, int dz_stride, void* dx, int dx_stride, int dtype, int B,
+                          int H, int W, int C, hipStream_t s);
+int launch_maxpool3x3s2_bwd(const void* x, int xs, const void* dz, int dzs, void* dx, int dxs, int dtype, int B, int H, int W, int C,
+                            int pad, int Ho, int Wo, hipStream_t s);
+int launch_ese_dot(const void* dy, int dys, const void* x, int xs, int dtype, int B, int HW, int C, float* out, hipStream_t s);
+int launch_ese_bwd(const void* dy, int dys, const float* g, const float* gp, void* dx, int dxs, int dtype, int B, int HW, int C,
+                   hipStream_t s);
+int launch_dwconvT_bwd(const void* x, int x_stride, const void* dz, int dz_stride, const float* w, void* dx, int dx_stride,
+                       float* dw, int dtype, int B, int H, int W, int C, int f, hipStream_t s);
+int launch_dcn_cols(const DcnBwdArgs& a, hipStream_t s);
+int launch_dcn_col2im_coord(const DcnBwdArgs& a, hipStream_t s);
+// 0 if launched, 1 if the shape does not qualify (the caller then produces d(columns) and calls ctdet_dcn_col2im_coord)
+int launch_dcn_col2im_fused(const DcnBwdArgs& a, hipStream_t s);

@@ -1433,11 +1433,6 @@ __global__ void __launch_bounds__(256) conv_direct_f32_kernel(const ConvArgs a) 
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-int launch_halo_split(const ConvArgs& a, hipStream_t s);   // conv_igemm.hip
-int launch_halo_pair(const ConvArgs& a, hipStream_t s);    // conv_igemm.hip
-int launch_halo_pair2(const ConvArgs& a, hipStream_t s);   // conv_igemm.hip
-bool halo_pair_x_ok(const ConvArgs& a, int korder);        // conv_igemm.hip
-
 static bool aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
 
 static bool f32_vector_ok(const ConvArgs& a, int bc) {

@@ -2824,17 +2824,14 @@ __global__ void __launch_bounds__(256, 2) dcn_window_rows_kernel(const ConvArgs 
 }
 
 // `columns` of the DCNv2 backward from the LDS window (train_bwd.hip's launch_dcn_cols decides when)
-int launch_dcn_cols_window(const f16* x, int x_stride, const float* om, int om_stride, f16* col, int B, int H, int W, int Cin,
-                           int mask_is_prob, hipStream_t s) {
+int launch_dcn_cols_window(const DcnBwdArgs& d, hipStream_t s) {
   ConvArgs a = {};
-  a.x = x; a.y = col; a.om = om; a.om_stride = om_stride; a.mask_is_prob = mask_is_prob;
-  a.B = B; a.H = H; a.W = W; a.Ho = H; a.Wo = W; a.Cin = Cin; a.in_stride = x_stride; a.Cout = 64; a.Cout_pad = 64;
-  a.R = a.S = 3; a.stride = 1; a.pad = 1; a.dil = 1; a.in_dil = 1; a.K = a.Kpad = 9 * Cin; a.M = B * H * W; a.korder = 1;
-  const int nbx = B * (H / 8) * (W / 16);
-  if (mask_is_prob == DCN_MASK_NONE)
-    hipLaunchKernelGGL((dcn_window_rows_kernel<f16, false, true, true>), dim3(8 * ((nbx + 7) / 8)), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((dcn_window_rows_kernel<f16, false, true>), dim3(8 * ((nbx + 7) / 8)), dim3(256), 0, s, a);
+  a.x = d.x; a.y = d.col; a.om = d.om; a.om_stride = d.om_stride; a.mask_is_prob = d.mask_mode;
+  a.B = d.B; a.H = d.H; a.W = d.W; a.Ho = d.H; a.Wo = d.W; a.Cin = d.Cin; a.in_stride = d.x_stride; a.Cout = 64; a.Cout_pad = 64;
+  a.R = a.S = 3; a.stride = 1; a.pad = 1; a.dil = 1; a.in_dil = 1; a.K = a.Kpad = 9 * d.Cin; a.M = d.B * d.H * d.W; a.korder = 1;
+  const int nbx = d.B * (d.H / 8) * (d.W / 16);
+  const auto kernel = d.mask_mode == DCN_MASK_NONE ? dcn_window_rows_kernel<f16, false, true, true> : dcn_window_rows_kernel<f16, false, true>;
+  hipLaunchKernelGGL(kernel, dim3(8 * ((nbx + 7) / 8)), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }

@@ -234,7 +234,6 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-// shape / dtype checks shared by the entry points (api.hip validates pointers first)
 int dwconv3x3_check(int dtype, int B, int H, int W, int C, int stride, const int* strides, int nstrides) {
   CTDET_CHECK(dtype == CTDET_F16 || dtype == CTDET_F32, "dwconv3x3: dtype %d (f16 or f32 tensors)", dtype);
   CTDET_CHECK(stride == 1 || stride == 2, "dwconv3x3: stride %d (1 or 2)", stride);
@@ -269,7 +268,8 @@ int launch_dwconv3x3(const void* x, int x_stride, const float* w, void* y, int y
   hipLaunchKernelGGL((dwconv3x3_kernel<T, S_>), grid, dim3(256), 0, s, (const T*)x, x_stride, w, (T*)y, y_stride, H, W, Ho, \
                      Wo, C, nchunk, rot180)
   if (dtype == CTDET_F16) { if (stride == 1) DW3(f16, 1); else DW3(f16, 2); }
-  else { if (stride == 1) DW3(float, 1); else DW3(float, 2); }
+  else if (dtype == CTDET_F32) { if (stride == 1) DW3(float, 1); else DW3(float, 2); }
+  else CTDET_CHECK(false, "dwconv3x3: bad dtype %d", dtype);
 #undef DW3
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -286,9 +286,10 @@ int launch_dwconv3x3_wgrad(const void* x, int x_stride, const void* dy, int dy_s
     if (dtype == CTDET_F16)
       hipLaunchKernelGGL(dwconv3x3_wgrad_kernel<f16>, dim3((unsigned)g.G), dim3(256), lds, s, (const f16*)x, x_stride,
                          (const f16*)dy, dy_stride, ws, H, W, C, g.XL, g.ncol, g.nstrip, g.ntiles);
-    else
+    else if (dtype == CTDET_F32)
       hipLaunchKernelGGL(dwconv3x3_wgrad_kernel<float>, dim3((unsigned)g.G), dim3(256), lds, s, (const float*)x, x_stride,
                          (const float*)dy, dy_stride, ws, H, W, C, g.XL, g.ncol, g.nstrip, g.ntiles);
+    else CTDET_CHECK(false, "dwconv3x3_wgrad: bad dtype %d", dtype);
     CTDET_LAUNCH_CHECK();
   }
   // an empty problem still writes dw (zeros, or leaves the accumulated gradient as it is)

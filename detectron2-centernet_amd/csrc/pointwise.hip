@@ -284,8 +284,6 @@ __global__ void __launch_bounds__(256) dwconvT_add_rows_kernel(const T* __restri
 
 static inline unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
 
-// mirror_from < 0: the plain kernel; otherwise output images [mirror_from, B) are mirrored copies of source images
-// [0, B - mirror_from)
 int launch_preprocess(const void* img, int img_dtype, void* out, int out_dtype, int B, int H, int W, int Hp, int Wp,
                       long img_batch_stride, const float* mean, const float* stdv, int out_stride, int border,
                       int mirror_from, hipStream_t s) {

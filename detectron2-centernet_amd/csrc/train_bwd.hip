@@ -403,18 +403,6 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_rows_kernel(const T* __restr
 // stay row-major [pixel][channel] and ds_read_b64_tr_b16 delivers the 4x16 blocks column-major.
 // Results are added to the f32 dW with atomics (split over pixel ranges across workgroups).
 // ------------------------------------------------------------------------------------------------
-struct WgradArgs {
-  const void* x; const void* dy; float* dw;   // x, dy: f16 (f16 mode) or f32 (f16x3 mode: split into hi + lo f16 halves on the way to LDS)
-  int B, H, W, Cin, in_stride, Cout, Ho, Wo, dy_stride, R, S, stride, pad, dil, K, M, msplit;
-  float scale;   // multiplier applied to every partial sum before it is added to dw
-  int lw, lh;    // log2(Wo), log2(Ho) when both are powers of two, else -1
-  // output layout: perm_rs == 0: dw[n][k], k = tap*Cin + c (tap-major).  perm_rs > 0: the parameter's own OIHW layout,
-  // dw[(n*cin_real + c)*perm_rs + tap] with k = tap*perm_cin + c, channels c >= cin_real (input padding) dropped -- the
-  // and rows n >= cout_real (output-channel padding of dy) dropped -- the kernel then accumulates straight into the
-  // optimizer's gradient buffer
-  int perm_rs, perm_cin, cin_real, cout_real;
-};
-
 template <typename A>
 __device__ __forceinline__ void wg_add(const A& a, int n, int k, float v) {
   if (a.perm_rs == 0) { atomicAdd(a.dw + (long)n * a.K + k, v); return; }
@@ -684,7 +672,6 @@ int launch_maxpool3x3s2_bwd(const void* x, int xs, const void* dz, int dzs, void
   if (dtype == CTDET_F16) return launch_maxpool3x3s2_bwd_t<f16>(x, xs, dz, dzs, dx, dxs, B, H, W, C, pad, Ho, Wo, s);
   if (dtype == CTDET_F32) return launch_maxpool3x3s2_bwd_t<float>(x, xs, dz, dzs, dx, dxs, B, H, W, C, pad, Ho, Wo, s);
   CTDET_CHECK(false, "maxpool3x3s2_bwd: bad dtype %d", dtype);
-  return 0;
 }
 
 // eSE attention backward (vovnet.py:200-213; forward: y = x * hsigmoid(s[b][c]) (+ identity), s = fc(mean over pixels of x)):
@@ -1356,100 +1343,83 @@ static int chan_blocks(int M, int C, int N) {
 }
 
 template <typename T>
-static int launch_bn_train_fwd_t(const T* y, int y_stride, const T* res, int res_stride, T* z, int z_stride, int M, int C,
-                                 const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                                 float* running_var, float* mean, float* invstd, float* scale, float* shift, void* workspace,
-                                 int relu, hipStream_t s) {
+static int launch_bn_train_fwd_t(const BnArgs& b, hipStream_t s) {
   constexpr int N = VecT<T>::N;
+  const T *y = (const T*)b.y, *res = (const T*)b.res;
+  T* z = (T*)b.z_out;
+  const int M = b.M, C = b.C;
   CTDET_CHECK(C % N == 0 && C / N <= 256, "bn: unsupported channel count %d", C);
-  CTDET_CHECK(y_stride % N == 0 && z_stride % N == 0 && (!res || res_stride % N == 0) && ((((size_t)y | (size_t)z | (size_t)res)) & 15) == 0,
+  CTDET_CHECK(b.y_stride % N == 0 && b.z_stride % N == 0 && (!res || b.res_stride % N == 0) && ((((size_t)y | (size_t)z | (size_t)res)) & 15) == 0,
               "bn: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
   ChanRedArgs<T> a = {};
-  a.y = y; a.y_stride = y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)workspace;
+  a.y = y; a.y_stride = b.y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)b.workspace;
   // f32 tensors: the pivot goes to the backward's [2][C] sums slot, free in the forward
-  a.pivot = std::is_same<T, float>::value ? (float*)workspace + (size_t)1024 * 2 * C : nullptr;
+  a.pivot = std::is_same<T, float>::value ? (float*)b.workspace + (size_t)1024 * 2 * C : nullptr;
   const int nb = chan_blocks(M, C, N);
   hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 0, eps,
-                     momentum, gamma, beta, mean, invstd, scale, shift, running_mean, running_var, (const float*)a.pivot);
+  hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 0, b.eps,
+                     b.momentum, b.gamma, b.beta, b.save_mean, b.save_invstd, b.save_scale, b.save_shift, b.running_mean,
+                     b.running_var, (const float*)a.pivot);
   const int CV = C / N;
   if ((CV & (CV - 1)) == 0) {
     int sh = 0;
     while ((1 << sh) < CV) ++sh;
     const long ppb = (256 >> sh) * AA_ROWS;
-    hipLaunchKernelGGL(affine_act_rows_kernel<T>, dim3((unsigned)(((long)M + ppb - 1) / ppb)), dim3(256), 0, s, y, y_stride,
-                       (const float*)scale, (const float*)shift, res, res_stride, z, z_stride, (long)M, sh, relu);
+    hipLaunchKernelGGL(affine_act_rows_kernel<T>, dim3((unsigned)(((long)M + ppb - 1) / ppb)), dim3(256), 0, s, y, b.y_stride,
+                       (const float*)b.save_scale, (const float*)b.save_shift, res, b.res_stride, z, b.z_stride, (long)M, sh, b.relu);
   } else {
-    hipLaunchKernelGGL(affine_act_kernel<T>, dim3(nblk256((long)M * CV)), dim3(256), 0, s, y, y_stride, (const float*)scale,
-                       (const float*)shift, res, res_stride, z, z_stride, (long)M, C, relu);
+    hipLaunchKernelGGL(affine_act_kernel<T>, dim3(nblk256((long)M * CV)), dim3(256), 0, s, y, b.y_stride, (const float*)b.save_scale,
+                       (const float*)b.save_shift, res, b.res_stride, z, b.z_stride, (long)M, C, b.relu);
   }
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T>
-static int launch_bn_train_bwd_t(const T* dz, int dz_stride, const T* z, int z_stride, const T* y, int y_stride,
-                                 const float* mean, const float* invstd, const float* scale, int M, int C, int relu, T* dy,
-                                 int dy_stride, T* dres, int dres_stride, float* dgamma, float* dbeta, float grad_mult,
-                                 void* workspace, hipStream_t s) {
+static int launch_bn_train_bwd_t(const BnArgs& b, hipStream_t s) {
   constexpr int N = VecT<T>::N;
+  const T *dz = (const T*)b.dz, *z = (const T*)b.z, *y = (const T*)b.y;
+  T *dy = (T*)b.dy, *dres = (T*)b.dres;
+  const int M = b.M, C = b.C;
   CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_bwd: unsupported channel count %d", C);
-  CTDET_CHECK(dz_stride % N == 0 && dy_stride % N == 0 && (!z || z_stride % N == 0) && (!y || y_stride % N == 0) &&
-                  (!dres || dres_stride % N == 0) && ((((size_t)dz | (size_t)z | (size_t)y | (size_t)dy | (size_t)dres)) & 15) == 0,
+  CTDET_CHECK(b.dz_stride % N == 0 && b.dy_stride % N == 0 && (!z || b.z_stride % N == 0) && (!y || b.y_stride % N == 0) &&
+                  (!dres || b.dres_stride % N == 0) && ((((size_t)dz | (size_t)z | (size_t)y | (size_t)dy | (size_t)dres)) & 15) == 0,
               "bn_bwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
   ChanRedArgs<T> a = {};
-  a.y = y; a.y_stride = y_stride; a.dz = dz; a.dz_stride = dz_stride; a.z = z; a.z_stride = z_stride;
-  a.mean = mean; a.invstd = invstd; a.M = M; a.C = C; a.mode = 1; a.relu = relu; a.partial = (float*)workspace;
+  a.y = y; a.y_stride = b.y_stride; a.dz = dz; a.dz_stride = b.dz_stride; a.z = z; a.z_stride = b.z_stride;
+  a.mean = b.mean; a.invstd = b.invstd; a.M = M; a.C = C; a.mode = 1; a.relu = b.relu; a.partial = (float*)b.workspace;
   const int nb = chan_blocks(M, C, N);
   hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
-  float* sums = (float*)workspace + (size_t)1024 * 2 * C;   // [2][C]: sum g, sum g*xhat
-  hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 1,
-                     grad_mult, 0.f, (const float*)nullptr, (const float*)nullptr, dbeta, dgamma, sums, sums + C,
+  float* sums = (float*)b.workspace + (size_t)1024 * 2 * C;   // [2][C]: sum g, sum g*xhat
+  hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 1,
+                     b.grad_mult, 0.f, (const float*)nullptr, (const float*)nullptr, b.dbeta, b.dgamma, sums, sums + C,
                      (float*)nullptr, (float*)nullptr, (const float*)nullptr);
   const int CV = C / N;
   if ((CV & (CV - 1)) == 0 && CV <= 256) {
     int sh = 0;
     while ((1 << sh) < CV) ++sh;
     const long ppb = (256 >> sh) * BN_ROWS;
-    hipLaunchKernelGGL(bn_bwd_apply_rows_kernel<T>, dim3((unsigned)(((long)M + ppb - 1) / ppb)), dim3(256), 0, s, dz, dz_stride, z,
-                       z_stride, y, y_stride, mean, invstd, scale, (const float*)sums, (const float*)(sums + C), dy, dy_stride,
-                       dres, dres_stride, (long)M, sh, relu);
+    hipLaunchKernelGGL(bn_bwd_apply_rows_kernel<T>, dim3((unsigned)(((long)M + ppb - 1) / ppb)), dim3(256), 0, s, dz, b.dz_stride, z,
+                       b.z_stride, y, b.y_stride, b.mean, b.invstd, b.scale, (const float*)sums, (const float*)(sums + C), dy,
+                       b.dy_stride, dres, b.dres_stride, (long)M, sh, b.relu);
   } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(nblk256((long)M * CV)), dim3(256), 0, s, dz, dz_stride, z, z_stride, y,
-                       y_stride, mean, invstd, scale, (const float*)sums, (const float*)(sums + C), dy, dy_stride, dres,
-                       dres_stride, (long)M, C, relu);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(nblk256((long)M * CV)), dim3(256), 0, s, dz, b.dz_stride, z, b.z_stride, y,
+                       b.y_stride, b.mean, b.invstd, b.scale, (const float*)sums, (const float*)(sums + C), dy, b.dy_stride, dres,
+                       b.dres_stride, (long)M, C, b.relu);
   }
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_bn_train_fwd(const f16* y, int y_stride, const f16* res, int res_stride, f16* z, int z_stride, int M, int C,
-                        const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                        float* running_var, float* mean, float* invstd, float* scale, float* shift, void* workspace,
-                        int relu, hipStream_t s) {
-  return launch_bn_train_fwd_t<f16>(y, y_stride, res, res_stride, z, z_stride, M, C, gamma, beta, eps, momentum, running_mean,
-                                    running_var, mean, invstd, scale, shift, workspace, relu, s);
+int launch_bn_train_fwd(const BnArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F16) return launch_bn_train_fwd_t<f16>(a, s);
+  if (a.dtype == CTDET_F32) return launch_bn_train_fwd_t<float>(a, s);
+  CTDET_CHECK(false, "bn_train_fwd: bad dtype %d", a.dtype);
 }
-int launch_bn_train_fwd_f32(const float* y, int y_stride, const float* res, int res_stride, float* z, int z_stride, int M, int C,
-                            const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                            float* running_var, float* mean, float* invstd, float* scale, float* shift, void* workspace,
-                            int relu, hipStream_t s) {
-  return launch_bn_train_fwd_t<float>(y, y_stride, res, res_stride, z, z_stride, M, C, gamma, beta, eps, momentum, running_mean,
-                                      running_var, mean, invstd, scale, shift, workspace, relu, s);
-}
-int launch_bn_train_bwd(const f16* dz, int dz_stride, const f16* z, int z_stride, const f16* y, int y_stride,
-                        const float* mean, const float* invstd, const float* scale, int M, int C, int relu, f16* dy,
-                        int dy_stride, f16* dres, int dres_stride, float* dgamma, float* dbeta, float grad_mult,
-                        void* workspace, hipStream_t s) {
-  return launch_bn_train_bwd_t<f16>(dz, dz_stride, z, z_stride, y, y_stride, mean, invstd, scale, M, C, relu, dy, dy_stride, dres,
-                                    dres_stride, dgamma, dbeta, grad_mult, workspace, s);
-}
-int launch_bn_train_bwd_f32(const float* dz, int dz_stride, const float* z, int z_stride, const float* y, int y_stride,
-                            const float* mean, const float* invstd, const float* scale, int M, int C, int relu, float* dy,
-                            int dy_stride, float* dres, int dres_stride, float* dgamma, float* dbeta, float grad_mult,
-                            void* workspace, hipStream_t s) {
-  return launch_bn_train_bwd_t<float>(dz, dz_stride, z, z_stride, y, y_stride, mean, invstd, scale, M, C, relu, dy, dy_stride,
-                                      dres, dres_stride, dgamma, dbeta, grad_mult, workspace, s);
+int launch_bn_train_bwd(const BnArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F16) return launch_bn_train_bwd_t<f16>(a, s);
+  if (a.dtype == CTDET_F32) return launch_bn_train_bwd_t<float>(a, s);
+  CTDET_CHECK(false, "bn_train_bwd: bad dtype %d", a.dtype);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1675,121 +1645,101 @@ static int sb_cv_shift(int CV) {
 }
 
 template <typename T>
-static int launch_bn_local_stats_t(const T* y, int y_stride, int M, int C, int rank, int world, double* stats, void* workspace,
-                                   hipStream_t s) {
+static int launch_bn_local_stats_t(const BnArgs& b, hipStream_t s) {
   constexpr int N = VecT<T>::N;
+  const int M = b.M, C = b.C;
   CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_local_stats: unsupported channel count %d", C);
-  CTDET_CHECK(y_stride % N == 0 && ((size_t)y & 15) == 0,
+  CTDET_CHECK(b.y_stride % N == 0 && ((size_t)b.y & 15) == 0,
               "bn_local_stats: y must be 16-byte aligned with a pixel stride that is a multiple of %d", N);
   ChanRedArgs<T> a = {};
-  a.y = y; a.y_stride = y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)workspace;
-  a.pivot = std::is_same<T, float>::value ? (float*)workspace + (size_t)1024 * 2 * C : nullptr;
+  a.y = (const T*)b.y; a.y_stride = b.y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)b.workspace;
+  a.pivot = std::is_same<T, float>::value ? (float*)b.workspace + (size_t)1024 * 2 * C : nullptr;
   const int nb = chan_blocks(M, C, N);
   hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 0,
-                     (const float*)a.pivot, stats, rank, world, 0.f, (float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 0,
+                     (const float*)a.pivot, b.slots, b.rank, b.world, 0.f, (float*)nullptr, (float*)nullptr);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T>
-static int launch_bn_sync_fwd_t(const T* y, int y_stride, const T* res, int res_stride, T* z, int z_stride, int M, int C,
-                                const double* stats, int world, const float* gamma, const float* beta, float eps, float momentum,
-                                float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
-                                float* shift, int relu, hipStream_t s) {
+static int launch_bn_sync_fwd_t(const BnArgs& b, hipStream_t s) {
   constexpr int N = VecT<T>::N;
+  const T *y = (const T*)b.y, *res = (const T*)b.res;
+  T* z = (T*)b.z_out;
+  const int C = b.C;
   CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_sync_fwd: unsupported channel count %d", C);
-  CTDET_CHECK(y_stride % N == 0 && z_stride % N == 0 && (!res || res_stride % N == 0) && ((((size_t)y | (size_t)z | (size_t)res)) & 15) == 0,
+  CTDET_CHECK(b.y_stride % N == 0 && b.z_stride % N == 0 && (!res || b.res_stride % N == 0) && ((((size_t)y | (size_t)z | (size_t)res)) & 15) == 0,
               "bn_sync_fwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
   const int CV = C / N;
-  const long total = (long)M * CV;
+  const long total = (long)b.M * CV;
   const unsigned grid = (unsigned)((total + 256L * SB_ROWS - 1) / (256L * SB_ROWS));
-  hipLaunchKernelGGL(bn_sync_fwd_apply_kernel<T>, dim3(grid), dim3(256), 2 * C * sizeof(float), s, y, y_stride, res,
-                     res_stride, z, z_stride, (long)M, C, sb_cv_shift(CV), stats, world, gamma, beta, eps, momentum,
-                     running_mean, running_var, save_mean, save_invstd, scale, shift, relu);
+  hipLaunchKernelGGL(bn_sync_fwd_apply_kernel<T>, dim3(grid), dim3(256), 2 * C * sizeof(float), s, y, b.y_stride, res,
+                     b.res_stride, z, b.z_stride, (long)b.M, C, sb_cv_shift(CV), b.stats, b.world, b.gamma, b.beta, b.eps, b.momentum,
+                     b.running_mean, b.running_var, b.save_mean, b.save_invstd, b.save_scale, b.save_shift, b.relu);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T>
-static int launch_bn_local_grad_sums_t(const T* dz, int dz_stride, const T* z, int z_stride, const T* y, int y_stride,
-                                       const float* mean, const float* invstd, int M, int C, int relu, int rank, int world,
-                                       double* sums, float* dgamma, float* dbeta, float grad_mult, void* workspace,
-                                       hipStream_t s) {
+static int launch_bn_local_grad_sums_t(const BnArgs& b, hipStream_t s) {
   constexpr int N = VecT<T>::N;
+  const T *dz = (const T*)b.dz, *z = (const T*)b.z, *y = (const T*)b.y;
+  const int M = b.M, C = b.C;
   CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_local_grad_sums: unsupported channel count %d", C);
-  CTDET_CHECK(dz_stride % N == 0 && (!z || z_stride % N == 0) && (!y || y_stride % N == 0) &&
+  CTDET_CHECK(b.dz_stride % N == 0 && (!z || b.z_stride % N == 0) && (!y || b.y_stride % N == 0) &&
                   ((((size_t)dz | (size_t)z | (size_t)y)) & 15) == 0,
               "bn_local_grad_sums: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
   ChanRedArgs<T> a = {};
-  a.y = y; a.y_stride = y_stride; a.dz = dz; a.dz_stride = dz_stride; a.z = z; a.z_stride = z_stride;
-  a.mean = mean; a.invstd = invstd; a.M = M; a.C = C; a.mode = 1; a.relu = relu; a.partial = (float*)workspace;
+  a.y = y; a.y_stride = b.y_stride; a.dz = dz; a.dz_stride = b.dz_stride; a.z = z; a.z_stride = b.z_stride;
+  a.mean = b.mean; a.invstd = b.invstd; a.M = M; a.C = C; a.mode = 1; a.relu = b.relu; a.partial = (float*)b.workspace;
   const int nb = chan_blocks(M, C, N);
   hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)workspace, nb, C, M, 1,
-                     (const float*)nullptr, sums, rank, world, grad_mult, dgamma, dbeta);
+  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 1,
+                     (const float*)nullptr, b.slots, b.rank, b.world, b.grad_mult, b.dgamma, b.dbeta);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T>
-static int launch_bn_sync_bwd_t(const T* dz, int dz_stride, const T* z, int z_stride, const T* y, int y_stride,
-                                const float* mean, const float* invstd, const float* scale, const double* stats,
-                                const double* sums, int world, int M, int C, int relu, T* dy, int dy_stride, T* dres,
-                                int dres_stride, hipStream_t s) {
+static int launch_bn_sync_bwd_t(const BnArgs& b, hipStream_t s) {
   constexpr int N = VecT<T>::N;
+  const T *dz = (const T*)b.dz, *z = (const T*)b.z, *y = (const T*)b.y;
+  T *dy = (T*)b.dy, *dres = (T*)b.dres;
+  const int C = b.C;
   CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_sync_bwd: unsupported channel count %d", C);
-  CTDET_CHECK(dz_stride % N == 0 && dy_stride % N == 0 && (!z || z_stride % N == 0) && y_stride % N == 0 &&
-                  (!dres || dres_stride % N == 0) && ((((size_t)dz | (size_t)z | (size_t)y | (size_t)dy | (size_t)dres)) & 15) == 0,
+  CTDET_CHECK(b.dz_stride % N == 0 && b.dy_stride % N == 0 && (!z || b.z_stride % N == 0) && b.y_stride % N == 0 &&
+                  (!dres || b.dres_stride % N == 0) && ((((size_t)dz | (size_t)z | (size_t)y | (size_t)dy | (size_t)dres)) & 15) == 0,
               "bn_sync_bwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
   const int CV = C / N;
-  const long total = (long)M * CV;
+  const long total = (long)b.M * CV;
   const unsigned grid = (unsigned)((total + 256L * SB_ROWS - 1) / (256L * SB_ROWS));
-  hipLaunchKernelGGL(bn_sync_bwd_apply_kernel<T>, dim3(grid), dim3(256), 5 * C * sizeof(float), s, dz, dz_stride, z, z_stride,
-                     y, y_stride, mean, invstd, scale, stats, sums, world, dy, dy_stride, dres, dres_stride, (long)M, C,
-                     sb_cv_shift(CV), relu);
+  hipLaunchKernelGGL(bn_sync_bwd_apply_kernel<T>, dim3(grid), dim3(256), 5 * C * sizeof(float), s, dz, b.dz_stride, z, b.z_stride,
+                     y, b.y_stride, b.mean, b.invstd, b.scale, b.stats, b.sums, b.world, dy, b.dy_stride, dres, b.dres_stride,
+                     (long)b.M, C, sb_cv_shift(CV), b.relu);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_bn_local_stats(const void* y, int y_stride, int M, int C, int rank, int world, double* stats, void* workspace,
-                          int f32, hipStream_t s) {
-  if (f32) return launch_bn_local_stats_t<float>((const float*)y, y_stride, M, C, rank, world, stats, workspace, s);
-  return launch_bn_local_stats_t<f16>((const f16*)y, y_stride, M, C, rank, world, stats, workspace, s);
+int launch_bn_local_stats(const BnArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F32) return launch_bn_local_stats_t<float>(a, s);
+  if (a.dtype == CTDET_F16) return launch_bn_local_stats_t<f16>(a, s);
+  CTDET_CHECK(false, "bn_local_stats: bad dtype %d", a.dtype);
 }
-int launch_bn_sync_fwd(const void* y, int y_stride, const void* res, int res_stride, void* z, int z_stride, int M, int C,
-                       const double* stats, int world, const float* gamma, const float* beta, float eps, float momentum,
-                       float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
-                       float* shift, int relu, int f32, hipStream_t s) {
-  if (f32)
-    return launch_bn_sync_fwd_t<float>((const float*)y, y_stride, (const float*)res, res_stride, (float*)z, z_stride, M, C,
-                                       stats, world, gamma, beta, eps, momentum, running_mean, running_var, save_mean,
-                                       save_invstd, scale, shift, relu, s);
-  return launch_bn_sync_fwd_t<f16>((const f16*)y, y_stride, (const f16*)res, res_stride, (f16*)z, z_stride, M, C, stats,
-                                   world, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd,
-                                   scale, shift, relu, s);
+int launch_bn_sync_fwd(const BnArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F32) return launch_bn_sync_fwd_t<float>(a, s);
+  if (a.dtype == CTDET_F16) return launch_bn_sync_fwd_t<f16>(a, s);
+  CTDET_CHECK(false, "bn_sync_fwd: bad dtype %d", a.dtype);
 }
-int launch_bn_local_grad_sums(const void* dz, int dz_stride, const void* z, int z_stride, const void* y, int y_stride,
-                              const float* mean, const float* invstd, int M, int C, int relu, int rank, int world,
-                              double* sums, float* dgamma, float* dbeta, float grad_mult, void* workspace, int f32,
-                              hipStream_t s) {
-  if (f32)
-    return launch_bn_local_grad_sums_t<float>((const float*)dz, dz_stride, (const float*)z, z_stride, (const float*)y,
-                                              y_stride, mean, invstd, M, C, relu, rank, world, sums, dgamma, dbeta,
-                                              grad_mult, workspace, s);
-  return launch_bn_local_grad_sums_t<f16>((const f16*)dz, dz_stride, (const f16*)z, z_stride, (const f16*)y, y_stride, mean,
-                                          invstd, M, C, relu, rank, world, sums, dgamma, dbeta, grad_mult, workspace, s);
+int launch_bn_local_grad_sums(const BnArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F32) return launch_bn_local_grad_sums_t<float>(a, s);
+  if (a.dtype == CTDET_F16) return launch_bn_local_grad_sums_t<f16>(a, s);
+  CTDET_CHECK(false, "bn_local_grad_sums: bad dtype %d", a.dtype);
 }
-int launch_bn_sync_bwd(const void* dz, int dz_stride, const void* z, int z_stride, const void* y, int y_stride,
-                       const float* mean, const float* invstd, const float* scale, const double* stats, const double* sums,
-                       int world, int M, int C, int relu, void* dy, int dy_stride, void* dres, int dres_stride, int f32,
-                       hipStream_t s) {
-  if (f32)
-    return launch_bn_sync_bwd_t<float>((const float*)dz, dz_stride, (const float*)z, z_stride, (const float*)y, y_stride,
-                                       mean, invstd, scale, stats, sums, world, M, C, relu, (float*)dy, dy_stride,
-                                       (float*)dres, dres_stride, s);
-  return launch_bn_sync_bwd_t<f16>((const f16*)dz, dz_stride, (const f16*)z, z_stride, (const f16*)y, y_stride, mean, invstd,
-                                   scale, stats, sums, world, M, C, relu, (f16*)dy, dy_stride, (f16*)dres, dres_stride, s);
+int launch_bn_sync_bwd(const BnArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F32) return launch_bn_sync_bwd_t<float>(a, s);
+  if (a.dtype == CTDET_F16) return launch_bn_sync_bwd_t<f16>(a, s);
+  CTDET_CHECK(false, "bn_sync_bwd: bad dtype %d", a.dtype);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2229,35 +2179,33 @@ static int launch_depth_to_space2_t(const T* src, int src_stride, T* dst, int ds
 }
 int launch_depth_to_space2(const void* src, int src_stride, void* dst, int dst_stride, int B, int H, int W, int C, int Hs, int Ws,
                            int dtype, hipStream_t s) {
-  if (dtype == CTDET_F32)
-    return launch_depth_to_space2_t<float>((const float*)src, src_stride, (float*)dst, dst_stride, B, H, W, C, Hs, Ws, s);
-  return launch_depth_to_space2_t<f16>((const f16*)src, src_stride, (f16*)dst, dst_stride, B, H, W, C, Hs, Ws, s);
+  if (dtype == CTDET_F32) return launch_depth_to_space2_t<float>((const float*)src, src_stride, (float*)dst, dst_stride, B, H, W, C, Hs, Ws, s);
+  if (dtype == CTDET_F16) return launch_depth_to_space2_t<f16>((const f16*)src, src_stride, (f16*)dst, dst_stride, B, H, W, C, Hs, Ws, s);
+  CTDET_CHECK(false, "depth_to_space2: bad dtype %d", dtype);
 }
 
 template <typename T>
-static int launch_maxpool2x2_bwd_t(const T* x, int x_stride, const T* dz, int dz_stride, T* dx, int dx_stride, int B, int H,
-                                   int W, int C, hipStream_t s) {
+static int launch_maxpool2x2_bwd_t(const void* x, int x_stride, const void* dz, int dz_stride, void* dx, int dx_stride, int B,
+                                   int H, int W, int C, hipStream_t s) {
   constexpr int N = VecT<T>::N;
   CTDET_CHECK(C % N == 0 && H % 2 == 0 && W % 2 == 0 && x_stride % N == 0 && dz_stride % N == 0 && dx_stride % N == 0,
               "maxpool_bwd: bad shape");
   const long total = (long)B * (H / 2) * (W / 2) * (C / N);
   if (total == 0) return 0;
-  hipLaunchKernelGGL(maxpool2x2_bwd_kernel<T>, dim3(nblk256(total)), dim3(256), 0, s, x, x_stride, dz, dz_stride, dx, dx_stride, B,
-                     H, W, C);
+  hipLaunchKernelGGL(maxpool2x2_bwd_kernel<T>, dim3(nblk256(total)), dim3(256), 0, s, (const T*)x, x_stride, (const T*)dz, dz_stride,
+                     (T*)dx, dx_stride, B, H, W, C);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
-int launch_maxpool2x2_bwd(const f16* x, int x_stride, const f16* dz, int dz_stride, f16* dx, int dx_stride, int B, int H,
-                          int W, int C, hipStream_t s) {
-  return launch_maxpool2x2_bwd_t<f16>(x, x_stride, dz, dz_stride, dx, dx_stride, B, H, W, C, s);
-}
-int launch_maxpool2x2_bwd_f32(const float* x, int x_stride, const float* dz, int dz_stride, float* dx, int dx_stride, int B,
-                              int H, int W, int C, hipStream_t s) {
-  return launch_maxpool2x2_bwd_t<float>(x, x_stride, dz, dz_stride, dx, dx_stride, B, H, W, C, s);
+int launch_maxpool2x2_bwd(const void* x, int x_stride, const void* dz, int dz_stride, void* dx, int dx_stride, int dtype, int B,
+                          int H, int W, int C, hipStream_t s) {
+  if (dtype == CTDET_F16) return launch_maxpool2x2_bwd_t<f16>(x, x_stride, dz, dz_stride, dx, dx_stride, B, H, W, C, s);
+  if (dtype == CTDET_F32) return launch_maxpool2x2_bwd_t<float>(x, x_stride, dz, dz_stride, dx, dx_stride, B, H, W, C, s);
+  CTDET_CHECK(false, "maxpool2x2_bwd: bad dtype %d", dtype);
 }
 
 template <typename T>
-static int launch_dwconvT_bwd_t(const T* x, int x_stride, const T* dz, int dz_stride, const float* w, T* dx, int dx_stride,
+static int launch_dwconvT_bwd_t(const void* x, int x_stride, const void* dz, int dz_stride, const float* w, void* dx, int dx_stride,
                                 float* dw, int B, int H, int W, int C, int f, hipStream_t s) {
   constexpr int N = VecT<T>::N;
   CTDET_CHECK(C % N == 0 && f % 2 == 0 && C / N <= 256 && x_stride % N == 0 && dz_stride % N == 0 && dx_stride % N == 0,
@@ -2267,110 +2215,94 @@ static int launch_dwconvT_bwd_t(const T* x, int x_stride, const T* dz, int dz_st
   long nb = ((long)B * (H + 1) * (W + 1) + S * 16 - 1) / (S * 16);
   if (nb > 512) nb = 512;
   if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(dwconvT_dw_kernel<T>, dim3((unsigned)nb, (unsigned)(f * f)), dim3(256), lds, s, x, x_stride, dz, dz_stride,
-                     dw, B, H, W, C, f);
+  hipLaunchKernelGGL(dwconvT_dw_kernel<T>, dim3((unsigned)nb, (unsigned)(f * f)), dim3(256), lds, s, (const T*)x, x_stride,
+                     (const T*)dz, dz_stride, dw, B, H, W, C, f);
   long nbx = ((long)B * H * W * (C / N) + 255) / 256;
   if (nbx > 4096) nbx = 4096;
-  hipLaunchKernelGGL(dwconvT_dx_kernel<T>, dim3((unsigned)nbx), dim3(256), 0, s, dz, dz_stride, w, dx, dx_stride, B, H, W, C, f);
+  hipLaunchKernelGGL(dwconvT_dx_kernel<T>, dim3((unsigned)nbx), dim3(256), 0, s, (const T*)dz, dz_stride, w, (T*)dx, dx_stride, B, H, W,
+                     C, f);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
-int launch_dwconvT_bwd(const f16* x, int x_stride, const f16* dz, int dz_stride, const float* w, f16* dx, int dx_stride,
-                       float* dw, int B, int H, int W, int C, int f, hipStream_t s) {
-  return launch_dwconvT_bwd_t<f16>(x, x_stride, dz, dz_stride, w, dx, dx_stride, dw, B, H, W, C, f, s);
-}
-int launch_dwconvT_bwd_f32(const float* x, int x_stride, const float* dz, int dz_stride, const float* w, float* dx,
-                           int dx_stride, float* dw, int B, int H, int W, int C, int f, hipStream_t s) {
-  return launch_dwconvT_bwd_t<float>(x, x_stride, dz, dz_stride, w, dx, dx_stride, dw, B, H, W, C, f, s);
+int launch_dwconvT_bwd(const void* x, int x_stride, const void* dz, int dz_stride, const float* w, void* dx, int dx_stride,
+                       float* dw, int dtype, int B, int H, int W, int C, int f, hipStream_t s) {
+  if (dtype == CTDET_F16) return launch_dwconvT_bwd_t<f16>(x, x_stride, dz, dz_stride, w, dx, dx_stride, dw, B, H, W, C, f, s);
+  if (dtype == CTDET_F32) return launch_dwconvT_bwd_t<float>(x, x_stride, dz, dz_stride, w, dx, dx_stride, dw, B, H, W, C, f, s);
+  CTDET_CHECK(false, "dwconvT_bwd: bad dtype %d", dtype);
 }
 
-int launch_dcn_cols_window(const f16* x, int x_stride, const float* om, int om_stride, f16* col, int B, int H, int W, int Cin,
-                           int mask_is_prob, hipStream_t s);   // conv_igemm.hip: the sampling kernel's LDS window
-int launch_dcn_cols(const f16* x, int x_stride, const float* om, int om_stride, f16* col, int B, int H, int W, int Cin,
-                    int mask_is_prob, hipStream_t s) {
-  CTDET_CHECK(Cin % 8 == 0 && om_stride >= dcn_om_channels(mask_is_prob), "dcn_cols: bad shape");
-  const long total = (long)B * H * W * 9 * (Cin / 8);
+static int dcn_cols_f16(const DcnBwdArgs& a, hipStream_t s) {
+  const f16* x = (const f16*)a.x;
+  f16* col = (f16*)a.col;
+  CTDET_CHECK(a.Cin % 8 == 0 && a.om_stride >= dcn_om_channels(a.mask_mode), "dcn_cols: bad shape");
+  const long total = (long)a.B * a.H * a.W * 9 * (a.Cin / 8);
   if (total == 0) return 0;
-  if (H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && x_stride % 8 == 0 && om_stride % 4 == 0 && H <= 65534 && W <= 65534 &&
-      (((size_t)x | (size_t)col | (size_t)om) & 15) == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
-    return launch_dcn_cols_window(x, x_stride, om, om_stride, col, B, H, W, Cin, mask_is_prob, s);
-  if (mask_is_prob == DCN_MASK_NONE)
-    hipLaunchKernelGGL(dcn_cols_kernel<true>, dim3(nblk256(total)), dim3(256), 0, s, x, x_stride, om, om_stride, col, B, H, W, Cin,
-                       mask_is_prob);
-  else
-    hipLaunchKernelGGL(dcn_cols_kernel<false>, dim3(nblk256(total)), dim3(256), 0, s, x, x_stride, om, om_stride, col, B, H, W, Cin,
-                       mask_is_prob);
+  if (a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 8 == 0 && a.om_stride % 4 == 0 && a.H <= 65534 && a.W <= 65534 &&
+      (((size_t)x | (size_t)col | (size_t)a.om) & 15) == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
+    return launch_dcn_cols_window(a, s);   // conv_igemm.hip: the sampling kernel's LDS window
+  const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_cols_kernel<true> : dcn_cols_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(nblk256(total)), dim3(256), 0, s, x, a.x_stride, a.om, a.om_stride, col, a.B, a.H, a.W, a.Cin,
+                     a.mask_mode);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename T, bool FUSED = false, bool NM = false>
-static void launch_col2im_window_t(const T* dcol, const T* x, int x_stride, const float* om, int om_stride, float* dx, void* dom,
-                                   int dom_stride, int dom_f16, int B, int H, int W, int Cin, int mask_is_prob, int chunked,
-                                   hipStream_t s, const FusedDcol fz) {
-  const unsigned tiles = (unsigned)(B * (H / 8) * (W / 16));
+// the LDS-window scatter: T = element type of a.x / a.dcol; FUSED: d(columns) comes from fz (a.dcol unused, chunked order)
+template <typename T, bool FUSED, bool NM>
+static void launch_col2im_window_t(const DcnBwdArgs& a, hipStream_t s, const FusedDcol fz) {
+  const T *dcol = (const T*)a.dcol, *x = (const T*)a.x;
+  const int dom_f16 = a.dom_dtype == CTDET_F16, chunked = FUSED ? 1 : a.dcol_chunked;
+  const unsigned tiles = (unsigned)(a.B * (a.H / 8) * (a.W / 16));
   const int ncu = ctdet_device_cu_count();    // one workgroup per CU at a time: with fewer tiles, split a tile's taps
   if ((int)tiles * 3 <= ncu)
-    hipLaunchKernelGGL((dcn_col2im_window_kernel<3, T, FUSED, NM>), dim3(tiles, 3), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+    hipLaunchKernelGGL((dcn_col2im_window_kernel<3, T, FUSED, NM>), dim3(tiles, 3), dim3(512), 0, s, dcol, x, a.x_stride, a.om, a.om_stride,
+                       a.dx, a.dom, a.dom_stride, dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, chunked, fz);
   else if ((int)tiles * 2 <= ncu)
-    hipLaunchKernelGGL((dcn_col2im_window_kernel<5, T, FUSED, NM>), dim3(tiles, 2), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+    hipLaunchKernelGGL((dcn_col2im_window_kernel<5, T, FUSED, NM>), dim3(tiles, 2), dim3(512), 0, s, dcol, x, a.x_stride, a.om, a.om_stride,
+                       a.dx, a.dom, a.dom_stride, dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, chunked, fz);
   else
-    hipLaunchKernelGGL((dcn_col2im_window_kernel<9, T, FUSED, NM>), dim3(tiles), dim3(512), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, fz);
+    hipLaunchKernelGGL((dcn_col2im_window_kernel<9, T, FUSED, NM>), dim3(tiles), dim3(512), 0, s, dcol, x, a.x_stride, a.om, a.om_stride,
+                       a.dx, a.dom, a.dom_stride, dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, chunked, fz);
 }
 template <typename T, bool FUSED = false>
-static void launch_col2im_window(const T* dcol, const T* x, int x_stride, const float* om, int om_stride, float* dx, void* dom,
-                                 int dom_stride, int dom_f16, int B, int H, int W, int Cin, int mask_is_prob, int chunked,
-                                 hipStream_t s, const FusedDcol fz = FusedDcol()) {
-  if (mask_is_prob == DCN_MASK_NONE)
-    launch_col2im_window_t<T, FUSED, true>(dcol, x, x_stride, om, om_stride, dx, dom, dom_stride, dom_f16, B, H, W, Cin, mask_is_prob,
-                                           chunked, s, fz);
-  else
-    launch_col2im_window_t<T, FUSED, false>(dcol, x, x_stride, om, om_stride, dx, dom, dom_stride, dom_f16, B, H, W, Cin, mask_is_prob,
-                                            chunked, s, fz);
+static void launch_col2im_window(const DcnBwdArgs& a, hipStream_t s, const FusedDcol fz = FusedDcol()) {
+  if (a.mask_mode == DCN_MASK_NONE) launch_col2im_window_t<T, FUSED, true>(a, s, fz);
+  else launch_col2im_window_t<T, FUSED, false>(a, s, fz);
 }
 
-// d(columns) GEMM + scatter in one kernel (f16x3 training mode): dy f32 [M][dy_stride] with K channels (multiple of 32; channels
-// beyond the layer's couts zero), wpk / wscale from ctdet_pack_weights_x3 (layout 5, transposed 3).  0 if launched, 1 if the
-// shape does not qualify (the caller then produces d(columns) and calls ctdet_dcn_col2im_coord).
-int launch_dcn_col2im_fused(const float* dy, int dy_stride, int K, const void* wpk, const float* wscale, const float* x, int x_stride,
-                            const float* om, int om_stride, float* dx, float* dom, int dom_stride, int B, int H, int W, int Cin,
-                            int mask_is_prob, hipStream_t s) {
-  CTDET_CHECK(dom_stride >= dcn_om_channels(mask_is_prob) && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
-  if ((long)B * H * W == 0) return 0;
-  if (!(H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && x_stride % 4 == 0 && K % 32 == 0 && K > 0 && dy_stride >= K && dy_stride % 4 == 0 &&
-        ((((size_t)x | (size_t)dy | (size_t)wpk | (size_t)wscale)) & 15) == 0) || (ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
+// d(columns) GEMM + scatter in one kernel (f16x3 training mode; DcnBwdArgs says what dy, wpk and wscale hold)
+int launch_dcn_col2im_fused(const DcnBwdArgs& a, hipStream_t s) {
+  CTDET_CHECK(a.dom_stride >= dcn_om_channels(a.mask_mode) && a.dom_stride <= 64, "dcn_col2im: dom_stride=%d", a.dom_stride);
+  if ((long)a.B * a.H * a.W == 0) return 0;
+  if (!(a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 4 == 0 && a.K % 32 == 0 && a.K > 0 && a.dy_stride >= a.K &&
+        a.dy_stride % 4 == 0 && ((((size_t)a.x | (size_t)a.dy | (size_t)a.wpk | (size_t)a.wscale)) & 15) == 0) ||
+      (ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
     return 1;
   FusedDcol fz;
-  fz.dy = dy; fz.dy_stride = dy_stride; fz.K = K; fz.wpk = (const f16*)wpk; fz.wscale = wscale;
-  launch_col2im_window<float, true>(nullptr, x, x_stride, om, om_stride, dx, (void*)dom, dom_stride, 0, B, H, W, Cin, mask_is_prob, 1, s, fz);
+  fz.dy = a.dy; fz.dy_stride = a.dy_stride; fz.K = a.K; fz.wpk = (const f16*)a.wpk; fz.wscale = a.wscale;
+  launch_col2im_window<float, true>(a, s, fz);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_dcn_col2im_coord(const f16* dcol, const f16* x, int x_stride, const float* om, int om_stride, float* dx,
-                            void* dom, int dom_stride, int dom_f16, int B, int H, int W, int Cin, int mask_is_prob, int chunked,
-                            hipStream_t s) {
-  CTDET_CHECK(dom_stride >= dcn_om_channels(mask_is_prob) && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
-  CTDET_CHECK(!chunked || Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", Cin);
-  CTDET_CHECK(Cin % 8 == 0, "dcn_col2im: Cin=%d must be a multiple of 8", Cin);
-  const long nwork = (long)B * H * W * 9;
+static int dcn_col2im_coord_f16(const DcnBwdArgs& a, hipStream_t s) {
+  const f16 *dcol = (const f16*)a.dcol, *x = (const f16*)a.x;
+  const int dom_f16 = a.dom_dtype == CTDET_F16;
+  CTDET_CHECK(a.dom_stride >= dcn_om_channels(a.mask_mode) && a.dom_stride <= 64, "dcn_col2im: dom_stride=%d", a.dom_stride);
+  CTDET_CHECK(!a.dcol_chunked || a.Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", a.Cin);
+  CTDET_CHECK(a.Cin % 8 == 0, "dcn_col2im: Cin=%d must be a multiple of 8", a.Cin);
+  const long nwork = (long)a.B * a.H * a.W * 9;
   if (nwork == 0) return 0;
-  if (H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && x_stride % 8 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW)) {
-    launch_col2im_window<f16>(dcol, x, x_stride, om, om_stride, dx, dom, dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked, s);
+  if (a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 8 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW)) {
+    launch_col2im_window<f16>(a, s);
     CTDET_LAUNCH_CHECK();
     return 0;
   }
   long nb = (nwork + 3) / 4;
   if (nb > 256 * 32) nb = 256 * 32;
-  if (mask_is_prob == DCN_MASK_NONE)
-    hipLaunchKernelGGL(dcn_col2im_coord_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked);
-  else
-    hipLaunchKernelGGL(dcn_col2im_coord_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx, dom,
-                       dom_stride, dom_f16, B, H, W, Cin, mask_is_prob, chunked);
+  const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_col2im_coord_kernel<true> : dcn_col2im_coord_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, a.x_stride, a.om, a.om_stride, a.dx, a.dom, a.dom_stride,
+                     dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, a.dcol_chunked);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -2541,48 +2473,54 @@ int launch_conv_wgrad_f32(const WgradArgs& h, hipStream_t s) {
   return 0;
 }
 
-int launch_dcn_cols_f32(const float* x, int x_stride, const float* om, int om_stride, float* col, int B, int H, int W, int Cin,
-                        int mask_is_prob, hipStream_t s) {
-  CTDET_CHECK(om_stride >= dcn_om_channels(mask_is_prob) && Cin % 4 == 0 && Cin >= 16 && Cin <= 1024 && x_stride % 4 == 0 && ((((size_t)x | (size_t)col)) & 15) == 0,
-              "dcn_cols(f32): Cin=%d (16..1024) / x_stride=%d must be multiples of 4, tensors 16-byte aligned", Cin, x_stride);
-  CTDET_CHECK((long)B * H * W * x_stride < (1L << 31), "dcn_cols(f32): input too large for 32-bit element offsets");
-  const long npairs = (long)B * H * W * 9;
+static int dcn_cols_f32(const DcnBwdArgs& a, hipStream_t s) {
+  const float* x = (const float*)a.x;
+  float* col = (float*)a.col;
+  CTDET_CHECK(a.om_stride >= dcn_om_channels(a.mask_mode) && a.Cin % 4 == 0 && a.Cin >= 16 && a.Cin <= 1024 && a.x_stride % 4 == 0 &&
+                  ((((size_t)x | (size_t)col)) & 15) == 0,
+              "dcn_cols(f32): Cin=%d (16..1024) / x_stride=%d must be multiples of 4, tensors 16-byte aligned", a.Cin, a.x_stride);
+  CTDET_CHECK((long)a.B * a.H * a.W * a.x_stride < (1L << 31), "dcn_cols(f32): input too large for 32-bit element offsets");
+  const long npairs = (long)a.B * a.H * a.W * 9;
   if (npairs == 0) return 0;
-  const int PP = 256 / (Cin / 4);
+  const int PP = 256 / (a.Cin / 4);
   const long per_block = (long)PP * COLS_PASSES;
-  if (mask_is_prob == DCN_MASK_NONE)
-    hipLaunchKernelGGL(dcn_cols_f32_kernel<true>, dim3((unsigned)((npairs + per_block - 1) / per_block)), dim3(256), 0, s, x, x_stride, om,
-                       om_stride, col, B, H, W, Cin, mask_is_prob);
-  else
-    hipLaunchKernelGGL(dcn_cols_f32_kernel<false>, dim3((unsigned)((npairs + per_block - 1) / per_block)), dim3(256), 0, s, x, x_stride, om,
-                       om_stride, col, B, H, W, Cin, mask_is_prob);
+  const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_cols_f32_kernel<true> : dcn_cols_f32_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((npairs + per_block - 1) / per_block)), dim3(256), 0, s, x, a.x_stride, a.om, a.om_stride,
+                     col, a.B, a.H, a.W, a.Cin, a.mask_mode);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 // window = 1 (the f16x3 training mode): the LDS-window scatter with fixed-point accumulation where the shape allows;
 // window = 0 (the f32 mode): the generic kernel, plain f32 atomics
-int launch_dcn_col2im_coord_f32(const float* dcol, const float* x, int x_stride, const float* om, int om_stride, float* dx,
-                                float* dom, int dom_stride, int B, int H, int W, int Cin, int mask_is_prob, int chunked, int window,
-                                hipStream_t s) {
-  CTDET_CHECK(dom_stride >= dcn_om_channels(mask_is_prob) && dom_stride <= 64, "dcn_col2im: dom_stride=%d", dom_stride);
-  const long nwork = (long)B * H * W * 9;
+static int dcn_col2im_coord_f32(const DcnBwdArgs& a, int window, hipStream_t s) {
+  const float *dcol = (const float*)a.dcol, *x = (const float*)a.x;
+  CTDET_CHECK(a.dom_stride >= dcn_om_channels(a.mask_mode) && a.dom_stride <= 64, "dcn_col2im: dom_stride=%d", a.dom_stride);
+  const long nwork = (long)a.B * a.H * a.W * 9;
   if (nwork == 0) return 0;
-  if (window && H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && x_stride % 4 == 0 && ((((size_t)x | (size_t)dcol)) & 15) == 0 &&
+  if (window && a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 4 == 0 && ((((size_t)x | (size_t)dcol)) & 15) == 0 &&
       !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW)) {
-    launch_col2im_window<float>(dcol, x, x_stride, om, om_stride, dx, (void*)dom, dom_stride, 0, B, H, W, Cin, mask_is_prob, chunked, s);
+    launch_col2im_window<float>(a, s);
     CTDET_LAUNCH_CHECK();
     return 0;
   }
-  CTDET_CHECK(!chunked || Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", Cin);
+  CTDET_CHECK(!a.dcol_chunked || a.Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", a.Cin);
   long nb = (nwork + 3) / 4;
   if (nb > 256 * 32) nb = 256 * 32;
-  if (mask_is_prob == DCN_MASK_NONE)
-    hipLaunchKernelGGL(dcn_col2im_coord_f32_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx,
-                       dom, dom_stride, B, H, W, Cin, mask_is_prob, chunked);
-  else
-    hipLaunchKernelGGL(dcn_col2im_coord_f32_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, x_stride, om, om_stride, dx,
-                       dom, dom_stride, B, H, W, Cin, mask_is_prob, chunked);
+  const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_col2im_coord_f32_kernel<true> : dcn_col2im_coord_f32_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, a.x_stride, a.om, a.om_stride, a.dx, (float*)a.dom,
+                     a.dom_stride, a.B, a.H, a.W, a.Cin, a.mask_mode, a.dcol_chunked);
   CTDET_LAUNCH_CHECK();
   return 0;
+}
+
+int launch_dcn_cols(const DcnBwdArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F16) return dcn_cols_f16(a, s);
+  if (a.dtype == CTDET_F32) return dcn_cols_f32(a, s);
+  CTDET_CHECK(false, "dcn_cols: bad dtype %d", a.dtype);
+}
+int launch_dcn_col2im_coord(const DcnBwdArgs& a, hipStream_t s) {
+  if (a.dtype == CTDET_F16) return dcn_col2im_coord_f16(a, s);
+  if (a.dtype == CTDET_F32 || a.dtype == CTDET_F16X3) return dcn_col2im_coord_f32(a, a.dtype == CTDET_F16X3, s);
+  CTDET_CHECK(false, "dcn_col2im_coord: bad dtype %d", a.dtype);
 }

@@ -164,6 +164,51 @@ def test_library_exports_every_declared_symbol():
     assert b"null" in l.ctdet_last_error()
 
 
+# Every entry point that takes a tensor dtype, with a tiny valid call: P = a non-null, 16-byte aligned dummy pointer, DT = where
+# the dtype goes.  (name, the op's name in the error message, arguments)
+P, DT = 0x1000, "dtype"
+_DTYPE_CALLS = [
+    ("ctdet_bn_train_fwd", b"bn_train_fwd", (P, 8, None, 0, P, 8, 4, 8, P, P, 1e-5, 0.1, P, P, P, P, P, P, P, 1, DT, None)),
+    ("ctdet_bn_train_bwd", b"bn_train_bwd", (P, 8, P, 8, P, 8, P, P, P, 4, 8, 1, P, 8, None, 0, P, P, 1.0, P, DT, None)),
+    ("ctdet_bn_local_stats", b"bn_local_stats", (P, 8, 4, 8, 0, 1, P, P, DT, None)),
+    ("ctdet_bn_sync_fwd", b"bn_sync_fwd", (P, 8, None, 0, P, 8, 4, 8, P, 1, P, P, 1e-5, 0.1, P, P, P, P, P, P, 1, DT, None)),
+    ("ctdet_bn_local_grad_sums", b"bn_local_grad_sums", (P, 8, P, 8, P, 8, P, P, 4, 8, 1, 0, 1, P, P, P, 1.0, P, DT, None)),
+    ("ctdet_bn_sync_bwd", b"bn_sync_bwd", (P, 8, P, 8, P, 8, P, P, P, P, P, 1, 4, 8, 1, P, 8, None, 0, DT, None)),
+    ("ctdet_maxpool2x2_bwd", b"maxpool2x2_bwd", (P, 8, P, 8, P, 8, 1, 2, 2, 8, DT, None)),
+    ("ctdet_maxpool3x3s2_bwd", b"maxpool3x3s2_bwd", (P, 8, P, 8, P, 8, DT, 1, 4, 4, 8, 0, None)),
+    ("ctdet_dwconvT_bwd", b"dwconvT_bwd", (P, 8, P, 8, P, P, 8, P, 1, 2, 2, 8, 2, DT, None)),
+    ("ctdet_dcn_cols", b"dcn_cols", (P, 16, P, 27, P, 1, 2, 2, 16, 0, DT, None)),
+    ("ctdet_dcn_col2im_coord", b"dcn_col2im_coord", (P, P, 16, P, 27, P, P, 27, 1, 1, 2, 2, 16, 0, 0, DT, None)),
+    ("ctdet_depth_to_space2", b"depth_to_space2", (P, 32, P, 8, 1, 2, 2, 8, 2, 2, DT, None)),
+    ("ctdet_ese_dot", b"ese_dot", (P, 8, P, 8, DT, 1, 4, 8, P, None)),
+    ("ctdet_ese_bwd", b"ese_bwd", (P, 8, P, P, P, 8, DT, 1, 4, 8, None)),
+    ("ctdet_maxpool2x2", b"maxpool2x2", (P, P, DT, 1, 2, 2, 8, 8, 8, None)),
+    ("ctdet_maxpool3x3s2", b"maxpool3x3s2", (P, P, DT, 1, 4, 4, 8, 8, 8, None)),
+    ("ctdet_maxpool3x3s2_ceil", b"maxpool3x3s2", (P, P, DT, 1, 4, 4, 8, 8, 8, None)),
+    ("ctdet_global_avgpool", b"global_avgpool", (P, DT, 1, 4, 8, 8, P, None)),
+    ("ctdet_ese_scale", b"ese_scale", (P, 8, P, None, 0, P, 8, DT, 1, 4, 8, None)),
+    ("ctdet_dwconvT_add", b"dwconvT", (P, P, None, P, DT, 1, 2, 2, 8, 2, 8, 0, 8, None)),
+    ("ctdet_dwconv3x3_fwd", b"dwconv3x3", (P, 8, P, P, 8, 1, 2, 2, 8, 1, 0, DT, None)),
+    ("ctdet_dwconv3x3_wgrad", b"dwconv3x3", (P, 8, P, 8, P, P, 1.0, 0, 1, 2, 2, 8, 1, DT, None)),
+]
+
+
+# Without a GPU only: the calls carry dummy pointers, so a regression (a dtype that runs as f16 again) must show as -5 "no
+# ROCm-capable device" from the attempted launch here, never as a kernel over those pointers on a device.
+@pytest.mark.skipif(torch.cuda.is_available(), reason="dummy pointers: must not reach a device")
+@pytest.mark.parametrize("name,op,args", _DTYPE_CALLS, ids=[c[0] for c in _DTYPE_CALLS])
+def test_unsupported_tensor_dtype_is_rejected_before_any_launch(name, op, args):
+    from detectron2_centernet_amd import _lib
+
+    l = _lib.lib()
+    assert len(args) == len(_lib.SIGNATURES[name][1]), name
+    for dtype in (2, 7):      # CTDET_DT_U8, and a value outside the enum
+        rc = getattr(l, name)(*[dtype if a is DT else a for a in args])
+        err = l.ctdet_last_error()
+        assert rc == -22, (name, dtype, rc, err)
+        assert op in err and b"dtype %d" % dtype in err, (name, dtype, err)
+
+
 def test_ops_refuse_cpu_tensors():
     import detectron2_centernet_amd.ops as ops
 
