@@ -37,8 +37,9 @@ def nchw(t):
 
 
 def test_conv_f32_random_shapes(ops, dev, comp):
-    """every tile of the f32 MFMA kernel (16..128 couts, 128/256-pixel tiles), Cin below / not dividing the 16-k step,
-    strides, dilation, ragged maps, residual; Cin % 4 != 0 takes the scalar kernel"""
+    """the 128-pixel tiles of the f32 MFMA kernels (32..128 couts) and the 256 x 16 one, Cin below / not dividing the 16-k step,
+    strides, dilation, ragged maps, residual; Cin % 4 != 0 takes the scalar kernel.  (The 256-pixel tiles of 32, 64 and 128 couts
+    start at 512 tiles: tests/conv_tile_cases.py has a row for each.)"""
     rng = np.random.RandomState(2026)
     for it in range(40):
         k = int(rng.choice([1, 3, 3, 7]))
@@ -49,7 +50,7 @@ def test_conv_f32_random_shapes(ops, dev, comp):
         B = int(rng.randint(1, 4))
         H, W = int(rng.randint(5, 45)), int(rng.randint(5, 45))
         if it % 5 == 0:
-            B, H, W = 5, 56, 64     # enough pixel tiles for the 256-pixel variants
+            B, H, W = 5, 56, 64     # 70 pixel tiles x at most 2 cout tiles: a larger grid of the same 128-pixel tiles
         use_res, relu = bool(rng.rand() < 0.4), bool(rng.rand() < 0.6)
         pad = dil * (k // 2)
         g = torch.Generator().manual_seed(3000 + it)

@@ -45,7 +45,9 @@ CONV_CASES = [
     (1, 16, 16, 64, 768, 3, 1, 1, False, True),
     (1, 16, 16, 256, 80, 1, 1, 0, False, False),
     (1, 10, 10, 64, 27, 3, 1, 1, False, False),
-    (5, 40, 40, 64, 64, 3, 1, 1, False, True),   # > 512 tiles -> 256-pixel tile variant
+    # 32 pixel tiles x 1 cout tile: still the 128-pixel tiles of the uniform-K kernels (the 256-pixel ones start at 512 tiles;
+    # tests/conv_tile_cases.py reaches each of them)
+    (5, 40, 40, 64, 64, 3, 1, 1, False, True),
     (4, 64, 64, 128, 128, 3, 1, 1, True, True),
     # 16-pixel-wide maps (DLA-34's 512-channel level at 512^2 input)
     (4, 16, 16, 128, 128, 3, 1, 1, True, True),
@@ -87,7 +89,9 @@ def test_conv2d(ops, dev, case, mode):
 
 def test_conv2d_random_shapes(ops, dev):
     """seeded sweep over shapes the fixed cases do not hit: every dispatch branch (halo / uniform-K / generic DMA / small-channel
-    kernels, 128- and 256-pixel tiles, ragged maps, padded couts) must agree with torch"""
+    kernels, ragged maps, padded couts) must agree with torch.  At most 19 pixel tiles x 5 cout tiles: the 128-pixel tiles and
+    the 256 x 16 one (always 256 pixels); the 256-pixel tiles of 32, 64 and 128 couts need 512 tiles and are compared with a
+    reference by tests/conv_tile_cases.py / test_conv_tiles_gpu.py"""
     rng = np.random.RandomState(20261004)
     for it in range(48):
         k = int(rng.choice([1, 3, 3]))
