@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include <type_traits>
+#include <utility>
 // slot permutation for 64-byte LDS rows read as 16-row fragments by ds_read_b128:
 // rows r and r+4 share banks, so the 4 rows {r, r+4, r+8, r+12} get distinct slot XORs.
 __device__ __forceinline__ int swz(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
@@ -156,6 +157,182 @@ __device__ __forceinline__ void epilogue_tiles(const ConvArgs& a, int m, int cba
         *(f32x4*)(yp + 4) = v1;
       }
     }
+  }
+}
+
+template <int... I, typename F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): the index is a constant inside f
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>{}, f); }
+
+// Wave-level epilogue: scale / bias / residual / activation + store of ALL accumulator tiles a lane holds, acc[p][c] for the
+// output pixels m[p] (GUARD: m[p] < 0 = no such pixel, nothing is stored) and the wave's first cout cbase.  Same arithmetic,
+// element for element, as epilogue_tiles per pixel (acc * scale, + bias, + residual, activation, in this order, every step
+// rounded on its own: contraction is off here, as the compiler could never contract across epilogue_tiles' null tests), but
+// the memory operations are batched.  epilogue_tiles issues, per (pixel tile, cout-tile pair) group, scale loads - wait -
+// bias loads - wait - residual loads - wait - stores, each wait also waiting for the previous group's stores (vmcnt counts
+// them): 2-3 exposed round trips per group, 8-16 groups per lane.  Here the groups go in batches of NB (epilogue_batch below):
+//   (a) every load of the batch is issued (scale, bias and the residual pieces of its NB groups),
+//   (b) the waits count down in issue order: nothing but the batch's own loads is waited for more than once,
+//   (c) the arithmetic of the batch, then all its stores back to back.
+// The null tests of scale / bias / residual, the activation switch and the layout test are made once per batch for all its
+// groups, not per group.  NB < all: kernels whose registers leave no room for a whole tile of residual (8 VGPRs per group
+// in flight: 128 accumulators per lane, or an occupancy of 3-4 waves to keep).
+// Groups are numbered g = h * TP + p (h = cout-tile pair, p = pixel tile); NB divides TP or is a multiple of it.
+// Aliasing: res may be y itself (same address, same stride: the input gradient of the DCNv2 offset conv accumulates into
+// dx that way, ops_train.py).  A lane reads exactly the residual elements of the positions it stores, and reads those of a batch before it
+// stores any position of that batch or a later one, so in-place use stays correct; any other overlap of res and y was never
+// supported and no caller has one (the residual of a block or Root is its input or projection, a tensor of its own).
+// Ragged cases (unaligned / odd strides, a cout-tile pair beyond Cout, odd TC) take epilogue_tiles for the whole wave.
+// Groups per batch.  8 VGPRs per group in flight (the residual) on top of the accumulators and 16 of scale / bias: a lane
+// with 128 accumulators takes 2 groups at a time, everything else the whole tile.  0 = the per-pixel epilogue_tiles.
+template <int TP, int TC>
+constexpr int epilogue_batch() { return TP * TC >= 32 ? 2 : TP * (TC / 2); }
+// the tiled kernels (BP pixels per workgroup): their 128-pixel forms run at 3-4 waves per SIMD on 128 VGPRs or fewer and keep
+// that with 2 groups; ACC_AGPR (the generic kernels: accumulators in AGPRs, copied out batch by batch, which costs a batch
+// twice): 2 groups, and the 128-pixel forms stay per pixel -- nothing batched fits under their 4 waves
+template <int BP, int TP, int TC, bool ACC_AGPR = false>
+constexpr int epilogue_batch_tiled() {
+  constexpr int whole = TP * (TC / 2);
+  if (ACC_AGPR) return BP == 128 ? 0 : (whole < 2 ? whole : 2);
+  if (TP * TC >= 32 || (BP == 128 && TP * TC >= 16)) return 2;
+  return whole < 8 ? whole : 8;
+}
+
+template <typename TOut, int TP, int TC, bool GUARD = false, int NB = epilogue_batch<TP, TC>()>
+__device__ __forceinline__ void epilogue_wave(const ConvArgs& a, const int (&m)[TP], int cbase, int q,
+                                              const f32x4 (&acc)[TP][TC]) {
+  constexpr int VEC = 16 / sizeof(TOut);  // elements per 16-byte store
+  bool batched = false;
+  if constexpr (TC % 2 == 0 && NB > 0)
+    batched = (a.out_stride % VEC) == 0 && (((size_t)a.y) & 15) == 0 &&
+              (!a.res || ((a.res_stride % VEC) == 0 && (((size_t)a.res) & 15) == 0)) && cbase + 16 * TC <= a.Cout;
+  if (NB == 0 || !batched) {
+#pragma unroll
+    for (int p = 0; p < TP; ++p)
+      if (!GUARD || m[p] >= 0) epilogue_tiles<TOut, TC>(a, m[p], cbase, q, acc[p]);
+    return;
+  }
+  if constexpr (TC % 2 == 0 && NB > 0) {
+#pragma clang fp contract(off)
+    constexpr int NG = TP * (TC / 2), NBATCH = NG / NB;
+    constexpr int HB = NB > TP ? NB / TP : 1;          // cout-tile pairs a batch spans
+    constexpr int RV = sizeof(TOut) == 2 ? 1 : 2;      // 16-byte pieces of a group's 8 residual elements
+    static_assert(NG % NB == 0 && (NB % TP == 0 || TP % NB == 0), "batch size");
+    const bool has_s = a.scale != nullptr, has_b = a.bias != nullptr, has_r = a.res != nullptr;
+    const int cw0 = cbase + q * 8;                     // the lane's 8 couts of pair h start at cw0 + 32 h
+    f32x4 sc[HB][2], bi[HB][2], rr[NB][RV];
+    int cw = cw0, mb[TP];
+    auto issue = [&](auto kc) {
+      constexpr int k = decltype(kc)::value, h0 = k * NB / TP;
+      // the batch's addresses are formed here, behind the stores of the batch before: hoisted to the top by the scheduler, the
+      // pointers of 16 groups (and their pixels' row offsets) cost more registers than the residual in flight
+      asm volatile("" : "+v"(cw) :: "memory");
+#pragma unroll
+      for (int j = 0; j < (NB < TP ? NB : TP); ++j) {
+        const int p = (k * NB + j) % TP;
+        mb[p] = m[p];
+        asm volatile("" : "+v"(mb[p]));
+      }
+      if (has_s) {
+#pragma unroll
+        for (int hl = 0; hl < HB; ++hl) {
+          sc[hl][0] = *(const f32x4*)(a.scale + cw + (h0 + hl) * 32);
+          sc[hl][1] = *(const f32x4*)(a.scale + cw + (h0 + hl) * 32 + 4);
+        }
+      }
+      if (has_b) {
+#pragma unroll
+        for (int hl = 0; hl < HB; ++hl) {
+          bi[hl][0] = *(const f32x4*)(a.bias + cw + (h0 + hl) * 32);
+          bi[hl][1] = *(const f32x4*)(a.bias + cw + (h0 + hl) * 32 + 4);
+        }
+      }
+      if (has_r) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          constexpr int g0 = k * NB;
+          const int p = (g0 + j) % TP, h = (g0 + j) / TP;
+          const int mm = (GUARD && mb[p] < 0) ? 0 : mb[p];      // a lane without a pixel reads pixel 0's and drops it
+          const TOut* rp = (const TOut*)a.res + (long)mm * a.res_stride + cw + h * 32;
+          rr[j][0] = *(const f32x4*)rp;
+          if constexpr (RV == 2) rr[j][1] = *(const f32x4*)(rp + 4);
+        }
+      }
+    };
+    auto finish = [&](auto kc) {
+      constexpr int k = decltype(kc)::value, g0 = k * NB, h0 = g0 / TP;
+      f32x4 v[NB][2];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int p = (g0 + j) % TP, h = (g0 + j) / TP;
+        v[j][0] = acc[p][2 * h];
+        v[j][1] = acc[p][2 * h + 1];
+      }
+      if (has_s) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const int hl = (g0 + j) / TP - h0;
+          v[j][0] = v[j][0] * sc[hl][0];
+          v[j][1] = v[j][1] * sc[hl][1];
+        }
+      }
+      if (has_b) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const int hl = (g0 + j) / TP - h0;
+          v[j][0] = v[j][0] + bi[hl][0];
+          v[j][1] = v[j][1] + bi[hl][1];
+        }
+      }
+      if (has_r) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          if constexpr (sizeof(TOut) == 2) {
+            const f16x8 r = __builtin_bit_cast(f16x8, rr[j][0]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { v[j][0][i] += (float)r[i]; v[j][1][i] += (float)r[4 + i]; }
+          } else {
+            v[j][0] = v[j][0] + rr[j][0];
+            v[j][1] = v[j][1] + rr[j][RV - 1];
+          }
+        }
+      }
+      if (a.act == CTDET_ACT_RELU) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { v[j][0][i] = fmaxf(v[j][0][i], 0.f); v[j][1][i] = fmaxf(v[j][1][i], 0.f); }
+      } else if (a.act == CTDET_ACT_SIGMOID_CLAMP) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            v[j][0][i] = fminf(fmaxf(ctdet_sigmoid_exact(v[j][0][i]), a.clamp_lo), a.clamp_hi);
+            v[j][1][i] = fminf(fmaxf(ctdet_sigmoid_exact(v[j][1][i]), a.clamp_lo), a.clamp_hi);
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int p = (g0 + j) % TP, h = (g0 + j) / TP;
+        if (GUARD && mb[p] < 0) continue;
+        TOut* yp = (TOut*)a.y + (long)mb[p] * a.out_stride + cw + h * 32;
+        if constexpr (sizeof(TOut) == 2) {
+          f16x8 o;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { o[i] = (f16)v[j][0][i]; o[4 + i] = (f16)v[j][1][i]; }
+          *(f16x8*)yp = o;
+        } else {
+          *(f32x4*)yp = v[j][0];
+          *(f32x4*)(yp + 4) = v[j][1];
+        }
+      }
+    };
+    static_for<NBATCH>([&](auto kc) {
+      issue(kc);
+      finish(kc);
+    });
   }
 }
 

@@ -169,12 +169,13 @@ __global__ void __launch_bounds__(256) conv_f32_mfma_kernel(const ConvArgs a) {
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int m = m0 + wp * 16 * TP + 16 * p + fr;
-    if (m >= a.M) continue;
-    epilogue_tiles<float, TC>(a, m, cb, q, acc[p]);
+    mo[p] = m < a.M ? m : -1;
   }
+  epilogue_wave<float, TP, TC, true, epilogue_batch_tiled<BP, TP, TC, true>()>(a, mo, cb, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -329,12 +330,13 @@ __global__ void __launch_bounds__(256, 2) conv_f32_uk_kernel(const ConvArgs a) {
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int m = m0 + wp * 16 * TP + 16 * p + fr;
-    if (m >= a.M) continue;
-    epilogue_tiles<float, TC>(a, m, cb, q, acc[p]);
+    mo[p] = m < a.M ? m : -1;
   }
+  epilogue_wave<float, TP, TC, true, epilogue_batch_tiled<BP, TP, TC>()>(a, mo, cb, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -484,12 +486,13 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_mfma_kernel(const ConvArgs a) 
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int m = m0 + wp * 16 * TP + 16 * p + fr;
-    if (m >= a.M) continue;
-    epilogue_tiles<float, TC>(a, m, cb, q, acc[p]);
+    mo[p] = m < a.M ? m : -1;
   }
+  epilogue_wave<float, TP, TC, true, epilogue_batch_tiled<BP, TP, TC>()>(a, mo, cb, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -728,11 +731,12 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
     tap(s + 2, chunk, std::integral_constant<int, 8>{});
   }
 
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
-    const int m = (b * a.H + ty0 + prow) * a.W + tx0 + 8 * p + pcol;
-    epilogue_tiles<float, TC>(a, m, n0, q, acc[p]);
+    mo[p] = (b * a.H + ty0 + prow) * a.W + tx0 + 8 * p + pcol;
   }
+  epilogue_wave<float, TP, TC>(a, mo, n0, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1208,11 +1212,12 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
     tap(s + 2, chunk, std::integral_constant<int, 8>{});
   }
 
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
-    const int m = (b * a.H + ty0 + prow) * a.W + tx0 + (TP == 2 ? 8 * p : 0) + pcol;
-    epilogue_tiles<float, TC>(a, m, n0, q, acc[p]);
+    mo[p] = (b * a.H + ty0 + prow) * a.W + tx0 + (TP == 2 ? 8 * p : 0) + pcol;
   }
+  epilogue_wave<float, TP, TC>(a, mo, n0, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1348,8 +1353,8 @@ __global__ void __launch_bounds__(256) conv_f32_win_kernel(const ConvArgs a) {
         }
       }
       const int m = (b * a.Ho + ty0 + wave * RW + rr) * a.Wo + tx0 + tc * 16 + fr;
-      epilogue_tiles<float, TC>(a, m, 0, q, acc[0]);
-      epilogue_tiles<float, TC>(a, m + 16, 0, q, acc[1]);
+      const int mo[2] = {m, m + 16};
+      epilogue_wave<float, 2, TC>(a, mo, 0, q, acc);
     }
   }
 }

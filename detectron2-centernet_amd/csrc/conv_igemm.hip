@@ -171,12 +171,13 @@ __global__ void __launch_bounds__(256) conv_igemm_dma_kernel(const ConvArgs a) {
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int m = m0 + wp * 16 * TP + 16 * p + fr;
-    if (m >= a.M) continue;
-    epilogue_tiles<TOut, TC>(a, m, cb, q, acc[p]);
+    mo[p] = m < a.M ? m : -1;
   }
+  epilogue_wave<TOut, TP, TC, true, epilogue_batch_tiled<BP, TP, TC, true>()>(a, mo, cb, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -336,12 +337,13 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_uk_kernel(const ConvArgs a)
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int m = m0 + wp * 16 * TP + 16 * p + fr;
-    if (m >= a.M) continue;
-    epilogue_tiles<TOut, TC>(a, m, cb, q, acc[p]);
+    mo[p] = m < a.M ? m : -1;
   }
+  epilogue_wave<TOut, TP, TC, true, epilogue_batch_tiled<BP, TP, TC>()>(a, mo, cb, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -522,12 +524,13 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_kernel(const ConvArgs a) 
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int y = ty0 + row0 + (p >> 1), x = tx0 + 16 * (p & 1) + l15;
-    const int m = (b * a.H + y) * a.W + x;
-    epilogue_tiles<TOut, TC>(a, m, cb, q, acc[p]);
+    mo[p] = (b * a.H + y) * a.W + x;
   }
+  epilogue_wave<TOut, TP, TC>(a, mo, cb, q, acc);
 }
 
 template <int BC, int WP, int WC_, typename TOut, bool SP = false>
@@ -817,12 +820,13 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int y = ty0 + row0 + (p >> 1), x = tx0 + 16 * (p & 1) + l15;
-    const int m = (b * a.H + y) * a.W + x;
-    epilogue_tiles<float, TC>(a, m, cb, q, acc[p]);
+    mo[p] = (b * a.H + y) * a.W + x;
   }
+  epilogue_wave<float, TP, TC>(a, mo, cb, q, acc);
 }
 
 // LDS bytes of pair2_kloop<BC, ...>: two halo buffers and a 3-stage {X, Y} weight ring
@@ -1106,12 +1110,13 @@ __global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kerne
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row0 = (wave / WC_) * ROWS_W, l15 = lane & 15, q = lane >> 4;
   const int cb = n0 + (wave % WC_) * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int y = ty0 + row0 + p / EN, x = tx0 + 16 * (p % EN) + l15;
-    const int m = (b * a.H + y) * a.W + x;
-    epilogue_tiles<float, TC>(a, m, cb, q, acc[p]);
+    mo[p] = (b * a.H + y) * a.W + x;
   }
+  epilogue_wave<float, TP, TC>(a, mo, cb, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1343,12 +1348,13 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
+  int mo[TP];
 #pragma unroll
   for (int p = 0; p < TP; ++p) {
     const int y = ty0 + row0 + p / EN, x = tx0 + 16 * (p % EN) + l15;
-    const int m = (b * a.H + y) * a.W + x;
-    epilogue_tiles<TOut, TC>(a, m, cb, q, acc[p]);
+    mo[p] = (b * a.H + y) * a.W + x;
   }
+  epilogue_wave<TOut, TP, TC>(a, mo, cb, q, acc);
 }
 
 template <int BC, int WP, int WC_>
@@ -1725,8 +1731,21 @@ __global__ void __launch_bounds__(256, 2) head_fused_x3_kernel(const HeadArgs a)
         lf[p][hb] = lo;
       }
     }
-    // 1x1 partial over the slice, output tile ot (16 outputs): this lane gets outputs ot*16 + 4q .. +4 of pixel l15
+    // 1x1 partial over the slice, output tile ot (16 outputs): this lane gets outputs ot*16 + 4q .. +4 of pixel l15.
+    // What the tail of a tile needs from memory -- the partial sums of the slices before, and in the last slice the rows'
+    // inverse scale and bias -- is requested ahead of the tile's MFMAs, all pixel tiles at once: loaded where it is used,
+    // each load sits behind the store of the pixel tile before (yh may alias itself) and is a round trip of its own.
     for (int ot = 0; ot < ntile2; ++ot) {
+      const int c0 = ot * 16 + 4 * q;
+      const bool live = c0 < cw;
+      f32x4 prev[TP] = {}, s2 = {}, bias2 = {};
+      if (live) {
+        if (sl > 0) {
+#pragma unroll
+          for (int p = 0; p < TP; ++p) prev[p] = *(const f32x4*)(yh + mpix[p] * ystride + c0);
+        }
+        if (sl == NSL - 1) { s2 = *(const f32x4*)(b2 + rows2 + c0); bias2 = *(const f32x4*)(b2 + c0); }
+      }
       f32x4 o[TP];
 #pragma unroll
       for (int p = 0; p < TP; ++p) o[p] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1741,15 +1760,14 @@ __global__ void __launch_bounds__(256, 2) head_fused_x3_kernel(const HeadArgs a)
 #pragma unroll
         for (int p = 0; p < TP; ++p) o[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(X, lf[p][hb], o[p], 0, 0, 0);
       }
-      const int c0 = ot * 16 + 4 * q;
-      if (c0 < cw) {
+      if (live) {
 #pragma unroll
         for (int p = 0; p < TP; ++p) {
           float* yp = yh + mpix[p] * ystride + c0;
           f32x4 v = o[p];
-          if (sl > 0) v = *(const f32x4*)yp + v;
+          if (sl > 0) v = prev[p] + v;
           if (sl == NSL - 1) {
-            v = v * *(const f32x4*)(b2 + rows2 + c0) + *(const f32x4*)(b2 + c0);
+            v = v * s2 + bias2;
             if (act == CTDET_ACT_RELU) {
 #pragma unroll
               for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
@@ -3064,17 +3082,17 @@ __global__ void __launch_bounds__(256) conv_win_kernel(const ConvArgs a) {
     for (int tc = 0; tc < NT; ++tc) {
       constexpr int dummy = 0; (void)dummy;
       const int toff = (rr * STRIDE * WW + tc * 16 * STRIDE) * PB;   // compile time after unrolling
-      f32x4 acc[TC];
+      f32x4 acc[1][TC];
 #pragma unroll
-      for (int c = 0; c < TC; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int c = 0; c < TC; ++c) acc[0][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kt = 0; kt < NK; ++kt) {
         const f16x8 pf = *(const f16x8*)(win + kaddr[kt] + toff);
 #pragma unroll
-        for (int c = 0; c < TC; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kt][c], pf, acc[c], 0, 0, 0);
+        for (int c = 0; c < TC; ++c) acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kt][c], pf, acc[0][c], 0, 0, 0);
       }
-      const int m = (b * a.Ho + ty0 + wave * RW + rr) * a.Wo + tx0 + tc * 16 + fr;
-      epilogue_tiles<TOut, TC>(a, m, 0, q, acc);
+      const int mo[1] = {(b * a.Ho + ty0 + wave * RW + rr) * a.Wo + tx0 + tc * 16 + fr};
+      epilogue_wave<TOut, 1, TC>(a, mo, 0, q, acc);
     }
   }
 }
