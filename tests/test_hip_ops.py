@@ -3,6 +3,11 @@
 Tolerances: index / class / mask outputs bit-exact; f32 kernels 1e-4 relative to the oracle's f32 result
 (different summation order only); f16-MFMA kernels are fed f16-representable inputs so the only differences
 are f32 accumulation order and the final f16 rounding (2e-3 relative).
+
+Which file pins what: this one runs every kernel at ordinary shapes; tests/conv_tile_cases.py / test_conv_tiles_gpu.py hold every
+forward conv tile variant to a float64 reference at its smallest shape; tests/objective_cases.py / test_objective_gpu.py do the
+same for gaussian_targets, focal_loss, reg_l1_loss and finite_flag at their edge cases (per-class alpha, ragged and wrapping
+grids, non-square maps, stale and strided buffers).
 """
 import numpy as np
 import pytest
