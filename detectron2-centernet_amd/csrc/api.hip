@@ -208,6 +208,12 @@ int32_t ctdet_dcnv2_offset_supported(const ctdet_conv_desc* d) {
 int32_t ctdet_dcnv2_offset_fwd(const ctdet_conv_desc* d, const void* x, const void* w_off_packed, const float* b_off,
                                float* om_out, int32_t om_out_stride, const void* w_packed, const float* scale,
                                const float* bias, void* y, void* stream) {
+  return ctdet_dcnv2_offset_finite_fwd(d, x, w_off_packed, b_off, om_out, om_out_stride, w_packed, scale, bias, y, nullptr, stream);
+}
+
+int32_t ctdet_dcnv2_offset_finite_fwd(const ctdet_conv_desc* d, const void* x, const void* w_off_packed, const float* b_off,
+                                      float* om_out, int32_t om_out_stride, const void* w_packed, const float* scale,
+                                      const float* bias, void* y, int32_t* finite, void* stream) {
   ConvArgs a;
   int rc = fill_args(d, a);
   if (rc) return rc;
@@ -218,9 +224,11 @@ int32_t ctdet_dcnv2_offset_fwd(const ctdet_conv_desc* d, const void* x, const vo
   if (d->compute_dtype == CTDET_DT_F16X3) {
     CTDET_CHECK(d->out_dtype == CTDET_DT_F32 && !om_out, "dcnv2_offset(f16x3): f32 output, no om_out (inference form)");
     a.mask_is_prob = DCN_MASK_LOGIT;
+    a.finite = (int*)finite;
     return launch_dcn_offset_x3(a, (hipStream_t)stream);
   }
   CTDET_CHECK(d->compute_dtype == CTDET_DT_F16, "dcnv2_offset: f16 or f16x3");
+  CTDET_CHECK(!finite, "dcnv2_offset: the finite flag is the f16x3 form's");
   CTDET_CHECK(!om_out || (om_out_stride >= 28 && om_out_stride % 4 == 0 && ((size_t)om_out & 15) == 0),
               "dcnv2_offset: om_out needs a 16-byte aligned row of >= 28 floats (stride %d)", om_out_stride);
   a.om_out = om_out; a.om_out_stride = om_out_stride;

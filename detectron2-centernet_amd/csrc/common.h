@@ -88,6 +88,9 @@ struct ConvArgs {
   // DCNv2, f16x3 window kernel, training: the sampled columns (mask * bilinear(x), f32 [M][9*Cin], k = tap*Cin + c -- what
   // modulated_deformable_im2col produces, kernel.cu:786-868) written as a by-product of the forward pass, or null
   float* cols_out;
+  // DCNv2 with the fused offset conv, f16x3 (ctdet_dcnv2_offset_finite_fwd): int32 flag that the epilogue sets to 0 when a value
+  // it stores is inf or NaN (the caller set it to 1), or null
+  int* finite;
 };
 
 // argument block of the fused CenterNet head kernels (conv_igemm.hip): per head 3x3 conv Cin->256 + bias + ReLU, then

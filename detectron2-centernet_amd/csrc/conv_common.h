@@ -62,8 +62,19 @@ __device__ __forceinline__ void dcn_setup(const ConvArgs& a, bool row_ok, int pi
   if (h_high <= a.H - 1 && w_high <= a.W - 1) sp.off[3] = (pix_base + h_high * a.W + w_high) * a.in_stride;
 }
 
-template <typename TOut>
+// FIN epilogues (ConvArgs::finite, f32 outputs): the values a lane is about to store get the test of finite_flag_kernel
+// (pointwise.hip) -- after scale, bias and activation, and only what reaches the tensor -- and a lane that holds a bad one
+// clears the flag with an ordinary store, as that kernel does: the map needs no pass of its own
+__device__ __forceinline__ void finite_note(const ConvArgs& a, const f32x4 v0, const f32x4 v1) {
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bad |= !(fabsf(v0[j]) <= 3.402823466e38f) || !(fabsf(v1[j]) <= 3.402823466e38f);     // NaN compares false
+  if (bad) *a.finite = 0;
+}
+
+template <typename TOut, bool FIN = false>
 __device__ __forceinline__ void epilogue_store4(const ConvArgs& a, int m, int c, f32x4 v) {
+  static_assert(!FIN || sizeof(TOut) == 4, "the finite test is made on f32 outputs");
   // c is a multiple of 4; Cout is a multiple of 4 (host guarantees), so a group is all-in or all-out
   if (c >= a.Cout) return;
   if (a.scale) { const f32x4 s = *(const f32x4*)(a.scale + c); v = v * s; }
@@ -89,6 +100,7 @@ __device__ __forceinline__ void epilogue_store4(const ConvArgs& a, int m, int c,
     f16x4 o; o[0] = (f16)v[0]; o[1] = (f16)v[1]; o[2] = (f16)v[2]; o[3] = (f16)v[3];
     *(f16x4*)yp = o;
   } else {
+    if constexpr (FIN) finite_note(a, v, v);
     *(f32x4*)yp = v;
   }
 }
@@ -106,11 +118,11 @@ __device__ __forceinline__ constexpr int cout_of(int c, int q, int i) {
 
 // scale/bias/residual/activation + store of the TC accumulator tiles one lane holds for output pixel m;
 // cbase = first cout of the wave.
-template <typename TOut, int TC>
+template <typename TOut, int TC, bool FIN = false>
 __device__ __forceinline__ void epilogue_tiles(const ConvArgs& a, int m, int cbase, int q, const f32x4 (&acc)[TC]) {
   if constexpr (TC % 2 != 0) {
 #pragma unroll
-    for (int c = 0; c < TC; ++c) epilogue_store4<TOut>(a, m, cbase + cout_of<TC>(c, q, 0), acc[c]);
+    for (int c = 0; c < TC; ++c) epilogue_store4<TOut, FIN>(a, m, cbase + cout_of<TC>(c, q, 0), acc[c]);
   } else {
     constexpr int VEC = 16 / sizeof(TOut);  // elements per 16-byte store
     const bool wide = (a.out_stride % VEC) == 0 && (((size_t)a.y) & 15) == 0 &&
@@ -119,8 +131,8 @@ __device__ __forceinline__ void epilogue_tiles(const ConvArgs& a, int m, int cba
     for (int h = 0; h < TC / 2; ++h) {
       const int c0 = cbase + h * 32 + q * 8;
       if (!wide || c0 + 8 > a.Cout) {
-        epilogue_store4<TOut>(a, m, c0, acc[2 * h]);
-        epilogue_store4<TOut>(a, m, c0 + 4, acc[2 * h + 1]);
+        epilogue_store4<TOut, FIN>(a, m, c0, acc[2 * h]);
+        epilogue_store4<TOut, FIN>(a, m, c0 + 4, acc[2 * h + 1]);
         continue;
       }
       f32x4 v0 = acc[2 * h], v1 = acc[2 * h + 1];
@@ -153,6 +165,7 @@ __device__ __forceinline__ void epilogue_tiles(const ConvArgs& a, int m, int cba
         for (int j = 0; j < 4; ++j) { o[j] = (f16)v0[j]; o[4 + j] = (f16)v1[j]; }
         *(f16x8*)yp = o;
       } else {
+        if constexpr (FIN) finite_note(a, v0, v1);
         *(f32x4*)yp = v0;
         *(f32x4*)(yp + 4) = v1;
       }
@@ -200,7 +213,8 @@ constexpr int epilogue_batch_tiled() {
   return whole < 8 ? whole : 8;
 }
 
-template <typename TOut, int TP, int TC, bool GUARD = false, int NB = epilogue_batch<TP, TC>()>
+// FIN: finite_note on every value stored (the DCNv2 layer that writes the heads' input, dcn_split_window_kernel<.., FIN>)
+template <typename TOut, int TP, int TC, bool GUARD = false, int NB = epilogue_batch<TP, TC>(), bool FIN = false>
 __device__ __forceinline__ void epilogue_wave(const ConvArgs& a, const int (&m)[TP], int cbase, int q,
                                               const f32x4 (&acc)[TP][TC]) {
   constexpr int VEC = 16 / sizeof(TOut);  // elements per 16-byte store
@@ -211,7 +225,7 @@ __device__ __forceinline__ void epilogue_wave(const ConvArgs& a, const int (&m)[
   if (NB == 0 || !batched) {
 #pragma unroll
     for (int p = 0; p < TP; ++p)
-      if (!GUARD || m[p] >= 0) epilogue_tiles<TOut, TC>(a, m[p], cbase, q, acc[p]);
+      if (!GUARD || m[p] >= 0) epilogue_tiles<TOut, TC, FIN>(a, m[p], cbase, q, acc[p]);
     return;
   }
   if constexpr (TC % 2 == 0 && NB > 0) {
@@ -327,6 +341,15 @@ __device__ __forceinline__ void epilogue_wave(const ConvArgs& a, const int (&m)[
           *(f32x4*)yp = v[j][0];
           *(f32x4*)(yp + 4) = v[j][1];
         }
+      }
+      if constexpr (FIN) {                                // behind the stores: one test and at most one flag store per batch
+        static_assert(!GUARD && sizeof(TOut) == 4, "the finite test is made on f32 outputs of unguarded tiles");
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < NB; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) bad |= !(fabsf(v[j][0][i]) <= 3.402823466e38f) || !(fabsf(v[j][1][i]) <= 3.402823466e38f);
+        if (bad) *a.finite = 0;
       }
     };
     static_for<NBATCH>([&](auto kc) {

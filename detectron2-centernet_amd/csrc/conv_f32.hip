@@ -763,9 +763,13 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
 // form (its tiles alternate between the product orders X.H, Y.H, X.L and X.L, X.H, Y.H by image row), so the offsets are
 // bit-identical to the two-launch path wherever that path runs the pair kernel.  A far sample keeps its integer corner in the
 // window-code word (12 bits each: the map is at most 4094 pixels a side), since there is no offset tensor to re-read.
-template <int TP, int BC, bool COLS = false, bool NM = false, bool FUS = false>
+// FIN (FUS only): the epilogue also tests what it stores for inf / NaN and reports into *a.finite (finite_note, conv_common.h):
+// the eval step's guard on the heads' input map, which this kernel writes, without a pass over that map.  A template
+// parameter for the reason COLS is one: the other instantiations keep their code and registers.
+template <int TP, int BC, bool COLS = false, bool NM = false, bool FUS = false, bool FIN = false>
 __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_split_window_kernel(const ConvArgs a) {
   static_assert(!FUS || (TP == 2 && BC == 64 && !COLS && !NM), "the fused offset conv: inference form of the 64-cout DCNv2 tile");
+  static_assert(!FIN || FUS, "the finite test: the fused form's epilogue only");
   constexpr int TH = 8, TW = 16, BP = 128, MG = 4;
   constexpr int NT = 512 / TP;                                  // TP = 2: 4 waves of 32 pixels, TP = 1: 8 waves of 16
   static_assert(BC * 4 <= NT, "at most one weight piece per thread and tap (waves beyond BC / 16 fetch none)");
@@ -1217,7 +1221,7 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
   for (int p = 0; p < TP; ++p) {
     mo[p] = (b * a.H + ty0 + prow) * a.W + tx0 + (TP == 2 ? 8 * p : 0) + pcol;
   }
-  epilogue_wave<float, TP, TC>(a, mo, n0, q, acc);
+  epilogue_wave<float, TP, TC, false, epilogue_batch<TP, TC>(), FIN>(a, mo, n0, q, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1627,6 +1631,13 @@ int launch_dcn_offset_x3(const ConvArgs& a, hipStream_t s) {
               "operands (Cin=%d, %dx%d, Cout_pad=%d; ctdet_dcnv2_offset_supported)", a.Cin, a.H, a.W, a.Cout_pad);
   const int nbx = a.B * (a.H / 8) * (a.W / 16);
   dim3 grid(8 * ((nbx + 7) / 8));
+  if (a.finite) {                       // the layer that also answers "is y finite?" (a.finite: set to 1 by the caller)
+    CTDET_CHECK(((size_t)a.finite & 3) == 0, "dcnv2_offset(f16x3): unaligned finite flag");
+    CTDET_KERNEL("dcn_f16x3_window_kernel<8x16,64,offset conv fused,finite>");
+    hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, false, false, true, true>), grid, dim3(256), 0, s, a);
+    CTDET_LAUNCH_CHECK();
+    return 0;
+  }
   CTDET_KERNEL("dcn_f16x3_window_kernel<8x16,64,offset conv fused>");
   hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, false, false, true>), grid, dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();

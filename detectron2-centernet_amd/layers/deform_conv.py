@@ -164,9 +164,10 @@ class DCN(nn.Module):
         self.conv_offset_mask.weight.data.zero_()
         self.conv_offset_mask.bias.data.zero_()
 
-    def hip_forward(self, x, ctx, bn=None, act=ACT_NONE):
+    def hip_forward(self, x, ctx, bn=None, act=ACT_NONE, fold=None):
         """x NHWC -> act(bn(dcn(x))) NHWC; the offset/mask conv writes f32 so sampling coordinates keep full
-        precision even in f16 mode."""
+        precision even in f16 mode.  fold (ops.FiniteFold): the f16x3 fused kernel tests its output for inf / NaN into
+        fold.flag and says so in fold.folded; every other path leaves both alone."""
         p = hipnn.packed(self, "dcn", ctx.compute, self.weight, bn, self.bias, self.stride, self.padding, self.dilation,
                          cout_align=64 if ctx.compute == F16 else None)
         com = self.conv_offset_mask
@@ -175,6 +176,9 @@ class DCN(nn.Module):
             # offset conv and deformable conv in one kernel where the geometry allows (64-cout layers on tile-divisible maps)
             p_off = hipnn.packed(com, "conv", ctx.compute, com.weight, None, com.bias, com.stride[0], com.padding[0], com.dilation[0])
             if ops.dcnv2_offset_supported(x, p_off, p):
+                if fold is not None and fused_x3:
+                    fold.folded = True
+                    return ops.dcnv2_offset(x, p_off, p, act=act, finite_flag=fold.flag)
                 return ops.dcnv2_offset(x, p_off, p, act=act)
         om = hipnn.conv_module(x, com, None, ACT_NONE, ctx=ctx, out_dtype=torch.float32)
         return ops.dcnv2(x, om, p, act=act)
@@ -203,8 +207,8 @@ class DeformConvV2(nn.Module):
         self.conv = DCN(chi, cho, kernel_size=(3, 3), stride=1, padding=1, dilation=1, deformable_groups=1)
         nn.init.uniform_(self.actf[0].weight.data)
 
-    def hip_forward(self, x, ctx):
-        return self.conv.hip_forward(x, ctx, bn=self.actf[0], act=ACT_RELU)
+    def hip_forward(self, x, ctx, fold=None):
+        return self.conv.hip_forward(x, ctx, bn=self.actf[0], act=ACT_RELU, fold=fold)
 
     def forward(self, x):
         ctx = hipnn.Ctx(F16 if x.dtype == torch.float16 else F32)

@@ -98,19 +98,24 @@ class Tree(nn.Module):
                                          _bn(out_channels))
 
     def hip_forward(self, x, ctx, residual=None, children=None, bottom=None):
-        """bottom: the down-sampled input when the caller already has it (the fused base kernel emits level1's pool)"""
+        """bottom: the down-sampled input when the caller already has it (the fused base kernel emits level1's pool; a tree of
+        several levels hands its own to tree1, which pools the same x the same way)"""
         children = [] if children is None else children
         if bottom is None:
             bottom = ops.maxpool2x2(x) if self.downsample else x
-        residual = hipnn.conv_module(bottom, self.project[0], self.project[1], ACT_NONE, ctx=ctx) if self.project \
-            else bottom
+        # levels > 1: tree1 is a Tree and replaces `residual` by its own projection of the same `bottom` (dla.py:139-143 computes
+        # this one all the same); nothing reads the outer one, so it is not computed
+        dedup = ops.TREE_DEDUP and self.levels > 1
+        if not dedup:
+            residual = hipnn.conv_module(bottom, self.project[0], self.project[1], ACT_NONE, ctx=ctx) if self.project \
+                else bottom
         if self.level_root:
             children.append(bottom)
         if self.levels == 1:
             x1 = self.tree1.hip_forward(x, ctx, residual)
             x2 = self.tree2.hip_forward(x1, ctx)
             return self.root.hip_forward([x2, x1] + children, ctx)
-        x1 = self.tree1.hip_forward(x, ctx, residual)
+        x1 = self.tree1.hip_forward(x, ctx, bottom=bottom) if dedup else self.tree1.hip_forward(x, ctx, residual)
         children.append(x1)
         return self.tree2.hip_forward(x1, ctx, children=children)
 
@@ -134,7 +139,8 @@ class IDAUp(nn.Module):
             self.add_module(f"up_{i}", up)
             self.add_module(f"node_{i}", node)
 
-    def hip_forward(self, layers, startp, endp, ctx):
+    def hip_forward(self, layers, startp, endp, ctx, fold=None):
+        """fold (ops.FiniteFold): handed to the last node, the layer that writes the final map"""
         for i in range(startp + 1, endp):
             up = getattr(self, "up_" + str(i - startp))
             proj = getattr(self, "proj_" + str(i - startp))
@@ -142,7 +148,7 @@ class IDAUp(nn.Module):
             # layers[i] = up(proj(layers[i])); layers[i] = node(layers[i] + layers[i-1])   (dla.py:175-177)
             t = proj.hip_forward(layers[i], ctx)
             t = ops.dwconvT_add(t, up.weight, up.stride[0], skip=layers[i - 1])
-            layers[i] = node.hip_forward(t, ctx)
+            layers[i] = node.hip_forward(t, ctx, fold=fold if i == endp - 1 else None)
 
 
 class DLAUp(nn.Module):
@@ -287,9 +293,10 @@ class DLA34(Backbone):
     def images_fusable(self, ctx, Hp, Wp):
         return self.first_level >= 1 and self.base.base_fusable(ctx, Hp, Wp)
 
-    def hip_forward(self, x, ctx, prepadded=False, level1=None):
+    def hip_forward(self, x, ctx, prepadded=False, level1=None, fold=None):
         """x: NHWC [B,H,W,8] normalised image -> list of NHWC maps; the last one is the [B,H/4,W/4,64] head input.
-        level1 = (map, pooled map or None): start from DLA.base_level1's outputs instead of the normalised image."""
+        level1 = (map, pooled map or None): start from DLA.base_level1's outputs instead of the normalised image.
+        fold (ops.FiniteFold): goes to the layer that writes the last map."""
         if level1 is not None:   # (level1 output, its 2x2 max-pool or None)
             x = self.base.hip_forward_level1(level1[0], ctx, pooled=level1[1])
         else:
@@ -298,7 +305,7 @@ class DLA34(Backbone):
         # the reference clones these maps (dla.py:311-313) because IDAUp mutates in place; buffers here are
         # never written twice, so no copy is needed
         y = [x[i] for i in range(self.last_level - self.first_level)]
-        self.ida_up.hip_forward(y, 0, len(y), ctx)
+        self.ida_up.hip_forward(y, 0, len(y), ctx, fold=fold)
         return y
 
     def forward(self, x):

@@ -160,9 +160,10 @@ class _EvalEngine:
             self._out = (self._hm, z[0][..., :2], z[1][..., :2])
         return self._out
 
-    def _run_sparse(self, y):
+    def _run_sparse(self, y, fold=None):
         """f16x3 step whose wh / reg heads run at the decoded peaks only: dense hm head (a third of the three-head grid),
-        map-free decode, then ops.heads_sparse on the decode's inds, which also assembles the boxes."""
+        map-free decode, then ops.heads_sparse on the decode's inds, which also assembles the boxes.
+        fold (ops.FiniteFold): y's producer has already tested y into fold.flag if fold.folded says so."""
         m = self.model
         K, dr = m.topk_candidates, m.backbone.down_ratio
         self._y, self._out = y, None
@@ -172,7 +173,10 @@ class _EvalEngine:
         self.dec = (boxes, scores, classes, inds)
         # the flag covers the peaks' wh / reg (both halves under flip: the mean of a non-finite value is non-finite) and the
         # heads' input y, which is what the dense wh / reg maps used to reflect away from the peaks
-        self.finite = ops.finite_flag(self.whreg.view(self.B, K, 1, 4), y).bool()
+        maps = [self.whreg.view(self.B, K, 1, 4)]
+        if fold is None or not fold.folded:      # else the layer that wrote y tested it in its epilogue: no pass over the map
+            maps.append(y)
+        self.finite = ops.finite_flag(*maps, flag=None if fold is None else fold.flag).bool()
 
     def _run(self):
         m = self.model
@@ -182,10 +186,13 @@ class _EvalEngine:
             x = ops.preprocess(self.images, m._mean_host, m._std_host, self.Hp, self.Wp, out=self.xpad, border=self.border,
                                mirror=self._mirror)
             prepadded, level1 = self.border > 0, None
-        y = m._features(x, prepadded, level1)
+        # a step that will be sparse (decided on y's shape below) has y's producer test y for the finite flag: the flag is made
+        # -- set to 1 -- here, inside the captured part and ahead of that launch
+        fold = ops.FiniteFold(m.device) if (ops.FINITE_FOLD and m.backbone_type == "dla34" and m._sparse_heads_possible()) else None
+        y = m._features(x, prepadded, level1, fold=fold)
         self.sparse = m._sparse_heads_ok(y)
         if self.sparse:
-            return self._run_sparse(y)
+            return self._run_sparse(y, fold)
         z = m._head_outputs(y, True)
         self._out = (m._hm_view(z["hm"]), z["wh"][..., :2], z["reg"][..., :2])
         hm, wh, reg = self._out
@@ -385,10 +392,14 @@ class CenterNet(nn.Module):
         """may the eval step compute wh / reg at the decoded peaks only (ops.heads_sparse)?  f16x3 with the fused heads, heads
         exactly hm / wh / reg (2 + 2 outputs, 1x1 final convs) on a 64-channel map, and K < h*w: with K >= h*w the decode pads
         its list with non-peak pixels and nothing is saved."""
-        names = sorted(h.lower() for h in self.heads)
-        return (ops.HEADS_SPARSE and self._ctx.compute == F16X3 and names == ["hm", "reg", "wh"] and self._heads_fusable(y)
-                and y.shape[3] == 64 and self.wh[2].out_channels == 2 and self.reg[2].out_channels == 2
+        return (self._sparse_heads_possible() and self._heads_fusable(y) and y.shape[3] == 64
                 and self.topk_candidates < y.shape[1] * y.shape[2])
+
+    def _sparse_heads_possible(self):
+        """the part of _sparse_heads_ok that is known before the map exists"""
+        names = sorted(h.lower() for h in self.heads)
+        return (ops.HEADS_SPARSE and self._ctx.compute == F16X3 and names == ["hm", "reg", "wh"]
+                and self.wh[2].out_channels == 2 and self.reg[2].out_channels == 2)
 
     def _head_outputs(self, y, apply_sigmoid, only=None):
         """y NHWC [B,h,w,64] -> dict head -> f32 NHWC buffer (channels padded to a multiple of 4).  only: a subset of the heads
@@ -453,11 +464,12 @@ class CenterNet(nn.Module):
                 y = y[..., :up.out_channels]
         return y
 
-    def _features(self, x_nhwc, prepadded=False, level1=None):
-        """the NHWC map the heads read"""
+    def _features(self, x_nhwc, prepadded=False, level1=None, fold=None):
+        """the NHWC map the heads read.  fold (ops.FiniteFold): for the layer that writes that map, where it can take one
+        (DLA-34's last DCNv2 node)"""
         if self.backbone_type in ("resnet", "vovnet"):
             return self._deconv_forward(self.backbone.hip_forward(x_nhwc, self._ctx, prepadded)[self.deconv_feature])
-        return self.backbone.hip_forward(x_nhwc, self._ctx, prepadded, level1=level1)[-1]
+        return self.backbone.hip_forward(x_nhwc, self._ctx, prepadded, level1=level1, fold=fold)[-1]
 
     def _hm_view(self, hm):
         assert hm.shape[3] == self.num_classes or hm.shape[3] == ops.round_up(self.num_classes, 4)

@@ -681,11 +681,14 @@ def dcnv2_offset_supported(x, p_off, p):
     return bool(_lib.lib().ctdet_dcnv2_offset_supported(C.byref(d)))
 
 
-def dcnv2_offset(x, p_off, p, out=None, act=ACT_NONE, out_dtype=None, om_out=None):
+def dcnv2_offset(x, p_off, p, out=None, act=ACT_NONE, out_dtype=None, om_out=None, finite_flag=None):
     """act(dcn(x, conv_offset_mask(x))) in one kernel (ctdet_dcnv2_offset_fwd): p_off = the packed 3x3 offset / mask conv with
-    its bias, p = the packed deformable conv.  om_out (f16 mode only; f32 [B,H,W,>=28]) receives the offsets / mask logits if given."""
-    _require_cuda(x, out, om_out)
+    its bias, p = the packed deformable conv.  om_out (f16 mode only; f32 [B,H,W,>=28]) receives the offsets / mask logits if given.
+    finite_flag (f16x3 only): an int32 [1] device tensor holding 1; the kernel's epilogue stores 0 into it when a value it writes
+    is inf or NaN -- what `finite_flag(out, flag=finite_flag)` would find, without the pass over `out`."""
+    _require_cuda(x, out, om_out, finite_flag)
     assert dt_of(x) == p.act_dt and p.compute in (F16, F16X3) and p_off.compute == p.compute and p_off.bias is not None
+    assert finite_flag is None or (p.compute == F16X3 and finite_flag.dtype == torch.int32 and finite_flag.numel() == 1)
     if p.compute == F16X3:
         assert om_out is None, "dcnv2_offset (f16x3) keeps no offsets: the inference form"
         ops_off = _off_operands_x3(p_off)
@@ -707,10 +710,10 @@ def dcnv2_offset(x, p_off, p, out=None, act=ACT_NONE, out_dtype=None, om_out=Non
     if prof.on:
         prof.bytes -= d.B * d.Ho * d.Wo * 27 * 4      # no offset tensor is read
     for _ in range(prof.reps()):
-        rc = _lib.lib().ctdet_dcnv2_offset_fwd(C.byref(d), _ptr(x), _ptr(w_off), _ptr(b_off), _ptr(om_out),
-                                               _nhwc_stride(om_out) if om_out is not None else 0, _ptr(p.w), _ptr(p.scale),
-                                               _ptr(p.bias), _ptr(out), _stream())
-    _lib.check(rc, "ctdet_dcnv2_offset_fwd")
+        rc = _lib.lib().ctdet_dcnv2_offset_finite_fwd(C.byref(d), _ptr(x), _ptr(w_off), _ptr(b_off), _ptr(om_out),
+                                                      _nhwc_stride(om_out) if om_out is not None else 0, _ptr(p.w), _ptr(p.scale),
+                                                      _ptr(p.bias), _ptr(out), _ptr(finite_flag), _stream())
+    _lib.check(rc, "ctdet_dcnv2_offset_finite_fwd")
     prof.done()
     if p.compute == F16X3:
         _range_check(out, p, "dcnv2_offset")
@@ -940,6 +943,10 @@ def heads_fused(x, ph, clamp=(0.0, 1.0), outs=None):
     return outs
 
 
+# CTDET_NO_TREE_DEDUP=1: a DLA tree of more than one level runs its unread 1x1 projection and its second max-pool of the same
+# input again (modeling/backbone/dla.py: Tree.hip_forward); the A/B switch of their removal
+TREE_DEDUP = os.environ.get("CTDET_NO_TREE_DEDUP", "0") != "1"
+
 # CTDET_NO_SPARSE_HEADS=1: the f16x3 eval step computes the wh / reg heads densely again (the launches before heads_sparse existed)
 HEADS_SPARSE = os.environ.get("CTDET_NO_SPARSE_HEADS", "0") != "1"
 
@@ -1005,11 +1012,29 @@ def maxpool3x3s2_ceil(x, out=None):
     return out
 
 
-def finite_flag(*tensors):
+# CTDET_NO_FINITE_FOLD=1: the sparse eval step scans the heads' input map with finite_flag again instead of having the DCNv2
+# layer that writes it test its own stores (dcnv2_offset(..., finite_flag=)); the A/B switch of that fold
+FINITE_FOLD = os.environ.get("CTDET_NO_FINITE_FOLD", "0") != "1"
+
+
+class FiniteFold:
+    """The eval step's finite flag on its way down to the layer that writes the heads' input: `flag` (int32 [1], set to 1
+    here) and `folded`, which that layer sets once its kernel has taken the flag -- if no layer did (two-launch DCNv2, range
+    check, another backbone, an unsupported shape), the caller scans the map as before."""
+
+    def __init__(self, device):
+        self.flag = torch.ones(1, dtype=torch.int32, device=device)
+        self.folded = False
+
+
+def finite_flag(*tensors, flag=None):
     """int32 [1] on the device: 1 if every value of the f32 NHWC maps (channel slices of wider buffers allowed) is finite, else
-    0 -- kernels only (no torch reduction: those clear their semaphores with a memset, which a captured step must not hold)"""
+    0 -- kernels only (no torch reduction: those clear their semaphores with a memset, which a captured step must not hold).
+    flag: an existing flag to go on with (it holds 1, or the 0 an earlier test left) instead of a fresh one."""
     _require_cuda(*tensors)
-    flag = torch.ones(1, dtype=torch.int32, device=tensors[0].device)
+    if flag is None:
+        flag = torch.ones(1, dtype=torch.int32, device=tensors[0].device)
+    assert flag.dtype == torch.int32 and flag.numel() == 1 and flag.is_cuda
     for t in tensors:
         assert t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1
         B, H, W, Cc = t.shape

@@ -150,6 +150,13 @@ int32_t ctdet_dcnv2_offset_supported(const ctdet_conv_desc* d);
 int32_t ctdet_dcnv2_offset_fwd(const ctdet_conv_desc* d, const void* x, const void* w_off_packed, const float* b_off,
                                float* om_out, int32_t om_out_stride, const void* w_packed, const float* scale,
                                const float* bias, void* y, void* stream);
+/* The same call with a finite flag (CTDET_DT_F16X3 only; null: exactly ctdet_dcnv2_offset_fwd): finite is an int32 on the
+ * device that the caller set to 1 earlier on the stream.  The kernel's epilogue tests every value it stores into y -- after
+ * scale, bias and activation, the Cout channels of the tensor only -- as ctdet_finite_flag tests a map, and stores 0 into
+ * *finite when one is inf or NaN: ctdet_finite_flag(y, ..., finite) without the pass over y. */
+int32_t ctdet_dcnv2_offset_finite_fwd(const ctdet_conv_desc* d, const void* x, const void* w_off_packed, const float* b_off,
+                                      float* om_out, int32_t om_out_stride, const void* w_packed, const float* scale,
+                                      const float* bias, void* y, int32_t* finite, void* stream);
 
 /* CenterNet.preprocess_image (centernet.py:173-185) + ImageList.from_tensors padding
  * (detectron2/structures/image_list.py:58-130): img is [B,3,H,W] (u8 or f32, CHW, batch stride given in
