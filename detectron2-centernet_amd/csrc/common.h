@@ -12,6 +12,21 @@ typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 typedef f16 f16x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// the split of the f16x3 mode (conv_common.h), spelled once: hi = f16(x), lo = f16(x - hi) of 4 f32
+__device__ __forceinline__ void split_parts(const f32x4 x, f16x4& hi, f16x4& lo) {
+  hi = __builtin_convertvector(x, f16x4);
+  f32x4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = x[j] - (float)hi[j];
+  lo = __builtin_convertvector(r, f16x4);
+}
+// 4 f32 -> the 16 bytes {hi[4], lo[4]}: split weights and split windows in memory
+__device__ __forceinline__ f16x8 split_hi_lo(const f32x4 x) {
+  f16x4 hi, lo;
+  split_parts(x, hi, lo);
+  return __builtin_shufflevector(hi, lo, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 // error plumbing (thread-local message, returned through ctdet_last_error()).
 void ctdet_set_error(const char* fmt, ...);
 #define CTDET_CHECK(cond, ...)            \
@@ -214,8 +229,7 @@ enum {
   CTDET_TUNE_NO_SMALL_GRID_TILES = 128, // convs whose 128-cout grid underfills the chip keep 128-cout tiles (default: 64-cout tiles)
   CTDET_TUNE_NO_HALO_TAP2 = 512,     // f16 3x3 halo conv with Cin % 64 == 0: the per-tap kernel instead of conv3x3_halo_tap2_kernel
   CTDET_TUNE_DCN_SPLIT_4W = 256,     // f16x3 DCNv2 window kernel: 64-cout tiles (four 32-pixel waves) also for the 128- and 256-cout layers
-  CTDET_TUNE_PAIR2_128 = 1024,       // f16x3 3x3 halo pair kernel: 128-cout tiles, one workgroup per CU (512 registers per wave)
-  CTDET_TUNE_DCN_SPLIT_8W64 = 2048,  // f16x3 DCNv2 window kernel, 64-cout layers: eight 16-pixel waves per workgroup, four waves per SIMD
+  // 1024, 2048: two variants that lost their A/B and are gone; the numbers are not reused
   CTDET_TUNE_TARGETS_MEMSET = 4096,   // gaussian targets: clear the heat map with hipMemsetAsync (round 3's form: a memset NODE in a captured step;
                                       // kept to reproduce profiles/r04_graph_memset_node.txt and to test the node check)
   CTDET_TUNE_DCN_WINDOW_V1 = 64,     // 64-cout f16 DCNv2: the per-tap-barrier window kernel instead of the row-step one

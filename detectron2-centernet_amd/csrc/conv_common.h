@@ -6,6 +6,8 @@
 // slot permutation for 64-byte LDS rows read as 16-row fragments by ds_read_b128:
 // rows r and r+4 share banks, so the 4 rows {r, r+4, r+8, r+12} get distinct slot XORs.
 __device__ __forceinline__ int swz(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
+// byte offset of a lane's 16-byte fragment in such a tile of 16 rows: row lane % 16, k group lane / 16
+__device__ __forceinline__ int swz_frag_off(int lane) { return (lane & 15) * 64 + (((lane >> 4) ^ swz(lane & 15)) << 4); }
 
 // XCD-aware tile mapping (1-D grid of 8*mchunk*nby workgroups).  Workgroups are dealt round-robin over the 8
 // XCDs, each with a private L2: XCD x gets the contiguous pixel-tile range [x*mchunk, (x+1)*mchunk) and walks it
@@ -421,12 +423,10 @@ __device__ __forceinline__ void dma16(const void* g, char* lds_wave_base) {
 // two v_mfma_f32_16x16x32_f16 of the same opcode on one accumulator (dependent issue needs no wait states; a 16x16x16
 // second product would cost 87 % of a 16x16x32 and mixes opcodes on one accumulator).
 // ------------------------------------------------------------------------------------------
+// 4 f32 -> the two B operands of mma_px
 __device__ __forceinline__ void split_b(const f32x4 x, f16x8& b1, f16x8& b2) {
-  const f16x4 hi = __builtin_convertvector(x, f16x4);
-  f32x4 r;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) r[j] = x[j] - (float)hi[j];
-  const f16x4 lo = __builtin_convertvector(r, f16x4);
+  f16x4 hi, lo;
+  split_parts(x, hi, lo);
   const f16x4 z = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
   b1 = __builtin_shufflevector(hi, z, 0, 1, 2, 3, 4, 5, 6, 7);
   b2 = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -461,6 +461,145 @@ __device__ __forceinline__ float packed_w(const float* row, int k) {
     return (float)g[k & 3] + (float)g[4 + (k & 3)];
   } else {
     return row[k];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// The LDS input window of the 3x3 / stride 1 / pad 1 halo kernels of conv_igemm.hip (conv3x3_halo_kernel, _pair_, _pair2_,
+// _tap2_ and head_fused_x3_kernel): the (TH + 2) x (TW + 2) pixels around a TH x TW output tile of 256 pixels (8 x 32 or
+// 16 x 16), one chunk of 64 bytes per pixel (32 f16 or 16 f32 channels).  This type is the only place that knows its image:
+//   main [TH + 2 rows][TW px][64 B], the four 16-byte slots of a pixel permuted by swz(px) like the weight tiles, padded to
+//        HMAIN = 5 DMA rounds of the workgroup;
+//   side [TH + 2 rows][left, right][64 B] behind it: the halo columns tx0 - 1 and tx0 + TW, row stride 128, slots in order.
+// A kernel keeps two such buffers (HBUF bytes each) at the start of its LDS and decides itself when to issue and wait.
+// ------------------------------------------------------------------------------------------
+template <typename TIn, int TW>
+struct HaloWindow {
+  static constexpr int TH = 256 / TW;
+  static constexpr int EN = TW / 16;           // 16-pixel tiles per tile row
+  static constexpr int RS = TW * 64;           // LDS bytes per window row
+  static constexpr int RPR = 256 * 16 / RS;    // window rows a DMA round of the workgroup covers (2 / 4)
+  static constexpr int EPV = 16 / sizeof(TIn), CH = 4 * EPV;   // elements per 16-byte piece, channels per chunk
+  static constexpr int HMAIN = 5 * 4096, HSIDE = 4096, HBUF = HMAIN + HSIDE;
+  static_assert((TH + 2 + RPR - 1) / RPR == 5 && 8 * (TH + 2) <= 256, "five main rounds and one side round cover the window");
+
+  const TIn *hp0, *hps, *zero;
+  long row2;
+  unsigned hmask;
+  int abase[EN][3], estride0, estride1;
+
+  // window of the tile at (ty0, tx0) of image b; row0 = first tile row of this wave (folded into the fragment bases)
+  __device__ __forceinline__ HaloWindow(const ConvArgs& a, int b, int ty0, int tx0, int row0) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    // the zero page pointer is opaque (conv_igemm_dma_kernel): one DMA per piece, real address or zero page by v_cndmask
+    zero = (const TIn*)g_zero_page;
+    asm volatile("" : "+v"(zero));
+    const TIn* ximg = (const TIn*)a.x + (long)b * a.H * a.W * a.in_stride;
+    // ---- loader: 5 main pieces + 1 side piece per thread and chunk ----
+    // main piece i of thread t: pid = t + 256 i -> halo row t / (4 TW) + RPR i, pixel (t >> 2) % TW, slot t & 3: rows RPR
+    // apart, so one base pointer + a uniform row stride suffice; bit i of hmask = the piece is inside the image (and the
+    // window: the 16 x 16 tile's fifth round has two rows), everything else reads the zero page
+    const int hslot = tid & 3, hpx = (tid >> 2) & (TW - 1), hr0 = tid / (4 * TW);
+    const int y0 = ty0 - 1 + hr0;
+    hp0 = ximg + ((long)y0 * a.W + tx0 + hpx) * a.in_stride + (hslot ^ swz(hpx)) * EPV;
+    row2 = (long)RPR * a.W * a.in_stride;
+    hmask = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) hmask |= (hr0 + RPR * i < TH + 2 && y0 + RPR * i >= 0 && y0 + RPR * i < a.H) ? (1u << i) : 0u;
+    {
+      const int side = (tid >> 2) & 1, hr = tid >> 3;   // [hr 0..TH+1][side][slot], tid < 8 * (TH + 2)
+      const int y = ty0 - 1 + hr, x = side ? tx0 + TW : tx0 - 1;
+      const bool ok = tid < 8 * (TH + 2) && y >= 0 && y < a.H && x >= 0 && x < a.W;
+      hps = ximg + ((long)(ok ? y : 0) * a.W + (ok ? x : 0)) * a.in_stride + hslot * EPV;
+      hmask |= ok ? 32u : 0u;
+    }
+    // ---- fragment addressing: per lane one LDS base per (px-tile e of the tile row, tap column s) with the wave's first
+    // tile row folded in; interior lanes then use immediates for (tile row + tap row) * RS.  The single edge lane of
+    // (e = 0, s = 0) [left halo column] and (e = EN - 1, s = 2) [right halo column] reads the side region. ----
+    const int l15 = lane & 15, kg = lane >> 4;
+#pragma unroll
+    for (int e = 0; e < EN; ++e)
+#pragma unroll
+      for (int s2 = 0; s2 < 3; ++s2) {
+        const int X = 16 * e + l15 + s2 - 1;
+        if (X < 0) abase[e][s2] = HMAIN + kg * 16 + row0 * 128;
+        else if (X > TW - 1) abase[e][s2] = HMAIN + 64 + kg * 16 + row0 * 128;
+        else abase[e][s2] = X * 64 + ((kg ^ swz(X)) << 4) + row0 * RS;
+      }
+    estride0 = (l15 == 0) ? 128 : RS;      // row stride of this lane for (e = 0, s = 0)
+    estride1 = (l15 == 15) ? 128 : RS;     // ... for (e = EN - 1, s = 2)
+  }
+
+  // this thread's six DMAs of `chunk` into halo buffer hb
+  __device__ __forceinline__ void issue(char* smem, int wave, int chunk, int hb) const {
+    char* dst = smem + hb * HBUF + wave * 1024;
+    const long coff = (long)chunk * CH;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) dma16((hmask & (1u << i)) ? hp0 + i * row2 + coff : zero, dst + i * 4096);
+    dma16((hmask & 32u) ? hps + coff : zero, dst + HMAIN);
+  }
+
+  // f32 windows: the thread's own six pieces of halo buffer hb, 4 f32 -> {hi[4], lo[4]} f16, in place.  A thread converts
+  // exactly what its own DMAs fetched, so the pass needs no barrier of its own
+  __device__ __forceinline__ void split_in_place(char* smem, int wave, int lane, int hb) const {
+    static_assert(std::is_same<TIn, float>::value, "only f32 windows are split");
+    char* base = smem + hb * HBUF + wave * 1024 + lane * 16;
+    f32x4 v[6];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) v[i] = *(const f32x4*)(base + i * 4096);
+    v[5] = *(const f32x4*)(base + HMAIN);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) *(f16x8*)(base + (i < 5 ? i * 4096 : HMAIN)) = split_hi_lo(v[i]);
+  }
+
+  // offset in a halo buffer of this lane's 16-byte fragment of the wave's pixel tile p for tap T
+  __device__ __forceinline__ int tap_off(int p, int T) const {
+    const int R_ = T / 3, S_ = T % 3;
+    const int e = p % EN, lr = p / EN;
+    if (e == 0 && S_ == 0) return abase[0][0] + (lr + R_) * estride0;
+    if (e == EN - 1 && S_ == 2) return abase[EN - 1][2] + (lr + R_) * estride1;
+    return abase[e][S_] + (lr + R_) * RS;
+  }
+};
+
+// workgroup -> (image b, tile origin, cout tile) of the halo kernels' 1-D grid (halo_grid); false: no tile for this workgroup
+template <int TW>
+__device__ __forceinline__ bool halo_tile_of_block(int B, int H, int W, int nby, int& b, int& ty0, int& tx0, int& n_tile) {
+  constexpr int TH = 256 / TW;
+  const int tiles_x = W / TW, tiles_y = H / TH;
+  int m_tile;
+  if (!tile_of_block(B * tiles_y * tiles_x, nby, m_tile, n_tile)) return false;
+  tx0 = (m_tile % tiles_x) * TW;
+  ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
+  b = m_tile / (tiles_x * tiles_y);
+  return true;
+}
+
+// output rows of the pixels a lane holds: pixel tile p of the wave = tile row row0 + p / EN, columns 16 (p % EN) + l15
+template <int TW, int TP>
+__device__ __forceinline__ void halo_out_rows(const ConvArgs& a, int b, int ty0, int tx0, int row0, int l15, int (&mo)[TP]) {
+  constexpr int EN = TW / 16;
+#pragma unroll
+  for (int p = 0; p < TP; ++p) {
+    const int y = ty0 + row0 + p / EN, x = tx0 + 16 * (p % EN) + l15;
+    mo[p] = (b * a.H + y) * a.W + x;
+  }
+}
+
+// packed weight rows this thread stages, NLD rounds of 64 LDS rows: LDS row (tile tt, row r) of a wave's TC cout tiles holds
+// cout_of<TC>(tt, r / 4, r % 4), slot = k group ^ swz(row); wptr[j] = that row of w (rows n0 on) + the thread's k group.
+// Rows beyond BC (only when BC < 64) re-read packed row 0: harmless, their LDS rows are never consumed
+template <int BC, int TC, typename T, int NLD>
+__device__ __forceinline__ void weight_row_ptrs(const void* w, int n0, int kpad, const T* (&wptr)[NLD]) {
+  const int tid = threadIdx.x, lrow = tid >> 2;
+  const int gw = (tid & 3) ^ swz(lrow);
+#pragma unroll
+  for (int j = 0; j < NLD; ++j) {
+    const int L = lrow + 64 * j;
+    const int Lw = L % (16 * TC), wv = L / (16 * TC);
+    const int tt = Lw >> 4, r = Lw & 15;
+    const int cl = wv * 16 * TC + cout_of<TC>(tt, r >> 2, r & 3);
+    wptr[j] = (const T*)w + (long)(n0 + (L < BC ? cl : 0)) * kpad + gw * (int)(16 / sizeof(T));
   }
 }
 

@@ -767,12 +767,12 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
 // the eval step's guard on the heads' input map, which this kernel writes, without a pass over that map.  A template
 // parameter for the reason COLS is one: the other instantiations keep their code and registers.
 template <int TP, int BC, bool COLS = false, bool NM = false, bool FUS = false, bool FIN = false>
-__global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_split_window_kernel(const ConvArgs a) {
+__global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const ConvArgs a) {
   static_assert(!FUS || (TP == 2 && BC == 64 && !COLS && !NM), "the fused offset conv: inference form of the 64-cout DCNv2 tile");
   static_assert(!FIN || FUS, "the finite test: the fused form's epilogue only");
   constexpr int TH = 8, TW = 16, BP = 128, MG = 4;
   constexpr int NT = 512 / TP;                                  // TP = 2: 4 waves of 32 pixels, TP = 1: 8 waves of 16
-  static_assert(BC * 4 <= NT, "at most one weight piece per thread and tap (waves beyond BC / 16 fetch none)");
+  static_assert(BC * 4 == NT, "one weight piece per thread and tap");
   constexpr int WR = TH + 2 + 2 * MG, WCOLS = TW + 2 + 2 * MG;  // 18 x 26 window pixels
   constexpr int NPIECE = WR * WCOLS * 4;                        // 1872 16-byte pieces
   constexpr int W_LD = (NPIECE + NT - 1) / NT;                  // DMA rounds; the last one ends with the window
@@ -780,7 +780,7 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
   constexpr int GEOW = 9 * BP * 16, GEOC = 9 * BP * 4;          // {w1 m, w2 m, w3 m, w4 m} and the window code per (tap, pixel)
   constexpr int TC = BC / 16;                                   // wave = 16 * TP pixels x all BC couts
   constexpr int WST = BC * 64, NST = 2, STG = 3 * WST;          // a stage = the three taps of a kernel row
-  static_assert(WINB + GEOW + GEOC + NST * STG <= ((TP == 2 || BC == 64) ? 81920 : 163840), "two workgroups / one (128 couts) per CU");
+  static_assert(WINB + GEOW + GEOC + NST * STG <= (TP == 2 ? 81920 : 163840), "two workgroups / one (128 couts) per CU");
   __shared__ __attribute__((aligned(16))) char smem[WINB + GEOW + GEOC + NST * STG];
   char* const win = smem;
   char* const geow = smem + WINB;
@@ -811,7 +811,6 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
     wptr = (const float*)a.w + (long)(n0 + cout_of<TC>(tt, r >> 2, r & 3)) * a.Kpad + gwk * 4;
   }
   auto issue_w = [&](int chunk, int tr, int st) {      // step (chunk, kernel row tr): 3 taps x 16 channels of every cout
-    if (BC * 4 < NT && wave >= BC / 16) return;        // (eight waves on a 64-cout tile: the first four carry the weights)
 #pragma unroll
     for (int ts = 0; ts < 3; ++ts)
       dma16(wptr + (tr * 3 + ts) * a.Cin + chunk * 16, ring + st * STG + ts * WST + wave * 1024);
@@ -877,14 +876,7 @@ __global__ void __launch_bounds__(512 / TP, (TP == 1 && BC == 64) ? 4 : 2) dcn_s
 #pragma unroll
       for (int i = 0; i < H_LD; ++i) v[i] = *(const f32x4*)(base + i * NT * 16);
 #pragma unroll
-      for (int i = 0; i < H_LD; ++i) {
-        const f16x4 hi = __builtin_convertvector(v[i], f16x4);
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = v[i][e] - (float)hi[e];
-        const f16x4 lo = __builtin_convertvector(r, f16x4);
-        *(f16x8*)(base + i * NT * 16) = __builtin_shufflevector(hi, lo, 0, 1, 2, 3, 4, 5, 6, 7);
-      }
+      for (int i = 0; i < H_LD; ++i) *(f16x8*)(base + i * NT * 16) = split_hi_lo(v[i]);
     };
     // weights: thread = (image X / Y, LDS row, slot); LDS row (tile tt, row r) = cout_of<2>(tt, r / 4, r % 4), slot = k group ^ swz(row)
     const int orow = a.Cin / 32 * 288;                          // floats per row of the pair image
@@ -1306,13 +1298,7 @@ __global__ void __launch_bounds__(256) conv_f32_win_kernel(const ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < ROUNDS; ++i) {
       char* pc = win + (tid + 256 * i) * 16;
-      const f32x4 v = *(const f32x4*)pc;
-      const f16x4 hi = __builtin_convertvector(v, f16x4);
-      f32x4 r;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) r[j] = v[j] - (float)hi[j];
-      const f16x4 lo = __builtin_convertvector(r, f16x4);
-      *(f16x8*)pc = __builtin_shufflevector(hi, lo, 0, 1, 2, 3, 4, 5, 6, 7);
+      *(f16x8*)pc = split_hi_lo(*(const f32x4*)pc);
     }
   }
   __syncthreads();
@@ -1515,8 +1501,6 @@ static int launch_f32_deform(const ConvArgs& a, bool vec, int bc, hipStream_t s)
           else hipLaunchKernelGGL((dcn_split_window_kernel<1, 128, false, NM>), grid128, dim3(512), 0, s, a);
         } else {
           if (a.cols_out) hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, true, NM>), grid, dim3(256), 0, s, a);
-          else if (ctdet_tuning_flags() & CTDET_TUNE_DCN_SPLIT_8W64)
-            hipLaunchKernelGGL((dcn_split_window_kernel<1, 64, false, NM>), grid, dim3(512), 0, s, a);
           else hipLaunchKernelGGL((dcn_split_window_kernel<2, 64, false, NM>), grid, dim3(256), 0, s, a);
         }
       }
@@ -1618,7 +1602,7 @@ bool dcn_split_window_ok(const ConvArgs& a) {
 // 64-cout tile covers Cout (two cout-tile workgroups per pixel tile would each repeat the offset conv) and the offset
 // conv's pair image pairs 16-channel chunks (Cin % 32 == 0).  Nothing here looks at the batch size.
 bool dcn_offset_fused_x3_ok(const ConvArgs& a) {
-  return dcn_split_window_ok(a) && a.Cin % 32 == 0 && a.Cout_pad == 64 && !a.res && !(ctdet_tuning_flags() & CTDET_TUNE_DCN_SPLIT_8W64);
+  return dcn_split_window_ok(a) && a.Cin % 32 == 0 && a.Cout_pad == 64 && !a.res;
 }
 
 // a.w_off: korder-3 pair image of the [27, Cin, 3, 3] offset / mask conv (32 rows x Cin / 32 * 288 f32 units), a.b_off: its 32
@@ -1652,15 +1636,7 @@ int launch_conv_f32(const ConvArgs& a, bool deform, bool split, hipStream_t s) {
 __global__ void __launch_bounds__(256) split_weights_kernel(const f32x4* __restrict__ src, f16x8* __restrict__ dst, long groups) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= groups) return;
-  const f32x4 w = src[i];
-  f16x8 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f16 h = (f16)w[j];
-    o[j] = h;
-    o[4 + j] = (f16)(w[j] - (float)h);
-  }
-  dst[i] = o;
+  dst[i] = split_hi_lo(src[i]);
 }
 
 int launch_split_weights(const float* src, void* dst, long n, hipStream_t s) {

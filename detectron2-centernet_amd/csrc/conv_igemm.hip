@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_uk_kernel(const ConvArgs a)
 // the kernels above this issues 2-3x fewer LDS-DMA instructions per MFMA (the measured limiter: the plain kernel
 // tops out at 44% / 23% of MFMA peak even with all loads served from one L1 line) and fetches each input byte from
 // L2 once per cout tile instead of nine times.
-// LDS: halo[2] x {main [10 rows][32 px][64 B] swizzled like the tiles above, side [10][left,right][64 B]} + ring[3].
+// LDS: two window buffers (HaloWindow, conv_common.h: the one description of their image) + ring[3].
 // ------------------------------------------------------------------------------------------
 // SP (the f16x3 mode of conv_f32.hip, TOut = float): the same kernel on f32 activations -- a chunk is 16 channels, again 64
 // bytes per window pixel, so the LDS images, the DMA schedule and every wait count are unchanged; the weights are the split
@@ -364,98 +364,40 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_uk_kernel(const ConvArgs a)
 template <int BC, int WP, int WC_, typename TOut, bool SP = false>
 __global__ void __launch_bounds__(256, 2) conv3x3_halo_kernel(const ConvArgs a) {
   using TIn = std::conditional_t<SP, float, f16>;
-  constexpr int CH = SP ? 16 : 32, EPV = SP ? 4 : 8;   // channels per chunk (64 bytes), elements per 16-byte vector
+  using Win = HaloWindow<TIn, 32>;
   static_assert(!SP || std::is_same<TOut, float>::value, "split mode stores f32");
-  constexpr int TH = 8, TW = 32, BP = TH * TW;
+  constexpr int TH = Win::TH, TW = 32, BP = TH * TW;
   constexpr int TP = BP / WP / 16;      // 16-pixel tiles per wave
   constexpr int TC = BC / WC_ / 16;
   constexpr int ROWS_W = TH / WP;       // tile rows per wave
   constexpr int BCL = BC < 64 ? 64 : BC;
   constexpr int B_LD = BCL / 64;
-  constexpr int HMAIN = 10 * 32 * 64, HSIDE = 4096, HBUF = HMAIN + HSIDE;
+  constexpr int HBUF = Win::HBUF;
   constexpr int WST = BCL * 64;
-  static_assert(WP * WC_ == 4 && TP == 2 * ROWS_W, "wave layout");
+  static_assert(WP * WC_ == 4 && TP == Win::EN * ROWS_W, "wave layout");
   __shared__ __attribute__((aligned(16))) char smem[2 * HBUF + 3 * WST];
   char* const ring = smem + 2 * HBUF;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave / WC_, wc = wave % WC_;
-  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
-  int m_tile, n_tile;
-  if (!tile_of_block(a.B * tiles_y * tiles_x, a.Cout_pad / BC, m_tile, n_tile)) return;
-  const int tx0 = (m_tile % tiles_x) * TW;
-  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
-  const int b = m_tile / (tiles_x * tiles_y);
+  int b, ty0, tx0, n_tile;
+  if (!halo_tile_of_block<TW>(a.B, a.H, a.W, a.Cout_pad / BC, b, ty0, tx0, n_tile)) return;
   const int n0 = n_tile * BC;
-  const TIn* zero = (const TIn*)g_zero_page;
-  asm volatile("" : "+v"(zero));
-  const TIn* ximg = (const TIn*)a.x + (long)b * a.H * a.W * a.in_stride;
-
-  // ---- halo loader: 5 main pieces + 1 side piece per thread and chunk ----
-  // main piece i of thread t: pid = t + 256 i -> halo row (t>>7) + 2i, pixel (t>>2)&31, slot t&3: rows two apart,
-  // so one base pointer + a uniform row-pair stride suffice
-  const int hslot = tid & 3, hpx = (tid >> 2) & 31, hr0 = tid >> 7;
-  const int y0 = ty0 - 1 + hr0;
-  const TIn* hp0 = ximg + ((long)y0 * a.W + tx0 + hpx) * a.in_stride + (hslot ^ swz(hpx)) * EPV;
-  const long row2 = 2L * a.W * a.in_stride;
-  unsigned hmask = 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) hmask |= (y0 + 2 * i >= 0 && y0 + 2 * i < a.H) ? (1u << i) : 0u;
-  const TIn* hps;
-  {
-    const int side = (tid >> 2) & 1, hr = tid >> 3;   // [hr 0..9][side][slot], tid < 80
-    const int y = ty0 - 1 + hr, x = side ? tx0 + TW : tx0 - 1;
-    const bool ok = tid < 80 && y >= 0 && y < a.H && x >= 0 && x < a.W;
-    hps = ximg + ((long)(ok ? y : 0) * a.W + (ok ? x : 0)) * a.in_stride + hslot * EPV;
-    hmask |= ok ? 32u : 0u;
-  }
-  const int lrow = tid >> 2;
-  const int gw = hslot ^ swz(lrow);
+  const int l15 = lane & 15;
+  const int row0 = wp * ROWS_W;
+  const Win win(a, b, ty0, tx0, row0);
   const TIn* wptr[B_LD];
-#pragma unroll
-  for (int j = 0; j < B_LD; ++j) {
-    const int L = lrow + 64 * j;
-    const int Lw = L % (16 * TC), wv = L / (16 * TC);
-    const int tt = Lw >> 4, r = Lw & 15;
-    const int cl = wv * 16 * TC + cout_of<TC>(tt, r >> 2, r & 3);
-    wptr[j] = (const TIn*)a.w + (long)(n0 + (L < BC ? cl : 0)) * a.Kpad + gw * EPV;
-  }
-  auto issue_halo = [&](int chunk, int hb) {
-    char* dst = smem + hb * HBUF + wave * 1024;
-    const long coff = (long)chunk * CH;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) dma16((hmask & (1u << i)) ? hp0 + i * row2 + coff : zero, dst + i * 4096);
-    dma16((hmask & 32u) ? hps + coff : zero, smem + hb * HBUF + HMAIN + wave * 1024);
-  };
+  weight_row_ptrs<BC, TC>(a.w, n0, a.Kpad, wptr);
   // K step kt = chunk * 9 + tap.  f16: packed chunk-major, step kt is the kt-th 32-k piece of a row; SP: packed tap-major
   auto issue_w = [&](int kt, int st) {
     long koff;
-    if constexpr (SP) { const int ch = kt / 9, tp = kt - 9 * ch; koff = (long)tp * a.Cin + ch * CH; }
+    if constexpr (SP) { const int ch = kt / 9, tp = kt - 9 * ch; koff = (long)tp * a.Cin + ch * Win::CH; }
     else koff = (long)kt * 32;
 #pragma unroll
     for (int j = 0; j < B_LD; ++j) dma16(wptr[j] + koff, ring + st * WST + wave * 1024 + j * 4096);
   };
-
-  // ---- fragment addressing: per lane one LDS base per (px-tile half e, tap column s) with the wave's first tile
-  // row folded in; interior lanes then use immediates for (tile row + tap row) * 2048.  The single edge lane of
-  // (e=0,s=0) [left halo column] and (e=1,s=2) [right halo column] reads the side region (row stride 128). ----
-  const int l15 = lane & 15, kg = lane >> 4;
-  const int row0 = wp * ROWS_W;
-  int abase[2][3];
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int s2 = 0; s2 < 3; ++s2) {
-      const int X = 16 * e + l15 + s2 - 1;
-      if (X < 0) abase[e][s2] = HMAIN + kg * 16 + row0 * 128;
-      else if (X > 31) abase[e][s2] = HMAIN + 64 + kg * 16 + row0 * 128;
-      else abase[e][s2] = X * 64 + ((kg ^ swz(X)) << 4) + row0 * 2048;
-    }
-  const int estride0 = (l15 == 0) ? 128 : 2048;    // row stride of this lane for (e=0, s=0)
-  const int estride1 = (l15 == 15) ? 128 : 2048;   // ... for (e=1, s=2)
-  const int fr_off = l15 * 64 + ((kg ^ swz(l15)) << 4);
-  const char* fragB = ring + (wc * 16 * TC) * 64 + fr_off;
+  const char* fragB = ring + (wc * 16 * TC) * 64 + swz_frag_off(lane);
 
   f32x4 acc[TP][TC];
 #pragma unroll
@@ -463,15 +405,15 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_kernel(const ConvArgs a) 
 #pragma unroll
     for (int c = 0; c < TC; ++c) acc[p][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int nch = a.Cin / CH, nk = nch * 9;
-  issue_halo(0, 0);
+  const int nch = a.Cin / Win::CH, nk = nch * 9;
+  win.issue(smem, wave, 0, 0);
   issue_w(0, 0);
   issue_w(1, 1);
 
   // one K step = tap T of the current chunk; tap, ring stage (9 % 3 == 0) and halo buffer are compile time
   auto kstep = [&](int kt, int chunk, auto tapc, auto hbc) {
     constexpr int T = decltype(tapc)::value, HB = decltype(hbc)::value;
-    constexpr int R_ = T / 3, S_ = T % 3, ST = T % 3, SL = (T + 2) % 3;
+    constexpr int ST = T % 3, SL = (T + 2) % 3;
     // outstanding DMAs allowed while waiting for weights(kt): the younger weight tile (B_LD) and, right after a
     // halo prefetch was queued behind it (T == 1), those 6 as well
     // (only when a prefetch WAS queued: in the last chunk the larger allowance would let the wait pass with
@@ -480,7 +422,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_kernel(const ConvArgs a) 
     else wait_vmcnt<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (T == 0 && chunk + 1 < nch) issue_halo(chunk + 1, HB ^ 1);
+    if (T == 0 && chunk + 1 < nch) win.issue(smem, wave, chunk + 1, HB ^ 1);
     if (kt + 2 < nk) issue_w(kt + 2, SL);
     const char* hbuf = smem + HB * HBUF;
     f32x4 wf[TC];    // 16 bytes: 8 f16 k (f16 mode) / the split group of 4 k (SP)
@@ -488,12 +430,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_kernel(const ConvArgs a) 
     for (int c = 0; c < TC; ++c) wf[c] = *(const f32x4*)(fragB + ST * WST + c * 1024);
 #pragma unroll
     for (int p = 0; p < TP; ++p) {
-      const int e = p & 1, lr = p >> 1;
-      int off;
-      if (e == 0 && S_ == 0) off = abase[0][0] + (lr + R_) * estride0;
-      else if (e == 1 && S_ == 2) off = abase[1][2] + (lr + R_) * estride1;
-      else off = abase[e][S_] + (lr + R_) * 2048;
-      const f32x4 pf = *(const f32x4*)(hbuf + off);
+      const f32x4 pf = *(const f32x4*)(hbuf + win.tap_off(p, T));
       if constexpr (SP) {
         mma_px<true, TC>(wf, pf, acc[p]);
       } else {
@@ -525,20 +462,21 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_kernel(const ConvArgs a) 
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
   int mo[TP];
-#pragma unroll
-  for (int p = 0; p < TP; ++p) {
-    const int y = ty0 + row0 + (p >> 1), x = tx0 + 16 * (p & 1) + l15;
-    mo[p] = (b * a.H + y) * a.W + x;
-  }
+  halo_out_rows<TW>(a, b, ty0, tx0, row0, l15, mo);
   epilogue_wave<TOut, TP, TC>(a, mo, cb, q, acc);
+}
+
+// 1-D grid of the halo kernels (tile_of_block): pixel tiles of TH x TW = 256 pixels, rounded up to the 8 XCDs, x cout tiles
+template <int TW = 32>
+static dim3 halo_grid(const ConvArgs& a, int bc) {
+  const int nbx = a.B * (a.H / (256 / TW)) * (a.W / TW), nby = a.Cout_pad / bc;
+  return dim3(8 * ((nbx + 7) / 8) * nby);
 }
 
 template <int BC, int WP, int WC_, typename TOut, bool SP = false>
 static int launch_halo(const ConvArgs& a, hipStream_t s) {
-  const int nbx = a.B * (a.H / 8) * (a.W / 32), nby = a.Cout_pad / BC;
-  dim3 grid(8 * ((nbx + 7) / 8) * nby);
   CTDET_KERNEL("conv3x3_halo_kernel<256x%d,%s>", BC, SP ? "f16x3" : out_name<TOut>());
-  hipLaunchKernelGGL((conv3x3_halo_kernel<BC, WP, WC_, TOut, SP>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((conv3x3_halo_kernel<BC, WP, WC_, TOut, SP>), halo_grid(a, BC), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -564,15 +502,16 @@ static int launch_halo(const ConvArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 template <int BC, int WP, int WC_>
 __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArgs a) {
-  constexpr int TH = 8, TW = 32, BP = TH * TW;
+  using Win = HaloWindow<float, 32>;
+  constexpr int TH = Win::TH, TW = 32, BP = TH * TW;
   constexpr int TP = BP / WP / 16;      // 16-pixel tiles per wave
   constexpr int TC = BC / WC_ / 16;
   constexpr int ROWS_W = TH / WP;       // tile rows per wave
   constexpr int BCL = BC < 64 ? 64 : BC;
   constexpr int W_LD = BCL / 64;        // DMA rounds per image (X or Y) and stage
-  constexpr int HMAIN = 10 * 32 * 64, HSIDE = 4096, HBUF = HMAIN + HSIDE;
+  constexpr int HBUF = Win::HBUF;
   constexpr int WIMG = BCL * 64, WST = 2 * WIMG, NST = 3;
-  static_assert(WP * WC_ == 4 && TP == 2 * ROWS_W, "wave layout");
+  static_assert(WP * WC_ == 4 && TP == Win::EN * ROWS_W, "wave layout");
   static_assert(2 * HBUF + NST * WST <= 81920, "two workgroups per CU");
   __shared__ __attribute__((aligned(16))) char smem[2 * HBUF + NST * WST];
   char* const ring = smem + 2 * HBUF;
@@ -580,51 +519,14 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave / WC_, wc = wave % WC_;
-  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
-  int m_tile, n_tile;
-  if (!tile_of_block(a.B * tiles_y * tiles_x, a.Cout_pad / BC, m_tile, n_tile)) return;
-  const int tx0 = (m_tile % tiles_x) * TW;
-  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
-  const int b = m_tile / (tiles_x * tiles_y);
+  int b, ty0, tx0, n_tile;
+  if (!halo_tile_of_block<TW>(a.B, a.H, a.W, a.Cout_pad / BC, b, ty0, tx0, n_tile)) return;
   const int n0 = n_tile * BC;
-  const float* zero = (const float*)g_zero_page;
-  asm volatile("" : "+v"(zero));
-  const float* ximg = (const float*)a.x + (long)b * a.H * a.W * a.in_stride;
-
-  // ---- halo loader (as conv3x3_halo_kernel): 5 main pieces + 1 side piece per thread and chunk ----
-  const int hslot = tid & 3, hpx = (tid >> 2) & 31, hr0 = tid >> 7;
-  const int y0 = ty0 - 1 + hr0;
-  const float* hp0 = ximg + ((long)y0 * a.W + tx0 + hpx) * a.in_stride + (hslot ^ swz(hpx)) * 4;
-  const long row2 = 2L * a.W * a.in_stride;
-  unsigned hmask = 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) hmask |= (y0 + 2 * i >= 0 && y0 + 2 * i < a.H) ? (1u << i) : 0u;
-  const float* hps;
-  {
-    const int side = (tid >> 2) & 1, hr = tid >> 3;   // [hr 0..9][side][slot], tid < 80
-    const int y = ty0 - 1 + hr, x = side ? tx0 + TW : tx0 - 1;
-    const bool ok = tid < 80 && y >= 0 && y < a.H && x >= 0 && x < a.W;
-    hps = ximg + ((long)(ok ? y : 0) * a.W + (ok ? x : 0)) * a.in_stride + hslot * 4;
-    hmask |= ok ? 32u : 0u;
-  }
-  const int lrow = tid >> 2;
-  const int gw = hslot ^ swz(lrow);
+  const int l15 = lane & 15;
+  const int row0 = wp * ROWS_W;
+  const Win win(a, b, ty0, tx0, row0);
   const float* wptr[W_LD];             // packed row (X image of step 0) of the cout this thread stages, + its k group
-#pragma unroll
-  for (int j = 0; j < W_LD; ++j) {
-    const int L = lrow + 64 * j;
-    const int Lw = L % (16 * TC), wv = L / (16 * TC);
-    const int tt = Lw >> 4, r = Lw & 15;
-    const int cl = wv * 16 * TC + cout_of<TC>(tt, r >> 2, r & 3);
-    wptr[j] = (const float*)a.w + (long)(n0 + (L < BC ? cl : 0)) * a.Kpad + gw * 4;
-  }
-  auto issue_halo = [&](int chunk, int hb) {
-    char* dst = smem + hb * HBUF + wave * 1024;
-    const long coff = (long)chunk * 16;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) dma16((hmask & (1u << i)) ? hp0 + i * row2 + coff : zero, dst + i * 4096);
-    dma16((hmask & 32u) ? hps + coff : zero, smem + hb * HBUF + HMAIN + wave * 1024);
-  };
+  weight_row_ptrs<BC, TC>(a.w, n0, a.Kpad, wptr);
   // K step kt = chunk * 5 + pair: 32 floats of every packed row = X (16) then Y (16)
   auto issue_w = [&](int kt, int st) {
 #pragma unroll
@@ -633,41 +535,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
       dma16(wptr[j] + (long)kt * 32 + 16, ring + st * WST + WIMG + wave * 1024 + j * 4096);
     }
   };
-  // the thread's own six pieces of halo buffer hb: 4 f32 -> {hi[4], lo[4]} f16, in place
-  auto convert = [&](int hb) {
-    char* base = smem + hb * HBUF + wave * 1024 + lane * 16;
-    f32x4 v[6];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) v[i] = *(const f32x4*)(base + i * 4096);
-    v[5] = *(const f32x4*)(base + HMAIN);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const f16x4 hi = __builtin_convertvector(v[i], f16x4);
-      f32x4 r;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) r[j] = v[i][j] - (float)hi[j];
-      const f16x4 lo = __builtin_convertvector(r, f16x4);
-      *(f16x8*)(base + (i < 5 ? i * 4096 : HMAIN)) = __builtin_shufflevector(hi, lo, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-  };
-
-  // ---- fragment addressing (as conv3x3_halo_kernel) ----
-  const int l15 = lane & 15, kg = lane >> 4;
-  const int row0 = wp * ROWS_W;
-  int abase[2][3];
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int s2 = 0; s2 < 3; ++s2) {
-      const int X = 16 * e + l15 + s2 - 1;
-      if (X < 0) abase[e][s2] = HMAIN + kg * 16 + row0 * 128;
-      else if (X > 31) abase[e][s2] = HMAIN + 64 + kg * 16 + row0 * 128;
-      else abase[e][s2] = X * 64 + ((kg ^ swz(X)) << 4) + row0 * 2048;
-    }
-  const int estride0 = (l15 == 0) ? 128 : 2048;    // row stride of this lane for (e=0, s=0)
-  const int estride1 = (l15 == 15) ? 128 : 2048;   // ... for (e=1, s=2)
-  const int fr_off = l15 * 64 + ((kg ^ swz(l15)) << 4);
-  const char* fragB = ring + (wc * 16 * TC) * 64 + fr_off;
+  const char* fragB = ring + (wc * 16 * TC) * 64 + swz_frag_off(lane);
 
   f32x4 acc[TP][TC];
 #pragma unroll
@@ -677,14 +545,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
 
   typedef unsigned long long u64;
   typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-  // window offset of this lane's fragment of pixel tile p for tap T
-  auto tap_off = [&](int p, int T) {
-    const int R_ = T / 3, S_ = T % 3;
-    const int e = p & 1, lr = p >> 1;
-    if (e == 0 && S_ == 0) return abase[0][0] + (lr + R_) * estride0;
-    if (e == 1 && S_ == 2) return abase[1][2] + (lr + R_) * estride1;
-    return abase[e][S_] + (lr + R_) * 2048;
-  };
   // operands of a K step: X / Y weight fragments (two register sets) and H / L pixel fragments
   static_assert(TP == 4, "two pixel-tile pairs per wave");
   typedef __attribute__((address_space(3))) const volatile u64 lds_u64;
@@ -704,7 +564,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
   auto load_px1 = [&](int p, auto prc, int hb, int q) {
     constexpr int PR = decltype(prc)::value;
     constexpr int T0 = 2 * PR, T1 = PR == 4 ? 8 : 2 * PR + 1;
-    const char* src = smem + hb * HBUF + tap_off(p, (q & 1) ? T1 : T0) + (q >> 1) * 8;
+    const char* src = smem + hb * HBUF + win.tap_off(p, (q & 1) ? T1 : T0) + (q >> 1) * 8;
     if (q >> 1) lq[p][q & 1] = *(lds_u64*)src;
     else hq[p][q & 1] = *(lds_u64*)src;
   };
@@ -721,12 +581,12 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
   };
 
   const int nch = a.Cin / 16, nk = nch * 5;      // nk >= 5: the three prologue stages exist
-  issue_halo(0, 0);
+  win.issue(smem, wave, 0, 0);
   issue_w(0, 0);
   issue_w(1, 1);
   issue_w(2, 2);
   wait_vmcnt<6 * W_LD>();               // the window of chunk 0 (older than the weight stages)
-  convert(0);
+  win.split_in_place(smem, wave, lane, 0);
   wait_vmcnt<4 * W_LD>();               // weights(0)
   wait_lgkm0();
   __builtin_amdgcn_s_barrier();
@@ -772,7 +632,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
       for (int i = 3 * sl; i < 3 * sl + 3; ++i) mfma1(parc, 0, i, 0, 1, 2);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (PR == 0 && !last) issue_halo(chunk + 1, HB ^ 1);
+    if (PR == 0 && !last) win.issue(smem, wave, chunk + 1, HB ^ 1);
     if (!last || PR < 2) issue_w(kt + 3, st);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -793,7 +653,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
     for (int r = 0; r < 4; ++r) load_px1(2 + (r >> 1), NextPR{}, NHB, r & 1);
     // the next chunk's window has landed (this step's wait left only weight stages in flight): split this thread's own
     // pieces of it; the barrier of step PR == 3 publishes them, the end of step PR == 4 reads the first operands from them
-    if (PR == 2 && !last) convert(HB ^ 1);
+    if (PR == 2 && !last) win.split_in_place(smem, wave, lane, HB ^ 1);
     __builtin_amdgcn_sched_barrier(0);
   };
   auto next_stage = [](int st) { return st == NST - 1 ? 0 : st + 1; };
@@ -821,18 +681,15 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_pair_kernel(const ConvArg
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
   int mo[TP];
-#pragma unroll
-  for (int p = 0; p < TP; ++p) {
-    const int y = ty0 + row0 + (p >> 1), x = tx0 + 16 * (p & 1) + l15;
-    mo[p] = (b * a.H + y) * a.W + x;
-  }
+  halo_out_rows<TW>(a, b, ty0, tx0, row0, l15, mo);
   epilogue_wave<float, TP, TC>(a, mo, cb, q, acc);
 }
 
 // LDS bytes of pair2_kloop<BC, ...>: two halo buffers and a 3-stage {X, Y} weight ring
 template <int BC>
 constexpr int pair2_smem_bytes() {
-  return 2 * (10 * 32 * 64 + 4096) + 3 * 2 * (BC < 64 ? 64 : BC) * 64;
+  static_assert(HaloWindow<float, 32>::HBUF == HaloWindow<float, 16>::HBUF, "one size for both tile shapes");
+  return 2 * HaloWindow<float, 32>::HBUF + 3 * 2 * (BC < 64 ? 64 : BC) * 64;
 }
 
 // K loop of conv3x3_halo_pair2_kernel for one (pixel tile, cout tile): on return acc[p][c] holds the raw sums (weight rows
@@ -842,63 +699,26 @@ template <int BC, int WP, int WC_, int TW>
 __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b, int ty0, int tx0, int n0,
                                             f32x4 (&acc)[256 / WP / 16][BC / WC_ / 16]) {
   // TW = 32: 8 x 32-pixel tiles; TW = 16: 16 x 16 (maps whose width is not a multiple of 32: the 16 x 16 level of DLA-34 at 512^2)
-  constexpr int TH = 256 / TW, BP = TH * TW;
-  constexpr int EN = TW / 16;           // 16-pixel tiles per tile row
-  constexpr int RS = TW * 64;           // LDS bytes per window row
-  constexpr int RPR = 256 * 16 / RS;    // window rows a DMA round of the workgroup covers (2 / 4)
+  using Win = HaloWindow<float, TW>;
+  constexpr int TH = Win::TH, BP = TH * TW;
   constexpr int TP = BP / WP / 16;      // 16-pixel tiles per wave
   constexpr int TC = BC / WC_ / 16;
   constexpr int ROWS_W = TH / WP;       // tile rows per wave
   constexpr int BCL = BC < 64 ? 64 : BC;
   constexpr int W_LD = BCL / 64;        // DMA rounds per image (X or Y) and stage
-  constexpr int HMAIN = 10 * 32 * 64, HSIDE = 4096, HBUF = HMAIN + HSIDE;
+  constexpr int HBUF = Win::HBUF;
   constexpr int WIMG = BCL * 64, WST = 2 * WIMG, NST = 3;
-  static_assert(WP * WC_ == 4 && TP == EN * ROWS_W && (TH + 2 + RPR - 1) / RPR == 5, "wave layout");
+  static_assert(WP * WC_ == 4 && TP == Win::EN * ROWS_W, "wave layout");
   static_assert(2 * HBUF + NST * WST == pair2_smem_bytes<BC>(), "LDS layout");
-  static_assert(BC > 64 || 2 * HBUF + NST * WST <= 81920, "two workgroups per CU");
+  static_assert(2 * HBUF + NST * WST <= 81920, "two workgroups per CU");
   char* const ring = smem + 2 * HBUF;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave / WC_, wc = wave % WC_;
-  const float* zero = (const float*)g_zero_page;
-  asm volatile("" : "+v"(zero));
-  const float* ximg = (const float*)a.x + (long)b * a.H * a.W * a.in_stride;
-
-  // ---- halo loader (as conv3x3_halo_kernel): 5 main pieces + 1 side piece per thread and chunk ----
-  const int hslot = tid & 3, hpx = (tid >> 2) & (TW - 1), hr0 = tid / (4 * TW);
-  const int y0 = ty0 - 1 + hr0;
-  const float* hp0 = ximg + ((long)y0 * a.W + tx0 + hpx) * a.in_stride + (hslot ^ swz(hpx)) * 4;
-  const long row2 = (long)RPR * a.W * a.in_stride;
-  unsigned hmask = 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) hmask |= (hr0 + RPR * i < TH + 2 && y0 + RPR * i >= 0 && y0 + RPR * i < a.H) ? (1u << i) : 0u;
-  const float* hps;
-  {
-    const int side = (tid >> 2) & 1, hr = tid >> 3;   // [hr 0..TH+1][side][slot], tid < 8 * (TH + 2)
-    const int y = ty0 - 1 + hr, x = side ? tx0 + TW : tx0 - 1;
-    const bool ok = tid < 8 * (TH + 2) && y >= 0 && y < a.H && x >= 0 && x < a.W;
-    hps = ximg + ((long)(ok ? y : 0) * a.W + (ok ? x : 0)) * a.in_stride + hslot * 4;
-    hmask |= ok ? 32u : 0u;
-  }
-  const int lrow = tid >> 2;
-  const int gw = hslot ^ swz(lrow);
+  const Win win(a, b, ty0, tx0, wp * ROWS_W);
   const float* wptr[W_LD];             // packed row (X image of step 0) of the cout this thread stages, + its k group
-#pragma unroll
-  for (int j = 0; j < W_LD; ++j) {
-    const int L = lrow + 64 * j;
-    const int Lw = L % (16 * TC), wv = L / (16 * TC);
-    const int tt = Lw >> 4, r = Lw & 15;
-    const int cl = wv * 16 * TC + cout_of<TC>(tt, r >> 2, r & 3);
-    wptr[j] = (const float*)a.w + (long)(n0 + (L < BC ? cl : 0)) * a.Kpad + gw * 4;
-  }
-  auto issue_halo = [&](int chunk, int hb) {
-    char* dst = smem + hb * HBUF + wave * 1024;
-    const long coff = (long)chunk * 16;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) dma16((hmask & (1u << i)) ? hp0 + i * row2 + coff : zero, dst + i * 4096);
-    dma16((hmask & 32u) ? hps + coff : zero, smem + hb * HBUF + HMAIN + wave * 1024);
-  };
+  weight_row_ptrs<BC, TC>(a.w, n0, a.Kpad, wptr);
   // K step kt = chunk * 5 + pair: 32 floats of every packed row = X (16) then Y (16)
   auto issue_w = [&](int kt, int st) {
 #pragma unroll
@@ -907,41 +727,7 @@ __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b
       dma16(wptr[j] + (long)kt * 32 + 16, ring + st * WST + WIMG + wave * 1024 + j * 4096);
     }
   };
-  // the thread's own six pieces of halo buffer hb: 4 f32 -> {hi[4], lo[4]} f16, in place
-  auto convert = [&](int hb) {
-    char* base = smem + hb * HBUF + wave * 1024 + lane * 16;
-    f32x4 v[6];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) v[i] = *(const f32x4*)(base + i * 4096);
-    v[5] = *(const f32x4*)(base + HMAIN);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const f16x4 hi = __builtin_convertvector(v[i], f16x4);
-      f32x4 r;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) r[j] = v[i][j] - (float)hi[j];
-      const f16x4 lo = __builtin_convertvector(r, f16x4);
-      *(f16x8*)(base + (i < 5 ? i * 4096 : HMAIN)) = __builtin_shufflevector(hi, lo, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-  };
-
-  // ---- fragment addressing (as conv3x3_halo_kernel) ----
-  const int l15 = lane & 15, kg = lane >> 4;
-  const int row0 = wp * ROWS_W;
-  int abase[EN][3];
-#pragma unroll
-  for (int e = 0; e < EN; ++e)
-#pragma unroll
-    for (int s2 = 0; s2 < 3; ++s2) {
-      const int X = 16 * e + l15 + s2 - 1;
-      if (X < 0) abase[e][s2] = HMAIN + kg * 16 + row0 * 128;
-      else if (X > TW - 1) abase[e][s2] = HMAIN + 64 + kg * 16 + row0 * 128;
-      else abase[e][s2] = X * 64 + ((kg ^ swz(X)) << 4) + row0 * RS;
-    }
-  const int estride0 = (l15 == 0) ? 128 : RS;      // row stride of this lane for (e = 0, s = 0)
-  const int estride1 = (l15 == 15) ? 128 : RS;     // ... for (e = EN - 1, s = 2)
-  const int fr_off = l15 * 64 + ((kg ^ swz(l15)) << 4);
-  const char* fragB = ring + (wc * 16 * TC) * 64 + fr_off;
+  const char* fragB = ring + (wc * 16 * TC) * 64 + swz_frag_off(lane);
 
 #pragma unroll
   for (int p = 0; p < TP; ++p)
@@ -950,14 +736,6 @@ __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b
 
   typedef unsigned long long u64;
   typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-  // window offset of this lane's fragment of pixel tile p for tap T
-  auto tap_off = [&](int p, int T) {
-    const int R_ = T / 3, S_ = T % 3;
-    const int e = p % EN, lr = p / EN;
-    if (e == 0 && S_ == 0) return abase[0][0] + (lr + R_) * estride0;
-    if (e == EN - 1 && S_ == 2) return abase[EN - 1][2] + (lr + R_) * estride1;
-    return abase[e][S_] + (lr + R_) * RS;
-  };
   // operands of a K step: X / Y weight fragments (two register sets) and H / L pixel fragments
   static_assert(TP == 4, "two pixel-tile pairs per wave");
   typedef __attribute__((address_space(3))) const volatile u64 lds_u64;
@@ -979,7 +757,7 @@ __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b
     constexpr int S = decltype(sc)::value;
     constexpr int B0 = S <= 4 ? 0 : 1, B1 = S < 4 ? 0 : 1;
     constexpr int T0 = S < 4 ? 2 * S : (S == 4 ? 8 : 2 * (S - 5)), T1 = S < 4 ? 2 * S + 1 : (S == 4 ? 8 : 2 * (S - 5) + 1);
-    const char* src = smem + ((q & 1) ? B1 : B0) * HBUF + tap_off(p, (q & 1) ? T1 : T0) + (q >> 1) * 8;
+    const char* src = smem + ((q & 1) ? B1 : B0) * HBUF + win.tap_off(p, (q & 1) ? T1 : T0) + (q >> 1) * 8;
     if (q >> 1) lq[p][q & 1] = *(lds_u64*)src;
     else hq[p][q & 1] = *(lds_u64*)src;
   };
@@ -997,14 +775,14 @@ __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b
 
   const int npair = a.Cin / 32, nk = npair * 9;
   using I0 = std::integral_constant<int, 0>;
-  issue_halo(0, 0);
-  issue_halo(1, 1);
+  win.issue(smem, wave, 0, 0);
+  win.issue(smem, wave, 1, 1);
   issue_w(0, 0);
   issue_w(1, 1);
   issue_w(2, 2);
   wait_vmcnt<6 * W_LD>();               // both windows of pair 0 (older than the weight stages)
-  convert(0);
-  convert(1);
+  win.split_in_place(smem, wave, lane, 0);
+  win.split_in_place(smem, wave, lane, 1);
   wait_vmcnt<4 * W_LD>();               // weights(0)
   wait_lgkm0();
   __builtin_amdgcn_s_barrier();
@@ -1047,8 +825,8 @@ __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b
       for (int i = 3 * sl; i < 3 * sl + 3; ++i) mfma1(Par{}, 0, i, 0, 1, 2);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (S == 0 && pair > 0) issue_halo(2 * pair + 1, 1);
-    if (S == 5 && !last) issue_halo(2 * pair + 2, 0);
+    if (S == 0 && pair > 0) win.issue(smem, wave, 2 * pair + 1, 1);
+    if (S == 5 && !last) win.issue(smem, wave, 2 * pair + 2, 0);
     if (kt + 3 < nk) issue_w(kt + 3, ST);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1067,8 +845,8 @@ __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) load_px1(2 + (r >> 1), NextS{}, r & 1);
-    if (S == 2 && pair > 0) convert(1);
-    if (S == 7 && !last) convert(0);
+    if (S == 2 && pair > 0) win.split_in_place(smem, wave, lane, 1);
+    if (S == 7 && !last) win.split_in_place(smem, wave, lane, 0);
     __builtin_amdgcn_sched_barrier(0);
   };
   for (int pair = 0; pair < npair; ++pair) {
@@ -1091,18 +869,12 @@ __device__ __forceinline__ void pair2_kloop(const ConvArgs& a, char* smem, int b
 // operand reads).  Both windows of a chunk pair sit in the two halo buffers at once (A = even chunk in buffer 0, B = odd
 // chunk in buffer 1); weights: ops.PackedConv._pack_pairs, nine 128-byte {X, Y} steps per chunk pair.  Cin % 32 == 0.
 // ------------------------------------------------------------------------------------------
-// BC = 128 (round 4, CTDET_TUNE_PAIR2_128): one workgroup per CU, a wave then has the whole 512-register file -- 128 accumulators
-// (AGPRs) next to both operand sets -- and every pixel fragment read feeds twice the MFMAs.
 template <int BC, int WP, int WC_, int TW = 32>
-__global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kernel(const ConvArgs a) {
-  constexpr int TH = 256 / TW, EN = TW / 16, TP = 256 / WP / 16, TC = BC / WC_ / 16, ROWS_W = TH / WP;
+__global__ void __launch_bounds__(256, 2) conv3x3_halo_pair2_kernel(const ConvArgs a) {
+  constexpr int TP = 256 / WP / 16, TC = BC / WC_ / 16, ROWS_W = 256 / TW / WP;
   __shared__ __attribute__((aligned(16))) char smem[pair2_smem_bytes<BC>()];
-  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
-  int m_tile, n_tile;
-  if (!tile_of_block(a.B * tiles_y * tiles_x, a.Cout_pad / BC, m_tile, n_tile)) return;
-  const int tx0 = (m_tile % tiles_x) * TW;
-  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
-  const int b = m_tile / (tiles_x * tiles_y);
+  int b, ty0, tx0, n_tile;
+  if (!halo_tile_of_block<TW>(a.B, a.H, a.W, a.Cout_pad / BC, b, ty0, tx0, n_tile)) return;
   const int n0 = n_tile * BC;
   f32x4 acc[TP][TC];
   pair2_kloop<BC, WP, WC_, TW>(a, smem, b, ty0, tx0, n0, acc);
@@ -1111,11 +883,7 @@ __global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kerne
   const int row0 = (wave / WC_) * ROWS_W, l15 = lane & 15, q = lane >> 4;
   const int cb = n0 + (wave % WC_) * 16 * TC;
   int mo[TP];
-#pragma unroll
-  for (int p = 0; p < TP; ++p) {
-    const int y = ty0 + row0 + p / EN, x = tx0 + 16 * (p % EN) + l15;
-    mo[p] = (b * a.H + y) * a.W + x;
-  }
+  halo_out_rows<TW>(a, b, ty0, tx0, row0, l15, mo);
   epilogue_wave<float, TP, TC>(a, mo, cb, q, acc);
 }
 
@@ -1128,16 +896,16 @@ __global__ void __launch_bounds__(256, BC > 64 ? 1 : 2) conv3x3_halo_pair2_kerne
 // ------------------------------------------------------------------------------------------
 template <int BC, int WP, int WC_, typename TOut, int TW = 32>
 __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArgs a) {
-  constexpr int TH = 256 / TW, BP = TH * TW;     // TW = 32: 8 x 32-pixel tiles; TW = 16: 16 x 16 (see conv3x3_halo_pair2_kernel)
-  constexpr int EN = TW / 16, RS = TW * 64, RPR = 256 * 16 / RS;
+  using Win = HaloWindow<f16, TW>;     // TW = 32: 8 x 32-pixel tiles; TW = 16: 16 x 16 (see conv3x3_halo_pair2_kernel)
+  constexpr int TH = Win::TH, BP = TH * TW;
   constexpr int TP = BP / WP / 16;      // 16-pixel tiles per wave
   constexpr int TC = BC / WC_ / 16;
   constexpr int ROWS_W = TH / WP;       // tile rows per wave
   constexpr int BCL = BC < 64 ? 64 : BC;
   constexpr int W_LD = BCL / 64;        // DMA rounds per image (X or Y) and stage
-  constexpr int HMAIN = 10 * 32 * 64, HSIDE = 4096, HBUF = HMAIN + HSIDE;
+  constexpr int HBUF = Win::HBUF;
   constexpr int WIMG = BCL * 64, WST = 2 * WIMG, NST = 3;
-  static_assert(WP * WC_ == 4 && TP == EN * ROWS_W && (TH + 2 + RPR - 1) / RPR == 5, "wave layout");
+  static_assert(WP * WC_ == 4 && TP == Win::EN * ROWS_W, "wave layout");
   static_assert(2 * HBUF + NST * WST <= 81920, "two workgroups per CU");
   __shared__ __attribute__((aligned(16))) char smem[2 * HBUF + NST * WST];
   char* const ring = smem + 2 * HBUF;
@@ -1145,51 +913,14 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave / WC_, wc = wave % WC_;
-  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
-  int m_tile, n_tile;
-  if (!tile_of_block(a.B * tiles_y * tiles_x, a.Cout_pad / BC, m_tile, n_tile)) return;
-  const int tx0 = (m_tile % tiles_x) * TW;
-  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
-  const int b = m_tile / (tiles_x * tiles_y);
+  int b, ty0, tx0, n_tile;
+  if (!halo_tile_of_block<TW>(a.B, a.H, a.W, a.Cout_pad / BC, b, ty0, tx0, n_tile)) return;
   const int n0 = n_tile * BC;
-  const f16* zero = (const f16*)g_zero_page;
-  asm volatile("" : "+v"(zero));
-  const f16* ximg = (const f16*)a.x + (long)b * a.H * a.W * a.in_stride;
-
-  // ---- halo loader (as conv3x3_halo_kernel): 5 main pieces + 1 side piece per thread and chunk ----
-  const int hslot = tid & 3, hpx = (tid >> 2) & (TW - 1), hr0 = tid / (4 * TW);
-  const int y0 = ty0 - 1 + hr0;
-  const f16* hp0 = ximg + ((long)y0 * a.W + tx0 + hpx) * a.in_stride + (hslot ^ swz(hpx)) * 8;
-  const long row2 = (long)RPR * a.W * a.in_stride;
-  unsigned hmask = 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) hmask |= (hr0 + RPR * i < TH + 2 && y0 + RPR * i >= 0 && y0 + RPR * i < a.H) ? (1u << i) : 0u;
-  const f16* hps;
-  {
-    const int side = (tid >> 2) & 1, hr = tid >> 3;   // [hr 0..9][side][slot], tid < 80
-    const int y = ty0 - 1 + hr, x = side ? tx0 + TW : tx0 - 1;
-    const bool ok = tid < 8 * (TH + 2) && y >= 0 && y < a.H && x >= 0 && x < a.W;
-    hps = ximg + ((long)(ok ? y : 0) * a.W + (ok ? x : 0)) * a.in_stride + hslot * 8;
-    hmask |= ok ? 32u : 0u;
-  }
-  const int lrow = tid >> 2;
-  const int gw = hslot ^ swz(lrow);
+  const int l15 = lane & 15;
+  const int row0 = wp * ROWS_W;
+  const Win win(a, b, ty0, tx0, row0);
   const f16* wptr[W_LD];               // chunk-major packed row of the cout this thread stages, + its k group
-#pragma unroll
-  for (int j = 0; j < W_LD; ++j) {
-    const int L = lrow + 64 * j;
-    const int Lw = L % (16 * TC), wv = L / (16 * TC);
-    const int tt = Lw >> 4, r = Lw & 15;
-    const int cl = wv * 16 * TC + cout_of<TC>(tt, r >> 2, r & 3);
-    wptr[j] = (const f16*)a.w + (long)(n0 + (L < BC ? cl : 0)) * a.Kpad + gw * 8;
-  }
-  auto issue_halo = [&](int chunk, int hb) {
-    char* dst = smem + hb * HBUF + wave * 1024;
-    const long coff = (long)chunk * 32;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) dma16((hmask & (1u << i)) ? hp0 + i * row2 + coff : zero, dst + i * 4096);
-    dma16((hmask & 32u) ? hps + coff : zero, smem + hb * HBUF + HMAIN + wave * 1024);
-  };
+  weight_row_ptrs<BC, TC>(a.w, n0, a.Kpad, wptr);
   // K step kt = 9 * pair + S: the 64-byte pieces (chunk, tap) of its two operands from the chunk-major rows (korder 1: piece
   // index chunk * 9 + tap) -- X = (A, 2S) / (A, 8) / (B, 2(S-5)), Y = (A, 2S+1) / (B, 8) / (B, 2(S-5)+1)
   auto issue_w = [&](int kt, int st) {
@@ -1202,24 +933,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
       dma16(wptr[j] + (long)ky * 32, ring + st * WST + WIMG + wave * 1024 + j * 4096);
     }
   };
-
-  // ---- fragment addressing (as conv3x3_halo_kernel) ----
-  const int l15 = lane & 15, kg = lane >> 4;
-  const int row0 = wp * ROWS_W;
-  int abase[EN][3];
-#pragma unroll
-  for (int e = 0; e < EN; ++e)
-#pragma unroll
-    for (int s2 = 0; s2 < 3; ++s2) {
-      const int X = 16 * e + l15 + s2 - 1;
-      if (X < 0) abase[e][s2] = HMAIN + kg * 16 + row0 * 128;
-      else if (X > TW - 1) abase[e][s2] = HMAIN + 64 + kg * 16 + row0 * 128;
-      else abase[e][s2] = X * 64 + ((kg ^ swz(X)) << 4) + row0 * RS;
-    }
-  const int estride0 = (l15 == 0) ? 128 : RS;      // row stride of this lane for (e = 0, s = 0)
-  const int estride1 = (l15 == 15) ? 128 : RS;     // ... for (e = EN - 1, s = 2)
-  const int fr_off = l15 * 64 + ((kg ^ swz(l15)) << 4);
-  const char* fragB = ring + (wc * 16 * TC) * 64 + fr_off;
+  const char* fragB = ring + (wc * 16 * TC) * 64 + swz_frag_off(lane);
 
   f32x4 acc[TP][TC];
 #pragma unroll
@@ -1227,14 +941,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
 #pragma unroll
     for (int c = 0; c < TC; ++c) acc[p][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  // window offset of this lane's fragment of pixel tile p for tap T
-  auto tap_off = [&](int p, int T) {
-    const int R_ = T / 3, S_ = T % 3;
-    const int e = p % EN, lr = p / EN;
-    if (e == 0 && S_ == 0) return abase[0][0] + (lr + R_) * estride0;
-    if (e == EN - 1 && S_ == 2) return abase[EN - 1][2] + (lr + R_) * estride1;
-    return abase[e][S_] + (lr + R_) * RS;
-  };
   // operands of a K step: X / Y weight fragments (two register sets) and the pixel fragments of its two (buffer, tap) operands
   static_assert(TP == 4, "two pixel-tile pairs per wave");
   f16x8 xf[2][TC], yf[2][TC], pf[TP][2];
@@ -1251,7 +957,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
     constexpr int S = decltype(sc)::value;
     constexpr int B0 = S <= 4 ? 0 : 1, B1 = S < 4 ? 0 : 1;
     constexpr int T0 = S < 4 ? 2 * S : (S == 4 ? 8 : 2 * (S - 5)), T1 = S < 4 ? 2 * S + 1 : (S == 4 ? 8 : 2 * (S - 5) + 1);
-    pf[p][q] = *(const f16x8*)(smem + (q ? B1 : B0) * HBUF + tap_off(p, q ? T1 : T0));
+    pf[p][q] = *(const f16x8*)(smem + (q ? B1 : B0) * HBUF + win.tap_off(p, q ? T1 : T0));
   };
   // MFMA i (0 .. 4 * TC) of the tile pair (p, p + 1): two groups of 2 * TC -- kind 0: X . operand 0, kind 1: Y . operand 1 --
   // each over (tile u, cout tile c)
@@ -1264,8 +970,8 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
 
   const int npair = a.Cin / 64, nk = npair * 9;      // a chunk = 32 f16 channels
   using I0 = std::integral_constant<int, 0>;
-  issue_halo(0, 0);
-  issue_halo(1, 1);
+  win.issue(smem, wave, 0, 0);
+  win.issue(smem, wave, 1, 1);
   issue_w(0, 0);
   issue_w(1, 1);
   issue_w(2, 2);
@@ -1311,8 +1017,8 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
       for (int i = 2 * sl; i < 2 * sl + 2; ++i) mfma1(Par{}, 0, i, 0, 1);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (S == 0 && pair > 0) issue_halo(2 * pair + 1, 1);
-    if (S == 5 && !last) issue_halo(2 * pair + 2, 0);
+    if (S == 0 && pair > 0) win.issue(smem, wave, 2 * pair + 1, 1);
+    if (S == 5 && !last) win.issue(smem, wave, 2 * pair + 2, 0);
     if (kt + 3 < nk) issue_w(kt + 3, ST);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1349,40 +1055,30 @@ __global__ void __launch_bounds__(256, 2) conv3x3_halo_tap2_kernel(const ConvArg
   const int q = lane >> 4;
   const int cb = n0 + wc * 16 * TC;
   int mo[TP];
-#pragma unroll
-  for (int p = 0; p < TP; ++p) {
-    const int y = ty0 + row0 + p / EN, x = tx0 + 16 * (p % EN) + l15;
-    mo[p] = (b * a.H + y) * a.W + x;
-  }
+  halo_out_rows<TW>(a, b, ty0, tx0, row0, l15, mo);
   epilogue_wave<TOut, TP, TC>(a, mo, cb, q, acc);
 }
 
 template <int BC, int WP, int WC_>
 static int launch_halo_pair_t(const ConvArgs& a, hipStream_t s) {
-  const int nbx = a.B * (a.H / 8) * (a.W / 32), nby = a.Cout_pad / BC;
-  dim3 grid(8 * ((nbx + 7) / 8) * nby);
   CTDET_KERNEL("conv3x3_halo_pair_kernel<256x%d,f16x3>", BC);
-  hipLaunchKernelGGL((conv3x3_halo_pair_kernel<BC, WP, WC_>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((conv3x3_halo_pair_kernel<BC, WP, WC_>), halo_grid(a, BC), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 template <int BC, int WP, int WC_, int TW = 32>
 static int launch_halo_pair2_t(const ConvArgs& a, hipStream_t s) {
-  const int nbx = a.B * (a.H / (256 / TW)) * (a.W / TW), nby = a.Cout_pad / BC;
-  dim3 grid(8 * ((nbx + 7) / 8) * nby);
   CTDET_KERNEL(TW == 32 ? "conv3x3_halo_pair2_kernel<256x%d,f16x3>" : "conv3x3_halo_pair2_kernel<16x16x%d,f16x3>", BC);
-  hipLaunchKernelGGL((conv3x3_halo_pair2_kernel<BC, WP, WC_, TW>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((conv3x3_halo_pair2_kernel<BC, WP, WC_, TW>), halo_grid<TW>(a, BC), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 template <int BC, int WP, int WC_, typename TOut, int TW = 32>
 static int launch_halo_tap2(const ConvArgs& a, hipStream_t s) {
-  const int nbx = a.B * (a.H / (256 / TW)) * (a.W / TW), nby = a.Cout_pad / BC;
-  dim3 grid(8 * ((nbx + 7) / 8) * nby);
   CTDET_KERNEL(TW == 32 ? "conv3x3_halo_tap2_kernel<256x%d,%s>" : "conv3x3_halo_tap2_kernel<16x16x%d,%s>", BC, out_name<TOut>());
-  hipLaunchKernelGGL((conv3x3_halo_tap2_kernel<BC, WP, WC_, TOut, TW>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((conv3x3_halo_tap2_kernel<BC, WP, WC_, TOut, TW>), halo_grid<TW>(a, BC), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -1410,7 +1106,6 @@ int launch_halo_pair2(const ConvArgs& a, hipStream_t s) {
     return launch_halo_pair2_t<64, 4, 1, 16>(a, s);
   }
   if (pick_bc(a.Cout) <= 32 || small_grid) return launch_halo_pair2_t<32, 4, 1>(a, s);
-  if ((ctdet_tuning_flags() & CTDET_TUNE_PAIR2_128) && a.Cout_pad % 128 == 0) return launch_halo_pair2_t<128, 4, 1>(a, s);
   return launch_halo_pair2_t<64, 4, 1>(a, s);
 }
 
@@ -1684,12 +1379,8 @@ __global__ void __launch_bounds__(256, 2) head_fused_x3_kernel(const HeadArgs a)
   constexpr int TH = 256 / TW, EN = TW / 16, TP = 256 / WP / 16, TC = BC / 16, ROWS_W = TH / WP;
   static_assert(TP == 4 && TC == 4, "four 16-pixel tiles x four 16-channel tiles per wave");
   __shared__ __attribute__((aligned(16))) char smem[pair2_smem_bytes<BC>()];
-  const int tiles_x = a.W / TW, tiles_y = a.H / TH;
-  int m_tile, head;
-  if (!tile_of_block(a.B * tiles_y * tiles_x, a.nheads, m_tile, head)) return;
-  const int tx0 = (m_tile % tiles_x) * TW;
-  const int ty0 = ((m_tile / tiles_x) % tiles_y) * TH;
-  const int b = m_tile / (tiles_x * tiles_y);
+  int b, ty0, tx0, head;
+  if (!halo_tile_of_block<TW>(a.B, a.H, a.W, a.nheads, b, ty0, tx0, head)) return;
   ConvArgs c = {};        // what pair2_kloop reads
   c.x = a.x; c.w = a.w1; c.H = a.H; c.W = a.W; c.in_stride = a.in_stride; c.Cin = a.Cin; c.Kpad = a.Cin / 32 * 288;
 

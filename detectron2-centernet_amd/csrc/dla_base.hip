@@ -429,14 +429,6 @@ static_assert((NIN + IN_PAD) * 16 <= 4 * X3_L0P, "the input window fits under th
 static_assert(3 * 256 * 4 <= 4 * X3_STP, "the byte table fits under the stem planes");
 static_assert(4 * X3_STP + 4 * X3_L0P <= 81920, "two workgroups per CU");
 
-__device__ __forceinline__ f16x8 split4(const f32x4 v) {
-  const f16x4 hi = __builtin_convertvector(v, f16x4);
-  f32x4 r;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) r[j] = v[j] - (float)hi[j];
-  const f16x4 lo = __builtin_convertvector(r, f16x4);
-  return __builtin_shufflevector(hi, lo, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 __device__ __forceinline__ f32x4 bn_relu_f32(const f32x4 acc, const f32x4 sc, const f32x4 bi) {
   f32x4 v = acc * sc;
   v = v + bi;
@@ -521,7 +513,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
     float* lut = (float*)stb;
     constexpr int ROUNDS = (NIN + 255) / 256;
     // tap column 7 (zero weights) of the window's last row reads the pixels behind it: finite values wanted
-    if (tid < IN_PAD) *(f16x8*)(inb + (NIN + tid) * 16) = split4((f32x4){0.f, 0.f, 0.f, 0.f});
+    if (tid < IN_PAD) *(f16x8*)(inb + (NIN + tid) * 16) = split_hi_lo((f32x4){0.f, 0.f, 0.f, 0.f});
     if constexpr (BYTES) {
       unsigned rawpx[ROUNDS];                                      // the three channels of a pixel, 0xffffffff = outside
 #pragma unroll
@@ -547,7 +539,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
           if (rawpx[i] != 0xffffffffu) {
             v[0] = lut[rawpx[i] & 255]; v[1] = lut[256 + ((rawpx[i] >> 8) & 255)]; v[2] = lut[512 + ((rawpx[i] >> 16) & 255)];
           }
-          *(f16x8*)(inb + p * 16) = split4(v);
+          *(f16x8*)(inb + p * 16) = split_hi_lo(v);
         }
       }
       }
@@ -565,7 +557,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
             v[1] = ((float)s[plane] / 255.f - a.mean[1]) / a.stdv[1];
             v[2] = ((float)s[2 * plane] / 255.f - a.mean[2]) / a.stdv[2];
           }
-          *(f16x8*)(inb + p * 16) = split4(v);
+          *(f16x8*)(inb + p * 16) = split_hi_lo(v);
         }
       }
     }
@@ -614,7 +606,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
           const int sy = 2 * oy - 2 + py[u], sx = 2 * ox - 2 + px[u];
           f32x4 v = bn_relu_f32(acc[u], sc, bi);
           if (!(sy >= 0 && sy < a.Hp && sx >= 0 && sx < a.Wp)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-          *(f16x8*)(stb + q * X3_STP + pp[u] * 16) = split4(v);
+          *(f16x8*)(stb + q * X3_STP + pp[u] * 16) = split_hi_lo(v);
         }
       }
     };
@@ -667,7 +659,7 @@ __global__ void __launch_bounds__(256, 2) dla_base_x3_kernel(const BaseArgs a, i
           const int ly = 2 * oy - 1 + py[u], lx = 2 * ox - 1 + px[u];
           f32x4 v = bn_relu_f32(acc[u], sc, bi);
           if (!(ly >= 0 && ly < a.Hp && lx >= 0 && lx < a.Wp)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-          *(f16x8*)(l0b + q * X3_L0P + pp[u] * 16) = split4(v);
+          *(f16x8*)(l0b + q * X3_L0P + pp[u] * 16) = split_hi_lo(v);
         }
       }
     };

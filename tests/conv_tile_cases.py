@@ -110,9 +110,13 @@ ROWS = _tiled("f16") + _tiled("f32") + _tiled("f16x3") + [
     conv("f16", "conv3x3_halo_kernel<256x128,f16>", 1, 128, 128, 32, 1024, k=3, epi=FULL),
     conv("f16", "conv3x3_halo_kernel<256x64,f16>", 1, 24, 32, 32, 128, k=3),
     conv("f16", "conv3x3_halo_kernel<256x64,f32>", 1, 24, 32, 32, 64, k=3, epi=FULL, out="f32"),
+    # 2 x 2 tiles: every tile has an image border and a neighbour, so the side halo columns hold pixels (on a map one tile
+    # wide they are the zero page throughout); the same for the tap-pair kernels below
+    conv("f16", "conv3x3_halo_kernel<256x64,f16>", 1, 16, 64, 32, 128, k=3, epi=FULL),
     # two taps per MFMA (Cin % 64 == 0), 8 x 32- and 16 x 16-pixel tiles
     conv("f16", "conv3x3_halo_tap2_kernel<256x64,f16>", 1, 24, 32, 64, 64, k=3, epi=FULL),
     conv("f16", "conv3x3_halo_tap2_kernel<256x32,f32>", 1, 24, 32, 64, 28, k=3, out="f32"),
+    conv("f16", "conv3x3_halo_tap2_kernel<256x64,f16>", 1, 16, 64, 64, 64, k=3),
     conv("f16", "conv3x3_halo_tap2_kernel<16x16x64,f16>", 1, 16, 48, 64, 128, k=3),
     conv("f16", "conv3x3_halo_tap2_kernel<16x16x32,f32>", 1, 16, 48, 64, 28, k=3, epi=FULL, out="f32"),
     # narrow inputs on dense pixels: the LDS-window kernels of the DLA base layers
@@ -149,6 +153,7 @@ ROWS = _tiled("f16") + _tiled("f32") + _tiled("f16x3") + [
     # korder 2 (an odd number of 16-channel chunks): 64-cout tiles whatever the grid
     conv("f16x3", "conv3x3_halo_pair_kernel<256x64,f16x3>", 1, 24, 32, 48, 192, k=3, epi=FULL),
     conv("f16x3", "conv3x3_halo_pair_kernel<256x32,f16x3>", 1, 24, 32, 48, 28, k=3),
+    conv("f16x3", "conv3x3_halo_pair_kernel<256x64,f16x3>", 1, 16, 64, 48, 192, k=3),
     # 16 dense channels on 64-pixel rows take no pair image: the halo kernel on split operands
     conv("f16x3", "conv3x3_halo_kernel<256x64,f16x3>", 1, 24, 64, 16, 128, k=3, epi=FULL),
     conv("f16x3", _win("f16x3", 7, 8, 16, 1), 2, 8, 64, 8, 16, k=7, epi=SBR),
