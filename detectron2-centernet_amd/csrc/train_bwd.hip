@@ -2097,6 +2097,7 @@ static int launch_conv_wgrad_t(const WgradArgs& a0, hipStream_t s) {
     const int ntiles = a.B * (a.H / 8) * (a.W / 32);
     int blocks = device_cu_count();   // 1x / 2x / 4x CUs measured the same within noise; fewest atomics wins
     if (blocks > ntiles) blocks = ntiles;
+    CTDET_KERNEL("conv_wgrad_narrow_kernel<%s,%s>,blocks=%d", a.R == 7 ? "7x7,Cin8" : "3x3,Cin16", X3 ? "f16x3" : "f16", blocks);
     if (a.R == 7) hipLaunchKernelGGL((conv_wgrad_narrow_kernel<7, 8, X3>), dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_wgrad_narrow_kernel<3, 16, X3>), dim3(blocks), dim3(256), 0, s, a);
     CTDET_LAUNCH_CHECK();
@@ -2112,6 +2113,7 @@ static int launch_conv_wgrad_t(const WgradArgs& a0, hipStream_t s) {
     if (split < 1) split = 1;
     if (split > ntiles) split = ntiles;
     a.msplit = split;
+    CTDET_KERNEL("conv_wgrad_win_kernel<%s>,split=%d", X3 ? "f16x3" : "f16", split);
     hipLaunchKernelGGL(conv_wgrad_win_kernel<X3>, dim3(gx * gy * split), dim3(X3 ? 512 : 256), 0, s, a);
     CTDET_LAUNCH_CHECK();
     return 0;
@@ -2131,6 +2133,7 @@ static int launch_conv_wgrad_t(const WgradArgs& a0, hipStream_t s) {
     while ((1 << a.lw) < a.Wo) ++a.lw;
     while ((1 << a.lh) < a.Ho) ++a.lh;
   }
+  CTDET_KERNEL("conv_wgrad_kernel<%s%s>,split=%d", X3 ? "f16x3" : "f16", a.perm_rs ? ",oihw" : "", split);
   if (a.perm_rs) hipLaunchKernelGGL((conv_wgrad_kernel<true, X3>), dim3(gx * gy * split), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_wgrad_kernel<false, X3>), dim3(gx * gy * split), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
@@ -2468,6 +2471,7 @@ int launch_conv_wgrad_f32(const WgradArgs& h, hipStream_t s) {
   if (ms > 65535) ms = 65535;
   a.msplit = (int)ms;
   if (a.M == 0) return 0;
+  CTDET_KERNEL("conv_wgrad_f32_kernel,split=%d", a.msplit);
   hipLaunchKernelGGL(conv_wgrad_f32_kernel, dim3(nkb, nnb, (unsigned)ms), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;

@@ -477,7 +477,7 @@ def _phase_tap_index(device):
     return t
 
 
-def _conv_dgrad_s2_phases(dy, weight, in_hw, comp=F16):
+def _conv_dgrad_s2_phases(dy, weight, in_hw, comp=F16, out=None):
     """input gradient of a 3x3 / stride 2 / pad 1 conv without zero-stuffing: one 2x2 conv over dy to the four output phases
     (4*Cin channels), then ctdet_depth_to_space2"""
     Cout, Cin, _, _ = weight.shape
@@ -492,15 +492,24 @@ def _conv_dgrad_s2_phases(dy, weight, in_hw, comp=F16):
     wd = wd.permute(2, 1, 0, 3, 4).reshape(4 * Cp, Cd, 2, 2).contiguous()
     p = ops.PackedConv(wd, None, None, stride=1, pad=1, compute=comp)
     ph = ops.conv2d(dy, p)                                                           # [B, Ho+1, Wo+1, 4*Cp]
-    dx = torch.empty(B, H, W, Cp, dtype=dy.dtype, device=dy.device)
+    dx = _dgrad_out(out, (B, H, W, Cp), dy)
     rc = _lib.lib().ctdet_depth_to_space2(_ptr(ph), _nhwc_stride(ph), _ptr(dx), _nhwc_stride(dx), B, H, W, Cp, ph.shape[1],
                                           ph.shape[2], dt_of(dx), _stream())
     _lib.check(rc, "ctdet_depth_to_space2")
     return dx if Cp == Cin else dx[..., :Cin]
 
 
-def conv_dgrad(dy, weight, stride, pad, in_hw, cin_pad=None, comp=None):
+def _dgrad_out(out, shape, dy):
+    """the buffer conv_dgrad writes: a new one, or the caller's `out` (an NHWC tensor or channel-slice view of exactly `shape`)"""
+    if out is None:
+        return torch.empty(*shape, dtype=dy.dtype, device=dy.device)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dy.dtype and out.device == dy.device, (tuple(out.shape), shape)
+    return out
+
+
+def conv_dgrad(dy, weight, stride, pad, in_hw, cin_pad=None, comp=None, out=None):
     """dx of y = conv(x, weight): a conv over dy with the taps flipped and in/out channels swapped;
+    out: write into this [B, H, W, channels padded as the result is] tensor (may be a view into a wider buffer) instead of a new one;
     cin_pad (f16 / f16x3): dy carries that many channels (>= Cout, the extra ones zero) -- the operand gets zero columns for them;
     f16 / f16x3: 3x3 / stride 2 / pad 1 goes through the four-phase form, other strides read dy as zero-stuffed (in_dil);
     f32: always the zero-stuffed form on the f32 MFMA kernel."""
@@ -510,19 +519,18 @@ def conv_dgrad(dy, weight, stride, pad, in_hw, cin_pad=None, comp=None):
         wt = ops.flip_taps(weight.detach()).permute(1, 0, 2, 3).contiguous()      # [Cin, Cout, R, S]: dX = conv(dY, wt)
         p = ops.PackedConv(wt, None, None, stride=1, pad=R - 1 - pad, compute=F32)
         p.in_dil = stride
-        dx = torch.empty(dy.shape[0], in_hw[0], in_hw[1], p.Cout_eff, dtype=torch.float32, device=dy.device)
+        dx = _dgrad_out(out, (dy.shape[0], in_hw[0], in_hw[1], p.Cout_eff), dy)
         ops.conv2d(dy, p, out=dx)
         return dx if p.Cout_eff == Cin else dx[..., :Cin]
     if stride == 2 and R == 3 and S == 3 and pad == 1 and dy.shape[3] % (8 if comp == F16 else 16) == 0:
-        return _conv_dgrad_s2_phases(dy, weight, in_hw, comp)     # pads the operand to dy's channel count itself
+        return _conv_dgrad_s2_phases(dy, weight, in_hw, comp, out)     # pads the operand to dy's channel count itself
     wsrc = weight.detach()
     if comp == F16X3 and not (wsrc.dtype == torch.float32 and wsrc.is_contiguous()):
         wsrc = wsrc.float().contiguous()
     p = ops.PackedConv(wsrc, None, None, stride=1, pad=R - 1 - pad, compute=comp, tap_major=stride > 1,
                        transposed=True, cin_pad=cin_pad)
     p.in_dil = stride
-    B = dy.shape[0]
-    dx = torch.empty(B, in_hw[0], in_hw[1], p.Cout_eff, dtype=dy.dtype, device=dy.device)
+    dx = _dgrad_out(out, (dy.shape[0], in_hw[0], in_hw[1], p.Cout_eff), dy)
     ops.conv2d(dy, p, out=dx)
     return dx if p.Cout_eff == Cin else dx[..., :Cin]
 

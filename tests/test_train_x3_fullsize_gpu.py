@@ -2,15 +2,19 @@
 reference over the whole output.  The small-map tests of test_train_x3_gpu.py give every workgroup one tile and every
 BatchNorm reduction one block; the launchers size their grids from the CU count, so only maps this large reach the
 multi-tile loops (a window weight-gradient workgroup prefetching its next tile while it works on the current one), the
-many-rounds-per-CU scatter and the BatchNorm blocks that loop over row groups.  Each case first asserts, from a mirror of its
-launcher's formulas, that it reaches the regime it exists for: a launcher change then fails here instead of silently
-testing something smaller.
+many-rounds-per-CU scatter and the BatchNorm blocks that loop over row groups.  Each case first asserts that it reaches the
+regime it exists for -- the weight gradients from the label the launcher gives the real call in a dry run, the scatter and
+BatchNorm from a mirror of their launchers' formulas: a launcher change then fails here instead of silently testing something
+smaller.
 
 References are computed on the GPU in f64 without MIOpen: shifted-view matmuls for the convolutions, the plain formulas for
 BatchNorm, autograd through the oracle's sampler (on the CPU, sampled images) for the DCNv2 scatter."""
 import pytest
 import torch
 
+import conv_grad_cases as G
+from conv_grad_cases import dgrad_ref, wgrad_ref
+from detectron2_centernet_amd import _lib
 from oracle import ctdet_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -51,29 +55,26 @@ def cu_count():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def wgrad_regime(B, H, W, Cin, Cout, k, s, p, dy_stride=None):
-    """which weight-gradient kernel launch_conv_wgrad_t (train_bwd.hip) picks for an f16x3 layer (x dense NHWC, dY with
-    dy_stride channels per pixel), and how it splits the work: tiles, workgroups per pixel range (split), tiles / 64-pixel K
-    steps per workgroup"""
-    ncu = cu_count()
-    dy_stride = Cout if dy_stride is None else dy_stride
-    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    window = (s == 1 and p == k // 2 and H % 8 == 0 and W % 32 == 0 and Cin % 8 == 0 and dy_stride % 8 == 0
-              and B * H * W * max(Cin, dy_stride) * 4 < 2 ** 31)
-    if window and Cout <= 16 and ((k == 7 and Cin == 8) or (k == 3 and Cin == 16)):
-        tiles = B * (H // 8) * (W // 32)
-        split = min(ncu, tiles)
-        return dict(kernel="narrow", tiles=tiles, split=split, per=-(-tiles // split))
-    if window and k == 3 and Cin % 32 == 0:
-        gx, gy = Cin // 32, -(-Cout // 32)
-        tiles = B * (H // 8) * (W // 32)
-        split = min(max(1, ncu // (gx * gy)), tiles)
-        return dict(kernel="window", tiles=tiles, split=split, per=-(-tiles // split))
-    M = B * Ho * Wo
-    gx, gy = -(-k * k * Cin // 128), -(-Cout // 64)
-    split = max(1, min(max(1, 1024 // (gx * gy)), -(-M // 256)))
-    m_per = -(-(-(-M // split)) // 64) * 64
-    return dict(kernel="generic", M=M, split=split, per=m_per // 64)
+def wgrad_regime(T, x, dy, Cout, k, s, p):
+    """which weight-gradient kernel the launcher picks for ot.conv_wgrad(x, dy, ...) in f16x3 and how it splits the work, from
+    the label of the real call's dry run: kernel, workgroups per pixel range (split), tiles (window, narrow) or 64-pixel K steps
+    (generic) of the longest range -- the arithmetic of conv_grad_cases.pixel_ranges"""
+    ops, ot = T
+    L = _lib.lib()
+    L.ctdet_set_label_mode(2)
+    try:
+        ot.conv_wgrad(x, dy, Cout, k, k, s, p, scale=1.0, comp=ops.F16X3)
+        label = L.ctdet_last_kernel_label().decode()
+    finally:
+        L.ctdet_set_label_mode(0)
+    B, H, W, Cin = x.shape
+    row = G.Case("f16x3", "wgrad", B, H, W, Cin, Cout, k, s, p, 1, Cin, dy.shape[3], label, ())
+    kind = {"win": "window"}.get(G.kernel_kind(row), G.kernel_kind(row))
+    ranges, total = G.pixel_ranges(row)
+    per = max(hi - lo for lo, hi in ranges)
+    r = dict(kernel=kind, label=label, split=G.label_split(label)[1], per=per // 64 if kind == "generic" else per)
+    r["M" if kind == "generic" else "tiles"] = total
+    return r
 
 
 def col2im_regime(B, H, W):
@@ -92,30 +93,7 @@ def bn_regime(M, C):
 
 
 # ------------------------------------------------------------------------------------------ f64 references
-def wgrad_ref(x, dy, k, s, p):
-    """dW [Cout, k, k, Cin] of y = conv(x, W) in f64: one [Cout, M] @ [M, Cin] product per tap on shifted views of x"""
-    B, H, W, Cin = x.shape
-    _, Ho, Wo, Cout = dy.shape
-    xp = torch.nn.functional.pad(x.double(), (0, 0, p, p, p, p))
-    d = dy.double().reshape(-1, Cout).t()
-    ref = torch.empty(Cout, k, k, Cin, dtype=torch.float64, device=x.device)
-    for r in range(k):
-        for c in range(k):
-            ref[:, r, c] = d @ xp[:, r:r + s * Ho:s, c:c + s * Wo:s, :].reshape(-1, Cin)
-    return ref
-
-
-def dgrad_ref(dy, w, s, p, H, W):
-    """dX [B, H, W, Cin] in f64: every tap's dY @ W_tap added into the padded input at its shifted (strided) positions"""
-    B, Ho, Wo, Cout = dy.shape
-    Cin, k = w.shape[1], w.shape[2]
-    d = dy.double().reshape(-1, Cout)
-    w = w.double()
-    dxp = torch.zeros(B, H + 2 * p, W + 2 * p, Cin, dtype=torch.float64, device=dy.device)
-    for r in range(k):
-        for c in range(k):
-            dxp[:, r:r + s * Ho:s, c:c + s * Wo:s, :] += (d @ w[:, :, r, c]).view(B, Ho, Wo, Cin)
-    return dxp[:, p:p + H, p:p + W, :]
+# wgrad_ref / dgrad_ref: conv_grad_cases.py (checked there against torch double autograd by test_conv_grad_host.py)
 
 
 # ------------------------------------------------------------------------------------------ convolution layers of the step
@@ -137,16 +115,16 @@ LAYERS = {
 DGRAD_LAYERS = [n for n in LAYERS if "offset" not in n]
 
 
-def _layer_data(name, dev):
+def _layer_data(name, dev, T):
     B, H, W, Cin, Cout, k, s, p, kern, ok = LAYERS[name]
     Cd = (Cout + 7) // 8 * 8          # dY pixel stride: the offset conv's 27 couts arrive padded to 32 channels
-    r = wgrad_regime(B, H, W, Cin, Cout, k, s, p, Cd)
-    assert r["kernel"] == kern and ok(r), f"{name} no longer reaches its regime: {r}"
-    print(name, r)
     g = torch.Generator(device=dev).manual_seed(sum(LAYERS[name][:8]))
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     x = randn((B, H, W, Cin), g, dev).relu_() * 1.5 + randn((B, H, W, Cin), g, dev, 0.1)   # f32, not f16-representable
     dy = randn((B, Ho, Wo, Cd), g, dev)
+    r = wgrad_regime(T, x, dy, Cout, k, s, p)
+    assert r["kernel"] == kern and ok(r), f"{name} no longer reaches its regime: {r}"
+    print(name, r)
     return x, dy, (B, H, W, Cin, Cout, k, s, p), g
 
 
@@ -155,7 +133,7 @@ def test_fullsize_wgrad_x3_vs_f64(T, dev, name):
     """ot.conv_wgrad in f16x3 over the whole [Cout, k*k*Cin] gradient.  Bound: 2e-5 of the largest element (as the small
     test; f32 accumulation over these lengths contributes ~1e-6)"""
     ops, ot = T
-    x, dy, (B, H, W, Cin, Cout, k, s, p), _ = _layer_data(name, dev)
+    x, dy, (B, H, W, Cin, Cout, k, s, p), _ = _layer_data(name, dev, T)
     dw = ot.conv_wgrad(x, dy, Cout, k, k, s, p, scale=1.0, comp=ops.F16X3)
     check(dw.view(Cout, k, k, Cin), wgrad_ref(x, dy[..., :Cout], k, s, p), 2e-5, f"dW {name}")
 
@@ -165,8 +143,6 @@ def test_fullsize_wgrad_x3_dcn_columns_vs_f64(T, dev):
     columns [262144][576] from ot.dcn_cols"""
     ops, ot = T
     B, H, W, C = 16, 128, 128, 64
-    r = wgrad_regime(B, H, W, 9 * C, C, 1, 1, 0)
-    assert r["kernel"] == "generic" and r["per"] >= 16, r
     g = torch.Generator(device=dev).manual_seed(29)
     x = randn((B, H, W, C), g, dev)
     om = randn((B, H, W, 28), g, dev)
@@ -175,6 +151,8 @@ def test_fullsize_wgrad_x3_dcn_columns_vs_f64(T, dev):
     del x, om
     assert cols.dtype == torch.float32 and cols.shape == (B, H, W, 9 * C)
     dy = randn((B, H, W, C), g, dev)
+    r = wgrad_regime(T, cols, dy, C, 1, 1, 0)
+    assert r["kernel"] == "generic" and r["per"] >= 16, r
     dw = ot.conv_wgrad(cols, dy, C, 1, 1, 1, 0, scale=1.0, comp=ops.F16X3)
     ref = dy.double().reshape(-1, C).t() @ cols.double().reshape(-1, 9 * C)
     check(dw, ref, 2e-5, "dW of the DCN layer (1x1 over the columns)")
@@ -185,7 +163,7 @@ def test_fullsize_dgrad_x3_vs_f64(T, dev, name):
     """ot.conv_dgrad in f16x3 (stride 2: the four-phase 2x2 conv + depth_to_space2_kernel<float>) on the whole batch; the
     f64 reference per 4-image slice.  Bound: 2e-5 of the largest element"""
     ops, ot = T
-    x, dy, (B, H, W, Cin, Cout, k, s, p), g = _layer_data(name, dev)
+    x, dy, (B, H, W, Cin, Cout, k, s, p), g = _layer_data(name, dev, T)
     del x
     w = randn((Cout, Cin, k, k), g, dev, 1.0 / (Cin * k * k) ** 0.5)
     dx = ot.conv_dgrad(dy, w, s, p, (H, W), comp=ops.F16X3)
