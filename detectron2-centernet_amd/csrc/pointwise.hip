@@ -660,7 +660,9 @@ int launch_pack_weights(const float* w, void* out, int O, int I, int R, int S, i
 int launch_dwconvT_add(const void* x, const float* w, const void* skip, void* y, int dtype, int B, int H, int W, int C,
                        int f, int in_stride, int skip_stride, int out_stride, hipStream_t s) {
   const int N = dtype == CTDET_F16 ? 8 : 4;
-  CTDET_CHECK(f >= 1 && (f == 1 || f % 2 == 0), "dwconvT: up factor %d unsupported", f);
+  // f = 1 is refused, as in launch_dwconvT_bwd: ConvTranspose2d(k=2, s=1, p=0) has H + 1 rows, not H * f, and no IDAUp builds
+  // it (the factor-1 input of every IDAUp is its first, which has no up_i: dla.py:129-131)
+  CTDET_CHECK(f >= 2 && f % 2 == 0, "dwconvT: up factor %d unsupported", f);
   CTDET_CHECK(C % N == 0 && in_stride % N == 0 && out_stride % N == 0 && (!skip || skip_stride % N == 0),
               "dwconvT: channels must be multiples of %d", N);
   const long total = (long)B * H * f * W * f * (C / N);
