@@ -117,6 +117,8 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_cocoeval_accumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp,
                                          _vp, _vp, _vp, _vp]),
+    "ctdet_resize_bilinear_u8": (_i32, [_vp, _vp, _vp]),
+    "ctdet_resize_bilinear_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "ctdet_set_tuning_flags": (_i32, [C.c_uint32]),
     "ctdet_get_tuning_flags": (C.c_uint32, []),
     "ctdet_comm_unique_id": (_i32, [_vp]),
@@ -171,6 +173,13 @@ class DlaBaseDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Hp", C.c_int32), ("Wp", C.c_int32),
                 ("img_dtype", C.c_int32), ("img_batch_stride", C.c_int64), ("mean", C.c_float * 3), ("std", C.c_float * 3),
                 ("out_stride", C.c_int32), ("pool_stride", C.c_int32)]
+
+
+class ResizeDesc(C.Structure):
+    """mirrors ctdet_resize_desc (ops.RESIZE_DESC_DTYPE is the same layout as a numpy record)"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int64) for n in (
+        "src_row", "src_pix", "src_chan", "dst_row", "dst_pix", "dst_chan")] + [(n, C.c_int32) for n in (
+        "H", "W", "new_h", "new_w", "hb", "hc", "vb", "vc", "kh", "kv", "blk0", "pad_")]
 
 
 class HeadDesc(C.Structure):

@@ -77,6 +77,10 @@ _C.INPUT.MIN_SIZE_TEST = 800
 _C.INPUT.MAX_SIZE_TEST = 1333
 _C.INPUT.FORMAT = "BGR"
 _C.INPUT.MASK_FORMAT = "polygon"
+# not in the reference (its mapper resizes on the host with Pillow): True = the test-time mapper leaves the image as read and
+# the model resizes it on the device, bit for bit what the host resize gives (ops.resize_u8).  The training
+# mapper refuses it: its colour jitters run after the resize
+_C.INPUT.DEVICE_RESIZE = False
 
 _C.DATASETS = CN()
 _C.DATASETS.TRAIN = ()

@@ -848,6 +848,26 @@ int32_t ctdet_adam_runs(float* param, const float* grad, float* exp_avg, float* 
                           run_lr_index, run_weight_decay, lr_table, nruns, bias_dev, beta1, beta2, eps, decoupled, amsgrad,
                           clip_type, clip_value, coefs, (hipStream_t)stream);
 }
+
+int32_t ctdet_resize_bilinear_u8(const ctdet_resize_desc* d, const int32_t* tables_dev, void* stream) {
+  CTDET_CHECK(d && d->src && d->dst, "resize_bilinear_u8: null pointer");
+  CTDET_CHECK(d->H >= 1 && d->W >= 1 && d->new_h >= 1 && d->new_w >= 1, "resize_bilinear_u8: %dx%d -> %dx%d", d->H, d->W,
+              d->new_h, d->new_w);
+  CTDET_CHECK(d->kh >= 0 && d->kv >= 0 && (d->kh > 0 || d->W == d->new_w) && (d->kv > 0 || d->H == d->new_h),
+              "resize_bilinear_u8: kh=%d kv=%d: a pass may be skipped only when its size does not change", d->kh, d->kv);
+  CTDET_CHECK(tables_dev || (d->kh == 0 && d->kv == 0), "resize_bilinear_u8: null table buffer");
+  CTDET_CHECK(d->kh == 0 || (d->hb >= 0 && d->hc >= 0), "resize_bilinear_u8: negative table offset");
+  CTDET_CHECK(d->kv == 0 || (d->vb >= 0 && d->vc >= 0), "resize_bilinear_u8: negative table offset");
+  return launch_resize_u8(*d, tables_dev, (hipStream_t)stream);
+}
+
+int32_t ctdet_resize_bilinear_u8_batch(const ctdet_resize_desc* descs_dev, int32_t n, int32_t total_blocks,
+                                       const int32_t* tables_dev, void* stream) {
+  CTDET_CHECK(descs_dev && tables_dev, "resize_bilinear_u8_batch: null pointer");
+  CTDET_CHECK(n >= 0 && total_blocks >= 0, "resize_bilinear_u8_batch: n=%d total_blocks=%d", n, total_blocks);
+  if (n == 0 || total_blocks == 0) return 0;
+  return launch_resize_u8_batch(descs_dev, n, total_blocks, tables_dev, (hipStream_t)stream);
+}
 #undef CTDET_ADAM_BETAS
 #undef CTDET_DCN_MASK_MODE
 

@@ -293,6 +293,12 @@ int launch_pack_weights_x3_batch(const void* table_dev, int n, int total_blocks,
 int launch_dwconvT_add(const void* x, const float* w, const void* skip, void* y, int dtype, int B, int H, int W, int C,
                        int f, int in_stride, int skip_stride, int out_stride, hipStream_t s);
 
+// resize.hip
+struct ctdet_resize_desc;                                    // include/ctdet_hip.h
+int resize_tiles(int new_h, int new_w);                      // blocks of one image
+int launch_resize_u8(const ctdet_resize_desc& d, const int* tab, hipStream_t s);
+int launch_resize_u8_batch(const ctdet_resize_desc* descs_dev, int n, int total_blocks, const int* tab, hipStream_t s);
+
 // dwconv.hip
 // shape / dtype checks shared by the entry points (api.hip validates pointers first)
 int dwconv3x3_check(int dtype, int B, int H, int W, int C, int stride, const int* strides, int nstrides);

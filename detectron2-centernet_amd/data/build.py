@@ -1,5 +1,6 @@
-"""Training sampler and a minimal batched loader (reference: data/samplers/distributed_sampler.py:12-55 TrainingSampler,
-data/build.py:270-355 build_detection_train_loader / per-GPU batch size).  The GPU path takes `list[dict]` batches of unequal image sizes as they come."""
+"""Training and inference samplers and minimal batched loaders (reference: data/samplers/distributed_sampler.py:12-55
+TrainingSampler, :172-199 InferenceSampler, data/build.py:270-355 build_detection_train_loader / per-GPU batch size, :358-403
+build_detection_test_loader).  The GPU path takes `list[dict]` batches of unequal image sizes as they come."""
 import itertools
 import torch
 
@@ -25,6 +26,21 @@ class TrainingSampler:
                 yield from torch.randperm(self._size, generator=g).tolist()
             else:
                 yield from range(self._size)
+
+
+class InferenceSampler:
+    """every index once, in order: rank r of W takes r, r + W, r + 2W, ... (the reference hands each rank one contiguous
+    shard; a strided split keeps the ranks within one image of each other for any dataset size)"""
+
+    def __init__(self, size, rank=0, world_size=1):
+        assert size > 0 and 0 <= rank < world_size
+        self._indices = range(rank, size, world_size)
+
+    def __iter__(self):
+        yield from self._indices
+
+    def __len__(self):
+        return len(self._indices)
 
 
 def filter_images_with_only_crowd_annotations(dataset_dicts):
@@ -79,3 +95,18 @@ def build_detection_train_loader(cfg, mapper=None, rank=0, world_size=1, seed=0,
                                          collate_fn=_trivial_batch_collator,
                                          worker_init_fn=_worker_init_reset_seed if workers > 0 else None)
     return iter(loader)
+
+
+def build_detection_test_loader(cfg, dataset_name, mapper=None, rank=0, world_size=1, num_workers=None):
+    """loader over `dataset_name` for inference (data/build.py:358-403): every record once and in order (InferenceSampler),
+    nothing filtered, lists of TEST.BATCH_SIZE mapped samples (the last one shorter).  The default mapper is
+    TrafficLightDatasetMapper(cfg, False): with INPUT.DEVICE_RESIZE its records carry the raw image and the model resizes
+    the batch on the device."""
+    dicts = list(DatasetCatalog.get(dataset_name))
+    assert len(dicts), f"dataset '{dataset_name}' is empty"
+    mapper = mapper if mapper is not None else TrafficLightDatasetMapper(cfg, False)
+    sampler = InferenceSampler(len(dicts), rank=rank, world_size=world_size)
+    workers = cfg.DATALOADER.NUM_WORKERS if num_workers is None else num_workers
+    batch_sampler = torch.utils.data.BatchSampler(sampler, int(cfg.TEST.BATCH_SIZE), drop_last=False)
+    return torch.utils.data.DataLoader(_MapDataset(dicts, mapper), batch_sampler=batch_sampler, num_workers=workers,
+                                       collate_fn=_trivial_batch_collator)

@@ -2,7 +2,11 @@
 input one Detectron2 dataset dict; output a copy with "image" (uint8 CHW tensor, channel order INPUT.FORMAT) and, when
 training, "instances" (gt_boxes XYXY in the resized image, gt_classes int64; crowd and empty boxes removed); the
 "annotations" list is consumed.  Pipeline: read -> ResizeShortestEdge -> four colour jitters, each applied with probability
-0.15 (training only) -> boxes through the same transform list."""
+0.15 (training only) -> boxes through the same transform list.
+
+INPUT.DEVICE_RESIZE (test time only): the resize is left to the model.  The record then carries "image_raw" (the uint8 HWC
+array as read, channel order INPUT.FORMAT) and "resize_hw" (the size ResizeShortestEdge would have resized it to) instead
+of "image"; CenterNet resizes the whole batch in one launch (ops.resize_u8) to the very bytes the host resize produces."""
 import copy
 
 import numpy as np
@@ -41,6 +45,10 @@ class TrafficLightDatasetMapper:
         if is_train and crop is not None and getattr(crop, "ENABLED", False):
             raise NotImplementedError("INPUT.CROP is off in the CenterNet configs and not built")
         self.is_train = is_train
+        self.device_resize = bool(getattr(cfg.INPUT, "DEVICE_RESIZE", False))
+        if self.device_resize and is_train:
+            raise NotImplementedError("INPUT.DEVICE_RESIZE is a test-time switch: the training pipeline's colour jitters follow the "
+                                      "resize on the host (build the training mapper with INPUT.DEVICE_RESIZE False)")
         self.img_format = cfg.INPUT.FORMAT
         self.augmentation = bulb_traffic_light_augmentation(cfg, is_train)
 
@@ -56,6 +64,16 @@ class TrafficLightDatasetMapper:
 
     def __call__(self, dataset_dict):
         record = copy.deepcopy(dataset_dict)       # the caller's dict (shared by every epoch) is never modified
+        if self.device_resize:
+            pixels = du.read_image(record["file_name"], format=self.img_format)
+            du.check_image_size(record, pixels)
+            resize = self.augmentation[0]
+            record["image_raw"] = np.ascontiguousarray(pixels)
+            size = int(resize.short_edge_length[0])      # test time: one size ("choice" of MIN_SIZE_TEST); 0 = no resize
+            record["resize_hw"] = (resize.output_size(pixels.shape[0], pixels.shape[1], size, resize.max_size) if size
+                                   else tuple(pixels.shape[:2]))
+            record.pop("annotations", None)
+            return record
         pixels, transforms = self._image(record)
         record["image"] = torch.as_tensor(np.ascontiguousarray(pixels.transpose(2, 0, 1)))
         annotations = record.pop("annotations", None)

@@ -1,4 +1,5 @@
+from .defaults import DefaultPredictor
 from .launch import launch
 from .train_loop import SimpleTrainer
 
-__all__ = ["SimpleTrainer", "launch"]
+__all__ = ["DefaultPredictor", "SimpleTrainer", "launch"]

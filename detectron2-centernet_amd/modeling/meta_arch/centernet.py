@@ -492,6 +492,11 @@ class CenterNet(nn.Module):
         dev = self.device
         if dev.type != "cuda":
             raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
+        if "image_raw" in batched_inputs[0]:
+            staged = self._stage_raw(batched_inputs, flip)
+            if isinstance(staged, tuple):
+                return self._finish_eval(*staged)
+            return self._raw_ragged(batched_inputs, staged, flip)
         imgs = [x["image"] for x in batched_inputs]
         sizes = [tuple(im.shape[-2:]) for im in imgs]
         B = len(imgs)
@@ -512,6 +517,11 @@ class CenterNet(nn.Module):
         `forward` returns.  Same-size images go through the captured engine (one step in flight is safe: the engine's
         post-processing writes fresh tensors per step); ragged batches run eagerly and come back already finished."""
         assert not self.training
+        if "image_raw" in batched_inputs[0]:
+            staged = self._stage_raw(batched_inputs, flip)
+            if isinstance(staged, tuple):
+                return self._launch_eval(*staged)
+            return _Done(self._raw_ragged(batched_inputs, staged, flip))
         imgs = [x["image"] for x in batched_inputs]
         sizes = [tuple(im.shape[-2:]) for im in imgs]
         if not (all(s == sizes[0] for s in sizes) and all(im.dtype == imgs[0].dtype for im in imgs)):
@@ -524,6 +534,38 @@ class CenterNet(nn.Module):
         for b, im in enumerate(imgs):
             stage[b].copy_(im if im.dtype == img_dtype else im.to(img_dtype), non_blocking=True)
         return self._launch_eval(eng, batched_inputs, sizes)
+
+    def _stage_raw(self, batched_inputs, flip=False):
+        """records of a mapper built with INPUT.DEVICE_RESIZE: "image_raw" (uint8 HWC, host array or tensor, or a device
+        tensor) and "resize_hw".  The raw images go to the device in one pinned copy and ONE launch (ops.resize_u8) resizes
+        them, to the bytes the host mapper's Pillow resize gives.  All targets equal: straight into the staging batch of the
+        captured engine -> (engine, batched_inputs, sizes), what _launch_eval takes.  Otherwise: the list of resized [3,h,w]
+        device tensors, for the ragged path."""
+        if self.device.type != "cuda":
+            raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
+        missing = [i for i, x in enumerate(batched_inputs) if "image_raw" not in x or "resize_hw" not in x]
+        if missing:
+            raise KeyError(f"record {missing[0]} of a raw batch lacks 'image_raw' / 'resize_hw': a batch is raw or resized as a whole")
+        raws = []
+        for x in batched_inputs:
+            raw = x["image_raw"]
+            assert raw.ndim == 3 and raw.shape[2] == 3, f"image_raw is uint8 [H, W, 3], got {tuple(raw.shape)}"
+            raws.append(raw.permute(2, 0, 1) if isinstance(raw, torch.Tensor) else raw.transpose(2, 0, 1))
+        sizes = [(int(x["resize_hw"][0]), int(x["resize_hw"][1])) for x in batched_inputs]
+        if any(s != sizes[0] for s in sizes):
+            return ops.resize_u8(raws, sizes, device=self.device)
+        H, W = sizes[0]
+        Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
+        eng = self._engine(len(raws), H, W, Hp, Wp, torch.uint8, flip)
+        stage = eng.staging(H, W)
+        ops.resize_u8(raws, sizes, outs=[stage[b] for b in range(len(raws))])
+        return eng, batched_inputs, sizes
+
+    def _raw_ragged(self, batched_inputs, resized, flip):
+        """raw records with more than one target size: the device-resized images through the ragged path"""
+        sizes = [tuple(im.shape[-2:]) for im in resized]
+        Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
+        return self._forward_eval_ragged(batched_inputs, resized, sizes, Hp, Wp, flip)
 
     def infer_batch_tensor(self, images, out_sizes=None, flip=False):
         """Fast path for an already-batched device tensor [B,3,H,W] (uint8 or float32, 0..255): the DLA base kernel reads

@@ -9,6 +9,7 @@ import ctypes as C
 import os
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -756,6 +757,163 @@ def preprocess(images, mean, std, Hp, Wp, out_dtype=torch.float16, out=None, par
                                                 images.stride(0), m, s, _nhwc_stride(out), int(border), mfrom, _stream())
     _lib.check(rc, "ctdet_preprocess")
     return out
+
+
+# ---------------------------------------------------------------------------------- uint8 bilinear resize (csrc/resize.hip)
+RESIZE_TW, RESIZE_RB = 64, 8      # output columns / rows of one block (csrc/resize.hip)
+# ctdet_resize_desc as a numpy record: the descriptors of a batch are one array, uploaded as it is
+RESIZE_DESC_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8")]
+                             + [(n, "<i8") for n in ("src_row", "src_pix", "src_chan", "dst_row", "dst_pix", "dst_chan")]
+                             + [(n, "<i4") for n in ("H", "W", "new_h", "new_w", "hb", "hc", "vb", "vc", "kh", "kv", "blk0", "pad_")])
+assert RESIZE_DESC_DTYPE.itemsize == C.sizeof(_lib.ResizeDesc)
+
+
+class _ResizeArena:
+    """pinned host buffer a resize call assembles its one upload in (descriptors, tables, host images); re-used by the next
+    call once the copy out of it has finished"""
+
+    def __init__(self):
+        self.host, self.event = None, None
+
+    def take(self, nbytes):
+        if self.event is not None:
+            self.event.synchronize()      # waits for the previous upload only, not for the kernels behind it
+        if self.host is None or self.host.numel() < nbytes:
+            self.host = torch.empty(max(round_up(nbytes, 1 << 20), 1 << 20), dtype=torch.uint8, pin_memory=True)
+        return self.host
+
+    def uploaded(self):
+        if self.event is None:
+            self.event = torch.cuda.Event()
+        self.event.record()
+
+
+_RESIZE_ARENA = _ResizeArena()
+
+
+def _u8_view(img):
+    """an image given as a logical [3, H, W] uint8 view -> (device pointer or None, host block or None, offset of element
+    [0,0,0] in that block, H, W, (row, pixel, channel) byte strides).  Host images (numpy arrays -- strides of either sign --
+    or CPU tensors) come back with the dense block of memory they live in, in its own order: an HWC image stays HWC."""
+    if isinstance(img, torch.Tensor):
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[0] == 3, (img.dtype, tuple(img.shape))
+        if img.is_cuda:
+            st = img.stride()
+            return img.data_ptr(), None, 0, img.shape[1], img.shape[2], (st[1], st[2], st[0])
+        img = img.numpy()
+    assert isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.ndim == 3 and img.shape[0] == 3, (
+        "resize_u8 takes logical [3, H, W] uint8 views (an HWC array a: a.transpose(2, 0, 1))")
+    lo = sum((n - 1) * st for n, st in zip(img.shape, img.strides) if st < 0)
+    hi = sum((n - 1) * st for n, st in zip(img.shape, img.strides) if st > 0)
+    if hi - lo + 1 != img.size:      # a crop or a strided view: its own dense copy
+        img = np.ascontiguousarray(img)
+        lo = 0
+    block = np.frombuffer((C.c_uint8 * img.size).from_address(img.ctypes.data + lo), dtype=np.uint8)
+    st = img.strides
+    return None, (block, img), -lo, img.shape[1], img.shape[2], (st[1], st[2], st[0])
+
+
+class ResizeLaunch:
+    """one prepared resize of a list of images (resize_u8_prepare): the uploaded descriptors, tables and host images, and the
+    destinations.  launch() may be repeated: it reads the same sources and writes the same destinations again."""
+
+    def __init__(self, dev, desc, tab_at, blocks, outs):
+        self.dev, self.desc, self.tab_at, self.blocks, self.outs = dev, desc, tab_at, blocks, outs
+
+    def launch(self):
+        n, tab = len(self.desc), C.c_void_p(self.dev.data_ptr() + self.tab_at)
+        with torch.cuda.device(self.dev.device):
+            if n == 1:      # the one-image entry point: the descriptor travels as a kernel argument
+                one = _lib.ResizeDesc.from_buffer_copy(self.desc[0].tobytes())
+                rc = _lib.lib().ctdet_resize_bilinear_u8(C.byref(one), tab, _stream())
+            else:
+                rc = _lib.lib().ctdet_resize_bilinear_u8_batch(C.c_void_p(self.dev.data_ptr()), n, self.blocks, tab, _stream())
+        _lib.check(rc, "ctdet_resize_bilinear_u8")
+        return self.outs
+
+
+def resize_u8(images, sizes, outs=None, device=None):
+    """Pillow's 8-bit bilinear resize (what data.transforms.ResizeTransform.apply_image computes on the host) of a list of
+    3-channel images on the device, bit for bit, in ONE launch whatever their sizes.
+
+    images: logical [3, H, W] uint8 views with any strides -- a device or CPU tensor, or a numpy array; an HWC image is
+      `a.transpose(2, 0, 1)` / `t.permute(2, 0, 1)`, a reversed channel order `a[::-1]` of a numpy view (stride -1).  Host images
+      travel to the device inside this call's single upload, in their own memory order.
+    sizes: (new_h, new_w) per image.  outs: device uint8 views [3, new_h, new_w] with any strides (a window of a staging
+      batch); None: fresh CHW tensors.  Returns outs.
+    One host-to-device copy per call carries the descriptors, the coefficient tables (data.resample.bilinear_tables, cached
+    per (in, out) pair and shared by the images of the call) and the host images."""
+    if len(images) == 0:
+        return []
+    return resize_u8_prepare(images, sizes, outs, device).launch()
+
+
+def resize_u8_prepare(images, sizes, outs=None, device=None):
+    """everything of resize_u8 but the launch: a ResizeLaunch"""
+    from .data import resample
+    n = len(images)
+    assert n >= 1 and n == len(sizes) and (outs is None or len(outs) == n)
+    views = [_u8_view(im) for im in images]
+    if device is None:
+        device = outs[0].device if outs is not None else next((im.device for im in images if isinstance(im, torch.Tensor) and im.is_cuda),
+                                                                torch.device("cuda", torch.cuda.current_device()))
+    if outs is None:
+        outs = [torch.empty(3, int(nh), int(nw), dtype=torch.uint8, device=device) for nh, nw in sizes]
+    desc = np.zeros(n, dtype=RESIZE_DESC_DTYPE)
+    tables, placed, words = [], {}, 0
+
+    def place(in_size, out_size):
+        """(bounds offset, coeffs offset, entries per coefficient row) of the axis' tables in this call's buffer"""
+        nonlocal words
+        hit = placed.get((in_size, out_size))
+        if hit is None:
+            bounds, coeffs = resample.bilinear_tables(in_size, out_size)
+            hit = placed[(in_size, out_size)] = (words, words + bounds.size, coeffs.shape[1])
+            tables.extend((bounds.reshape(-1), coeffs.reshape(-1)))
+            words += bounds.size + coeffs.size
+        return hit
+
+    blocks = 0
+    for i, ((ptr, host, org, H, W, st), (nh, nw), out) in enumerate(zip(views, sizes, outs)):
+        nh, nw = int(nh), int(nw)
+        assert nh >= 1 and nw >= 1 and H >= 1 and W >= 1, (H, W, nh, nw)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (3, nh, nw), (
+            f"image {i}: the destination must be a device uint8 view [3, {nh}, {nw}], got {tuple(out.shape)} {out.dtype} on {out.device}")
+        d = desc[i]
+        d["dst"] = out.data_ptr()
+        d["dst_row"], d["dst_pix"], d["dst_chan"] = out.stride(1), out.stride(2), out.stride(0)
+        d["src_row"], d["src_pix"], d["src_chan"] = st
+        d["H"], d["W"], d["new_h"], d["new_w"] = H, W, nh, nw
+        if W != nw:
+            d["hb"], d["hc"], d["kh"] = place(W, nw)
+        if H != nh:
+            d["vb"], d["vc"], d["kv"] = place(H, nh)
+        d["blk0"] = blocks
+        blocks += -(-nw // RESIZE_TW) * -(-nh // RESIZE_RB)
+    assert blocks < 2 ** 31 and words < 2 ** 31
+    # the call's upload: [descriptors][tables][host images], each part 16-byte aligned
+    tab_at = round_up(desc.nbytes, 16)
+    total = round_up(tab_at + 4 * max(words, 1), 16)
+    host_at = []
+    for ptr, host, org, H, W, st in views:
+        host_at.append(total)
+        if host is not None:
+            total = round_up(total + host[0].size, 16)
+    arena = _RESIZE_ARENA.take(total)
+    dev = torch.empty(total, dtype=torch.uint8, device=device)
+    staged = arena.numpy()
+    for i, (ptr, host, org, H, W, st) in enumerate(views):
+        if host is not None:
+            staged[host_at[i]:host_at[i] + host[0].size] = host[0]
+            ptr = dev.data_ptr() + host_at[i] + org
+        desc["src"][i] = ptr
+    if tables:
+        staged[tab_at:tab_at + 4 * words] = np.concatenate(tables).view(np.uint8)
+    staged[:desc.nbytes] = desc.view(np.uint8)
+    with torch.cuda.device(device):
+        dev.copy_(arena[:total], non_blocking=True)
+        _RESIZE_ARENA.uploaded()
+    return ResizeLaunch(dev, desc, tab_at, blocks, outs)
 
 
 class PackedDlaBase:

@@ -641,6 +641,35 @@ int32_t ctdet_cocoeval_accumulate(const float* scores, const int32_t* classes, c
                                   const double* rec_thrs, int32_t R, const int32_t* max_dets, int32_t M, int32_t max_det,
                                   void* workspace, double* precision, double* scores_out, double* recall, void* stream);
 
+/* ---- uint8 bilinear resize, Pillow's arithmetic bit for bit ---------------------------------------------------------
+ * What the host data mapper's ResizeShortestEdge computes (PIL.Image.resize(..., BILINEAR) on an 8-bit, 3-channel image), on the
+ * device: a horizontal pass, its result rounded and clipped to a byte, then a vertical pass over those bytes; both accumulate
+ * byte * coefficient in int32 from 1 << 21, shift right by 22 and clip to [0, 255].  The coefficients are 22-bit fixed-point
+ * triangle weights in a DEVICE int32 table buffer the caller fills (data/resample.py: bilinear_tables); per axis
+ *   bounds [out][2] = {first source index, tap count}, first + count <= source size (the kernel clamps, it never reads outside),
+ *   coeffs [out][k] with k = kh (horizontal) or kv (vertical) entries per output index, zero padded.
+ * kh = 0 / kv = 0: that pass is skipped (W == new_w / H == new_h) and its table offsets are unused.
+ * Every address is base + row * row_stride + column * pix_stride + channel * chan_stride in BYTES, strides of either sign:
+ * HWC images (W*3, 3, 1), CHW planes (W, 1, H*W), a reversed channel order (base at channel 2, chan_stride -1), a window of a
+ * larger buffer.  Only the new_h x new_w x 3 bytes of the destination window are written.  No alignment is required.  Source
+ * and destination must not overlap.  One launch each; graph-capturable.
+ *
+ * ctdet_resize_bilinear_u8: one image, `desc` in HOST memory (blk0 ignored).
+ * ctdet_resize_bilinear_u8_batch: n images of any sizes in ONE launch, `descs_dev` in DEVICE memory, sorted by blk0 = the
+ *   number of blocks of the descriptors before it, ceil(new_w / 64) * ceil(new_h / 8) each; total_blocks = their sum. */
+typedef struct ctdet_resize_desc {
+  const void* src; void* dst;
+  int64_t src_row, src_pix, src_chan;   /* byte strides of the source */
+  int64_t dst_row, dst_pix, dst_chan;   /* byte strides of the destination */
+  int32_t H, W, new_h, new_w;
+  int32_t hb, hc, vb, vc;               /* offsets (int32 elements) of the horizontal bounds / coeffs and the vertical ones */
+  int32_t kh, kv;                       /* entries per row of the two coefficient tables; 0: the pass is skipped */
+  int32_t blk0, pad_;
+} ctdet_resize_desc;
+int32_t ctdet_resize_bilinear_u8(const ctdet_resize_desc* desc, const int32_t* tables_dev, void* stream);
+int32_t ctdet_resize_bilinear_u8_batch(const ctdet_resize_desc* descs_dev, int32_t n, int32_t total_blocks,
+                                       const int32_t* tables_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
