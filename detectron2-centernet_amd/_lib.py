@@ -119,6 +119,8 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp]),
     "ctdet_resize_bilinear_u8": (_i32, [_vp, _vp, _vp]),
     "ctdet_resize_bilinear_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "ctdet_byte_sum_u8_batch": (_i32, [_vp, _i32, _vp, _i32, _vp]),
+    "ctdet_colour_jitter_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "ctdet_set_tuning_flags": (_i32, [C.c_uint32]),
     "ctdet_get_tuning_flags": (C.c_uint32, []),
     "ctdet_comm_unique_id": (_i32, [_vp]),
@@ -180,6 +182,13 @@ class ResizeDesc(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int64) for n in (
         "src_row", "src_pix", "src_chan", "dst_row", "dst_pix", "dst_chan")] + [(n, C.c_int32) for n in (
         "H", "W", "new_h", "new_w", "hb", "hc", "vb", "vc", "kh", "kv", "blk0", "pad_")]
+
+
+class JitterDesc(C.Structure):
+    """mirrors ctdet_jitter_desc (ops.JITTER_DESC_DTYPE is the same layout as a numpy record)"""
+    _fields_ = [("img", C.c_void_p)] + [(n, C.c_int64) for n in ("row", "pix", "chan")] + [(n, C.c_int32) for n in (
+        "h", "w", "blk0", "sum_slot")] + [("on", C.c_int32 * 4)] + [(n, C.c_double * 2) for n in (
+        "contrast", "brightness", "saturation")] + [("lighting", C.c_double * 3)]
 
 
 class HeadDesc(C.Structure):

@@ -81,6 +81,10 @@ _C.INPUT.MASK_FORMAT = "polygon"
 # the model resizes it on the device, bit for bit what the host resize gives (ops.resize_u8).  The training
 # mapper refuses it: its colour jitters run after the resize
 _C.INPUT.DEVICE_RESIZE = False
+# not in the reference either: True = the TRAINING mapper leaves resize and colour jitters to the model.  Its records carry the
+# raw image, the size and the jitter draws it made (the host pipeline's draws, in its order); CenterNet.stage_raw_train produces
+# the bytes the host pipeline gives from them (ops.resize_u8, ops.colour_jitter_u8).  The test-time mapper ignores it.
+_C.INPUT.DEVICE_AUGMENT = False
 
 _C.DATASETS = CN()
 _C.DATASETS.TRAIN = ()

@@ -868,6 +868,24 @@ int32_t ctdet_resize_bilinear_u8_batch(const ctdet_resize_desc* descs_dev, int32
   if (n == 0 || total_blocks == 0) return 0;
   return launch_resize_u8_batch(descs_dev, n, total_blocks, tables_dev, (hipStream_t)stream);
 }
+
+int32_t ctdet_byte_sum_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t n, uint64_t* sums_dev, int32_t n_sums, void* stream) {
+  CTDET_CHECK(n >= 0 && n < (1 << 24) && n_sums >= 0, "byte_sum_u8_batch: n=%d n_sums=%d", n, n_sums);
+  if (n_sums == 0) return 0;
+  CTDET_CHECK(sums_dev && ((uintptr_t)sums_dev & 7) == 0, "byte_sum_u8_batch: the sums must be a non-null, 8-byte aligned buffer");
+  CTDET_CHECK(descs_dev || n == 0, "byte_sum_u8_batch: null descriptor table");
+  return launch_byte_sum_u8_batch(descs_dev, n, sums_dev, n_sums, (hipStream_t)stream);
+}
+
+int32_t ctdet_colour_jitter_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t n, int32_t total_blocks, const uint64_t* sums_dev,
+                                     int32_t n_sums, void* stream) {
+  CTDET_CHECK(n >= 0 && total_blocks >= 0 && n_sums >= 0, "colour_jitter_u8_batch: n=%d total_blocks=%d n_sums=%d", n, total_blocks,
+              n_sums);
+  if (n == 0 || total_blocks == 0) return 0;      // nothing was drawn: nothing is launched
+  CTDET_CHECK(descs_dev, "colour_jitter_u8_batch: null descriptor table");
+  CTDET_CHECK(n_sums == 0 || sums_dev, "colour_jitter_u8_batch: n_sums=%d without a sums buffer", n_sums);
+  return launch_colour_jitter_u8_batch(descs_dev, n, total_blocks, sums_dev, n_sums, (hipStream_t)stream);
+}
 #undef CTDET_ADAM_BETAS
 #undef CTDET_DCN_MASK_MODE
 

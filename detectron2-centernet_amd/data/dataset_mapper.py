@@ -6,7 +6,14 @@ training, "instances" (gt_boxes XYXY in the resized image, gt_classes int64; cro
 
 INPUT.DEVICE_RESIZE (test time only): the resize is left to the model.  The record then carries "image_raw" (the uint8 HWC
 array as read, channel order INPUT.FORMAT) and "resize_hw" (the size ResizeShortestEdge would have resized it to) instead
-of "image"; CenterNet resizes the whole batch in one launch (ops.resize_u8) to the very bytes the host resize produces."""
+of "image"; CenterNet resizes the whole batch in one launch (ops.resize_u8) to the very bytes the host resize produces.
+
+INPUT.DEVICE_AUGMENT (training only): resize AND colour jitters are left to the model.  The mapper decodes the image and makes
+exactly the random draws of the host pipeline, in its order, from numpy's global RNG -- the size draw, per jitter the
+apply-or-not uniform and, when it applies, its weight (or lighting's normal(size=3)); none of them depends on a pixel.  The
+record carries "image_raw" (uint8 HWC torch tensor: shared memory across the loader's worker boundary), "resize_hw", "jitter"
+(float64 [4, 4] tensor, data/jitter.py) and "instances" (the boxes through the resize alone: a colour transform moves no
+coordinate).  CenterNet.stage_raw_train turns a batch of them into the bytes the host pipeline gives from the same draws."""
 import copy
 
 import numpy as np
@@ -14,6 +21,7 @@ import torch
 
 from . import detection_utils as du
 from . import transforms as T
+from .jitter import JITTER_ORDER, empty_spec
 
 # colour jitters of the training pipeline (:36-43 of the reference mapper): (augmentation, constructor arguments)
 _COLOUR_JITTER = ((T.RandomContrast, (0.8, 1.2)), (T.RandomBrightness, (0.8, 1.2)), (T.RandomSaturation, (0.8, 1.2)),
@@ -48,9 +56,17 @@ class TrafficLightDatasetMapper:
         self.device_resize = bool(getattr(cfg.INPUT, "DEVICE_RESIZE", False))
         if self.device_resize and is_train:
             raise NotImplementedError("INPUT.DEVICE_RESIZE is a test-time switch: the training pipeline's colour jitters follow the "
-                                      "resize on the host (build the training mapper with INPUT.DEVICE_RESIZE False)")
+                                      "resize on the host (build the training mapper with INPUT.DEVICE_RESIZE False; "
+                                      "INPUT.DEVICE_AUGMENT moves the training resize and the jitters to the device)")
+        self.device_augment = bool(getattr(cfg.INPUT, "DEVICE_AUGMENT", False)) and is_train      # test time: ignored
         self.img_format = cfg.INPUT.FORMAT
         self.augmentation = bulb_traffic_light_augmentation(cfg, is_train)
+        if self.device_augment:
+            order = tuple(type(a.aug).__name__ for a in self.augmentation[1:])
+            if order != JITTER_ORDER:
+                raise NotImplementedError(
+                    f"INPUT.DEVICE_AUGMENT: the device kernel applies {', '.join(JITTER_ORDER)} in that order (contrast first: its "
+                    f"mean is the resized image's); _COLOUR_JITTER is now {', '.join(order)} -- train with INPUT.DEVICE_AUGMENT False")
 
     def _image(self, record):
         pixels = du.read_image(record["file_name"], format=self.img_format)
@@ -62,8 +78,29 @@ class TrafficLightDatasetMapper:
         kept = [du.transform_instance_annotations(a, transforms, hw) for a in annotations if not a.get("iscrowd", 0)]
         return du.filter_empty_instances(du.annotations_to_instances(kept, hw))
 
+    def _raw_train_record(self, record):
+        """INPUT.DEVICE_AUGMENT: the draws of the host pipeline, in its order, and no pixel work beyond the decode"""
+        pixels = du.read_image(record["file_name"], format=self.img_format)
+        du.check_image_size(record, pixels)
+        resize = self.augmentation[0].get_transform(pixels)      # the size draw; reads the image's shape only
+        hw = (resize.new_h, resize.new_w) if isinstance(resize, T.ResizeTransform) else tuple(pixels.shape[:2])
+        spec = empty_spec()
+        for t, apply in enumerate(self.augmentation[1:]):
+            params = apply.draw()
+            if params is not None:
+                spec[t, 0], spec[t, 1:] = 1.0, apply.aug.spec_row(params)
+        record["image_raw"] = torch.from_numpy(np.require(pixels, requirements="CW"))      # a copy only where the decoder's array is a view or read-only
+        record["resize_hw"] = hw
+        record["jitter"] = torch.from_numpy(spec)
+        annotations = record.pop("annotations", None)
+        if annotations is not None:
+            record["instances"] = self._targets(annotations, T.TransformList([resize]), hw)
+        return record
+
     def __call__(self, dataset_dict):
         record = copy.deepcopy(dataset_dict)       # the caller's dict (shared by every epoch) is never modified
+        if self.device_augment:
+            return self._raw_train_record(record)
         if self.device_resize:
             pixels = du.read_image(record["file_name"], format=self.img_format)
             du.check_image_size(record, pixels)

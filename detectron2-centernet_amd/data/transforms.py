@@ -153,16 +153,22 @@ class ResizeShortestEdge(Augmentation):
             newh, neww = newh * scale, neww * scale
         return int(newh + 0.5), int(neww + 0.5)
 
-    def get_transform(self, image):
-        h, w = image.shape[:2]
+    def draw_size(self, h, w):
+        """the size draw: (new_h, new_w) of an h x w image, or None when the drawn size is 0 (no resize)"""
         if self.is_range:
             size = np.random.randint(self.short_edge_length[0], self.short_edge_length[1] + 1)
         else:
             size = np.random.choice(self.short_edge_length)
         if size == 0:
+            return None
+        return self.output_size(h, w, int(size), self.max_size)
+
+    def get_transform(self, image):
+        h, w = image.shape[:2]
+        new = self.draw_size(h, w)
+        if new is None:
             return NoOpTransform()
-        newh, neww = self.output_size(h, w, int(size), self.max_size)
-        return ResizeTransform(h, w, newh, neww, self.interp)
+        return ResizeTransform(h, w, new[0], new[1], self.interp)
 
 
 class RandomApply(Augmentation):
@@ -170,10 +176,17 @@ class RandomApply(Augmentation):
         assert 0.0 <= prob <= 1.0
         self.aug, self.prob = aug, prob
 
-    def get_transform(self, image):
+    def draw(self):
+        """the apply-or-not uniform, then the wrapped augmentation's own draws: its parameters, or None when it is not applied"""
         if np.random.uniform(0, 1) < self.prob:
-            return self.aug.get_transform(image)
-        return NoOpTransform()
+            return self.aug.draw()
+        return None
+
+    def get_transform(self, image):
+        params = self.draw()
+        if params is None:
+            return NoOpTransform()
+        return self.aug.transform_of(params, image)
 
 
 class RandomFlip(Augmentation):
@@ -186,34 +199,56 @@ class RandomFlip(Augmentation):
         return NoOpTransform()
 
 
-class _RandomIntensity(Augmentation):
+class _ColourJitter(Augmentation):
+    """a colour jitter in two halves: draw() makes the random draws (none depends on the pixels) and returns the parameters,
+    transform_of(params, image) builds the BlendTransform from them.  The host pipeline runs both (get_transform); the
+    raw-record mapper (INPUT.DEVICE_AUGMENT) runs draw() alone and ships spec_row(params) to the device kernel."""
+
+    def draw(self):
+        raise NotImplementedError
+
+    def transform_of(self, params, image):
+        raise NotImplementedError
+
+    def spec_row(self, params):
+        """the three numbers of this transform's row of a jitter spec (data/jitter.py)"""
+        raise NotImplementedError
+
+    def get_transform(self, image):
+        return self.transform_of(self.draw(), image)
+
+
+class _RandomIntensity(_ColourJitter):
     def __init__(self, intensity_min, intensity_max):
         self.intensity_min, self.intensity_max = intensity_min, intensity_max
 
+    def draw(self):
+        return np.random.uniform(self.intensity_min, self.intensity_max)
+
+    def spec_row(self, w):
+        return (1 - w, w, 0.0)      # (src_weight, dst_weight) exactly as transform_of forms them
+
 
 class RandomContrast(_RandomIntensity):
-    def get_transform(self, image):
-        w = np.random.uniform(self.intensity_min, self.intensity_max)
+    def transform_of(self, w, image):
         return BlendTransform(src_image=image.mean(), src_weight=1 - w, dst_weight=w)
 
 
 class RandomBrightness(_RandomIntensity):
-    def get_transform(self, image):
-        w = np.random.uniform(self.intensity_min, self.intensity_max)
+    def transform_of(self, w, image):
         return BlendTransform(src_image=0, src_weight=1 - w, dst_weight=w)
 
 
 class RandomSaturation(_RandomIntensity):
-    def get_transform(self, image):
+    def transform_of(self, w, image):
         assert image.shape[-1] == 3, "RandomSaturation only works on RGB images"
-        w = np.random.uniform(self.intensity_min, self.intensity_max)
         # image.dot([0.299, 0.587, 0.114]) in the reference: the same float64 sum channel by channel (numpy's generic
         # uint8 x float64 dot is 6x slower)
         grayscale = (image[..., 0] * 0.299 + image[..., 1] * 0.587 + image[..., 2] * 0.114)[:, :, np.newaxis]
         return BlendTransform(src_image=grayscale, src_weight=1 - w, dst_weight=w)
 
 
-class RandomLighting(Augmentation):
+class RandomLighting(_ColourJitter):
     """AlexNet's PCA lighting noise with the fixed ImageNet eigen-decomposition (augmentation_impl.py:505-508)"""
 
     def __init__(self, scale):
@@ -221,10 +256,17 @@ class RandomLighting(Augmentation):
         self.eigen_vecs = np.array([[-0.5675, 0.7192, 0.4009], [-0.5808, -0.0045, -0.8140], [-0.5836, -0.6948, 0.4203]])
         self.eigen_vals = np.array([0.2175, 0.0188, 0.0045])
 
-    def get_transform(self, image):
-        assert image.shape[-1] == 3, "RandomLighting only works on RGB images"
+    def draw(self):
+        """the per-channel offsets"""
         weights = np.random.normal(scale=self.scale, size=3)
-        return BlendTransform(src_image=self.eigen_vecs.dot(weights * self.eigen_vals), src_weight=1.0, dst_weight=1.0)
+        return self.eigen_vecs.dot(weights * self.eigen_vals)
+
+    def spec_row(self, offsets):
+        return tuple(float(v) for v in offsets)
+
+    def transform_of(self, offsets, image):
+        assert image.shape[-1] == 3, "RandomLighting only works on RGB images"
+        return BlendTransform(src_image=offsets, src_weight=1.0, dst_weight=1.0)
 
 
 def apply_augmentations(augmentations, image):

@@ -296,10 +296,15 @@ def heads(model, y):
 
 
 def centernet_train_forward(model, batched_inputs):
-    """list[dict] with "image" and "instances" -> {"hm_loss","wh_loss","off_loss"} (0-d tensors with autograd)."""
+    """list[dict] with "image" and "instances" -> {"hm_loss","wh_loss","off_loss"} (0-d tensors with autograd).  Raw records
+    (INPUT.DEVICE_AUGMENT: "image_raw" / "resize_hw" / "jitter" instead of "image") are resized and jittered on the device
+    first (CenterNet.stage_raw_train) and then take the same path; a batch is raw or host-mapped as a whole."""
     if model.device.type != "cuda":
         raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
     assert "instances" in batched_inputs[0], "Instance annotations are missing in training!"
+    if any("image_raw" in x for x in batched_inputs):
+        staged = model.stage_raw_train(batched_inputs)
+        batched_inputs = [dict(x, image=im) for x, im in zip(batched_inputs, staged)]
     images, targets = model.preprocess_image(batched_inputs)
     return train_forward_tensors(model, images.nhwc, targets)
 

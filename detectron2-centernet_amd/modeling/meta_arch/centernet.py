@@ -561,6 +561,25 @@ class CenterNet(nn.Module):
         ops.resize_u8(raws, sizes, outs=[stage[b] for b in range(len(raws))])
         return eng, batched_inputs, sizes
 
+    def stage_raw_train(self, batched_inputs):
+        """records of a training mapper built with INPUT.DEVICE_AUGMENT ("image_raw", "resize_hw", "jitter") -> the list of
+        device uint8 [3, h, w] images the host pipeline would have produced from the same draws, byte for byte: one pinned copy
+        and ONE resize launch for the batch (ops.resize_u8), then at most one byte-sum launch (the images whose contrast was
+        drawn) and one jitter launch (ops.colour_jitter_u8), whatever the sizes and whichever transforms each image drew."""
+        if self.device.type != "cuda":
+            raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
+        missing = [i for i, x in enumerate(batched_inputs) if "image_raw" not in x or "resize_hw" not in x]
+        if missing:
+            raise KeyError(f"record {missing[0]} of a raw batch lacks 'image_raw' / 'resize_hw': a batch is raw or host-mapped as a whole")
+        raws = []
+        for x in batched_inputs:
+            raw = x["image_raw"]
+            assert raw.ndim == 3 and raw.shape[2] == 3, f"image_raw is uint8 [H, W, 3], got {tuple(raw.shape)}"
+            raws.append(raw.permute(2, 0, 1) if isinstance(raw, torch.Tensor) else raw.transpose(2, 0, 1))
+        sizes = [(int(x["resize_hw"][0]), int(x["resize_hw"][1])) for x in batched_inputs]
+        images = ops.resize_u8(raws, sizes, device=self.device)
+        return ops.colour_jitter_u8(images, [x.get("jitter") for x in batched_inputs])
+
     def _raw_ragged(self, batched_inputs, resized, flip):
         """raw records with more than one target size: the device-resized images through the ragged path"""
         sizes = [tuple(im.shape[-2:]) for im in resized]

@@ -916,6 +916,118 @@ def resize_u8_prepare(images, sizes, outs=None, device=None):
     return ResizeLaunch(dev, desc, tab_at, blocks, outs)
 
 
+# ---------------------------------------------------------------------------------- uint8 colour jitter (csrc/jitter.hip)
+JITTER_TW, JITTER_TH = 64, 4      # pixel columns / rows of one block (csrc/jitter.hip)
+# ctdet_jitter_desc as a numpy record
+JITTER_DESC_DTYPE = np.dtype([("img", "<u8"), ("row", "<i8"), ("pix", "<i8"), ("chan", "<i8"), ("h", "<i4"), ("w", "<i4"),
+                              ("blk0", "<i4"), ("sum_slot", "<i4"), ("on", "<i4", (4,)), ("contrast", "<f8", (2,)),
+                              ("brightness", "<f8", (2,)), ("saturation", "<f8", (2,)), ("lighting", "<f8", (3,))])
+assert JITTER_DESC_DTYPE.itemsize == C.sizeof(_lib.JitterDesc)
+
+
+class JitterLaunch:
+    """one prepared colour jitter of a list of images (colour_jitter_u8_prepare): the uploaded descriptors and the sum slots.
+    n = 0 (nothing drawn): launch() launches nothing."""
+
+    def __init__(self, dev, n, blocks, sums, images):
+        self.dev, self.n, self.blocks, self.sums, self.images = dev, n, blocks, sums, images
+
+    def launch_sum(self):
+        """the byte sums of the images whose contrast was drawn (none: no launch)"""
+        if self.n and self.sums.numel():
+            with torch.cuda.device(self.sums.device):
+                rc = _lib.lib().ctdet_byte_sum_u8_batch(C.c_void_p(self.dev.data_ptr()), self.n, _ptr(self.sums), self.sums.numel(),
+                                                        _stream())
+            _lib.check(rc, "ctdet_byte_sum_u8_batch")
+
+    def launch_jitter(self):
+        if self.n:
+            with torch.cuda.device(self.sums.device):
+                rc = _lib.lib().ctdet_colour_jitter_u8_batch(C.c_void_p(self.dev.data_ptr()), self.n, self.blocks, _ptr(self.sums),
+                                                             self.sums.numel(), _stream())
+            _lib.check(rc, "ctdet_colour_jitter_u8_batch")
+
+    def launch(self):
+        self.launch_sum()
+        self.launch_jitter()
+        return self.images
+
+
+def _jitter_table(images, specs, all_sums=False):
+    """descriptors (numpy records) of the images that drew a transform, their block count and the number of sum slots.
+    all_sums: every image gets a descriptor and a slot (byte_sum_u8)."""
+    from .data.jitter import spec_array
+    desc = np.zeros(len(images), dtype=JITTER_DESC_DTYPE)
+    n = blocks = slots = 0
+    for i, (im, spec) in enumerate(zip(images, specs)):
+        assert isinstance(im, torch.Tensor) and im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[0] == 3, (
+            f"image {i}: colour_jitter_u8 takes device uint8 views [3, h, w]")
+        spec = spec_array(spec)
+        if not (all_sums or spec[:, 0].any()):
+            continue
+        d = desc[n]
+        n += 1
+        h, w = int(im.shape[1]), int(im.shape[2])
+        assert h >= 1 and w >= 1 and 3 * h * w < 2 ** 53, (h, w)
+        d["img"], d["row"], d["pix"], d["chan"], d["h"], d["w"], d["blk0"] = im.data_ptr(), im.stride(1), im.stride(2), im.stride(0), h, w, blocks
+        blocks += -(-w // JITTER_TW) * -(-h // JITTER_TH)
+        d["on"] = spec[:, 0] != 0
+        d["contrast"], d["brightness"], d["saturation"], d["lighting"] = spec[0, 1:3], spec[1, 1:3], spec[2, 1:3], spec[3, 1:4]
+        d["sum_slot"] = -1
+        if all_sums or spec[0, 0]:
+            d["sum_slot"] = slots
+            slots += 1
+    assert blocks < 2 ** 31
+    return desc[:n], blocks, slots
+
+
+def _jitter_upload(desc, device):
+    """the descriptors on the device, through the pinned arena of the resize upload"""
+    nbytes = max(desc.nbytes, 16)
+    arena = _RESIZE_ARENA.take(nbytes)
+    arena.numpy()[:desc.nbytes] = desc.view(np.uint8).reshape(-1)
+    dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        dev.copy_(arena[:nbytes], non_blocking=True)
+        _RESIZE_ARENA.uploaded()
+    return dev
+
+
+def colour_jitter_u8_prepare(images, specs):
+    """everything of colour_jitter_u8 but the launches: a JitterLaunch"""
+    assert len(images) == len(specs)
+    desc, blocks, slots = _jitter_table(images, specs)
+    device = images[0].device if len(images) else torch.device("cuda", torch.cuda.current_device())
+    sums = torch.empty(slots, dtype=torch.int64, device=device)      # cleared by the sum call, on the stream
+    dev = _jitter_upload(desc, device) if len(desc) else None
+    return JitterLaunch(dev, len(desc), blocks, sums, images)
+
+
+def colour_jitter_u8(images, specs):
+    """The training mapper's colour jitters (data.transforms: RandomContrast, RandomBrightness, RandomSaturation,
+    RandomLighting, in that order) on device images, in place, to the bytes the host's BlendTransform chain gives.
+
+    images: device uint8 views [3, h, w] with any strides (what resize_u8 returns, or windows of a batch).
+    specs: per image the draws, a float64 [4, 4] array / tensor (data.jitter: row t = (drawn, parameters of transform t)) or
+      None for an image that drew nothing.
+    One pinned upload carries the descriptors; one launch sums the bytes of the images whose contrast was drawn (the image
+    mean is formed on the device), one launch applies every transform of every image.  Images that drew nothing are not
+    touched; a batch in which nothing was drawn launches nothing.  Returns images."""
+    if len(images) == 0:
+        return images
+    return colour_jitter_u8_prepare(images, specs).launch()
+
+
+def byte_sum_u8(images):
+    """int64 device tensor [n]: the sum of the 3 * h * w bytes of each device uint8 view [3, h, w], one launch for all"""
+    if len(images) == 0:
+        return torch.empty(0, dtype=torch.int64)
+    desc, blocks, slots = _jitter_table(images, [None] * len(images), all_sums=True)
+    sums = torch.empty(slots, dtype=torch.int64, device=images[0].device)
+    JitterLaunch(_jitter_upload(desc, images[0].device), len(desc), blocks, sums, images).launch_sum()
+    return sums
+
+
 class PackedDlaBase:
     """operands of ctdet_dla_base_fwd: the 7x7 stem [16,3,7,7], level0 [16,16,3,3] and level1 [32,16,3,3] weights with
     their folded BatchNorm (scale, bias) pairs."""

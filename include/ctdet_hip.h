@@ -670,6 +670,33 @@ int32_t ctdet_resize_bilinear_u8(const ctdet_resize_desc* desc, const int32_t* t
 int32_t ctdet_resize_bilinear_u8_batch(const ctdet_resize_desc* descs_dev, int32_t n, int32_t total_blocks,
                                        const int32_t* tables_dev, void* stream);
 
+/* ---- uint8 colour jitter, the host mapper's arithmetic byte for byte ---------------------------------------------------
+ * The training mapper's RandomContrast, RandomBrightness, RandomSaturation and RandomLighting (in that order, each a blend on
+ * the uint8 result of the one before), in place on 3-channel uint8 windows.  Per byte of a transform that is on
+ *   out = trunc(clip(ws * src + (double)((float)wd * (float)byte), 0, 255))      -- no product is fused with a sum
+ * with src = sum / (3 h w) of the image as it arrives (contrast), 0 (brightness), (c0 * 0.299 + c1 * 0.587) + c2 * 0.114 of the
+ * pixel's channels in stored order (saturation), lighting[c] with ws = wd = 1 (lighting).  {ws, wd} are the pairs below.
+ * Addresses as in ctdet_resize_desc: img + row * y + pix * x + chan * c, in bytes, strides of either sign.
+ *
+ * descs_dev: n descriptors in DEVICE memory sorted by blk0 = the number of blocks of the descriptors before it,
+ *   ceil(w / 64) * ceil(h / 4) each; total_blocks = their sum.  Both calls take the same table.
+ * ctdet_byte_sum_u8_batch: clears sums_dev[0 .. n_sums) on the stream, then adds the h * w * 3 bytes of every descriptor with
+ *   0 <= sum_slot < n_sums into sums_dev[sum_slot] (exact; no wrap: 64-bit; one launch, 64 blocks per descriptor, blk0 unused).
+ *   Descriptors with sum_slot < 0 are skipped.
+ * ctdet_colour_jitter_u8_batch: one launch for the whole table; reads sums_dev[sum_slot] of the descriptors whose contrast is
+ *   on (filled by ctdet_byte_sum_u8_batch before it on the same stream).  n = 0 launches nothing.  Graph-capturable, no LDS. */
+typedef struct ctdet_jitter_desc {
+  void* img;
+  int64_t row, pix, chan;               /* byte strides */
+  int32_t h, w, blk0, sum_slot;         /* sum_slot: index into sums_dev, -1 = none (contrast off) */
+  int32_t on[4];                        /* contrast, brightness, saturation, lighting */
+  double contrast[2], brightness[2], saturation[2];   /* {ws, wd} = {1 - weight, weight} as the host formed them */
+  double lighting[3];                   /* per-channel offsets, stored channel order */
+} ctdet_jitter_desc;
+int32_t ctdet_byte_sum_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t n, uint64_t* sums_dev, int32_t n_sums, void* stream);
+int32_t ctdet_colour_jitter_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t n, int32_t total_blocks,
+                                     const uint64_t* sums_dev, int32_t n_sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
