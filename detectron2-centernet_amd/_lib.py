@@ -121,6 +121,7 @@ SIGNATURES = {
     "ctdet_resize_bilinear_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "ctdet_byte_sum_u8_batch": (_i32, [_vp, _i32, _vp, _i32, _vp]),
     "ctdet_colour_jitter_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),
+    "ctdet_soft_nms_merge": (_i32, [_vp, _i32, _i32, _i32, C.c_float, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctdet_set_tuning_flags": (_i32, [C.c_uint32]),
     "ctdet_get_tuning_flags": (C.c_uint32, []),
     "ctdet_comm_unique_id": (_i32, [_vp]),
@@ -156,6 +157,12 @@ def check(rc, what):
     if rc != 0:
         msg = lib().ctdet_last_error()
         raise RuntimeError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+class SoftNmsPass(C.Structure):
+    """mirrors ctdet_softnms_pass"""
+    _fields_ = [("boxes", C.c_void_p), ("scores", C.c_void_p), ("classes", C.c_void_p), ("counts", C.c_void_p),
+                ("K", C.c_int32), ("pad_", C.c_int32)]
 
 
 class PackDesc(C.Structure):

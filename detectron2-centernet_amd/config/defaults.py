@@ -131,11 +131,16 @@ _C.TEST.EVAL_PERIOD = 0
 _C.TEST.DETECTIONS_PER_IMAGE = 100
 _C.TEST.BATCH_SIZE = 1
 # test-time augmentation (detectron2/config/defaults.py:634-638).  Built for the CenterNet meta-architecture as its flip
-# test (modeling/test_time_augmentation.py: CenterNetWithTTA): FLIP with at most one entry in MIN_SIZES
+# test (modeling/test_time_augmentation.py: CenterNetWithTTA): FLIP with at most one entry in MIN_SIZES, any number of entries with TEST.SOFT_NMS
 _C.TEST.AUG = CN({"ENABLED": False})
 _C.TEST.AUG.MIN_SIZES = (400, 500, 600, 700, 800, 900, 1000, 1100, 1200)
 _C.TEST.AUG.MAX_SIZE = 4000
 _C.TEST.AUG.FLIP = True
+# CenterNet's `--nms`: per-class Gaussian soft-NMS of the detections (sigma, score floor of a decayed detection), the merge of
+# multi-scale testing -- with it CenterNetWithTTA takes any number of TEST.AUG.MIN_SIZES (ops.soft_nms_merge)
+_C.TEST.SOFT_NMS = CN({"ENABLED": False})
+_C.TEST.SOFT_NMS.SIGMA = 0.5
+_C.TEST.SOFT_NMS.MIN_SCORE = 0.001
 
 _C.OUTPUT_DIR = "./output"
 _C.SEED = -1

@@ -886,6 +886,31 @@ int32_t ctdet_colour_jitter_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t
   CTDET_CHECK(n_sums == 0 || sums_dev, "colour_jitter_u8_batch: n_sums=%d without a sums buffer", n_sums);
   return launch_colour_jitter_u8_batch(descs_dev, n, total_blocks, sums_dev, n_sums, (hipStream_t)stream);
 }
+int32_t ctdet_soft_nms_merge(const ctdet_softnms_pass* passes, int32_t npass, int32_t B, int32_t num_classes, float sigma,
+                             float min_score, int32_t max_det, void* workspace, float* out_boxes, float* out_scores,
+                             int32_t* out_classes, int32_t* out_counts, void* stream) {
+  CTDET_CHECK(npass >= 1 && npass <= CTDET_SOFTNMS_MAX_PASSES, "soft_nms_merge: %d passes (1..%d)", npass,
+              CTDET_SOFTNMS_MAX_PASSES);
+  CTDET_CHECK(passes, "soft_nms_merge: null pass table");
+  CTDET_CHECK(B >= 0 && num_classes >= 1 && num_classes <= (1 << 20) && (int64_t)B * num_classes < (1LL << 26),
+              "soft_nms_merge: B=%d images x %d classes out of range (classes <= 2^20, B*classes < 2^26)", B, num_classes);
+  CTDET_CHECK(max_det >= 1, "soft_nms_merge: max_det=%d", max_det);
+  CTDET_CHECK(sigma > 0.f, "soft_nms_merge: sigma=%g must be positive", (double)sigma);   // a NaN fails too
+  int64_t total = 0;
+  for (int i = 0; i < npass; ++i) {
+    CTDET_CHECK(passes[i].K >= 0, "soft_nms_merge: pass %d has width %d", i, passes[i].K);
+    CTDET_CHECK(passes[i].counts && (passes[i].K == 0 || (passes[i].boxes && passes[i].scores && passes[i].classes)),
+                "soft_nms_merge: null pointer in pass %d", i);
+    total += passes[i].K;
+  }
+  CTDET_CHECK(total <= CTDET_SOFTNMS_MAX_CANDIDATES, "soft_nms_merge: %lld candidates per image (at most %d)", (long long)total,
+              CTDET_SOFTNMS_MAX_CANDIDATES);
+  CTDET_CHECK(B == 0 || (out_boxes && out_scores && out_classes && out_counts), "soft_nms_merge: null output pointer");
+  CTDET_CHECK(B == 0 || total == 0 || (workspace && ((uintptr_t)workspace & 3) == 0),
+              "soft_nms_merge: the workspace must be a non-null, 4-byte aligned buffer");
+  return launch_soft_nms(passes, npass, B, num_classes, sigma, min_score, max_det, workspace, out_boxes, out_scores, out_classes,
+                         out_counts, (hipStream_t)stream);
+}
 #undef CTDET_ADAM_BETAS
 #undef CTDET_DCN_MASK_MODE
 

@@ -306,6 +306,11 @@ int launch_byte_sum_u8_batch(const ctdet_jitter_desc* descs_dev, int n, uint64_t
 int launch_colour_jitter_u8_batch(const ctdet_jitter_desc* descs_dev, int n, int total_blocks, const uint64_t* sums, int n_sums,
                                   hipStream_t s);
 
+// softnms.hip
+struct ctdet_softnms_pass;                                   // include/ctdet_hip.h
+int launch_soft_nms(const ctdet_softnms_pass* passes, int npass, int B, int C, float sigma, float min_score, int max_det,
+                    void* workspace, float* out_boxes, float* out_scores, int* out_classes, int* out_counts, hipStream_t s);
+
 // dwconv.hip
 // shape / dtype checks shared by the entry points (api.hip validates pointers first)
 int dwconv3x3_check(int dtype, int B, int H, int W, int C, int stride, const int* strides, int nstrides);

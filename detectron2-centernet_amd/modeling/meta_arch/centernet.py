@@ -512,15 +512,17 @@ class CenterNet(nn.Module):
             stage[b].copy_(im if im.dtype == img_dtype else im.to(img_dtype), non_blocking=True)
         return self._finish_eval(eng, batched_inputs, sizes)
 
-    def forward_async(self, batched_inputs, flip=False):
+    def forward_async(self, batched_inputs, flip=False, read_back=True):
         """eval forward of a `list[dict]` batch without waiting for it: returns a handle whose `.result()` is what
         `forward` returns.  Same-size images go through the captured engine (one step in flight is safe: the engine's
-        post-processing writes fresh tensors per step); ragged batches run eagerly and come back already finished."""
+        post-processing writes fresh tensors per step); ragged batches run eagerly and come back already finished.
+        read_back=False: the handle starts no copy of the counts to the host (a caller that only merges the handle's device
+        tensors with other steps', modeling/tta_multi_scale.py)."""
         assert not self.training
         if "image_raw" in batched_inputs[0]:
             staged = self._stage_raw(batched_inputs, flip)
             if isinstance(staged, tuple):
-                return self._launch_eval(*staged)
+                return self._launch_eval(*staged, read_back=read_back)
             return _Done(self._raw_ragged(batched_inputs, staged, flip))
         imgs = [x["image"] for x in batched_inputs]
         sizes = [tuple(im.shape[-2:]) for im in imgs]
@@ -533,7 +535,7 @@ class CenterNet(nn.Module):
         stage = eng.staging(H, W)
         for b, im in enumerate(imgs):
             stage[b].copy_(im if im.dtype == img_dtype else im.to(img_dtype), non_blocking=True)
-        return self._launch_eval(eng, batched_inputs, sizes)
+        return self._launch_eval(eng, batched_inputs, sizes, read_back=read_back)
 
     def _stage_raw(self, batched_inputs, flip=False):
         """records of a mapper built with INPUT.DEVICE_RESIZE: "image_raw" (uint8 HWC, host array or tensor, or a device
@@ -608,7 +610,7 @@ class CenterNet(nn.Module):
     def _finish_eval(self, eng, batched_inputs, sizes):
         return self._launch_eval(eng, batched_inputs, sizes).result()
 
-    def _launch_eval(self, eng, batched_inputs, sizes, images=None):
+    def _launch_eval(self, eng, batched_inputs, sizes, images=None, read_back=True):
         out_sizes = tuple((inp.get("height", size[0]), inp.get("width", size[1])) for inp, size in zip(batched_inputs, sizes))
         pkey = (out_sizes, tuple(sizes))
         if getattr(eng, "_params_key", None) != pkey:  # rescale parameters change only with the requested sizes
@@ -617,7 +619,7 @@ class CenterNet(nn.Module):
             eng.img_params.copy_(params, non_blocking=False)
             eng._params_key = pkey
         boxes, scores, classes, counts = eng(images)   # fresh tensors per step (the engine's post-processing allocates them)
-        return _EvalHandle(boxes, scores, classes, counts, out_sizes)
+        return _EvalHandle(boxes, scores, classes, counts, out_sizes, read_back)
 
     def _forward_eval_ragged(self, batched_inputs, imgs, sizes, Hp, Wp, flip=False):
         """images of different sizes: per-image preprocess launches into the zero-padded batch, eager launches.
@@ -771,14 +773,22 @@ class _Done:
 class _EvalHandle:
     """One in-flight eval step: device snapshots of the outputs + a pinned host copy of the counts."""
 
-    def __init__(self, boxes, scores, classes, counts, out_sizes):
+    def __init__(self, boxes, scores, classes, counts, out_sizes, read_back=True):
         self.boxes, self.scores, self.classes, self.out_sizes = boxes, scores, classes, out_sizes
-        self.counts_host = torch.empty(counts.shape, dtype=counts.dtype, pin_memory=True)
-        self.counts_host.copy_(counts, non_blocking=True)
+        self.counts = counts      # on the device: what a merge of several steps reads (ops.soft_nms_merge)
+        self.counts_host = None
+        if read_back:
+            self._read_back()
+
+    def _read_back(self):
+        self.counts_host = torch.empty(self.counts.shape, dtype=self.counts.dtype, pin_memory=True)
+        self.counts_host.copy_(self.counts, non_blocking=True)
         self.event = torch.cuda.Event()
         self.event.record()
 
     def result(self):
+        if self.counts_host is None:      # a handle made with read_back=False and asked after all
+            self._read_back()
         self.event.synchronize()  # the only host<->device synchronisation of the eval step
         counts = self.counts_host.tolist()
         if counts and counts[0] < 0:

@@ -1507,6 +1507,46 @@ def postprocess(boxes, scores, classes, max_det, score_thresh, img_params):
     return ob, os_, oc, counts
 
 
+def soft_nms_merge(passes, num_classes, sigma, min_score, max_det):
+    """Multi-scale test augmentation's merge: per-class Gaussian soft-NMS over the union of the passes'
+    detections, then the per-image cap, on the device.  passes: a list of (boxes f32 [B,K_s,4], scores f32 [B,K_s], classes
+    i32 [B,K_s], counts i32 [B]) device tuples in one frame -- what an eval step returns -- read in place when contiguous, as an
+    eval step's are (a non-contiguous tensor is copied first; K_s may differ per pass; the counts are never read on the host).
+    Candidates are ordered pass-major; ties of the score go to the earlier one.
+    An image with a count of -1 in any pass (the engine's non-finite flag) gets the count -1.
+    Returns fresh (boxes [B,max_det,4], scores [B,max_det], classes [B,max_det] i32, counts [B] i32), best score first."""
+    passes = [tuple(p) for p in passes]
+    if not passes:
+        raise ValueError("soft_nms_merge: no pass to merge")
+    _require_cuda(*[t for p in passes for t in p])
+    B, dev = passes[0][3].shape[0], passes[0][0].device
+    table = (_lib.SoftNmsPass * len(passes))()
+    keep = []
+    for i, (boxes, scores, classes, counts) in enumerate(passes):
+        K = scores.shape[1]
+        if not (boxes.dtype == torch.float32 and scores.dtype == torch.float32 and classes.dtype == torch.int32 and
+                counts.dtype == torch.int32):
+            raise ValueError(f"soft_nms_merge: pass {i}: boxes / scores must be f32, classes / counts i32")
+        if not (tuple(boxes.shape) == (B, K, 4) and tuple(scores.shape) == (B, K) and tuple(classes.shape) == (B, K) and
+                tuple(counts.shape) == (B,)):
+            raise ValueError(f"soft_nms_merge: pass {i} is not ([B,K,4], [B,K], [B,K], [B]) with B={B}")
+        ts = [t.contiguous() for t in (boxes, scores, classes, counts)]
+        keep.append(ts)
+        table[i].boxes, table[i].scores, table[i].classes, table[i].counts = (t.data_ptr() for t in ts)
+        table[i].K = K
+    total = sum(int(table[i].K) for i in range(len(passes)))
+    md = max(int(max_det), 0)
+    ws = torch.empty(max(B * total * 2, 1), dtype=torch.int32, device=dev)
+    ob = torch.empty(B, md, 4, dtype=torch.float32, device=dev)
+    os_ = torch.empty(B, md, dtype=torch.float32, device=dev)
+    oc = torch.empty(B, md, dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    rc = _lib.lib().ctdet_soft_nms_merge(table, len(passes), B, int(num_classes), float(sigma), float(min_score), int(max_det),
+                                         _ptr(ws), _ptr(ob), _ptr(os_), _ptr(oc), _ptr(counts), _stream())
+    _lib.check(rc, "ctdet_soft_nms_merge")
+    return ob, os_, oc, counts
+
+
 def gaussian_targets(boxes, classes, counts, H, W, num_classes, hm=None):
     """Batched gen_heatmap. boxes f32 [B,Nmax,4], classes i64 [B,Nmax], counts i32 [B].
     Returns dict(hm [B,H,W,C] NHWC f32, wh [B,128,2], reg [B,128,2], ind [B,128] i64, reg_mask [B,128] u8)."""

@@ -697,6 +697,29 @@ int32_t ctdet_byte_sum_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t n, u
 int32_t ctdet_colour_jitter_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t n, int32_t total_blocks,
                                      const uint64_t* sums_dev, int32_t n_sums, void* stream);
 
+/* ---- multi-scale test augmentation: per-class Gaussian soft-NMS over the passes, then the per-image cap ----------------
+ * CenterNet's merge (`soft_nms(..., Nt=0.5, method=2)` per class, then `max_per_image`), defined in DESIGN.md 7.10.  The passes
+ * are read in place: `passes` is a HOST array of npass descriptors whose pointers are DEVICE addresses (what an eval step
+ * returns: boxes f32 [B,K,4], scores f32 [B,K], classes i32 [B,K], counts i32 [B], dense); it is copied into the kernel
+ * arguments, so it may be freed when the call returns.  The counts are read on the device only: no synchronisation.  A
+ * candidate's index is its position in the pass-major concatenation (ties of the score go to the lower index).  Candidates
+ * whose class is outside [0, num_classes) are dropped.  An image with a count < 0 in any pass (the non-finite flag of an eval
+ * step) gets out_counts = -1.
+ * Limits: 1 <= npass <= CTDET_SOFTNMS_MAX_PASSES, sum of K <= CTDET_SOFTNMS_MAX_CANDIDATES, B * num_classes < 2^26,
+ * num_classes <= 2^20, max_det >= 1, sigma > 0; otherwise -EINVAL.
+ * workspace: B * (sum of K) * 8 bytes, 4-byte aligned, caller-owned.  Outputs: out_boxes f32 [B,max_det,4], out_scores f32
+ * [B,max_det], out_classes i32 [B,max_det] (entries at and beyond the count are zero), out_counts i32 [B].
+ * Two launches; f32 arithmetic, no float atomics: two runs give the same bits.  Graph-capturable. */
+#define CTDET_SOFTNMS_MAX_PASSES 16
+#define CTDET_SOFTNMS_MAX_CANDIDATES 2048
+typedef struct ctdet_softnms_pass {
+  const float* boxes; const float* scores; const int32_t* classes; const int32_t* counts;
+  int32_t K, pad_;
+} ctdet_softnms_pass;
+int32_t ctdet_soft_nms_merge(const ctdet_softnms_pass* passes, int32_t npass, int32_t B, int32_t num_classes, float sigma,
+                             float min_score, int32_t max_det, void* workspace, float* out_boxes, float* out_scores,
+                             int32_t* out_classes, int32_t* out_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,13 @@ trained-like maps (background on the clamp floor) of --decode-shape:
 and, as the separate-merge alternative the fused form replaces, a torch merge of the 2B maps followed by decode plain B.
 The legs alternate over --rounds, so that a drift of the machine shows as spread inside a leg.
 
+  --multi-scale  instead of the above, multi-scale testing (TEST.SOFT_NMS):
+                 the merge alone (ops.soft_nms_merge) at B = --batch, --ms-passes passes of 100 clustered candidates, with 80
+                 classes and with 1 class (the deepest sequential chain): per call in a back-to-back stream, and its device time
+                 from a captured graph of 10 merges;
+                 the multi-size step of CenterNetWithTTA on raw device records (--ms-sizes, wall clock around whole calls, one
+                 host synchronisation each) against the single-size steps at the same sizes, alternating in the same run.
+
   --lib PATH     the plain legs (plain B, plain 2B, decode plain B / 2B) once more in a child process that loads another
                  build of libctdet_hip.so (a parent commit's: it needs none of the new entry points): the plain path of this
                  build against the parent's, and the parent's own run-to-run spread"""
@@ -39,6 +46,11 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--decode-shape", default="128,128,80", help="H,W,C of the decode-alone legs (batch: --batch)")
 ap.add_argument("--no-steps", action="store_true")
 ap.add_argument("--no-decode", action="store_true")
+ap.add_argument("--multi-scale", action="store_true")
+ap.add_argument("--ms-sizes", default="384,512,640")
+ap.add_argument("--ms-passes", type=int, default=5)
+ap.add_argument("--ms-warm", type=int, default=5)
+ap.add_argument("--ms-reps", type=int, default=20)
 ap.add_argument("--lib", default=None)
 ap.add_argument("--plain-only", action="store_true", help="(the --lib child) the legs every ABI-8 build can run")
 a = ap.parse_args()
@@ -128,7 +140,99 @@ def decode_legs():
             print(f"round {r}  {name:30s} (B={B}, {H}x{W}x{C}){TAG}: {us:9.2f} us{rate}", flush=True)
 
 
+def merge_inputs(B, npass, C, seed=0):
+    """npass passes of 100 detections per image: 25 objects, every pass sees each one four times, jittered"""
+    import numpy as np
+    g = np.random.default_rng(seed)
+    K, nobj = 100, 25
+    xy = g.uniform(0, 900, (B, nobj, 2))
+    wh = g.uniform(20, 150, (B, nobj, 2))
+    cls = g.integers(0, C, (B, nobj))
+    base = g.uniform(0.1, 0.95, (B, nobj))
+    passes = []
+    for _ in range(npass):
+        o = np.tile(np.arange(nobj), K // nobj)
+        p1 = xy[:, o] + g.normal(0, 0.05, (B, K, 2)) * wh[:, o]
+        p2 = p1 + wh[:, o] * (1 + g.normal(0, 0.05, (B, K, 2)))
+        sc = base[:, o] * g.uniform(0.3, 1.0, (B, K))
+        order = np.argsort(-sc, axis=1)                      # a pass returns its detections best first
+        bx = np.take_along_axis(np.concatenate([p1, p2], axis=2), order[:, :, None], axis=1)
+        passes.append((torch.from_numpy(bx.astype(np.float32)).to(dev), torch.from_numpy(np.take_along_axis(sc, order, 1).astype(np.float32)).to(dev),
+                       torch.from_numpy(np.take_along_axis(cls[:, o], order, 1).astype(np.int32)).to(dev),
+                       torch.full((B,), K, dtype=torch.int32, device=dev)))
+    return passes
+
+
+def merge_legs():
+    B = a.batch
+    legs = []
+    for C in (80, 1):
+        passes = merge_inputs(B, a.ms_passes, C)
+
+        def f(passes=passes, C=C):
+            return ops.soft_nms_merge(passes, C, 0.5, 0.001, 100)
+        f()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(10):
+                f()
+        legs.append((C, f, g))
+    for r in range(a.rounds):
+        for C, f, g in legs:
+            us = timed(f, a.warm, a.reps) * 1e3
+            dev_us = timed(g.replay, 20, 100) * 1e2
+            print(f"round {r}  soft_nms_merge (B={B}, {a.ms_passes} passes of 100, {C:2d} classes): {us:9.2f} us per call, "
+                  f"{dev_us:9.2f} us device time (graph of 10)", flush=True)
+
+
+def multi_scale_step_legs(config, precision):
+    import time
+
+    from detectron2_centernet_amd.modeling import CenterNetWithTTA
+    model, cfg = bench.build_model(precision, dev, seed=1, config=config)
+    model.eval()
+    model.score_threshold = 0.0            # every pass returns its 100 candidates: the merge at its fullest
+    model.wh[-1].bias.data.fill_(3.0)      # boxes of non-degenerate size (random-init wh is ~0: every box would be dropped as empty)
+    B, S = a.batch, a.size
+    sizes = tuple(int(v) for v in a.ms_sizes.split(","))
+    imgs = bench.synthetic_images(B, S, 0, dev)
+    recs = [{"image_raw": imgs[b].permute(1, 2, 0).contiguous()} for b in range(B)]
+
+    def wrapper(min_sizes, soft_nms):
+        c = cfg.clone()
+        c.TEST.AUG.ENABLED, c.TEST.AUG.MIN_SIZES, c.TEST.AUG.FLIP, c.TEST.SOFT_NMS.ENABLED = True, min_sizes, True, soft_nms
+        return CenterNetWithTTA(c, model)
+    legs = [(f"single {s}", wrapper((s,), False)) for s in sizes] + [(f"multi {sizes}", wrapper(sizes, True))]
+
+    def wall(t):
+        for _ in range(a.ms_warm):
+            t(recs)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.ms_reps):
+            t(recs)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.ms_reps * 1e3
+    with torch.no_grad():
+        for r in range(a.rounds):
+            row = [wall(t) for _, t in legs]
+            for (name, _), ms in zip(legs, row):
+                print(f"round {r}  step {config:5s} {precision:5s} flip {name} (B={B}, raw {S}x{S}): {ms:8.3f} ms", flush=True)
+            print(f"round {r}  step {config:5s} {precision:5s} multi - sum of singles: {row[-1] - sum(row[:-1]):+8.3f} ms "
+                  f"(sum {sum(row[:-1]):8.3f} ms)", flush=True)
+
+
 def main():
+    if a.multi_scale:
+        print(f"merge legs: {a.warm} warm + {a.reps} timed calls; step legs: {a.ms_warm} warm + {a.ms_reps} timed calls (wall clock); "
+              f"{a.rounds} rounds", flush=True)
+        merge_legs()
+        if not a.no_steps:
+            for config in a.configs.split(","):
+                for precision in a.precisions.split(","):
+                    multi_scale_step_legs(config, precision)
+        return
     if not a.plain_only:
         print(f"step legs: {a.step_warm} warm + {a.step_reps} timed steps; decode legs: {a.warm} warm + {a.reps} timed launches; "
               f"{a.rounds} rounds", flush=True)
