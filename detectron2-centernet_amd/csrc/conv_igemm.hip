@@ -2540,6 +2540,7 @@ int launch_dcn_cols_window(const DcnBwdArgs& d, hipStream_t s) {
   a.R = a.S = 3; a.stride = 1; a.pad = 1; a.dil = 1; a.in_dil = 1; a.K = a.Kpad = 9 * d.Cin; a.M = d.B * d.H * d.W; a.korder = 1;
   const int nbx = d.B * (d.H / 8) * (d.W / 16);
   const auto kernel = d.mask_mode == DCN_MASK_NONE ? dcn_window_rows_kernel<f16, false, true, true> : dcn_window_rows_kernel<f16, false, true>;
+  CTDET_KERNEL("dcn_window_rows_kernel<columns only,f16,%s>", d.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
   hipLaunchKernelGGL(kernel, dim3(8 * ((nbx + 7) / 8)), dim3(256), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;

@@ -1011,8 +1011,8 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __rest
 // wave-instruction 256 contiguous bytes).
 // The LDS accumulation is FIXED POINT (ds_add_u32): ds_add_f32 measured ~170 cycles per wave-instruction here (3.2 ms
 // for the layer above, slower than the global atomics it replaced), the integer form 0.48 ms.  Scale per (tile, chunk):
-// 2^k with max|dcol| * 2^k <= 2^19; at most 128*9 contributions (|weight*mask| <= 1) can meet in one element, so
-// the int32 sum cannot overflow, and the quantum is 2^-19 of the tile's largest dcol magnitude (the inputs are f16,
+// 2^k with max|dcol| * 2^k <= 2^19 (the maximum over the samples inside the image: the others add nothing); at most
+// 128*9 contributions (|weight*mask| <= 1) can meet in one element, so the int32 sum cannot overflow, and the quantum is 2^-19 of the tile's largest dcol magnitude (the inputs are f16,
 // the result is rounded to f16).  Integer accumulation also makes the in-tile sum order independent.
 // The x window (f16) needed by d(offset)/d(mask) is staged in LDS too; lane = (pixel, 8-channel group); the four
 // corner dot products use v_dot2_f32_f16.  Samples whose corners leave the window take the global path (per lane).
@@ -1107,6 +1107,7 @@ __global__ void __launch_bounds__(512) dcn_col2im_window_kernel(const T* __restr
     }
     geo[tl * (TH * TW) + pl] = g;
   }
+  __syncthreads();   // the fixed-point scale below asks the geometry which samples count
 
   const int fr = lane & 15, q = lane >> 4;
   const int prow = wave, pcol = fr;   // 8 waves = 8 tile rows; lane = (column, 8-channel group)
@@ -1167,11 +1168,12 @@ __global__ void __launch_bounds__(512) dcn_col2im_window_kernel(const T* __restr
         }
         // the lane's four rows of tile j: columns (tap, 16 * (j & 1) + 4 q + r); the pack scaled every row by a power of two
         const f32x4 sc = *(const f32x4*)(fz.wscale + (long)chunk * 288 + (t0 + (j >> 1)) * 32 + (j & 1) * 16 + 4 * q);
+        const bool live = (geo[(j >> 1) * (TH * TW) + pl].off & 0x40000000u) != 0;   // see the plain path below
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float v = accd[j][e] * sc[e];
           dv[j >> 1][(j & 1) * 4 + e] = v;
-          amax = fmaxf(amax, fabsf(v));
+          if (live) amax = fmaxf(amax, fabsf(v));
         }
       }
     } else {
@@ -1186,8 +1188,11 @@ __global__ void __launch_bounds__(512) dcn_col2im_window_kernel(const T* __restr
           continue;
         }
         load8f<T>(dcp + (t0 + t) * tstep, dv[t]);
+        // a sample outside the image scatters nothing: its dcol must not coarsen the quantum of the samples that do
+        if (geo[t * (TH * TW) + pl].off & 0x40000000u) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(dv[t][e]));
+          for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(dv[t][e]));
+        }
       }
     }
 #pragma unroll
@@ -2244,6 +2249,7 @@ static int dcn_cols_f16(const DcnBwdArgs& a, hipStream_t s) {
       (((size_t)x | (size_t)col | (size_t)a.om) & 15) == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
     return launch_dcn_cols_window(a, s);   // conv_igemm.hip: the sampling kernel's LDS window
   const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_cols_kernel<true> : dcn_cols_kernel<false>;
+  CTDET_KERNEL("dcn_cols_kernel<f16,%s>", a.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
   hipLaunchKernelGGL(kernel, dim3(nblk256(total)), dim3(256), 0, s, x, a.x_stride, a.om, a.om_stride, col, a.B, a.H, a.W, a.Cin,
                      a.mask_mode);
   CTDET_LAUNCH_CHECK();
@@ -2251,26 +2257,32 @@ static int dcn_cols_f16(const DcnBwdArgs& a, hipStream_t s) {
 }
 
 // the LDS-window scatter: T = element type of a.x / a.dcol; FUSED: d(columns) comes from fz (a.dcol unused, chunked order)
+// (returns like a launcher: 0 when launched or, in the labels' dry run, named only; -EIO when the launch failed)
 template <typename T, bool FUSED, bool NM>
-static void launch_col2im_window_t(const DcnBwdArgs& a, hipStream_t s, const FusedDcol fz) {
+static int launch_col2im_window_t(const DcnBwdArgs& a, hipStream_t s, const FusedDcol fz) {
   const T *dcol = (const T*)a.dcol, *x = (const T*)a.x;
   const int dom_f16 = a.dom_dtype == CTDET_F16, chunked = FUSED ? 1 : a.dcol_chunked;
   const unsigned tiles = (unsigned)(a.B * (a.H / 8) * (a.W / 16));
   const int ncu = ctdet_device_cu_count();    // one workgroup per CU at a time: with fewer tiles, split a tile's taps
-  if ((int)tiles * 3 <= ncu)
+  const int nt = (int)tiles * 3 <= ncu ? 3 : (int)tiles * 2 <= ncu ? 5 : 9;
+  CTDET_KERNEL("dcn_col2im_window_kernel<%d taps,%s,%s%s>", nt, sizeof(T) == 2 ? "f16" : "f32", FUSED ? "fused dcol," : "",
+               NM ? "no mask" : "mask");
+  if (nt == 3)
     hipLaunchKernelGGL((dcn_col2im_window_kernel<3, T, FUSED, NM>), dim3(tiles, 3), dim3(512), 0, s, dcol, x, a.x_stride, a.om, a.om_stride,
                        a.dx, a.dom, a.dom_stride, dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, chunked, fz);
-  else if ((int)tiles * 2 <= ncu)
+  else if (nt == 5)
     hipLaunchKernelGGL((dcn_col2im_window_kernel<5, T, FUSED, NM>), dim3(tiles, 2), dim3(512), 0, s, dcol, x, a.x_stride, a.om, a.om_stride,
                        a.dx, a.dom, a.dom_stride, dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, chunked, fz);
   else
     hipLaunchKernelGGL((dcn_col2im_window_kernel<9, T, FUSED, NM>), dim3(tiles), dim3(512), 0, s, dcol, x, a.x_stride, a.om, a.om_stride,
                        a.dx, a.dom, a.dom_stride, dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, chunked, fz);
+  CTDET_LAUNCH_CHECK();
+  return 0;
 }
 template <typename T, bool FUSED = false>
-static void launch_col2im_window(const DcnBwdArgs& a, hipStream_t s, const FusedDcol fz = FusedDcol()) {
-  if (a.mask_mode == DCN_MASK_NONE) launch_col2im_window_t<T, FUSED, true>(a, s, fz);
-  else launch_col2im_window_t<T, FUSED, false>(a, s, fz);
+static int launch_col2im_window(const DcnBwdArgs& a, hipStream_t s, const FusedDcol fz = FusedDcol()) {
+  if (a.mask_mode == DCN_MASK_NONE) return launch_col2im_window_t<T, FUSED, true>(a, s, fz);
+  return launch_col2im_window_t<T, FUSED, false>(a, s, fz);
 }
 
 // d(columns) GEMM + scatter in one kernel (f16x3 training mode; DcnBwdArgs says what dy, wpk and wscale hold)
@@ -2283,9 +2295,7 @@ int launch_dcn_col2im_fused(const DcnBwdArgs& a, hipStream_t s) {
     return 1;
   FusedDcol fz;
   fz.dy = a.dy; fz.dy_stride = a.dy_stride; fz.K = a.K; fz.wpk = (const f16*)a.wpk; fz.wscale = a.wscale;
-  launch_col2im_window<float, true>(a, s, fz);
-  CTDET_LAUNCH_CHECK();
-  return 0;
+  return launch_col2im_window<float, true>(a, s, fz);
 }
 
 static int dcn_col2im_coord_f16(const DcnBwdArgs& a, hipStream_t s) {
@@ -2297,13 +2307,12 @@ static int dcn_col2im_coord_f16(const DcnBwdArgs& a, hipStream_t s) {
   const long nwork = (long)a.B * a.H * a.W * 9;
   if (nwork == 0) return 0;
   if (a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 8 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW)) {
-    launch_col2im_window<f16>(a, s);
-    CTDET_LAUNCH_CHECK();
-    return 0;
+    return launch_col2im_window<f16>(a, s);
   }
   long nb = (nwork + 3) / 4;
   if (nb > 256 * 32) nb = 256 * 32;
   const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_col2im_coord_kernel<true> : dcn_col2im_coord_kernel<false>;
+  CTDET_KERNEL("dcn_col2im_coord_kernel<f16,%s>", a.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
   hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, a.x_stride, a.om, a.om_stride, a.dx, a.dom, a.dom_stride,
                      dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, a.dcol_chunked);
   CTDET_LAUNCH_CHECK();
@@ -2489,6 +2498,7 @@ static int dcn_cols_f32(const DcnBwdArgs& a, hipStream_t s) {
   const int PP = 256 / (a.Cin / 4);
   const long per_block = (long)PP * COLS_PASSES;
   const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_cols_f32_kernel<true> : dcn_cols_f32_kernel<false>;
+  CTDET_KERNEL("dcn_cols_f32_kernel<%s>", a.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
   hipLaunchKernelGGL(kernel, dim3((unsigned)((npairs + per_block - 1) / per_block)), dim3(256), 0, s, x, a.x_stride, a.om, a.om_stride,
                      col, a.B, a.H, a.W, a.Cin, a.mask_mode);
   CTDET_LAUNCH_CHECK();
@@ -2504,14 +2514,13 @@ static int dcn_col2im_coord_f32(const DcnBwdArgs& a, int window, hipStream_t s) 
   if (nwork == 0) return 0;
   if (window && a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 4 == 0 && ((((size_t)x | (size_t)dcol)) & 15) == 0 &&
       !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW)) {
-    launch_col2im_window<float>(a, s);
-    CTDET_LAUNCH_CHECK();
-    return 0;
+    return launch_col2im_window<float>(a, s);
   }
   CTDET_CHECK(!a.dcol_chunked || a.Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", a.Cin);
   long nb = (nwork + 3) / 4;
   if (nb > 256 * 32) nb = 256 * 32;
   const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_col2im_coord_f32_kernel<true> : dcn_col2im_coord_f32_kernel<false>;
+  CTDET_KERNEL("dcn_col2im_coord_f32_kernel<%s>", a.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
   hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, a.x_stride, a.om, a.om_stride, a.dx, (float*)a.dom,
                      a.dom_stride, a.B, a.H, a.W, a.Cin, a.mask_mode, a.dcol_chunked);
   CTDET_LAUNCH_CHECK();

@@ -369,10 +369,12 @@ def dwconvT_bwd(x, dz, weight, f, wk=None, raw=False):
     return dx, (dw if raw else dw.permute(2, 0, 1).reshape(Cc, 1, 2 * f, 2 * f))
 
 
-def dcn_cols(x, om, mask_is_prob=False):
-    """the sampled columns [B, H, W, 9*Cin] (mask * bilinear(x), tap-major); mask_is_prob: the mask mode (ops.dcnv2)"""
+def dcn_cols(x, om, mask_is_prob=False, out=None):
+    """the sampled columns [B, H, W, 9*Cin] (mask * bilinear(x), tap-major); mask_is_prob: the mask mode (ops.dcnv2); out: a
+    dense tensor of that shape and x's dtype to write instead of a new one"""
     B, H, W, Cin = x.shape
-    col = torch.empty(B, H, W, 9 * Cin, dtype=x.dtype, device=x.device)
+    col = torch.empty(B, H, W, 9 * Cin, dtype=x.dtype, device=x.device) if out is None else out
+    assert col.is_contiguous() and col.dtype == x.dtype and tuple(col.shape) == (B, H, W, 9 * Cin)
     with ops.prof_region("dcn_cols", flops=0.0, nbytes=float(B * H * W * Cin * x.element_size() * 10 + B * H * W * 27 * 4)):
         rc = _lib.lib().ctdet_dcn_cols(_ptr(x), _nhwc_stride(x), _ptr(om), _nhwc_stride(om), _ptr(col), B, H, W, Cin, int(mask_is_prob), dt_of(x), _stream())
     _lib.check(rc, "ctdet_dcn_cols")
@@ -408,17 +410,26 @@ def dcn_dcol(dyp, weight, chunked, comp=None):
     return dcol
 
 
-def dcn_col2im_coord(dcol, x, om, mask_is_prob=False, dom_channels=None, dcol_chunked=False, comp=None):
+def _dcn_grad_out(out, x, dom_shape, dom_dtype):
+    """(dx, dom) of the DCN scatter entry points: new tensors, or the caller's `out` pair (dx dense f32, ZERO -- the kernels add
+    into it; dom dense, of the shape and type the call would allocate)"""
+    if out is None:
+        return (torch.zeros(*x.shape, dtype=torch.float32, device=x.device), torch.empty(*dom_shape, dtype=dom_dtype, device=x.device))
+    dx, dom = out
+    assert dx.is_contiguous() and dx.dtype == torch.float32 and dx.shape == x.shape
+    assert dom.is_contiguous() and dom.dtype == dom_dtype and tuple(dom.shape) == tuple(dom_shape)
+    return dx, dom
+
+
+def dcn_col2im_coord(dcol, x, om, mask_is_prob=False, dom_channels=None, dcol_chunked=False, comp=None, out=None):
     """dx (f32, atomically accumulated) and dom = d(offsets, mask logits).  dom_channels=None: f32, the shape of om;
     dom_channels=C (f16 data): an f16 [B, H, W, C] tensor whose channels 27.. are zero -- directly the dY of the offset conv's
     backward, without a cast or a channel pad in between.  mask_is_prob = DCN_MASK_NONE (DCNv1): no d(mask), channels 18.. of
     dom are zero"""
     B, H, W, Cin = x.shape
-    dx = torch.zeros(B, H, W, Cin, dtype=torch.float32, device=x.device)
-    if dom_channels is None or x.dtype == torch.float32:
-        dom = torch.empty(B, H, W, om.shape[3] if dom_channels is None else dom_channels, dtype=torch.float32, device=x.device)
-    else:
-        dom = torch.empty(B, H, W, dom_channels, dtype=torch.float16, device=x.device)
+    dom_f16 = dom_channels is not None and x.dtype != torch.float32
+    dx, dom = _dcn_grad_out(out, x, (B, H, W, om.shape[3] if dom_channels is None else dom_channels),
+                            torch.float16 if dom_f16 else torch.float32)
     es = x.element_size()
     with ops.prof_region("dcn_col2im", flops=0.0, nbytes=float(B * H * W * Cin * (9 * es + es + 4) + B * H * W * 27 * 8)):
         rc = _lib.lib().ctdet_dcn_col2im_coord(_ptr(dcol), _ptr(x), _nhwc_stride(x), _ptr(om), _nhwc_stride(om), _ptr(dx),
@@ -429,7 +440,7 @@ def dcn_col2im_coord(dcol, x, om, mask_is_prob=False, dom_channels=None, dcol_ch
     return dx, dom
 
 
-def dcn_col2im_fused(dyp, weight, x, om, mask_is_prob=False, dom_channels=None):
+def dcn_col2im_fused(dyp, weight, x, om, mask_is_prob=False, dom_channels=None, out=None):
     """the f16x3 mode's DCNv2 backward through the sampler with the d(columns) GEMM inside the scatter kernel
     (ctdet_dcn_col2im_fused): (dx f32, dom f32) or None when the shape does not qualify (the caller then materialises
     d(columns)).  dyp f32 [B, H, W, K]: K % 32 == 0, channels beyond the layer's couts zero."""
@@ -439,8 +450,7 @@ def dcn_col2im_fused(dyp, weight, x, om, mask_is_prob=False, dom_channels=None):
             or weight.dtype != torch.float32 or not weight.is_contiguous()):
         return None
     wpk, wscale = ops.pack_x3(weight.detach(), (Cout, Cin, 1, 1, K, 9 * Cin, K, 5, 3, 9 * Cin))
-    dx = torch.zeros(B, H, W, Cin, dtype=torch.float32, device=x.device)
-    dom = torch.empty(B, H, W, om.shape[3] if dom_channels is None else dom_channels, dtype=torch.float32, device=x.device)
+    dx, dom = _dcn_grad_out(out, x, (B, H, W, om.shape[3] if dom_channels is None else dom_channels), torch.float32)
     with ops.prof_region("dcn_col2im_fused", flops=2.0 * B * H * W * K * 9 * Cin, nbytes=float(B * H * W * (Cin * 8 + K * 4 + 27 * 8))):
         rc = _lib.lib().ctdet_dcn_col2im_fused(_ptr(dyp), _nhwc_stride(dyp), K, _ptr(wpk), _ptr(wscale), _ptr(x), _nhwc_stride(x),
                                                _ptr(om), _nhwc_stride(om), _ptr(dx), _ptr(dom), dom.shape[3], B, H, W, Cin,
