@@ -88,10 +88,19 @@ def _ws(Cc, device):
 
 
 # ------------------------------------------------------------------------------------------ raw wrappers
-def bn_train_fwd(y, gamma, beta, running_mean, running_var, eps, momentum, res=None, relu=True):
+def _bn_out(out, like):
+    """the caller's output view (a channel slice of a wider NHWC buffer) or a fresh dense tensor shaped like `like`"""
+    if out is None:
+        return torch.empty(like.shape, dtype=like.dtype, device=like.device)
+    assert out.shape == like.shape and out.dtype == like.dtype and out.device == like.device
+    return out
+
+
+def bn_train_fwd(y, gamma, beta, running_mean, running_var, eps, momentum, res=None, relu=True, out=None):
+    """out: z is written into this view instead of a fresh tensor"""
     B, H, W, Cc = y.shape
     dev = y.device
-    z = torch.empty(B, H, W, Cc, dtype=y.dtype, device=dev)
+    z = _bn_out(out, y)
     mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(4))
     # algorithmic bytes: y read twice (statistics, apply), z written, the residual read once
     with ops.prof_region("bn_train_fwd", flops=0.0, nbytes=float(B * H * W * Cc * y.element_size() * (3 if res is None else 4))):
@@ -103,14 +112,16 @@ def bn_train_fwd(y, gamma, beta, running_mean, running_var, eps, momentum, res=N
     return z, mean, invstd, scale
 
 
-def bn_train_bwd(dz, z, y, mean, invstd, scale, relu=True, want_dres=False, grad_mult=None, into=None):
+def bn_train_bwd(dz, z, y, mean, invstd, scale, relu=True, want_dres=False, grad_mult=None, into=None, out=None):
     """dgamma / dbeta come back multiplied by grad_mult (default: PARAM_GRAD_MULT, what every parameter gradient carries).
     into=(dgamma_slot, dbeta_slot): write them (Cc floats each; either may be None) straight into the parameters' gradient
-    slices -- each BatchNorm / bias parameter has one producer per step, so a plain store is the accumulation"""
+    slices -- each BatchNorm / bias parameter has one producer per step, so a plain store is the accumulation.
+    out=(dy, dres): write into these views (either may be None) instead of fresh tensors"""
     B, H, W, Cc = dz.shape
     dev = dz.device
-    dy = torch.empty(B, H, W, Cc, dtype=dz.dtype, device=dev)
-    dres = torch.empty(B, H, W, Cc, dtype=dz.dtype, device=dev) if want_dres else None
+    out = out or (None, None)
+    dy = _bn_out(out[0], dz)
+    dres = _bn_out(out[1], dz) if want_dres else None
     slots = [t if t is not None and t.numel() == Cc and t.is_contiguous() else None for t in (into or (None, None))]
     dgamma, dbeta = slots
     if dgamma is None or dbeta is None:
@@ -141,11 +152,11 @@ def bn_local_stats(y, rank, world):
     return stats
 
 
-def bn_sync_fwd(y, stats, gamma, beta, running_mean, running_var, eps, momentum, res=None, relu=True):
+def bn_sync_fwd(y, stats, gamma, beta, running_mean, running_var, eps, momentum, res=None, relu=True, out=None):
     """bn_train_fwd with the statistics of the gathered rank slots (bn_local_stats after the all-reduce)"""
     B, H, W, Cc = y.shape
     dev = y.device
-    z = torch.empty(B, H, W, Cc, dtype=y.dtype, device=dev)
+    z = _bn_out(out, y)
     mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(4))
     with ops.prof_region("bn_sync_fwd", flops=0.0, nbytes=float(B * H * W * Cc * y.element_size() * (2 if res is None else 3))):
         rc = _lib.lib().ctdet_bn_sync_fwd(_ptr(y), _nhwc_stride(y), _ptr(res), _nhwc_stride(res) if res is not None else 0,
@@ -177,13 +188,14 @@ def bn_local_grad_sums(dz, z, y, mean, invstd, rank, world, relu=True, grad_mult
     return sums, dgamma, dbeta
 
 
-def bn_sync_bwd(dz, z, y, mean, invstd, scale, stats, sums, relu=True, want_dres=False):
+def bn_sync_bwd(dz, z, y, mean, invstd, scale, stats, sums, relu=True, want_dres=False, out=None):
     """dy (and dres) from the gathered backward sums (bn_local_grad_sums after the all-reduce) over the global row count of
-    the gathered forward slots `stats`"""
+    the gathered forward slots `stats`; out: as bn_train_bwd"""
     B, H, W, Cc = dz.shape
     dev = dz.device
-    dy = torch.empty(B, H, W, Cc, dtype=dz.dtype, device=dev)
-    dres = torch.empty(B, H, W, Cc, dtype=dz.dtype, device=dev) if want_dres else None
+    out = out or (None, None)
+    dy = _bn_out(out[0], dz)
+    dres = _bn_out(out[1], dz) if want_dres else None
     with ops.prof_region("bn_sync_bwd", flops=0.0, nbytes=float(B * H * W * Cc * dz.element_size() * (4 + int(want_dres)))):
         rc = _lib.lib().ctdet_bn_sync_bwd(_ptr(dz), _nhwc_stride(dz), _ptr(z), _nhwc_stride(z) if z is not None else 0, _ptr(y),
                                           _nhwc_stride(y), _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(stats), _ptr(sums),

@@ -5,8 +5,7 @@
 each in f16 and f32.  Every shape is the smallest that takes the branch named next to it.  test_pointwise_host.py checks the tables
 against their own conditions on the CPU; test_pointwise_gpu.py runs the kernels over them.
 
-Out of scope: the BatchNorm kernels (test_syncbn_gpu.py holds them to float64 at the partial-block cap and at channel-vector counts
-that are no powers of two), the weight-pack kernels, the mirrored preprocess (test_tta_gpu.py), and NaN inputs to the pools: the
+Out of scope: the BatchNorm kernels (bn_cases.py holds their tables; test_bn_gpu.py runs them), the weight-pack kernels, the mirrored preprocess (test_tta_gpu.py), and NaN inputs to the pools: the
 kernels compare with `>`, which drops a NaN, where torch propagates it.  The eval step is behind the finite guard, so no NaN reaches
 a pool there; that difference is written down here and not tested.  The `gy > 65535` fall-back of launch_dwconvT_add to the generic
 kernel needs B * ceil(H / 8) * f > 65535, which no map of test size reaches.
