@@ -153,6 +153,31 @@ def lib():
     return _lib
 
 
+# libctdet_metrics.so (include/ctdet_metrics.h): the training loop's metric push, loaded when a metric ring is first built
+METRICS_LIB_PATH = os.path.join(_HERE, "lib", "libctdet_metrics.so")
+METRICS_SIGNATURES = {
+    "ctdet_metric_push": (_i32, [_vp, _i32, _f32, _vp, _i32, _i32, _vp, _i64, _vp]),
+}
+_metrics_lib = None
+
+
+def metrics_lib():
+    """Loads libctdet_metrics.so once (after libctdet_hip.so, which it links against); raises if it has not been built"""
+    global _metrics_lib
+    if _metrics_lib is None:
+        lib()
+        if not os.path.exists(METRICS_LIB_PATH):
+            raise RuntimeError(f"{METRICS_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C detectron2-centernet_amd/csrc`). There is no CPU fallback.")
+        l = C.CDLL(METRICS_LIB_PATH)
+        for name, (res, args) in METRICS_SIGNATURES.items():
+            fn = getattr(l, name)
+            fn.restype = res
+            fn.argtypes = args
+        _metrics_lib = l
+    return _metrics_lib
+
+
 def check(rc, what):
     if rc != 0:
         msg = lib().ctdet_last_error()

@@ -98,3 +98,32 @@ def register_synthetic(name, num_classes=80, length=1000, size=512):
 
     DatasetCatalog.register(name, _load)
     MetadataCatalog.get(name).set(thing_classes=[f"class_{i}" for i in range(num_classes)], synthetic=True)
+
+
+def register_synthetic_files(name, root, length=64, size=512, num_classes=80, max_boxes=8, replace=False):
+    """Registers `name` as a synthetic dataset a loader can read: the images of `synthetic_sample` are written as PNG files
+    under `root` (once; PNG is lossless, so a mapper decodes the sample's bytes) and the records carry their boxes as
+    annotations -- what `tools/train_net.py` trains on when the config's datasets are not registered, and what the trainer's
+    tests use.  A name that is registered already is an error unless `replace` is set."""
+    import os
+
+    from PIL import Image
+
+    from ..structures import BoxMode
+    if name in DatasetCatalog and not replace:
+        raise ValueError(f"Dataset '{name}' is already registered (replace=True replaces the registration)")
+    os.makedirs(root, exist_ok=True)
+    records = []
+    for i in range(length):
+        s = synthetic_sample(i, size=size, num_classes=num_classes, max_boxes=max_boxes)
+        path = os.path.join(root, f"{name}_{size}_{i:06d}.png")
+        if not os.path.exists(path):
+            Image.fromarray(s["image"].permute(1, 2, 0).contiguous().numpy()).save(path)
+        records.append({"file_name": path, "image_id": i, "height": size, "width": size, "annotations": [
+            {"bbox": b.tolist(), "bbox_mode": BoxMode.XYXY_ABS, "category_id": int(c), "iscrowd": 0}
+            for b, c in zip(s["boxes"], s["classes"])]})
+    if name in DatasetCatalog:
+        DatasetCatalog.remove(name)
+    DatasetCatalog.register(name, lambda: records)
+    MetadataCatalog.get(name).set(thing_classes=[f"class_{i}" for i in range(num_classes)], synthetic=True)
+    return records

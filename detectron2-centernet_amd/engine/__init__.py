@@ -1,5 +1,10 @@
-from .defaults import DefaultPredictor
+from . import hooks
+from .defaults import DefaultPredictor, DefaultTrainer, default_argument_parser, default_setup
+from .hooks import CallbackHook, EvalHook, IterationTimer, LRScheduler, PeriodicCheckpointer, PeriodicWriter
 from .launch import launch
-from .train_loop import SimpleTrainer
+from .metric_ring import MetricRing
+from .train_loop import HookBase, SimpleTrainer, TrainerBase
 
-__all__ = ["DefaultPredictor", "SimpleTrainer", "launch"]
+__all__ = ["DefaultPredictor", "DefaultTrainer", "default_argument_parser", "default_setup", "SimpleTrainer", "TrainerBase",
+           "HookBase", "MetricRing", "hooks", "CallbackHook", "EvalHook", "IterationTimer", "LRScheduler",
+           "PeriodicCheckpointer", "PeriodicWriter", "launch"]

@@ -1,26 +1,123 @@
-"""SimpleTrainer.run_step (detectron2/engine/train_loop.py:212-251) for the HIP training path."""
+"""HookBase, TrainerBase (detectron2/engine/train_loop.py:20-168) and SimpleTrainer.run_step (:212-251) for the HIP training
+path."""
+import logging
 import os
 import time
+import weakref
 
 import torch
 
 from .. import ops_train
 from ..solver import build_lr_scheduler, build_optimizer
+from ..utils import comm
+from ..utils.events import EventStorage
 from . import graph_nodes, train_step
 from .reducer import BucketedReducer
 
+__all__ = ["HookBase", "TrainerBase", "SimpleTrainer"]
 
 MAX_TRAIN_GRAPHS = int(os.environ.get("CTDET_MAX_TRAIN_GRAPHS", "4"))
+TARGET_CAPACITY = 128      # objects per image ops.gaussian_targets emits, whatever the width of the box tensor
 
 
-class SimpleTrainer:
+class HookBase:
+    """What runs around the steps of a TrainerBase:
+
+        hook.before_train()
+        for iter in range(start_iter, max_iter):
+            hook.before_step()
+            trainer.run_step()
+            hook.after_step()
+        hook.after_train()
+
+    `self.trainer` is a weak proxy of the trainer the hook is registered with.  In before_step and after_step,
+    `trainer.iter` is the iteration of the step and equals `trainer.storage.iter`."""
+
+    def before_train(self):
+        pass
+
+    def after_train(self):
+        pass
+
+    def before_step(self):
+        pass
+
+    def after_step(self):
+        pass
+
+
+class TrainerBase:
+    """an iterative trainer with hooks: `iter`, `start_iter`, `max_iter`, and `storage`, the EventStorage open while
+    `train` runs.  A subclass says what a step is (`run_step`)."""
+
+    def __init__(self):
+        self._hooks = []
+        self._in_train = False
+
+    def register_hooks(self, hooks):
+        """hooks run in the order they are registered; None entries are dropped"""
+        hooks = [h for h in hooks if h is not None]
+        for h in hooks:
+            assert isinstance(h, HookBase)
+            h.trainer = weakref.proxy(self)      # hooks and trainer must not own each other
+        self._hooks.extend(hooks)
+
+    def train(self, start_iter, max_iter):
+        logger = logging.getLogger(__name__)
+        logger.info("Starting training from iteration {}".format(start_iter))
+        self.iter = self.start_iter = start_iter
+        self.max_iter = max_iter
+        with EventStorage(start_iter) as self.storage:
+            self._in_train = True
+            try:
+                self.before_train()
+                for self.iter in range(start_iter, max_iter):
+                    self.before_step()
+                    self.run_step()
+                    self.after_step()
+            except Exception:
+                logger.exception("Exception during training:")
+                raise
+            finally:
+                self._in_train = False
+                self.after_train()
+
+    def before_train(self):
+        for h in self._hooks:
+            h.before_train()
+
+    def after_train(self):
+        for h in self._hooks:
+            h.after_train()
+
+    def before_step(self):
+        for h in self._hooks:
+            h.before_step()
+
+    def after_step(self):
+        for h in self._hooks:
+            h.after_step()
+        self.storage.step()      # so that in every hook's after_step, storage.iter == trainer.iter
+
+    def run_step(self):
+        raise NotImplementedError
+
+
+class SimpleTrainer(TrainerBase):
     """model(data) -> loss dict; sum; zero_grad; backward (bucketed all-reduce overlapped); SGD step; LR schedule.
 
     Per-iteration metrics are kept on the device and only fetched when `metrics()` is called: the reference does a
     `.item()` sync plus a Gloo pickle gather every step (train_loop.py:261-290), which this build avoids."""
 
-    def __init__(self, model, data_loader, cfg, optimizer=None, process_group=None):
+    def __init__(self, model, data_loader, cfg, optimizer=None, process_group=None, route_records=False):
+        """route_records: `run_step` sends a record batch whose images share one size to the captured step of
+        `run_step_tensors` (see `_record_tensors`); off, every record batch takes the eager path"""
+        super().__init__()
         model.train()
+        self.route_records = bool(route_records)
+        self.metric_ring = None        # attach_metric_ring(): per-step metrics without a host synchronisation
+        self.time_from_iteration = None
+        self.data_time = 0.0
         self.model, self.cfg = model, cfg
         self._data_iter = iter(data_loader) if data_loader is not None else None
         self.optimizer = optimizer or build_optimizer(cfg, model)
@@ -67,11 +164,92 @@ class SimpleTrainer:
 
     def run_step(self, data=None):
         assert self.model.training, "[SimpleTrainer] model was changed to eval mode!"
+        if self.metric_ring is not None:
+            self.metric_ring.begin_step()
         start = time.perf_counter()
         if data is None:
             data = next(self._data_iter)
         self.data_time = time.perf_counter() - start
+        if self.route_records:
+            tensors = self._record_tensors(data)
+            if tensors is not None:
+                return self.run_step_tensors(*tensors)
         return self._finish_step(self.model(data))
+
+    def _record_tensors(self, data):
+        """a record batch as the device tensors of `run_step_tensors`, or None when it has to stay on the eager path.
+        It qualifies when its images all have one size after mapping -- host-mapped uint8 "image" tensors, or raw
+        INPUT.DEVICE_AUGMENT records, which CenterNet.stage_raw_train resizes and jitters on the device -- and no image holds
+        more than TARGET_CAPACITY objects.  The images are stacked to uint8 [B,3,H,W]; boxes and classes are padded to
+        TARGET_CAPACITY, so that the key of the captured graph does not change with the object count.  Ragged batches are
+        zero-padded per image AFTER normalisation, which a stacked byte tensor cannot express: they stay eager.  The host
+        side of every copy is pinned memory: a pageable source would make the copy wait for the stream."""
+        dev = self.optimizer.flat_param.device
+        if dev.type != "cuda" or not data or any("instances" not in x for x in data):
+            return None
+        insts = [x["instances"] for x in data]
+        if max(len(i) for i in insts) > TARGET_CAPACITY:
+            return None
+        if any("image_raw" in x for x in data):
+            if any("image_raw" not in x or "resize_hw" not in x for x in data):
+                return None           # the eager path raises its own error for a mixed batch
+            if len({(int(x["resize_hw"][0]), int(x["resize_hw"][1])) for x in data}) != 1:
+                return None
+            images = torch.stack(self.model.stage_raw_train(data))
+        else:
+            imgs = [x["image"] for x in data]
+            if any(im.dtype != torch.uint8 or im.shape != imgs[0].shape or im.device != imgs[0].device for im in imgs):
+                return None
+            if imgs[0].is_cuda:
+                images = torch.stack(imgs)
+            else:
+                host = torch.empty((len(imgs),) + tuple(imgs[0].shape), dtype=torch.uint8, pin_memory=True)
+                torch.stack(imgs, out=host)
+                images = host.to(dev, non_blocking=True)
+        B = len(data)
+        boxes = torch.zeros(B, TARGET_CAPACITY, 4, dtype=torch.float32, pin_memory=True)
+        classes = torch.zeros(B, TARGET_CAPACITY, dtype=torch.int64, pin_memory=True)
+        counts = torch.zeros(B, dtype=torch.int32, pin_memory=True)
+        for b, inst in enumerate(insts):
+            n = len(inst)
+            counts[b] = n
+            if n:
+                boxes[b, :n] = inst.gt_boxes.tensor.detach().float().cpu()
+                classes[b, :n] = inst.gt_classes.detach().cpu()
+        return (images, boxes.to(dev, non_blocking=True), classes.to(dev, non_blocking=True),
+                counts.to(dev, non_blocking=True))
+
+    def attach_metric_ring(self, ring=None):
+        """from now on every step pushes its losses, its data time and its iteration into a device-side ring
+        (engine/metric_ring.py) instead of anybody reading them back; `flush_metrics()` fetches them"""
+        from .metric_ring import MetricRing
+        if ring is None:
+            group = self.reducer.group if self.reducer.world > 1 else None
+            ring = MetricRing(self.optimizer.flat_param.device, process_group=group)
+        self.metric_ring = ring
+        return ring
+
+    def flush_metrics(self):
+        """the ring's unread iterations into the event storage, each at its own iteration (main process only, like
+        train_loop.py:275); raises FloatingPointError when a loss of one of them was not finite.  Whatever saves or scores the
+        model calls this first.  Returns the records."""
+        if self.metric_ring is None:
+            return []
+        from .metric_ring import put_records
+        records = self.metric_ring.flush()
+        storage = getattr(self, "storage", None)
+        if records and storage is not None and comm.is_main_process():
+            put_records(storage, records, self.time_from_iteration)
+        return records
+
+    def _step_done(self, losses):
+        """the end of every step: the metrics push (when a ring is attached) and the iteration counter, which the loop of
+        `train` owns while it runs"""
+        if self.metric_ring is not None:
+            self.metric_ring.push(losses, self.data_time, self.iter)
+            self.data_time = 0.0
+        if not self._in_train:
+            self.iter += 1
 
     def run_step_tensors(self, images, boxes, classes, counts):
         """device-resident batch (uint8 [B,3,H,W], boxes f32 [B,N,4], classes i64 [B,N], counts i32 [B]).
@@ -84,6 +262,8 @@ class SimpleTrainer:
         they overlap backward).  Two ranks on one device == the single-process trajectory to 1e-7
         (tests/test_dp_gpu.py::test_two_rank_graph_steps_equal_single_rank_steps).  The LR schedule and the per-parameter
         version counters stay on the host.  CTDET_TRAIN_GRAPH=0 keeps every step eager."""
+        if self.metric_ring is not None:
+            self.metric_ring.begin_step()
         multi = self.reducer.world > 1
         if not self.use_hip_graph or (multi and not self.graph_ddp):
             return self._finish_step(self.model.train_batch_tensor(images, boxes, classes, counts))
@@ -132,8 +312,8 @@ class SimpleTrainer:
         for p in self.optimizer.params:   # the captured update kernels (SGD / Adam) wrote the parameters behind autograd's back
             torch.autograd.graph.increment_version(p)
         self.scheduler.step()
-        self.iter += 1
         self.last_losses = g["losses"]
+        self._step_done(self.last_losses)
         return self.last_losses
 
     def _log_step(self, col, losses=None):
@@ -251,8 +431,8 @@ class SimpleTrainer:
         self.reducer.finish()
         self.optimizer.step()
         self.scheduler.step()
-        self.iter += 1
         self.last_losses = {k: v.detach() for k, v in loss_dict.items()}
+        self._step_done(self.last_losses)
         if train_step.STEP_CHECK == 1:
             self._check_step("after the eager step", self.last_losses)
         return self.last_losses

@@ -45,6 +45,25 @@ def set_world_size(world):
     PARAM_GRAD_MULT = 1.0 / (GRAD_SCALE * max(1, int(world)))
 
 
+METRIC_MAX_SCALARS = 8
+METRIC_NO_BAD_ITERATION = 0x7FFFFFFF
+
+
+def metric_push(scalars, host_scalar, ring, first_bad, iteration):
+    """one launch behind a step: the f32 device scalars `scalars` (at most 8 one-element tensors), `host_scalar` and the tag
+    `iteration` into row `iteration % ring.shape[0]` of `ring` (f32 [rows, row_floats]); `first_bad` (int32 [1]) keeps the
+    smallest iteration with a non-finite scalar (see ctdet_metric_push).  No synchronisation."""
+    scalars = list(scalars)
+    _require_cuda(ring, first_bad, *scalars)
+    assert ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous()
+    assert first_bad.dtype == torch.int32 and first_bad.numel() == 1
+    assert all(t.dtype == torch.float32 and t.numel() == 1 for t in scalars), "metric_push takes one-element f32 tensors"
+    ptrs = (C.c_void_p * max(1, len(scalars)))(*[t.data_ptr() for t in scalars])
+    rc = _lib.metrics_lib().ctdet_metric_push(ptrs, len(scalars), float(host_scalar), _ptr(ring), ring.shape[0], ring.shape[1],
+                                      _ptr(first_bad), int(iteration), _stream())
+    _lib.check(rc, "ctdet_metric_push")
+
+
 class ZeroArena:
     """One f32 buffer that is cleared with a single fill at the start of a training step and handed out in slices to the
     kernels that accumulate with atomics (the weight gradients): ~80 fills per step become one.  A slice lives until the
