@@ -748,7 +748,9 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
 //     its channel-group bits, the blend 16 FMAs per 4 channels (was: 6 for the weights + 20 + 9 of address arithmetic);
 //   * far samples (outside the +-4 px window) re-derive their coordinates from the offsets in the wave-uniform slow path
 //     instead of carrying a second LDS table;
-//   * the split of a sampled fragment feeds the MFMAs directly: b1 = {hi, 0}, b2 = {lo, hi} (conv_common.h).
+//   * the split of a sampled fragment feeds the MFMAs directly: b1 = {hi, 0}, b2 = {lo, hi} (conv_common.h);
+//   * the window addresses of a lane's pixels are read from the code table once per tile and held in registers, with one
+//     wave-uniform far bit per tap: the tap loop has no code read, wait or compare in front of its corner reads.
 // Same tile (8x16 pixels x 64 couts), window (18x26 pixels, 16-channel chunks of f32), ring (a stage = the three taps of a
 // kernel row) and barriers as dcn_f32_window_kernel.
 // ------------------------------------------------------------------------------------------
@@ -766,6 +768,12 @@ __global__ void __launch_bounds__(256, 2) dcn_f32_window_kernel(const ConvArgs a
 // FIN (FUS only): the epilogue also tests what it stores for inf / NaN and reports into *a.finite (finite_note, conv_common.h):
 // the eval step's guard on the heads' input map, which this kernel writes, without a pass over that map.  A template
 // parameter for the reason COLS is one: the other instantiations keep their code and registers.
+// measurement builds only (tools/ablate_dcn.sh; never set by the Makefile): CTDET_DCN_ABLATE & 1 samples every tap at tap 0's
+// window addresses (finite, in-window offsets: every read stays, nothing in the loop depends on the tap's table entry any more),
+// & 2 drops the wait for the next chunk's window behind its DMAs (wrong results; what that wait costs).  profiles/r20_dcn_sampler_ablation.txt
+#ifndef CTDET_DCN_ABLATE
+#define CTDET_DCN_ABLATE 0
+#endif
 template <int TP, int BC, bool COLS = false, bool NM = false, bool FUS = false, bool FIN = false>
 __global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const ConvArgs a) {
   static_assert(!FUS || (TP == 2 && BC == 64 && !COLS && !NM), "the fused offset conv: inference form of the 64-cout DCNv2 tile");
@@ -786,6 +794,10 @@ __global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const Con
   char* const geow = smem + WINB;
   char* const geoc = smem + WINB + GEOW;
   char* const ring = smem + WINB + GEOW + GEOC;
+  // row of tile pixel px in the weight table: the consumer's ds_read_b128 serves lanes fr 0..15 of one q in one LDS cycle, and
+  // with TP = 2 those are the pixels px0 + 0..7 and px0 + 16 + 0..7 -- 256 B apart, the same banks twice.  Odd tile rows swap
+  // their halves: the 16 rows of a lane group are then 16 different 16-byte slots (TP = 1: 16 consecutive pixels, as before)
+  auto geow_row = [](int px) { return px ^ (((px >> 4) & 1) << 3); };
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1058,7 +1070,7 @@ __global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const Con
         const unsigned code = (valid && inside) ? ((unsigned)((wr * WCOLS + wcn) * 64) | ((unsigned)(wr & 1) << 5)) : (oow ? farcode : 0u);
         f32x4 gv;
         gv[0] = hh * hw * mk; gv[1] = hh * lw * mk; gv[2] = lh * hw * mk; gv[3] = lh * lw * mk;
-        *(f32x4*)(geow + (t * BP + gp) * 16) = gv;
+        *(f32x4*)(geow + (t * BP + geow_row(gp)) * 16) = gv;
         *(unsigned*)(geoc + (t * BP + gp) * 4) = code;
       }
     }
@@ -1071,37 +1083,75 @@ __global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const Con
   const int prow = TP == 2 ? 2 * wave + (fr >> 3) : wave, pcol = TP == 2 ? (fr & 7) : fr;
   const unsigned q4 = (unsigned)q << 4;
 
-  // sampling of tap t in two halves, so that the MFMAs of the previous tap can be issued between them: `gather` starts the
-  // LDS reads (weights, window code, the four corner fragments of both pixel tiles), `blend` turns them into split operands
-  struct Raw { f32x4 w[TP], v[TP][4]; };
-  auto gather = [&](int t, int chunk, Raw& r) {
-    unsigned code[TP];
+  // The window code of a (tap, pixel) is the same for every channel chunk: each lane reads the codes of its own pixels once,
+  // here, and keeps the window addresses A[t][p] = (code & 0xFFFF) ^ q4 in registers (indexed by the compile-time tap only).
+  // Bit t of far_taps (wave-uniform, an SGPR): some lane of this wave has a far sample at tap t.  The tap loop then has no
+  // LDS round trip and no vector compare in front of its corner reads; geoc is re-read only by the slow path.
+  // ALLC = false (the <2,64> forms without the fused offset conv: 18 more registers spill there): far_taps as above, but only
+  // the codes of the NEXT tap to be gathered are carried (cnext, TP registers), read behind the corner reads of the tap before:
+  // the round trip is off the chain, the re-reads per chunk stay.
+  constexpr bool ALLC = FUS || TP == 1;
+  unsigned A[ALLC ? 9 : 1][TP];
+  unsigned cnext[TP];
+  unsigned far_taps = 0;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
     unsigned far = 0;
 #pragma unroll
     for (int p = 0; p < TP; ++p) {
       const int px = prow * 16 + (TP == 2 ? 8 * p : 0) + pcol;
-      r.w[p] = *(const f32x4*)(geow + (t * BP + px) * 16);
-      code[p] = *(const unsigned*)(geoc + (t * BP + px) * 4);
-      far |= code[p] >> 31;
+      const unsigned c = *(const unsigned*)(geoc + (t * BP + px) * 4);
+      if constexpr (ALLC) A[t][p] = (c & 0xFFFFu) ^ q4;
+      else if (t == 0) cnext[p] = c;
+      far |= c >> 31;
     }
-    const bool any_far = __builtin_amdgcn_ballot_w64(far != 0) != 0;      // wave-uniform
+    if (__builtin_amdgcn_ballot_w64(far != 0) != 0) far_taps |= 1u << t;
+  }
+  far_taps = __builtin_amdgcn_readfirstlane(far_taps);
+
+  // sampling of tap t in two halves, so that the MFMAs of the previous tap can be issued between them: `gather` starts the
+  // LDS reads (weights, the four corner fragments of both pixel tiles), `blend` turns them into split operands
+  struct Raw { f32x4 w[TP], v[TP][4]; };
+  auto gather = [&](auto tc, int chunk, Raw& r) {
+    constexpr int t = decltype(tc)::value;
+    constexpr int ta = (CTDET_DCN_ABLATE & 1) ? 0 : t;       // measurement builds: tap 0's addresses and far bit for every tap
 #pragma unroll
     for (int p = 0; p < TP; ++p) {
-      const unsigned A = (code[p] & 0xFFFFu) ^ q4;
-      const char* c0p = win + A;
-      const char* c2p = win + (A ^ 32u) + WCOLS * 64;       // next window row: the other slot swizzle
+      const int px = prow * 16 + (TP == 2 ? 8 * p : 0) + pcol;
+      r.w[p] = *(const f32x4*)(geow + (t * BP + geow_row(px)) * 16);
+    }
+#pragma unroll
+    for (int p = 0; p < TP; ++p) {
+      unsigned Ap;
+      if constexpr (ALLC) Ap = A[ta][p];
+      else Ap = (cnext[p] & 0xFFFFu) ^ q4;
+      const char* c0p = win + Ap;
+      const char* c2p = win + (Ap ^ 32u) + WCOLS * 64;       // next window row: the other slot swizzle
       r.v[p][0] = *(const f32x4*)(c0p); r.v[p][1] = *(const f32x4*)(c0p + 64);
       r.v[p][2] = *(const f32x4*)(c2p); r.v[p][3] = *(const f32x4*)(c2p + 64);
-      if (any_far) {                                          // rare: the lanes concerned re-derive the sample from the offsets
-        const bool out = code[p] >> 31;
-        const int py = ty0 + prow, pxx = tx0 + (TP == 2 ? 8 * p : 0) + pcol, tr = t / 3, ts = t - 3 * (t / 3);
+    }
+    if constexpr (!ALLC && !(CTDET_DCN_ABLATE & 1)) {         // the gathers go round the nine taps: the next one's codes
+#pragma unroll
+      for (int p = 0; p < TP; ++p) {
+        const int px = prow * 16 + (TP == 2 ? 8 * p : 0) + pcol;
+        cnext[p] = *(const unsigned*)(geoc + ((t + 1) % 9 * BP + px) * 4);
+      }
+    }
+    if ((far_taps >> ta) & 1u) {                              // rare: the lanes concerned re-derive the sample from the offsets
+#pragma unroll
+      for (int p = 0; p < TP; ++p) {
+        const int px = prow * 16 + (TP == 2 ? 8 * p : 0) + pcol;
+        const unsigned code = *(const unsigned*)(geoc + (ta * BP + px) * 4);
+        const bool out = code >> 31;
+        // (ta throughout: `out` says that the sample of tap ta is valid, which is what keeps the corners below inside the image)
+        const int py = ty0 + prow, pxx = tx0 + (TP == 2 ? 8 * p : 0) + pcol, tr = ta / 3, ts = ta - 3 * (ta / 3);
         int h_low, w_low;
         if constexpr (FUS) {                                  // the corner the geometry stage left in the code word
-          h_low = (int)((code[p] >> 16) & 0xFFFu) - 1; w_low = (int)((code[p] >> 4) & 0xFFFu) - 1;
+          h_low = (int)((code >> 16) & 0xFFFu) - 1; w_low = (int)((code >> 4) & 0xFFFu) - 1;
         } else {
           const float* omrow = a.om + ((long)(b * a.H + py) * a.W + pxx) * a.om_stride;
           float dh, dw;
-          gload2_sync(omrow + 2 * t, dh, dw);                // (asm loads: see gload2_sync)
+          gload2_sync(omrow + 2 * ta, dh, dw);               // (asm loads: see gload2_sync)
           const float h_im = (float)(py - 1 + tr) + dh, w_im = (float)(pxx - 1 + ts) + dw;
           h_low = (int)floorf(h_im); w_low = (int)floorf(w_im);
         }
@@ -1151,7 +1201,7 @@ __global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const Con
   f16x8 b1[TP], b2[TP], wf[TC];
   {
     Raw r0;
-    gather(0, 0, r0);
+    gather(std::integral_constant<int, 0>{}, 0, r0);
     blend(r0, b1, b2, 0, 0);
   }
   const int ns = nch * 3;
@@ -1168,8 +1218,8 @@ __global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const Con
     }
     Raw raw;
     frags(st, TS, wf);                                             // this tap's weight fragments
-    if (T < 8) {
-      gather(T + 1, chunk, raw);                                   // LDS reads in flight behind the MFMAs below
+    if constexpr (T < 8) {
+      gather(std::integral_constant<int, T + 1>{}, chunk, raw);    // LDS reads in flight behind the MFMAs below
     } else if (chunk + 1 < nch) {                                  // tap 8 was sampled during tap 7: the window is free
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -1185,13 +1235,13 @@ __global__ void __launch_bounds__(512 / TP, 2) dcn_split_window_kernel(const Con
       for (int c = 0; c < TC; ++c) acc[p][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[c], b2[p], acc[p][c], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);                             // the operands above are consumed: b1 / b2 may be rewritten
-    if (T < 8) {
+    if constexpr (T < 8) {
       blend(raw, b1, b2, T + 1, chunk);
     } else if (chunk + 1 < nch) {
-      wait_vmcnt<0>();                                             // next chunk's window, behind this tap's MFMAs
+      if (!(CTDET_DCN_ABLATE & 2)) wait_vmcnt<0>();                // next chunk's window, behind this tap's MFMAs
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      gather(0, chunk + 1, raw);
+      gather(std::integral_constant<int, 0>{}, chunk + 1, raw);
       blend(raw, b1, b2, 0, chunk + 1);
     }
   };
