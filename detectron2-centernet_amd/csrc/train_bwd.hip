@@ -8,6 +8,7 @@
 // Input-gradient of plain convs reuses the forward implicit-GEMM kernels with transposed/flipped weights.
 #include "common.h"
 #include <stdlib.h>
+#include <initializer_list>
 #include <type_traits>
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -151,9 +152,35 @@ __global__ void __launch_bounds__(256) chan_reduce_kernel(ChanRedArgs<T> a) {
   }
 }
 
+// chan_reduce's block partials of channel c summed by a 256-thread workgroup: threads stride over the blocks, then a
+// fixed-order f64 shuffle + LDS reduction (deterministic).  True on thread 0, which holds the two sums; the others are done.
+__device__ __forceinline__ bool chan_partial_sums(const float* __restrict__ partial, int nblocks, int C, int c, double& s0,
+                                                  double& s1) {
+  __shared__ double sh[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  s0 = 0; s1 = 0;
+  for (int b = threadIdx.x; b < nblocks; b += 256) { s0 += partial[((long)b * 2 + 0) * C + c]; s1 += partial[((long)b * 2 + 1) * C + c]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_down(s0, o, 64); s1 += __shfl_down(s1, o, 64); }
+  if (lane == 0) { sh[0][wave] = s0; sh[1][wave] = s1; }
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  s0 = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
+  s1 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
+  return true;
+}
+
+// mode 0 sums of M rows around the pivot K (null: plain sums) -> mean and biased variance
+__device__ __forceinline__ void chan_mean_var(double s0, double s1, int M, const float* __restrict__ pivot, int c, double& mean,
+                                              double& var) {
+  const double dm = s0 / M;                   // mean - K
+  mean = pivot ? (double)pivot[c] + dm : dm;
+  var = s1 / M - dm * dm;
+  if (var < 0) var = 0;
+}
+
 // mode 0: mean/invstd/scale/shift (+ running stats) from the sums around the pivot (null: plain sums);
 // mode 1: out0 = sum g (dbeta / dbias), out1 = sum g*xhat (dgamma)
-// threads stride over the block partials, fixed-order f64 shuffle + LDS reduction (deterministic)
 __global__ void __launch_bounds__(256) chan_finalize_kernel(const float* __restrict__ partial, int nblocks, int C, int M,
                                                             int mode, float eps, float momentum,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -164,23 +191,12 @@ __global__ void __launch_bounds__(256) chan_finalize_kernel(const float* __restr
                                                             const float* __restrict__ pivot) {
   // one workgroup per channel (the kernel sits on the step's dependency chain 146 times: with one wave per channel and 16
   // serial loads per lane it took 6 us)
-  __shared__ double sh[2][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x;
-  double s0 = 0, s1 = 0;
-  for (int b = threadIdx.x; b < nblocks; b += 256) { s0 += partial[((long)b * 2 + 0) * C + c]; s1 += partial[((long)b * 2 + 1) * C + c]; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_down(s0, o, 64); s1 += __shfl_down(s1, o, 64); }
-  if (lane == 0) { sh[0][wave] = s0; sh[1][wave] = s1; }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  s0 = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
-  s1 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
+  double s0, s1;
+  if (!chan_partial_sums(partial, nblocks, C, c, s0, s1)) return;
   if (mode == 0) {
-    const double dm = s0 / M;                   // mean - K
-    const double mean = pivot ? (double)pivot[c] + dm : dm;
-    double var = s1 / M - dm * dm;
-    if (var < 0) var = 0;
+    double mean, var;
+    chan_mean_var(s0, s1, M, pivot, c, mean, var);
     const double invstd = 1.0 / sqrt(var + (double)eps);
     out0[c] = (float)mean;
     out1[c] = (float)invstd;
@@ -202,6 +218,45 @@ __global__ void __launch_bounds__(256) chan_finalize_kernel(const float* __restr
   }
 }
 
+// The BN forward element, one channel vector: z = act(y * scale + shift + res).  The vector's coefficients are scale[c0 + e],
+// shift[c0 + e] (global memory, registers or LDS, as the calling kernel keeps them); r is read only with has_res.
+template <typename T, typename V = typename VecT<T>::type>
+__device__ __forceinline__ V bn_fwd_elem(const V& v, const V& r, bool has_res, const float* scale, const float* shift, int c0,
+                                         int relu) {
+  V o;
+#pragma unroll
+  for (int e = 0; e < VecT<T>::N; ++e) {
+    float f = (float)v[e] * scale[c0 + e] + shift[c0 + e];
+    if (has_res) f += (float)r[e];
+    if (relu) f = fmaxf(f, 0.f);
+    o[e] = (T)f;
+  }
+  return o;
+}
+
+// The BN backward element, one channel vector: g = dz * (z > 0 if relu) (the residual branch's gradient);
+// dy = scale * (g - a0 - xhat * a1), xhat = (y - mean) * invstd, a0 = sum g / M, a1 = sum g*xhat / M formed per channel by
+// the caller; the vector's coefficients are mean[c0 + e] etc.  Without y (bias + act layers) dy = g and none of them is read.
+template <typename V> struct BnGrad { V g, dy; };
+template <typename T, typename V = typename VecT<T>::type>
+__device__ __forceinline__ BnGrad<V> bn_bwd_elem(V dz, V z, V y, bool has_y, const float* mean, const float* invstd,
+                                                 const float* scale, const float* a0, const float* a1, int c0, int relu) {
+  BnGrad<V> o;
+#pragma unroll
+  for (int e = 0; e < VecT<T>::N; ++e) {
+    const float gf = (relu && !((float)z[e] > 0.f)) ? 0.f : (float)dz[e];
+    o.g[e] = (T)gf;
+    if (has_y) {
+      const int c = c0 + e;
+      const float xh = ((float)y[e] - mean[c]) * invstd[c];
+      o.dy[e] = (T)(scale[c] * (gf - a0[c] - xh * a1[c]));
+    } else {
+      o.dy[e] = (T)gf;
+    }
+  }
+  return o;
+}
+
 // z = act(y * scale + shift + res)   (BN apply)
 template <typename T>
 __global__ void __launch_bounds__(256) affine_act_kernel(const T* __restrict__ y, int y_stride,
@@ -218,15 +273,7 @@ __global__ void __launch_bounds__(256) affine_act_kernel(const T* __restrict__ y
   const V v = *(const V*)(y + m * y_stride + cv * N);
   V r = v;
   if (res) r = *(const V*)(res + m * res_stride + cv * N);
-  V o;
-#pragma unroll
-  for (int e = 0; e < N; ++e) {
-    float f = (float)v[e] * scale[cv * N + e] + shift[cv * N + e];
-    if (res) f += (float)r[e];
-    if (relu) f = fmaxf(f, 0.f);
-    o[e] = (T)f;
-  }
-  *(V*)(z + m * z_stride + cv * N) = o;
+  *(V*)(z + m * z_stride + cv * N) = bn_fwd_elem<T>(v, r, res != nullptr, scale, shift, cv * N, relu);
 }
 
 // the same for channel-vector counts that are powers of two: a thread owns one channel group, keeps its coefficients in
@@ -247,15 +294,7 @@ __global__ void __launch_bounds__(256) affine_act_rows_kernel(const T* __restric
 #pragma unroll
   for (int e = 0; e < N; ++e) { sc[e] = scale[cv * N + e]; sh[e] = shift[cv * N + e]; }
   auto finish = [&](long m, const V& v, const V& r) {
-    V o;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      float f = (float)v[e] * sc[e] + sh[e];      // same expression as the generic kernel
-      if (res) f += (float)r[e];
-      if (relu) f = fmaxf(f, 0.f);
-      o[e] = (T)f;
-    }
-    *(V*)(z + m * z_stride + cv * N) = o;
+    *(V*)(z + m * z_stride + cv * N) = bn_fwd_elem<T>(v, r, res != nullptr, sc, sh, 0, relu);
   };
   if (m0 + (long)(AA_ROWS - 1) * ppb < M) {
 #pragma unroll
@@ -283,8 +322,7 @@ __global__ void __launch_bounds__(256) affine_act_rows_kernel(const T* __restric
   }
 }
 
-// BN backward apply: g = dz*(z>0); dy = scale*(g - s0/M - xhat*s1/M); optional dres = g.
-// With y == null (bias+act layers): dy = g.
+// BN backward apply (bn_bwd_elem with a0 = s0/M, a1 = s1/M); optional dres = g.
 template <typename T>
 __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __restrict__ dz, int dz_stride,
                                                            const T* __restrict__ z, int z_stride,
@@ -305,21 +343,14 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __restrict__
   if (relu) zz = *(const V*)(z + m * z_stride + cv * N);
   if (y) yy = *(const V*)(y + m * y_stride + cv * N);
   const float invM = 1.f / (float)M;
-  V o, gr;
+  float a0[N], a1[N];
+  if (y) {
 #pragma unroll
-  for (int e = 0; e < N; ++e) {
-    const int c = cv * N + e;
-    const float gf = (relu && !((float)zz[e] > 0.f)) ? 0.f : (float)g[e];
-    gr[e] = (T)gf;
-    if (y) {
-      const float xh = ((float)yy[e] - mean[c]) * invstd[c];
-      o[e] = (T)(scale[c] * (gf - s0[c] * invM - xh * s1[c] * invM));
-    } else {
-      o[e] = (T)gf;
-    }
+    for (int e = 0; e < N; ++e) { a0[e] = s0[cv * N + e] * invM; a1[e] = s1[cv * N + e] * invM; }
   }
-  *(V*)(dy + m * dy_stride + cv * N) = o;
-  if (dres) *(V*)(dres + m * dres_stride + cv * N) = gr;
+  const BnGrad<V> o = bn_bwd_elem<T>(g, zz, yy, y != nullptr, mean + cv * N, invstd + cv * N, scale + cv * N, a0, a1, 0, relu);
+  *(V*)(dy + m * dy_stride + cv * N) = o.dy;
+  if (dres) *(V*)(dres + m * dres_stride + cv * N) = o.g;
 }
 
 // the same for channel-vector counts that are powers of two (every BatchNorm of DLA-34): a thread owns one channel group,
@@ -351,20 +382,9 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_rows_kernel(const T* __restr
     }
   }
   auto finish = [&](long m, const V& g, const V& zz, const V& yy) {
-    V o, gr;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      const float gf = (relu && !((float)zz[e] > 0.f)) ? 0.f : (float)g[e];
-      gr[e] = (T)gf;
-      if (y) {
-        const float xh = ((float)yy[e] - mu[e]) * is[e];
-        o[e] = (T)(sc[e] * (gf - a0[e] - xh * a1[e]));     // same expression as the generic kernel
-      } else {
-        o[e] = (T)gf;
-      }
-    }
-    *(V*)(dy + m * dy_stride + cv * N) = o;
-    if (dres) *(V*)(dres + m * dres_stride + cv * N) = gr;
+    const BnGrad<V> o = bn_bwd_elem<T>(g, zz, yy, y != nullptr, mu, is, sc, a0, a1, 0, relu);
+    *(V*)(dy + m * dy_stride + cv * N) = o.dy;
+    if (dres) *(V*)(dres + m * dres_stride + cv * N) = o.g;
   };
   if (m0 + (long)(BN_ROWS - 1) * ppb < M) {
     // whole range in bounds: four rows of the three tensors in flight before the first use (a loop with a bounds `break`
@@ -922,6 +942,18 @@ __device__ __forceinline__ void dom_store(void* dom, int dom_f16, long m, int do
   }
 }
 
+// a (pixel, tap) work index -> the tap, the pixel's row m of the NHWC tensors and its (b, ho, wo)
+struct DcnWork { int tap; long m; int b, ho, wo; };
+__device__ __forceinline__ DcnWork dcn_work(long wk, int H, int W) {
+  DcnWork k;
+  k.tap = (int)(wk % 9);
+  k.m = wk / 9;
+  k.wo = (int)(k.m % W);
+  const long t2 = k.m / W;
+  k.ho = (int)(t2 % H); k.b = (int)(t2 / H);
+  return k;
+}
+
 // col[m][tap*Cin + c] = mask * bilinear(x)   (the `columns` of the reference, f16, tap-major)
 template <bool NM>
 __global__ void __launch_bounds__(256) dcn_cols_kernel(const f16* __restrict__ x, int x_stride, const float* __restrict__ om,
@@ -931,13 +963,10 @@ __global__ void __launch_bounds__(256) dcn_cols_kernel(const f16* __restrict__ x
   const long total = (long)B * H * W * 9 * CV;
   if (idx >= total) return;
   const int cv = (int)(idx % CV);
-  long t = idx / CV;
-  const int tap = (int)(t % 9);
-  const long m = t / 9;
-  const int wo = (int)(m % W);
-  const long t2 = m / W;
-  const int ho = (int)(t2 % H), b = (int)(t2 / H);
-  const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
+  const DcnWork k = dcn_work(idx / CV, H, W);
+  const int tap = k.tap;
+  const long m = k.m;
+  const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, k.b, k.ho, k.wo, H, W, x_stride, mask_is_prob);
   float acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
@@ -954,12 +983,13 @@ __global__ void __launch_bounds__(256) dcn_cols_kernel(const f16* __restrict__ x
   *(f16x8*)(col + m * (9L * Cin) + (long)tap * Cin + cv * 8) = o;
 }
 
-// given dcol (= W^T dY, [M][9*Cin] f16): dx (f32 atomics), d(offset), d(mask logit) -> dom [M][om_stride] f32.
+// given dcol (= W^T dY, [M][9*Cin]): dx (f32 atomics), d(offset), d(mask logit) -> dom [M][dom_stride].  T: the element type of
+// dcol and x, f16 or float; f32 tensors always take an f32 dom (decided at compile time), f16 ones dom_f16 says which.
 // One wave per (pixel, tap) pass over the channels, one lane per channel: every atomic wave-instruction adds 64
 // consecutive floats (256 contiguous bytes, the shape the memory-side atomic units run at full rate with); the
 // three per-(pixel,tap) dot products are wave reductions.
-template <bool NM>
-__global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __restrict__ dcol, const f16* __restrict__ x,
+template <typename T, bool NM>
+__global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const T* __restrict__ dcol, const T* __restrict__ x,
                                                                int x_stride, const float* __restrict__ om, int om_stride,
                                                                float* __restrict__ dx, void* __restrict__ dom, int dom_stride,
                                                                int dom_f16, int B, int H, int W, int Cin, int mask_is_prob,
@@ -968,16 +998,14 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __rest
   const long wave_id = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const long nwork = (long)B * H * W * 9;
   for (long wk = wave_id; wk < nwork; wk += (long)gridDim.x * 4) {
-    const int tap = (int)(wk % 9);
-    const long m = wk / 9;
-    const int wo = (int)(m % W);
-    const long t2 = m / W;
-    const int ho = (int)(t2 % H), b = (int)(t2 / H);
-    const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);  // wave-uniform
+    const DcnWork k = dcn_work(wk, H, W);
+    const int tap = k.tap;
+    const long m = k.m;
+    const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, k.b, k.ho, k.wo, H, W, x_stride, mask_is_prob);  // wave-uniform
     float val_dot = 0.f, dh = 0.f, dwv = 0.f;
     if (g.inside) {
       // dcol row of a pixel: [tap][Cin], or chunked [Cin/32][tap][32]
-      const f16* dcp = dcol + m * (9L * Cin) + (chunked ? tap * 32 : tap * Cin);
+      const T* dcp = dcol + m * (9L * Cin) + (chunked ? tap * 32 : tap * Cin);
       for (int c = lane; c < Cin; c += 64) {
         const float d = (float)dcp[chunked ? (c >> 5) * 288 + (c & 31) : c];
         float v[4];
@@ -999,7 +1027,8 @@ __global__ void __launch_bounds__(256) dcn_col2im_coord_kernel(const f16* __rest
       dwv += __shfl_down(dwv, o, 64);
     }
     if (lane == 0)   // the mask logit's gradient goes through its sigmoid
-      dom_store<NM>(dom, dom_f16, m, dom_stride, tap, dh * g.mask, dwv * g.mask, mask_is_prob ? val_dot : val_dot * g.mask * (1.f - g.mask));
+      dom_store<NM>(dom, sizeof(T) == 2 ? dom_f16 : 0, m, dom_stride, tap, dh * g.mask, dwv * g.mask,
+                    mask_is_prob ? val_dot : val_dot * g.mask * (1.f - g.mask));
   }
 }
 
@@ -1347,28 +1376,63 @@ static int chan_blocks(int M, int C, int N) {
   return (int)nb;
 }
 
+// log2 of a channel-vector count that is a power of two, -1 for any other
+static int cv_shift_of(int CV) {
+  if (CV & (CV - 1)) return -1;
+  int sh = 0;
+  while ((1 << sh) < CV) ++sh;
+  return sh;
+}
+
+// what every BN launcher (`who`) asks: whole channel vectors, at most 256 of them, and every tensor it was given 16-byte
+// aligned with a pixel stride of whole vectors (an optional tensor that is absent arrives as null and is passed over; the
+// entry points have refused a required one that is null)
+struct BnTensor { const void* p; int stride; };
+template <typename T>
+static int bn_check(const char* who, int C, std::initializer_list<BnTensor> tensors) {
+  constexpr int N = VecT<T>::N;
+  CTDET_CHECK(C % N == 0 && C / N <= 256, "%s: unsupported channel count %d", who, C);
+  bool ok = true;
+  for (const BnTensor& t : tensors) ok = ok && (!t.p || (t.stride % N == 0 && ((size_t)t.p & 15) == 0));
+  CTDET_CHECK(ok, "%s: tensors must be 16-byte aligned with pixel strides that are multiples of %d", who, N);
+  return 0;
+}
+
+// the [2][C] floats behind the block partials in the workspace: the finalized sums of the fused backward
+static float* bn_sums_slot(const BnArgs& b) { return (float*)b.workspace + (size_t)1024 * 2 * b.C; }
+
+// chan_reduce_kernel over b's tensors in `mode` into the block partials at the head of b.workspace; returns the block count.
+// Mode 0 hands the finalize kernel its pivot: f32 tensors keep it in the sums slot, free in the forward; f16 ones have none.
+template <typename T>
+static int bn_chan_reduce(const BnArgs& b, int mode, hipStream_t s, const float** pivot = nullptr) {
+  ChanRedArgs<T> a = {};
+  a.y = (const T*)b.y; a.y_stride = b.y_stride; a.M = b.M; a.C = b.C; a.mode = mode; a.partial = (float*)b.workspace;
+  if (mode == 0) {
+    a.pivot = std::is_same<T, float>::value ? bn_sums_slot(b) : nullptr;
+    *pivot = a.pivot;
+  } else {
+    a.dz = (const T*)b.dz; a.dz_stride = b.dz_stride; a.z = (const T*)b.z; a.z_stride = b.z_stride;
+    a.mean = b.mean; a.invstd = b.invstd; a.relu = b.relu;
+  }
+  const int nb = chan_blocks(b.M, b.C, VecT<T>::N);
+  hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
+  return nb;
+}
+
 template <typename T>
 static int launch_bn_train_fwd_t(const BnArgs& b, hipStream_t s) {
   constexpr int N = VecT<T>::N;
   const T *y = (const T*)b.y, *res = (const T*)b.res;
   T* z = (T*)b.z_out;
   const int M = b.M, C = b.C;
-  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn: unsupported channel count %d", C);
-  CTDET_CHECK(b.y_stride % N == 0 && b.z_stride % N == 0 && (!res || b.res_stride % N == 0) && ((((size_t)y | (size_t)z | (size_t)res)) & 15) == 0,
-              "bn: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
-  ChanRedArgs<T> a = {};
-  a.y = y; a.y_stride = b.y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)b.workspace;
-  // f32 tensors: the pivot goes to the backward's [2][C] sums slot, free in the forward
-  a.pivot = std::is_same<T, float>::value ? (float*)b.workspace + (size_t)1024 * 2 * C : nullptr;
-  const int nb = chan_blocks(M, C, N);
-  hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
+  if (const int e = bn_check<T>("bn", C, {{y, b.y_stride}, {z, b.z_stride}, {res, b.res_stride}})) return e;
+  const float* pivot;
+  const int nb = bn_chan_reduce<T>(b, 0, s, &pivot);
   hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 0, b.eps,
                      b.momentum, b.gamma, b.beta, b.save_mean, b.save_invstd, b.save_scale, b.save_shift, b.running_mean,
-                     b.running_var, (const float*)a.pivot);
-  const int CV = C / N;
-  if ((CV & (CV - 1)) == 0) {
-    int sh = 0;
-    while ((1 << sh) < CV) ++sh;
+                     b.running_var, pivot);
+  const int CV = C / N, sh = cv_shift_of(CV);
+  if (sh >= 0) {
     const long ppb = (256 >> sh) * AA_ROWS;
     hipLaunchKernelGGL(affine_act_rows_kernel<T>, dim3((unsigned)(((long)M + ppb - 1) / ppb)), dim3(256), 0, s, y, b.y_stride,
                        (const float*)b.save_scale, (const float*)b.save_shift, res, b.res_stride, z, b.z_stride, (long)M, sh, b.relu);
@@ -1386,23 +1450,15 @@ static int launch_bn_train_bwd_t(const BnArgs& b, hipStream_t s) {
   const T *dz = (const T*)b.dz, *z = (const T*)b.z, *y = (const T*)b.y;
   T *dy = (T*)b.dy, *dres = (T*)b.dres;
   const int M = b.M, C = b.C;
-  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_bwd: unsupported channel count %d", C);
-  CTDET_CHECK(b.dz_stride % N == 0 && b.dy_stride % N == 0 && (!z || b.z_stride % N == 0) && (!y || b.y_stride % N == 0) &&
-                  (!dres || b.dres_stride % N == 0) && ((((size_t)dz | (size_t)z | (size_t)y | (size_t)dy | (size_t)dres)) & 15) == 0,
-              "bn_bwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
-  ChanRedArgs<T> a = {};
-  a.y = y; a.y_stride = b.y_stride; a.dz = dz; a.dz_stride = b.dz_stride; a.z = z; a.z_stride = b.z_stride;
-  a.mean = b.mean; a.invstd = b.invstd; a.M = M; a.C = C; a.mode = 1; a.relu = b.relu; a.partial = (float*)b.workspace;
-  const int nb = chan_blocks(M, C, N);
-  hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
-  float* sums = (float*)b.workspace + (size_t)1024 * 2 * C;   // [2][C]: sum g, sum g*xhat
+  if (const int e = bn_check<T>("bn_bwd", C, {{dz, b.dz_stride}, {z, b.z_stride}, {y, b.y_stride}, {dy, b.dy_stride}, {dres, b.dres_stride}}))
+    return e;
+  const int nb = bn_chan_reduce<T>(b, 1, s);
+  float* sums = bn_sums_slot(b);   // [2][C]: sum g, sum g*xhat
   hipLaunchKernelGGL(chan_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 1,
                      b.grad_mult, 0.f, (const float*)nullptr, (const float*)nullptr, b.dbeta, b.dgamma, sums, sums + C,
                      (float*)nullptr, (float*)nullptr, (const float*)nullptr);
-  const int CV = C / N;
-  if ((CV & (CV - 1)) == 0 && CV <= 256) {
-    int sh = 0;
-    while ((1 << sh) < CV) ++sh;
+  const int CV = C / N, sh = cv_shift_of(CV);
+  if (sh >= 0) {
     const long ppb = (256 >> sh) * BN_ROWS;
     hipLaunchKernelGGL(bn_bwd_apply_rows_kernel<T>, dim3((unsigned)(((long)M + ppb - 1) / ppb)), dim3(256), 0, s, dz, b.dz_stride, z,
                        b.z_stride, y, b.y_stride, b.mean, b.invstd, b.scale, (const float*)sums, (const float*)(sums + C), dy,
@@ -1444,27 +1500,14 @@ __global__ void __launch_bounds__(256) bn_slot_finalize_kernel(const float* __re
                                                                double* __restrict__ slots, int rank, int world,
                                                                float grad_mult, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta) {
-  __shared__ double sh[2][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x;
-  double s0 = 0, s1 = 0;
-  for (int b = threadIdx.x; b < nblocks; b += 256) { s0 += partial[((long)b * 2 + 0) * C + c]; s1 += partial[((long)b * 2 + 1) * C + c]; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_down(s0, o, 64); s1 += __shfl_down(s1, o, 64); }
-  if (lane == 0) { sh[0][wave] = s0; sh[1][wave] = s1; }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  s0 = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
-  s1 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
+  double s0, s1;
+  if (!chan_partial_sums(partial, nblocks, C, c, s0, s1)) return;
   double v[3];
   int K;
   if (mode == 0) {
-    const double dm = s0 / M;
-    double var = s1 / M - dm * dm;
-    if (var < 0) var = 0;
     v[0] = (double)M;
-    v[1] = pivot ? (double)pivot[c] + dm : dm;
-    v[2] = var;
+    chan_mean_var(s0, s1, M, pivot, c, v[1], v[2]);
     K = 3;
   } else {
     v[0] = s0;
@@ -1503,8 +1546,8 @@ __device__ __forceinline__ void sb_split(long idx, int CV, int cv_shift, long& m
 }
 
 // forward after the collective, one launch: every workgroup combines the slots of all C channels into LDS (world x 3
-// loads per channel), workgroup 0 also writes the saved and running statistics, then z = act(y*scale + shift + res) for
-// SB_ROWS x 256 channel vectors (the fused kernels' expression).  Dynamic LDS: 2*C floats.
+// loads per channel), workgroup 0 also writes the saved and running statistics, then bn_fwd_elem for SB_ROWS x 256 channel
+// vectors.  Dynamic LDS: 2*C floats.
 constexpr int SB_ROWS = 8;
 template <typename T>
 __global__ void __launch_bounds__(256) bn_sync_fwd_apply_kernel(const T* __restrict__ y, int y_stride, const T* __restrict__ res,
@@ -1560,22 +1603,14 @@ __global__ void __launch_bounds__(256) bn_sync_fwd_apply_kernel(const T* __restr
     if (idx < total) {
       long m; int cv;
       sb_split(idx, CV, cv_shift, m, cv);
-      V o;
-#pragma unroll
-      for (int e = 0; e < N; ++e) {
-        float f = (float)v[u][e] * sb_coef[cv * N + e] + sb_coef[C + cv * N + e];   // same expression as the fused kernels
-        if (res) f += (float)r[u][e];
-        if (relu) f = fmaxf(f, 0.f);
-        o[e] = (T)f;
-      }
-      *(V*)(z + m * z_stride + cv * N) = o;
+      *(V*)(z + m * z_stride + cv * N) = bn_fwd_elem<T>(v[u], r[u], res != nullptr, sb_coef, sb_coef + C, cv * N, relu);
     }
   }
 }
 
 // backward after the collective: every workgroup sums the gathered (sum g, sum g*xhat) slots and the forward slots' row
-// counts in rank order into LDS coefficients (the global sums over the global count), then
-// dy = scale*(g - sum g/N - xhat * sum g*xhat/N) (bn_bwd_apply_rows_kernel's expression), dres = g.  Dynamic LDS: 5*C floats.
+// counts in rank order into LDS coefficients (the global sums over the global count), then bn_bwd_elem, dres = g.
+// Dynamic LDS: 5*C floats.
 template <typename T>
 __global__ void __launch_bounds__(256) bn_sync_bwd_apply_kernel(const T* __restrict__ dz, int dz_stride, const T* __restrict__ z,
                                                                 int z_stride, const T* __restrict__ y, int y_stride,
@@ -1626,46 +1661,28 @@ __global__ void __launch_bounds__(256) bn_sync_bwd_apply_kernel(const T* __restr
       if (idx < total) {
         long m; int cv;
         sb_split(idx, CV, cv_shift, m, cv);
-        V o, gr;
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-          const int c = cv * N + e;
-          const float gf = (relu && !((float)zz[u][e] > 0.f)) ? 0.f : (float)g[u][e];
-          gr[e] = (T)gf;
-          const float xh = ((float)yy[u][e] - sb_coef[c]) * sb_coef[C + c];
-          o[e] = (T)(sb_coef[2 * C + c] * (gf - sb_coef[3 * C + c] - xh * sb_coef[4 * C + c]));
-        }
-        *(V*)(dy + m * dy_stride + cv * N) = o;
-        if (dres) *(V*)(dres + m * dres_stride + cv * N) = gr;
+        const BnGrad<V> o = bn_bwd_elem<T>(g[u], zz[u], yy[u], true, sb_coef, sb_coef + C, sb_coef + 2 * C, sb_coef + 3 * C,
+                                           sb_coef + 4 * C, cv * N, relu);
+        *(V*)(dy + m * dy_stride + cv * N) = o.dy;
+        if (dres) *(V*)(dres + m * dres_stride + cv * N) = o.g;
       }
     }
   }
 }
 
-static int sb_cv_shift(int CV) {
-  if (CV & (CV - 1)) return -1;
-  int sh = 0;
-  while ((1 << sh) < CV) ++sh;
-  return sh;
-}
-
 template <typename T>
 static int launch_bn_local_stats_t(const BnArgs& b, hipStream_t s) {
-  constexpr int N = VecT<T>::N;
-  const int M = b.M, C = b.C;
-  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_local_stats: unsupported channel count %d", C);
-  CTDET_CHECK(b.y_stride % N == 0 && ((size_t)b.y & 15) == 0,
-              "bn_local_stats: y must be 16-byte aligned with a pixel stride that is a multiple of %d", N);
-  ChanRedArgs<T> a = {};
-  a.y = (const T*)b.y; a.y_stride = b.y_stride; a.M = M; a.C = C; a.mode = 0; a.partial = (float*)b.workspace;
-  a.pivot = std::is_same<T, float>::value ? (float*)b.workspace + (size_t)1024 * 2 * C : nullptr;
-  const int nb = chan_blocks(M, C, N);
-  hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 0,
-                     (const float*)a.pivot, b.slots, b.rank, b.world, 0.f, (float*)nullptr, (float*)nullptr);
+  if (const int e = bn_check<T>("bn_local_stats", b.C, {{b.y, b.y_stride}})) return e;
+  const float* pivot;
+  const int nb = bn_chan_reduce<T>(b, 0, s, &pivot);
+  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(b.C), dim3(256), 0, s, (const float*)b.workspace, nb, b.C, b.M, 0, pivot,
+                     b.slots, b.rank, b.world, 0.f, (float*)nullptr, (float*)nullptr);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
+
+// workgroups of the sync apply kernels: SB_ROWS x 256 channel vectors each
+static unsigned sb_grid(long M, int CV) { return (unsigned)((M * CV + 256L * SB_ROWS - 1) / (256L * SB_ROWS)); }
 
 template <typename T>
 static int launch_bn_sync_fwd_t(const BnArgs& b, hipStream_t s) {
@@ -1673,14 +1690,10 @@ static int launch_bn_sync_fwd_t(const BnArgs& b, hipStream_t s) {
   const T *y = (const T*)b.y, *res = (const T*)b.res;
   T* z = (T*)b.z_out;
   const int C = b.C;
-  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_sync_fwd: unsupported channel count %d", C);
-  CTDET_CHECK(b.y_stride % N == 0 && b.z_stride % N == 0 && (!res || b.res_stride % N == 0) && ((((size_t)y | (size_t)z | (size_t)res)) & 15) == 0,
-              "bn_sync_fwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
+  if (const int e = bn_check<T>("bn_sync_fwd", C, {{y, b.y_stride}, {z, b.z_stride}, {res, b.res_stride}})) return e;
   const int CV = C / N;
-  const long total = (long)b.M * CV;
-  const unsigned grid = (unsigned)((total + 256L * SB_ROWS - 1) / (256L * SB_ROWS));
-  hipLaunchKernelGGL(bn_sync_fwd_apply_kernel<T>, dim3(grid), dim3(256), 2 * C * sizeof(float), s, y, b.y_stride, res,
-                     b.res_stride, z, b.z_stride, (long)b.M, C, sb_cv_shift(CV), b.stats, b.world, b.gamma, b.beta, b.eps, b.momentum,
+  hipLaunchKernelGGL(bn_sync_fwd_apply_kernel<T>, dim3(sb_grid(b.M, CV)), dim3(256), 2 * C * sizeof(float), s, y, b.y_stride, res,
+                     b.res_stride, z, b.z_stride, (long)b.M, C, cv_shift_of(CV), b.stats, b.world, b.gamma, b.beta, b.eps, b.momentum,
                      b.running_mean, b.running_var, b.save_mean, b.save_invstd, b.save_scale, b.save_shift, b.relu);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -1688,19 +1701,9 @@ static int launch_bn_sync_fwd_t(const BnArgs& b, hipStream_t s) {
 
 template <typename T>
 static int launch_bn_local_grad_sums_t(const BnArgs& b, hipStream_t s) {
-  constexpr int N = VecT<T>::N;
-  const T *dz = (const T*)b.dz, *z = (const T*)b.z, *y = (const T*)b.y;
-  const int M = b.M, C = b.C;
-  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_local_grad_sums: unsupported channel count %d", C);
-  CTDET_CHECK(b.dz_stride % N == 0 && (!z || b.z_stride % N == 0) && (!y || b.y_stride % N == 0) &&
-                  ((((size_t)dz | (size_t)z | (size_t)y)) & 15) == 0,
-              "bn_local_grad_sums: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
-  ChanRedArgs<T> a = {};
-  a.y = y; a.y_stride = b.y_stride; a.dz = dz; a.dz_stride = b.dz_stride; a.z = z; a.z_stride = b.z_stride;
-  a.mean = b.mean; a.invstd = b.invstd; a.M = M; a.C = C; a.mode = 1; a.relu = b.relu; a.partial = (float*)b.workspace;
-  const int nb = chan_blocks(M, C, N);
-  hipLaunchKernelGGL(chan_reduce_kernel<T>, dim3(nb), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(C), dim3(256), 0, s, (const float*)b.workspace, nb, C, M, 1,
+  if (const int e = bn_check<T>("bn_local_grad_sums", b.C, {{b.dz, b.dz_stride}, {b.z, b.z_stride}, {b.y, b.y_stride}})) return e;
+  const int nb = bn_chan_reduce<T>(b, 1, s);
+  hipLaunchKernelGGL(bn_slot_finalize_kernel, dim3(b.C), dim3(256), 0, s, (const float*)b.workspace, nb, b.C, b.M, 1,
                      (const float*)nullptr, b.slots, b.rank, b.world, b.grad_mult, b.dgamma, b.dbeta);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -1712,16 +1715,12 @@ static int launch_bn_sync_bwd_t(const BnArgs& b, hipStream_t s) {
   const T *dz = (const T*)b.dz, *z = (const T*)b.z, *y = (const T*)b.y;
   T *dy = (T*)b.dy, *dres = (T*)b.dres;
   const int C = b.C;
-  CTDET_CHECK(C % N == 0 && C / N <= 256, "bn_sync_bwd: unsupported channel count %d", C);
-  CTDET_CHECK(b.dz_stride % N == 0 && b.dy_stride % N == 0 && (!z || b.z_stride % N == 0) && b.y_stride % N == 0 &&
-                  (!dres || b.dres_stride % N == 0) && ((((size_t)dz | (size_t)z | (size_t)y | (size_t)dy | (size_t)dres)) & 15) == 0,
-              "bn_sync_bwd: tensors must be 16-byte aligned with pixel strides that are multiples of %d", N);
+  if (const int e = bn_check<T>("bn_sync_bwd", C, {{dz, b.dz_stride}, {z, b.z_stride}, {y, b.y_stride}, {dy, b.dy_stride}, {dres, b.dres_stride}}))
+    return e;
   const int CV = C / N;
-  const long total = (long)b.M * CV;
-  const unsigned grid = (unsigned)((total + 256L * SB_ROWS - 1) / (256L * SB_ROWS));
-  hipLaunchKernelGGL(bn_sync_bwd_apply_kernel<T>, dim3(grid), dim3(256), 5 * C * sizeof(float), s, dz, b.dz_stride, z, b.z_stride,
-                     y, b.y_stride, b.mean, b.invstd, b.scale, b.stats, b.sums, b.world, dy, b.dy_stride, dres, b.dres_stride,
-                     (long)b.M, C, sb_cv_shift(CV), b.relu);
+  hipLaunchKernelGGL(bn_sync_bwd_apply_kernel<T>, dim3(sb_grid(b.M, CV)), dim3(256), 5 * C * sizeof(float), s, dz, b.dz_stride, z,
+                     b.z_stride, y, b.y_stride, b.mean, b.invstd, b.scale, b.stats, b.sums, b.world, dy, b.dy_stride, dres,
+                     b.dres_stride, (long)b.M, C, cv_shift_of(CV), b.relu);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
@@ -2298,32 +2297,38 @@ int launch_dcn_col2im_fused(const DcnBwdArgs& a, hipStream_t s) {
   return launch_col2im_window<float, true>(a, s, fz);
 }
 
-static int dcn_col2im_coord_f16(const DcnBwdArgs& a, hipStream_t s) {
-  const f16 *dcol = (const f16*)a.dcol, *x = (const f16*)a.x;
-  const int dom_f16 = a.dom_dtype == CTDET_F16;
+// T: element type of a.x / a.dcol.  window: may the LDS-window scatter (fixed-point accumulation) run where the shape allows?
+// f16 tensors and the f16x3 training mode (f32 tensors): yes; the f32 mode: no, the generic kernel's plain f32 atomics.
+// An f32 dom is what the generic kernel writes for f32 tensors, whatever a.dom_dtype says.
+template <typename T>
+static int dcn_col2im_coord_t(const DcnBwdArgs& a, bool window, hipStream_t s) {
+  constexpr bool HALF = sizeof(T) == 2;
+  const T *dcol = (const T*)a.dcol, *x = (const T*)a.x;
   CTDET_CHECK(a.dom_stride >= dcn_om_channels(a.mask_mode) && a.dom_stride <= 64, "dcn_col2im: dom_stride=%d", a.dom_stride);
   CTDET_CHECK(!a.dcol_chunked || a.Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", a.Cin);
-  CTDET_CHECK(a.Cin % 8 == 0, "dcn_col2im: Cin=%d must be a multiple of 8", a.Cin);
+  CTDET_CHECK(!HALF || a.Cin % 8 == 0, "dcn_col2im: Cin=%d must be a multiple of 8", a.Cin);
   const long nwork = (long)a.B * a.H * a.W * 9;
   if (nwork == 0) return 0;
-  if (a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 8 == 0 && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW)) {
-    return launch_col2im_window<f16>(a, s);
-  }
+  // the window kernel's 16-byte loads (the f32 path also asks for the alignment of the two tensors)
+  const bool vec_ok = HALF ? a.x_stride % 8 == 0 : a.x_stride % 4 == 0 && ((((size_t)x | (size_t)dcol)) & 15) == 0;
+  if (window && a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && vec_ok && !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW))
+    return launch_col2im_window<T>(a, s);
   long nb = (nwork + 3) / 4;
   if (nb > 256 * 32) nb = 256 * 32;
-  const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_col2im_coord_kernel<true> : dcn_col2im_coord_kernel<false>;
-  CTDET_KERNEL("dcn_col2im_coord_kernel<f16,%s>", a.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
+  const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_col2im_coord_kernel<T, true> : dcn_col2im_coord_kernel<T, false>;
+  CTDET_KERNEL("dcn_col2im_coord_kernel<%s,%s>", HALF ? "f16" : "f32", a.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
   hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, a.x_stride, a.om, a.om_stride, a.dx, a.dom, a.dom_stride,
-                     dom_f16, a.B, a.H, a.W, a.Cin, a.mask_mode, a.dcol_chunked);
+                     (int)(a.dom_dtype == CTDET_F16), a.B, a.H, a.W, a.Cin, a.mask_mode, a.dcol_chunked);
   CTDET_LAUNCH_CHECK();
   return 0;
 }
 
 // ================================================================================================================
 // f32-tensor training kernels.  BatchNorm, pooling and the depthwise up-convolution are the templates above instantiated
-// for float (16-byte vectors of 4 channels): they serve both modes that keep f32 tensors -- f32 (the reference's own
-// arithmetic: contractions as f32 FMA chains) and f16x3 (contractions as three f16 MFMA products, f32 accumulation).
-// What is specific to the f32 mode is below: the weight gradient as plain f32 FMAs and the DCNv2 scatter with f32 atomics.
+// for float (16-byte vectors of 4 channels), and so is the DCNv2 coordinate / col2im kernel with its plain f32 atomics: they
+// serve both modes that keep f32 tensors -- f32 (the reference's own arithmetic: contractions as f32 FMA chains) and f16x3
+// (contractions as three f16 MFMA products, f32 accumulation).
+// What is specific to the f32 mode is below: the weight gradient as plain f32 FMAs and the f32 column sampler.
 // ================================================================================================================
 // dW[n][k] += scale * sum_m dY[m][n] * im2col(x)[m][k], k = tap*Cin + c.  Block = 16 couts x 16 k, 16 pixels per step
 // staged in LDS, pixel range split over blockIdx.z, f32 atomics at the end.
@@ -2390,13 +2395,8 @@ __global__ void __launch_bounds__(256) dcn_cols_f32_kernel(const float* __restri
     if (pair0 >= npairs) break;                  // block-uniform
     ColsGeoS* gs = geo[pass & 1];
     if (threadIdx.x < PP && pair0 + threadIdx.x < npairs) {
-      const long pr = pair0 + threadIdx.x;
-      const int tap = (int)(pr % 9);
-      const long m = pr / 9;
-      const int wo = (int)(m % W);
-      const long t2 = m / W;
-      const int ho = (int)(t2 % H), b = (int)(t2 / H);
-      const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
+      const DcnWork k = dcn_work(pair0 + threadIdx.x, H, W);
+      const DcnGeom g = dcn_geom<NM>(om + k.m * om_stride, k.tap, k.b, k.ho, k.wo, H, W, x_stride, mask_is_prob);
       ColsGeoS o;
 #pragma unroll
       for (int q = 0; q < 4; ++q) { o.w[q] = g.w[q]; o.off[q] = (int)g.off[q]; }
@@ -2418,51 +2418,6 @@ __global__ void __launch_bounds__(256) dcn_cols_f32_kernel(const float* __restri
       const long m = pr / 9;
       *(f32x4*)(col + m * (9L * Cin) + (long)tap * Cin + cv * 4) = o;
     }
-  }
-}
-
-// the generic coordinate / col2im kernel above for f32 columns and inputs (same wave-per-(pixel, tap) structure)
-template <bool NM>
-__global__ void __launch_bounds__(256) dcn_col2im_coord_f32_kernel(const float* __restrict__ dcol, const float* __restrict__ x,
-                                                                   int x_stride, const float* __restrict__ om, int om_stride,
-                                                                   float* __restrict__ dx, float* __restrict__ dom, int dom_stride, int B,
-                                                                   int H, int W, int Cin, int mask_is_prob, int chunked) {
-  const int lane = threadIdx.x & 63;
-  const long wave_id = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long nwork = (long)B * H * W * 9;
-  for (long wk = wave_id; wk < nwork; wk += (long)gridDim.x * 4) {
-    const int tap = (int)(wk % 9);
-    const long m = wk / 9;
-    const int wo = (int)(m % W);
-    const long t2 = m / W;
-    const int ho = (int)(t2 % H), b = (int)(t2 / H);
-    const DcnGeom g = dcn_geom<NM>(om + m * om_stride, tap, b, ho, wo, H, W, x_stride, mask_is_prob);
-    float val_dot = 0.f, dh = 0.f, dwv = 0.f;
-    if (g.inside) {
-      // dcol row of a pixel: [tap][Cin], or chunked [Cin/32][tap][32]
-      const float* dcp = dcol + m * (9L * Cin) + (chunked ? tap * 32 : tap * Cin);
-      for (int c = lane; c < Cin; c += 64) {
-        const float d = dcp[chunked ? (c >> 5) * 288 + (c & 31) : c];
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = g.off[q] >= 0 ? x[g.off[q] + c] : 0.f;
-        if constexpr (!NM) val_dot += d * (g.w[0] * v[0] + g.w[1] * v[1] + g.w[2] * v[2] + g.w[3] * v[3]);
-        dh += d * (-g.hw * v[0] - g.lw * v[1] + g.hw * v[2] + g.lw * v[3]);
-        dwv += d * (-g.hh * v[0] + g.hh * v[1] - g.lh * v[2] + g.lh * v[3]);
-        const float dm = d * g.mask;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (g.off[q] >= 0) atomicAdd(dx + g.off[q] / x_stride * (long)Cin + c, g.w[q] * dm);
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      if constexpr (!NM) val_dot += __shfl_down(val_dot, o, 64);
-      dh += __shfl_down(dh, o, 64);
-      dwv += __shfl_down(dwv, o, 64);
-    }
-    if (lane == 0)
-      dom_store<NM>(dom, 0, m, dom_stride, tap, dh * g.mask, dwv * g.mask, mask_is_prob ? val_dot : val_dot * g.mask * (1.f - g.mask));
   }
 }
 
@@ -2505,35 +2460,13 @@ static int dcn_cols_f32(const DcnBwdArgs& a, hipStream_t s) {
   return 0;
 }
 
-// window = 1 (the f16x3 training mode): the LDS-window scatter with fixed-point accumulation where the shape allows;
-// window = 0 (the f32 mode): the generic kernel, plain f32 atomics
-static int dcn_col2im_coord_f32(const DcnBwdArgs& a, int window, hipStream_t s) {
-  const float *dcol = (const float*)a.dcol, *x = (const float*)a.x;
-  CTDET_CHECK(a.dom_stride >= dcn_om_channels(a.mask_mode) && a.dom_stride <= 64, "dcn_col2im: dom_stride=%d", a.dom_stride);
-  const long nwork = (long)a.B * a.H * a.W * 9;
-  if (nwork == 0) return 0;
-  if (window && a.H % 8 == 0 && a.W % 16 == 0 && a.Cin % 32 == 0 && a.x_stride % 4 == 0 && ((((size_t)x | (size_t)dcol)) & 15) == 0 &&
-      !(ctdet_tuning_flags() & CTDET_TUNE_NO_COL2IM_WINDOW)) {
-    return launch_col2im_window<float>(a, s);
-  }
-  CTDET_CHECK(!a.dcol_chunked || a.Cin % 32 == 0, "dcn_col2im: the chunked dcol layout needs Cin %% 32 == 0 (Cin=%d)", a.Cin);
-  long nb = (nwork + 3) / 4;
-  if (nb > 256 * 32) nb = 256 * 32;
-  const auto kernel = a.mask_mode == DCN_MASK_NONE ? dcn_col2im_coord_f32_kernel<true> : dcn_col2im_coord_f32_kernel<false>;
-  CTDET_KERNEL("dcn_col2im_coord_f32_kernel<%s>", a.mask_mode == DCN_MASK_NONE ? "no mask" : "mask");
-  hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), 0, s, dcol, x, a.x_stride, a.om, a.om_stride, a.dx, (float*)a.dom,
-                     a.dom_stride, a.B, a.H, a.W, a.Cin, a.mask_mode, a.dcol_chunked);
-  CTDET_LAUNCH_CHECK();
-  return 0;
-}
-
 int launch_dcn_cols(const DcnBwdArgs& a, hipStream_t s) {
   if (a.dtype == CTDET_F16) return dcn_cols_f16(a, s);
   if (a.dtype == CTDET_F32) return dcn_cols_f32(a, s);
   CTDET_CHECK(false, "dcn_cols: bad dtype %d", a.dtype);
 }
 int launch_dcn_col2im_coord(const DcnBwdArgs& a, hipStream_t s) {
-  if (a.dtype == CTDET_F16) return dcn_col2im_coord_f16(a, s);
-  if (a.dtype == CTDET_F32 || a.dtype == CTDET_F16X3) return dcn_col2im_coord_f32(a, a.dtype == CTDET_F16X3, s);
+  if (a.dtype == CTDET_F16) return dcn_col2im_coord_t<f16>(a, true, s);
+  if (a.dtype == CTDET_F32 || a.dtype == CTDET_F16X3) return dcn_col2im_coord_t<float>(a, a.dtype == CTDET_F16X3, s);
   CTDET_CHECK(false, "dcn_col2im_coord: bad dtype %d", a.dtype);
 }

@@ -61,7 +61,8 @@ Worst err / bound per kernel path, mode and dtype, measured on an MI355X on 2026
     path and quantity                           f16    f32
     affine_act z                                0.995  0.200
     affine_act_rows z                           0.998  0.209
-    bn_bwd_apply dy                             0.993  0.172
+    bn_bwd_apply dy                             0.993  0.186     (2026-10-20, at the commit that gives the three backward-apply
+                                                                  kernels one expression, parent 7976952; before: 0.993  0.172)
     bn_bwd_apply_rows dy                        0.998  0.226
     bn_sync_bwd_apply w1-3 dy                   0.998  0.235
     bn_sync_fwd_apply w1-3 z                    0.998  0.209

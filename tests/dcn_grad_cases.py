@@ -97,7 +97,7 @@ def _generic_rows():
     f16 = lambda Cin, mask, dom_c: _row("f16", "col2im", "generic", 2, 5, 7, Cin, mask,          # noqa: E731
                                         f"dcn_col2im_coord_kernel<f16,{_m(mask)}>", dom_c)
     f32 = lambda mode, B, H, W, Cin, mask, dom_c: _row(mode, "col2im", "generic", B, H, W, Cin, mask,      # noqa: E731
-                                                       f"dcn_col2im_coord_f32_kernel<{_m(mask)}>", dom_c, edges=BASE_EDGES)
+                                                       f"dcn_col2im_coord_kernel<f32,{_m(mask)}>", dom_c, edges=BASE_EDGES)
     return [
         f16(8, "logit", 27), f16(8, "none", 18), f16(8, "prob", 28),
         f16(72, "logit", 32), f16(72, "none", 32), f16(72, "none", 20),

@@ -304,9 +304,11 @@ def test_empty_slot_changes_nothing(ot, dev, case, dt, where):
 @pytest.mark.parametrize("dt", T.DTYPES, ids=T.dt_name)
 @pytest.mark.parametrize("case", T.BN_CASES, ids=T.bn_id)
 def test_world_one_equals_fused(ot, dev, case, dt):
-    """world 1, each pipeline on its own forward's statistics: bit-identical, except dy where test_one_slot_equals_fused_kernels
-    documents a difference (the fused generic apply kernel multiplies xhat * sum * (1/M), the others xhat * (sum/M); f16 tensors: the
-    two kernels' f32 arithmetic before the rounding of dy is not evaluated identically) -- bounded there as here"""
+    """world 1, each pipeline on its own forward's statistics: bit-identical, dy of f32 tensors included -- the three backward-apply
+    kernels share one expression (bn_bwd_elem: scale * (g - s0/M - xhat * (s1/M))), at power-of-two and other channel-vector counts
+    alike.  dy of f16 tensors is not: the compiler contracts that f32 arithmetic differently in the two kernels before the rounding
+    to f16 (measured on an MI355X: 13 of the 24 cases differ, by at most 1.6e-4 of max |dy|) -- bounded as in
+    test_one_slot_equals_fused_kernels"""
     inp, ops, par = _operands(case, dt, dev)
     y, dz, zin = ops["y"].view, ops["dz"].view, ops["zin"].view
     res = ops["res"].view if case.res else None
@@ -319,8 +321,8 @@ def test_world_one_equals_fused(ot, dev, case, dt):
     sums, dgs, dbs = ot.bn_local_grad_sums(dz, zin, y, ms, iss, 0, 1, relu=case.relu, grad_mult=case.grad_mult)
     dys, dress = ot.bn_sync_bwd(dz, zin, y, ms, iss, scs, stats, sums, relu=case.relu, want_dres=True)
     _same((dgf, dbf, dresf), (dgs, dbs, dress))
-    if T.is_pow2(case.CV) and dt == F32:
+    if dt == F32:
         _same((dyf,), (dys,))
     else:
         a, b = dys.double(), dyf.double()
-        assert (a - b).abs().max().item() <= (1e-6 if dt == F32 else 2e-3) * max(1e-30, b.abs().max().item())
+        assert (a - b).abs().max().item() <= 2e-3 * max(1e-30, b.abs().max().item())

@@ -31,13 +31,19 @@ def test_mirrored_constants_match_the_source():
     assert f"long nb = ((long)M + rows * {T.CHAN_ROWS} - 1) / (rows * {T.CHAN_ROWS});" in body
     assert f"if (nb > {T.CHAN_BLOCK_CAP}) nb = {T.CHAN_BLOCK_CAP};" in body
     assert f"(size_t)({T.CHAN_BLOCK_CAP} * 2 + 2) * C * sizeof(float)" in src
+    assert f"return (float*)b.workspace + (size_t){T.CHAN_BLOCK_CAP} * 2 * b.C;" in src      # the sums slot behind the partials
     red = src[src.index("void __launch_bounds__(256) chan_reduce_kernel"):src.index("chan_finalize_kernel(")]
     assert f"const int rows_per_pass = {T.BLOCK} / CV;" in red
     assert "for (; m + 3 * step < a.M; m += 4 * step)" in red and T.UNROLL[0] == 4
     assert "for (; m + step < a.M; m += 2 * step)" in red and T.UNROLL[1] == 2
+    # the channel-count check stands once, in the helper that every launcher calls before it launches anything
+    check = src[src.index("static int bn_check("):src.index("static float* bn_sums_slot(")]
+    assert f"CTDET_CHECK(C % N == 0 && C / N <= {T.CV_MAX}," in check and src.count("CTDET_CHECK(C % N == 0 && C / N <=") == 1
     for fn in ("bn_train_fwd", "bn_train_bwd", "bn_local_stats", "bn_sync_fwd", "bn_local_grad_sums", "bn_sync_bwd"):
         launcher = src[src.index(f"static int launch_{fn}_t("):]
-        assert f"CTDET_CHECK(C % N == 0 && C / N <= {T.CV_MAX}," in launcher[:launcher.index("CTDET_LAUNCH_CHECK();")], fn
+        launcher = launcher[:launcher.index("CTDET_LAUNCH_CHECK();")]
+        assert "if (const int e = bn_check<T>(" in launcher and launcher.index("bn_check<T>(") < launcher.index("hipLaunchKernelGGL") and \
+            ("bn_chan_reduce" not in launcher or launcher.index("bn_check<T>(") < launcher.index("bn_chan_reduce")), fn
     assert "struct VecT<f16> { typedef f16x8 type; static constexpr int N = 8; }" in src and T.VEC[F16] == 8
     assert "struct VecT<float> { typedef f32x4 type; static constexpr int N = 4; }" in src and T.VEC[F32] == 4
     assert src.count("__launch_bounds__(256) ") >= 9 and "dim3(256), 0, s, a);" in src

@@ -102,7 +102,7 @@ INSTANTIATIONS = (
      "dcn_window_rows_kernel<columns only,f16,mask>", "dcn_window_rows_kernel<columns only,f16,no mask>",
      "dcn_cols_f32_kernel<mask>", "dcn_cols_f32_kernel<no mask>",
      "dcn_col2im_coord_kernel<f16,mask>", "dcn_col2im_coord_kernel<f16,no mask>",
-     "dcn_col2im_coord_f32_kernel<mask>", "dcn_col2im_coord_f32_kernel<no mask>"]
+     "dcn_col2im_coord_kernel<f32,mask>", "dcn_col2im_coord_kernel<f32,no mask>"]
     + [f"dcn_col2im_window_kernel<{nt} taps,{t}{m}>" for nt in (3, 5, 9) for t in ("f16,", "f32,", "f32,fused dcol,")
        for m in ("mask", "no mask")])
 

@@ -140,11 +140,11 @@ def test_split_kernels_two_simulated_ranks(ot, name, dt):
 @pytest.mark.parametrize("C", [64, 96, 256])
 def test_one_slot_equals_fused_kernels(ot, dt, C):
     """world 1: the split kernels give the fused ctdet_bn_train_fwd / _bwd results bit for bit -- the same statistics
-    (the single slot is taken as it stands), the same apply expressions -- except dy in two places, bounded here instead:
-    the fused backward's generic apply kernel (channel-vector counts that are not powers of two) multiplies
-    xhat * sum * (1/M) where the split kernel (and the fused rows kernel) use xhat * (sum/M); and on f16 tensors the two
-    kernels' f32 arithmetic before the f16 rounding of dy is not evaluated identically by the compiler (measured: differences
-    of f16 rounding size, f32 tensors bit-identical)."""
+    (the single slot is taken as it stands), the same apply expressions -- except dy, bounded here instead: on f16 tensors
+    the two kernels' f32 arithmetic before the f16 rounding of dy is not evaluated identically by the compiler (measured:
+    differences of f16 rounding size, f32 tensors bit-identical).  The f32 bound at channel-vector counts that are not powers
+    of two dates from when the fused generic apply kernel multiplied xhat * sum * (1/M); all three apply kernels now share
+    bn_bwd_elem's xhat * (sum/M), and tests/test_bn_gpu.py::test_world_one_equals_fused asserts f32 dy bit for bit."""
     dev = torch.device("cuda:0")
     ys, rs, dzs, gamma, beta = _case_tensors((5000,), C, dt, dev, C, False, True)
     y, r0, dz = ys[0], rs[0], dzs[0]
