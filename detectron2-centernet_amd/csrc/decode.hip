@@ -534,6 +534,9 @@ __global__ void __launch_bounds__(64) dec_postprocess_kernel(const float* __rest
   const int b = blockIdx.x, lane = threadIdx.x;
   const float sx = img_params[b * 4 + 0], sy = img_params[b * 4 + 1];
   const float ow = img_params[b * 4 + 2], oh = img_params[b * 4 + 3];
+  // Boxes.clip's clamp hands a NaN coordinate on, and nonempty() then drops the box (NaN > 0 is false); fminf / fmaxf would
+  // return their other operand and turn the coordinate into 0
+  auto clip = [](float v, float hi) { return v != v ? v : fminf(fmaxf(v, 0.f), hi); };
   int base = 0;
   for (int k0 = 0; k0 < K; k0 += 64) {
     const int k = k0 + lane;
@@ -544,10 +547,10 @@ __global__ void __launch_bounds__(64) dec_postprocess_kernel(const float* __rest
       const long o = (long)b * K + k;
       sc = scores[o];
       cl = classes[o];
-      x1 = fminf(fmaxf(boxes[o * 4 + 0] * sx, 0.f), ow);
-      y1 = fminf(fmaxf(boxes[o * 4 + 1] * sy, 0.f), oh);
-      x2 = fminf(fmaxf(boxes[o * 4 + 2] * sx, 0.f), ow);
-      y2 = fminf(fmaxf(boxes[o * 4 + 3] * sy, 0.f), oh);
+      x1 = clip(boxes[o * 4 + 0] * sx, ow);
+      y1 = clip(boxes[o * 4 + 1] * sy, oh);
+      x2 = clip(boxes[o * 4 + 2] * sx, ow);
+      y2 = clip(boxes[o * 4 + 3] * sy, oh);
       keep = sc > thresh && (x2 - x1) > 0.f && (y2 - y1) > 0.f;
     }
     const unsigned long long m = __ballot(keep);

@@ -360,7 +360,9 @@ int32_t ctdet_decode_flip(const float* heat, int32_t heat_stride, const float* w
 /* CenterNet.inference_single_image (centernet.py:251-261) + detector_postprocess
  * (detectron2/modeling/postprocessing.py:11-72, structures/boxes.py:184-213,271-278) for a whole batch:
  * keep k < max_det with score > score_thresh, scale boxes by (scale_x, scale_y), clip to (out_w, out_h), drop
- * empty boxes, compact in order.  img_params f32 [B,4] = {scale_x, scale_y, out_w, out_h}; counts i32 [B]. */
+ * empty boxes, compact in order.  img_params f32 [B,4] = {scale_x, scale_y, out_w, out_h}; counts i32 [B].
+ * Non-finite values as in the reference: a NaN score or a box with a NaN coordinate is dropped, +-inf coordinates
+ * clip to the image.  Rows behind counts[b] are unspecified. */
 int32_t ctdet_postprocess(const float* boxes, const float* scores, const int32_t* classes, int32_t B, int32_t K,
                           int32_t max_det, float score_thresh, const float* img_params, float* out_boxes,
                           float* out_scores, int32_t* out_classes, int32_t* counts, void* stream);
