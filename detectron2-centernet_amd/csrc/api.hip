@@ -450,7 +450,8 @@ size_t ctdet_dwconv3x3_wgrad_workspace_bytes(int32_t B, int32_t H, int32_t W, in
 int32_t ctdet_dwconv3x3_wgrad(const void* x, int32_t x_stride, const void* dy, int32_t dy_stride, float* workspace, float* dw,
                               float scale, int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
                               int32_t dtype, void* stream) {
-  CTDET_CHECK(x && dy && dw, "dwconv3x3_wgrad: null pointer");
+  // an empty problem (the tensors of an empty batch have no storage) still writes dw: only then may x / dy be null
+  CTDET_CHECK(dw && ((x && dy) || B == 0 || H == 0 || W == 0), "dwconv3x3_wgrad: null pointer");
   CTDET_CHECK(accumulate == 0 || accumulate == 1, "dwconv3x3_wgrad: accumulate %d", accumulate);
   const int strides[2] = {x_stride, dy_stride};
   const int rc = dwconv3x3_check(dtype, B, H, W, C, stride, strides, 2);
@@ -774,6 +775,7 @@ int32_t ctdet_dcn_col2im_fused(const float* dy, int32_t dy_stride, int32_t K, co
 int32_t ctdet_sgd_momentum(float* param, const float* grad, float* momentum_buf, int64_t n, const float* lr_dev,
                            float momentum, float weight_decay, int32_t first_step, void* stream) {
   CTDET_CHECK(param && grad && momentum_buf && lr_dev, "sgd: null pointer");
+  CTDET_CHECK(n >= 0, "sgd: n=%lld", (long long)n);
   return launch_sgd(param, grad, momentum_buf, (long)n, lr_dev, momentum, weight_decay, first_step, (hipStream_t)stream);
 }
 
@@ -781,6 +783,9 @@ int32_t ctdet_sgd_momentum_runs(float* param, const float* grad, float* momentum
                                 const int32_t* run_lr_index, const float* run_weight_decay, const float* lr_table,
                                 int32_t nruns, float momentum, int32_t first_step, void* stream) {
   CTDET_CHECK(param && grad && momentum_buf && run_end && run_lr_index && run_weight_decay && lr_table, "sgd_runs: null pointer");
+  CTDET_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0,
+              "sgd_runs: param, grad and momentum_buf must be 16-byte aligned");
+  CTDET_CHECK(n >= 0 && nruns >= 0, "sgd_runs: n=%lld nruns=%d", (long long)n, nruns);
   return launch_sgd_runs(param, grad, momentum_buf, (long)n, (const long*)run_end, run_lr_index, run_weight_decay, lr_table,
                          nruns, momentum, first_step, (hipStream_t)stream);
 }
@@ -811,6 +816,9 @@ int32_t ctdet_sgd_momentum_runs_clip(float* param, const float* grad, float* mom
                                      float clip_value, const float* coefs, void* stream) {
   CTDET_CHECK(param && grad && momentum_buf && run_end && run_lr_index && run_weight_decay && lr_table,
               "sgd_runs_clip: null pointer");
+  CTDET_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0,
+              "sgd_runs_clip: param, grad and momentum_buf must be 16-byte aligned");
+  CTDET_CHECK(n >= 0 && nruns >= 0, "sgd_runs_clip: n=%lld nruns=%d", (long long)n, nruns);
   CTDET_CHECK(clip_type >= CTDET_CLIP_NONE && clip_type <= CTDET_CLIP_NORM, "sgd_runs_clip: clip type %d", clip_type);
   CTDET_CHECK(clip_type == CTDET_CLIP_NONE || clip_value > 0.f, "sgd_runs_clip: clip value %g", (double)clip_value);
   CTDET_CHECK(clip_type != CTDET_CLIP_NORM || coefs, "sgd_runs_clip: norm clipping needs coefs (one per run)");

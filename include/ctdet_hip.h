@@ -401,13 +401,16 @@ int32_t ctdet_reg_l1_loss(const float* pred, int32_t pred_stride, const uint8_t*
 
 /* torch.optim.SGD step with momentum/weight decay (detectron2/solver/build.py:93-137):
  * g' = g + wd*p; buf = mom*buf + g'; p -= lr*buf   (first step: buf = g'). lr is read from device memory
- * so the captured graph stays valid across the WarmupMultiStepLR schedule. */
+ * so the captured graph stays valid across the WarmupMultiStepLR schedule.  Element-wise accesses: no alignment is
+ * asked of the buffers; n >= 0 (a negative n is refused with -22). */
 int32_t ctdet_sgd_momentum(float* param, const float* grad, float* momentum_buf, int64_t n, const float* lr_dev,
                            float momentum, float weight_decay, int32_t first_step, void* stream);
 
 /* The same step over a flat buffer holding several parameter groups back to back: run r covers elements
  * [run_end[r-1], run_end[r]) (device i64 array, ascending, run_end[nruns-1] == n) with weight decay run_weight_decay[r] and
- * learning rate lr_table[run_lr_index[r]] (all device memory: the captured training graph stays valid across the schedule). */
+ * learning rate lr_table[run_lr_index[r]] (all device memory: the captured training graph stays valid across the schedule).
+ * param, grad and momentum_buf: f32[n], 16-byte aligned (they are read and written four elements at a time); n >= 0 and
+ * nruns >= 0.  A misaligned buffer or a negative count is refused with -22 before anything is launched. */
 int32_t ctdet_sgd_momentum_runs(float* param, const float* grad, float* momentum_buf, int64_t n, const int64_t* run_end,
                                 const int32_t* run_lr_index, const float* run_weight_decay, const float* lr_table,
                                 int32_t nruns, float momentum, int32_t first_step, void* stream);
@@ -434,7 +437,8 @@ int32_t ctdet_grad_clip_coefs(const float* partials, const int32_t* param_chunk_
  * [-clip_value, clip_value]; CTDET_CLIP_NORM scales the gradient of run r by coefs[r] (device f32[nruns]) -- the caller passes
  * one run per parameter, so that the search that finds a run's learning rate finds its coefficient; coefs is ignored
  * otherwise.  nesterov: p -= lr * (g' + momentum * buf) with the updated buf.  CTDET_CLIP_NONE without nesterov is
- * ctdet_sgd_momentum_runs itself. */
+ * ctdet_sgd_momentum_runs itself, and the alignment and count contract is the same: param, grad and momentum_buf 16-byte
+ * aligned, n >= 0, nruns >= 0, else -22. */
 int32_t ctdet_sgd_momentum_runs_clip(float* param, const float* grad, float* momentum_buf, int64_t n, const int64_t* run_end,
                                      const int32_t* run_lr_index, const float* run_weight_decay, const float* lr_table,
                                      int32_t nruns, float momentum, int32_t first_step, int32_t nesterov, int32_t clip_type,
@@ -555,7 +559,9 @@ int32_t ctdet_dwconvT_bwd(const void* x, int32_t x_stride, const void* dz, int32
  * ctdet_dwconv3x3_wgrad: dw[c][0][ky][kx] (OIHW [C,1,3,3], f32) = scale * sum over n, y, x of dy[n,y,x,c] * x[n, y-1+ky, x-1+kx, c]
  *   for a stride-1 layer (x and dy both [B,H,W,*]); accumulate = 1 adds into dw instead of overwriting it.  No atomics:
  *   workgroups write f32 partial sums to their own slots of `workspace` (ctdet_dwconv3x3_wgrad_workspace_bytes; every slot
- *   is written on every call, the caller never clears it), a second kernel sums the slots in a fixed order in f64. */
+ *   is written on every call, the caller never clears it), a second kernel sums the slots in a fixed order in f64.  An empty
+ *   problem (B, H or W zero; x and dy may then be NULL, as the tensors of an empty batch are) still writes zeros to dw, or
+ *   with accumulate = 1 leaves it as it is. */
 int32_t ctdet_dwconv3x3_fwd(const void* x, int32_t x_stride, const float* w, void* y, int32_t y_stride, int32_t B, int32_t H,
                             int32_t W, int32_t C, int32_t stride, int32_t rot180, int32_t dtype, void* stream);
 size_t ctdet_dwconv3x3_wgrad_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype);
