@@ -484,7 +484,11 @@ int launch_pack_weights_batch(const void* table_dev, int n, int total_blocks, hi
 // Weight packing for the f16x3 kernels (f32 tensors, products as hi*hi + lo*hi + hi*lo on the f16 matrix pipe), one
 // workgroup per packed row.  A row is first scaled by the power of two that brings its largest magnitude into [1024, 2048)
 // (exact; the lo halves of the row's significant weights then stay f16 normals whatever the layer's weight scale is), the
-// inverse goes to scale_out[row] -- the conv epilogue's per-cout multiplier.  Layouts (ctdet_pack3_desc.layout):
+// inverse goes to scale_out[row] -- the conv epilogue's per-cout multiplier.  The rule, with (m, ex) = frexp(max |row|):
+// sh = min(11 - ex, 126), the row is multiplied by 2^sh and scale_out[row] = 2^-sh; a row of zeros (or of padding) has
+// scale 1.  The cap keeps both factors normal f32 numbers: a row whose maximum is below 2^-116 is multiplied by 2^126 only
+// (its maximum lands below 1024, its weights stay finite and scale_out stays the exact inverse) where 2^(11 - ex) would be
+// +inf and its inverse a subnormal or 0.  Layouts (ctdet_pack3_desc.layout):
 //   0  split tap-major image [rows_pad][Kpad f32 units], k = tap*chans_pad + c, every group of 4 k = 16 bytes {hi[4], lo[4]} f16
 //      (what ctdet_split_weights makes of an f32 image): 1x1 / strided / 7x7 convs, DCNv2, the d(columns) operand
 //   3  tap-pair image of conv3x3_halo_pair2_kernel (chans_pad % 32 == 0): per chunk PAIR (A, B) of 16-channel chunks nine
@@ -517,8 +521,9 @@ __device__ __forceinline__ void pack3_row(const Pack3Desc& d, int row, float* re
   amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   int ex = 0;
   (void)frexpf(amax, &ex);                       // amax = f * 2^ex, f in [0.5, 1): floor(log2(amax)) = ex - 1
-  const float pw = amax > 0.f ? ldexpf(1.f, 11 - ex) : 1.f;
-  if (tid == 0 && row < d.scale_n) d.scale_out[row] = amax > 0.f ? ldexpf(1.f, ex - 11) : 1.f;
+  const int sh = min(11 - ex, 126);              // capped: 2^sh and 2^-sh are both normal f32 numbers, exact inverses
+  const float pw = amax > 0.f ? ldexpf(1.f, sh) : 1.f;
+  if (tid == 0 && row < d.scale_n) d.scale_out[row] = amax > 0.f ? ldexpf(1.f, -sh) : 1.f;
   auto val = [&](int tap, int c) -> float {      // scaled weight of (row, tap, channel); taps >= R*S and padding are zero
     if (row >= rows || tap >= d.R * d.S) return 0.f;
     return pw * pack_value(d.w, d.O, d.I, d.R, d.S, d.chans_pad, 0, d.transposed, row, tap * d.chans_pad + c);

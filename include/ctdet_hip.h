@@ -305,8 +305,12 @@ int32_t ctdet_pack_weights_batch(const ctdet_pack_desc* table_dev, int32_t n, in
 /* Weight packing for CTDET_DT_F16X3 contractions in one launch per weight (round 4; replaces a chain of ~30 torch kernels per
  * conv: permute, pad, row maximum, scale, split, pair interleave): the f32 OIHW parameter -> the split operand the kernels
  * read.  Every packed row is scaled by the power of two that brings its largest magnitude into [1024, 2048) -- the lo halves
- * then stay f16 normals -- and the inverse is written to scale_out[row] for row < scale_n (1.0 for rows of padding): pass
- * it as the `scale` of ctdet_conv2d_fwd / ctdet_dcnv2_fwd (multiply it into a folded BatchNorm scale if there is one).
+ * then stay f16 normals -- and the inverse is written to scale_out[row] for row < scale_n (1.0 for rows of zeros and of
+ * padding): pass it as the `scale` of ctdet_conv2d_fwd / ctdet_dcnv2_fwd (multiply it into a folded BatchNorm scale if there
+ * is one).  With (m, ex) = frexp(max |row|) the factor is 2^sh, sh = min(11 - ex, 126), and scale_out[row] = 2^-sh: both
+ * are normal f32 numbers and exact inverses for every finite row, subnormal maxima included; a row whose maximum is below
+ * 2^-116 is scaled by 2^126 only, so its largest magnitude lands below 1024 and its weights stay finite.  A NaN or infinite
+ * weight leaves a non-finite hi half at its place in the image.
  * layout 0: tap-major split image, rows of Kpad f32 units (Kpad % 4 == 0, >= R*S*chans_pad), each group of 4 k = {hi[4],
  *           lo[4]} f16 -- ctdet_conv_desc.korder 0: 1x1 / strided / 7x7 convs, DCNv2, the d(columns) operand;
  * layout 3: tap-pair image of the 3x3 halo kernel, korder 3 (chans_pad % 32 == 0, Kpad = chans_pad/32*288, rows_pad % 32 == 0);
