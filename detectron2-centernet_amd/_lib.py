@@ -119,6 +119,7 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp]),
     "ctdet_resize_bilinear_u8": (_i32, [_vp, _vp, _vp]),
     "ctdet_resize_bilinear_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "ctdet_warp_affine_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "ctdet_byte_sum_u8_batch": (_i32, [_vp, _i32, _vp, _i32, _vp]),
     "ctdet_colour_jitter_u8_batch": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "ctdet_soft_nms_merge": (_i32, [_vp, _i32, _i32, _i32, C.c_float, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -214,6 +215,13 @@ class ResizeDesc(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int64) for n in (
         "src_row", "src_pix", "src_chan", "dst_row", "dst_pix", "dst_chan")] + [(n, C.c_int32) for n in (
         "H", "W", "new_h", "new_w", "hb", "hc", "vb", "vc", "kh", "kv", "blk0", "pad_")]
+
+
+class WarpDesc(C.Structure):
+    """mirrors ctdet_warp_desc (ops.WARP_DESC_DTYPE is the same layout as a numpy record)"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int64) for n in (
+        "src_row", "src_pix", "src_chan", "dst_row", "dst_pix", "dst_chan")] + [(n, C.c_int32) for n in (
+        "H", "W", "out_h", "out_w", "ax", "bx", "x0", "y0", "blk0", "pad_")]
 
 
 class JitterDesc(C.Structure):

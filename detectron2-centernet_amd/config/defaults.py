@@ -85,6 +85,17 @@ _C.INPUT.DEVICE_RESIZE = False
 # raw image, the size and the jitter draws it made (the host pipeline's draws, in its order); CenterNet.stage_raw_train produces
 # the bytes the host pipeline gives from them (ops.resize_u8, ops.colour_jitter_u8).  The test-time mapper ignores it.
 _C.INPUT.DEVICE_AUGMENT = False
+# not in the reference either: CenterNet's own training input (data/warp.py).  ENABLED: the TRAINING mapper
+# replaces ResizeShortestEdge by one affine warp to OUTPUT_SIZE = (out_h, out_w), each a multiple of
+# MODEL.CENTERNET.SIZE_DIVISIBILITY: the source window has side max(h, w) * one of SCALES, its centre is drawn at least
+# BORDER pixels from the edges (halved until it fits) and the image is mirrored with FLIP_PROB.  With INPUT.DEVICE_AUGMENT
+# the warp runs on the device (ops.warp_affine_u8).  The test-time mapper ignores these keys.
+_C.INPUT.AFFINE = CN()
+_C.INPUT.AFFINE.ENABLED = False
+_C.INPUT.AFFINE.OUTPUT_SIZE = (512, 512)
+_C.INPUT.AFFINE.SCALES = (0.6, 0.7, 0.8, 0.9, 1.0, 1.1, 1.2, 1.3)
+_C.INPUT.AFFINE.BORDER = 128
+_C.INPUT.AFFINE.FLIP_PROB = 0.5
 
 _C.DATASETS = CN()
 _C.DATASETS.TRAIN = ()

@@ -877,6 +877,18 @@ int32_t ctdet_resize_bilinear_u8_batch(const ctdet_resize_desc* descs_dev, int32
   return launch_resize_u8_batch(descs_dev, n, total_blocks, tables_dev, (hipStream_t)stream);
 }
 
+int32_t ctdet_warp_affine_u8_batch(const ctdet_warp_desc* descs_dev, int32_t n, int32_t total_blocks, const int32_t* tables_dev,
+                                   void* stream) {
+  static_assert(sizeof(ctdet_warp_desc) == 104, "ctdet_warp_desc layout");
+  CTDET_CHECK(descs_dev && tables_dev, "warp_affine_u8_batch: null pointer");
+  CTDET_CHECK(n >= 0 && total_blocks >= 0, "warp_affine_u8_batch: n=%d total_blocks=%d", n, total_blocks);
+  if (n == 0) return 0;      // nothing to warp: nothing is launched
+  // the descriptors live on the device and are not read here; what the counts alone can show is checked
+  CTDET_CHECK(total_blocks >= n, "warp_affine_u8_batch: total_blocks=%d is not the sum over %d descriptors (at least one block each)",
+              total_blocks, n);
+  return launch_warp_affine_u8_batch(descs_dev, n, total_blocks, tables_dev, (hipStream_t)stream);
+}
+
 int32_t ctdet_byte_sum_u8_batch(const ctdet_jitter_desc* descs_dev, int32_t n, uint64_t* sums_dev, int32_t n_sums, void* stream) {
   CTDET_CHECK(n >= 0 && n < (1 << 24) && n_sums >= 0, "byte_sum_u8_batch: n=%d n_sums=%d", n, n_sums);
   if (n_sums == 0) return 0;

@@ -299,8 +299,13 @@ int resize_tiles(int new_h, int new_w);                      // blocks of one im
 int launch_resize_u8(const ctdet_resize_desc& d, const int* tab, hipStream_t s);
 int launch_resize_u8_batch(const ctdet_resize_desc* descs_dev, int n, int total_blocks, const int* tab, hipStream_t s);
 
+// warp.hip
+struct ctdet_warp_desc;                                      // include/ctdet_hip.h
+int warp_tiles(int out_h, int out_w);                        // blocks of one image
+int launch_warp_affine_u8_batch(const ctdet_warp_desc* descs_dev, int n, int total_blocks, const int* tab, hipStream_t s);
+
 // jitter.hip
-struct ctdet_jitter_desc;                                    // include/ctdet_hip.h
+struct ctdet_jitter_desc;                                   // include/ctdet_hip.h
 int jitter_tiles(int h, int w);                              // blocks of one image
 int launch_byte_sum_u8_batch(const ctdet_jitter_desc* descs_dev, int n, uint64_t* sums, int n_sums, hipStream_t s);
 int launch_colour_jitter_u8_batch(const ctdet_jitter_desc* descs_dev, int n, int total_blocks, const uint64_t* sums, int n_sums,

@@ -13,7 +13,12 @@ exactly the random draws of the host pipeline, in its order, from numpy's global
 apply-or-not uniform and, when it applies, its weight (or lighting's normal(size=3)); none of them depends on a pixel.  The
 record carries "image_raw" (uint8 HWC torch tensor: shared memory across the loader's worker boundary), "resize_hw", "jitter"
 (float64 [4, 4] tensor, data/jitter.py) and "instances" (the boxes through the resize alone: a colour transform moves no
-coordinate).  CenterNet.stage_raw_train turns a batch of them into the bytes the host pipeline gives from the same draws."""
+coordinate).  CenterNet.stage_raw_train turns a batch of them into the bytes the host pipeline gives from the same draws.
+
+INPUT.AFFINE.ENABLED (training only, not in the reference): CenterNet's random scale-and-crop sampler (T.RandomAffineCrop,
+data/warp.py) takes ResizeShortestEdge's place as the first augmentation; every image leaves it at INPUT.AFFINE.OUTPUT_SIZE.
+Its draws come first, the jitters' follow as before.  A raw record then also carries "warp" (float64 [2, 4] tensor,
+data.warp.pack_warp: the inverse matrix and the flip flag) and "resize_hw" is the output size."""
 import copy
 
 import numpy as np
@@ -22,6 +27,7 @@ import torch
 from . import detection_utils as du
 from . import transforms as T
 from .jitter import JITTER_ORDER, empty_spec
+from .warp import pack_warp
 
 # colour jitters of the training pipeline (:36-43 of the reference mapper): (augmentation, constructor arguments)
 _COLOUR_JITTER = ((T.RandomContrast, (0.8, 1.2)), (T.RandomBrightness, (0.8, 1.2)), (T.RandomSaturation, (0.8, 1.2)),
@@ -39,6 +45,9 @@ def bulb_traffic_light_augmentation(cfg, is_train):
     else:
         sizes, longest, style = inp.MIN_SIZE_TEST, inp.MAX_SIZE_TEST, "choice"
     pipeline = [T.ResizeShortestEdge(sizes, longest, style)]
+    affine = getattr(inp, "AFFINE", None)
+    if is_train and affine is not None and affine.ENABLED:      # CenterNet's sampler takes the resize's place
+        pipeline = [T.RandomAffineCrop(cfg)]
     if is_train:
         pipeline += [T.RandomApply(aug(*args), prob=_JITTER_PROB) for aug, args in _COLOUR_JITTER]
     return pipeline
@@ -82,8 +91,12 @@ class TrafficLightDatasetMapper:
         """INPUT.DEVICE_AUGMENT: the draws of the host pipeline, in its order, and no pixel work beyond the decode"""
         pixels = du.read_image(record["file_name"], format=self.img_format)
         du.check_image_size(record, pixels)
-        resize = self.augmentation[0].get_transform(pixels)      # the size draw; reads the image's shape only
-        hw = (resize.new_h, resize.new_w) if isinstance(resize, T.ResizeTransform) else tuple(pixels.shape[:2])
+        resize = self.augmentation[0].get_transform(pixels)      # the size draw (INPUT.AFFINE: the sampler's draws); reads the image's shape only
+        if isinstance(resize, T.AffineTransform):
+            hw = (resize.out_h, resize.out_w)
+            record["warp"] = torch.from_numpy(pack_warp(resize.Minv, resize.flip))
+        else:
+            hw = (resize.new_h, resize.new_w) if isinstance(resize, T.ResizeTransform) else tuple(pixels.shape[:2])
         spec = empty_spec()
         for t, apply in enumerate(self.augmentation[1:]):
             params = apply.draw()

@@ -12,6 +12,8 @@ import sys
 import numpy as np
 from PIL import Image
 
+from . import warp as W
+
 
 class Transform:
     def apply_image(self, img):
@@ -68,6 +70,25 @@ class HFlipTransform(Transform):
         coords = np.asarray(coords, dtype=np.float64)
         coords[:, 0] = self.width - coords[:, 0]
         return coords
+
+
+class AffineTransform(Transform):
+    """one affine warp of a uint8 image to out_h x out_w (data/warp.py holds every definition): Minv [2, 3] maps a destination
+    pixel index to a source pixel index, of the mirrored image when `flip`"""
+
+    def __init__(self, Minv, flip, out_h, out_w, src_w=None):
+        self.Minv, self.flip = np.asarray(Minv, dtype=np.float64).reshape(2, 3), bool(flip)
+        self.out_h, self.out_w = int(out_h), int(out_w)
+        self.w = src_w      # the source width the mirror of a coordinate needs; None: learnt from the image apply_image gets
+
+    def apply_image(self, img):
+        assert self.w is None or self.w == img.shape[1], (self.w, img.shape)
+        self.w = img.shape[1]
+        return W.warp_affine_u8_reference(img, self.Minv, self.out_h, self.out_w, self.flip)
+
+    def apply_coords(self, coords):
+        assert self.w is not None or not self.flip, "a flipped AffineTransform maps coordinates once it knows the source width"
+        return W.forward_coords(coords, self.Minv, self.flip, self.w)
 
 
 class BlendTransform(Transform):
@@ -197,6 +218,38 @@ class RandomFlip(Augmentation):
         if np.random.uniform(0, 1) < self.prob:
             return HFlipTransform(image.shape[1])
         return NoOpTransform()
+
+
+class RandomAffineCrop(Augmentation):
+    """CenterNet's training sampler (INPUT.AFFINE): a random centre inside a border, a scale from a list, a flip, one warp to a
+    fixed size.  In two halves like the colour jitters: draw(h, w) makes the draws (none depends on a pixel),
+    transform_of(params, image) builds the AffineTransform."""
+
+    def __init__(self, cfg):
+        a = cfg.INPUT.AFFINE
+        self.out_h, self.out_w = (int(v) for v in a.OUTPUT_SIZE)
+        div = int(cfg.MODEL.CENTERNET.SIZE_DIVISIBILITY)
+        if self.out_h < 1 or self.out_w < 1 or (div > 0 and (self.out_h % div or self.out_w % div)):
+            raise ValueError(f"INPUT.AFFINE.OUTPUT_SIZE {tuple(a.OUTPUT_SIZE)}: (out_h, out_w), each a positive multiple of "
+                             f"MODEL.CENTERNET.SIZE_DIVISIBILITY ({div})")
+        self.scales = tuple(float(v) for v in a.SCALES)
+        if not self.scales or min(self.scales) <= 0:
+            raise ValueError(f"INPUT.AFFINE.SCALES {tuple(a.SCALES)}: at least one positive scale")
+        self.border, self.flip_prob = int(a.BORDER), float(a.FLIP_PROB)
+        if self.border < 0 or not 0.0 <= self.flip_prob <= 1.0:
+            raise ValueError(f"INPUT.AFFINE: BORDER {a.BORDER} must not be negative, FLIP_PROB {a.FLIP_PROB} lies in [0, 1]")
+
+    def draw(self, h, w):
+        """(s, cx, cy, flip) for an h x w source, data.warp.draw_params"""
+        return W.draw_params(h, w, self.scales, self.border, self.flip_prob)
+
+    def transform_of(self, params, image):
+        s, cx, cy, flip = params
+        w = image.shape[1]
+        return AffineTransform(W.inverse_matrix(s, cx, cy, flip, w, self.out_h, self.out_w), flip, self.out_h, self.out_w, src_w=w)
+
+    def get_transform(self, image):
+        return self.transform_of(self.draw(*image.shape[:2]), image)
 
 
 class _ColourJitter(Augmentation):

@@ -567,7 +567,9 @@ class CenterNet(nn.Module):
         """records of a training mapper built with INPUT.DEVICE_AUGMENT ("image_raw", "resize_hw", "jitter") -> the list of
         device uint8 [3, h, w] images the host pipeline would have produced from the same draws, byte for byte: one pinned copy
         and ONE resize launch for the batch (ops.resize_u8), then at most one byte-sum launch (the images whose contrast was
-        drawn) and one jitter launch (ops.colour_jitter_u8), whatever the sizes and whichever transforms each image drew."""
+        drawn) and one jitter launch (ops.colour_jitter_u8), whatever the sizes and whichever transforms each image drew.
+        Records that also carry "warp" (INPUT.AFFINE) go through one affine warp launch (ops.warp_affine_u8) in the resize's
+        place; a batch is warped or resized as a whole."""
         if self.device.type != "cuda":
             raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
         missing = [i for i, x in enumerate(batched_inputs) if "image_raw" not in x or "resize_hw" not in x]
@@ -579,7 +581,17 @@ class CenterNet(nn.Module):
             assert raw.ndim == 3 and raw.shape[2] == 3, f"image_raw is uint8 [H, W, 3], got {tuple(raw.shape)}"
             raws.append(raw.permute(2, 0, 1) if isinstance(raw, torch.Tensor) else raw.transpose(2, 0, 1))
         sizes = [(int(x["resize_hw"][0]), int(x["resize_hw"][1])) for x in batched_inputs]
-        images = ops.resize_u8(raws, sizes, device=self.device)
+        warped = [i for i, x in enumerate(batched_inputs) if "warp" in x]
+        if warped and len(warped) != len(batched_inputs):
+            plain = next(i for i, x in enumerate(batched_inputs) if "warp" not in x)
+            raise KeyError(f"record {plain} of a raw batch lacks 'warp' and record {warped[0]} has it: a batch is warped "
+                           f"(INPUT.AFFINE) or resized as a whole")
+        if warped:      # INPUT.AFFINE: one size for the batch, one warp launch in the resize's place
+            if len(set(sizes)) != 1:
+                raise KeyError(f"warp records of one batch share 'resize_hw' (INPUT.AFFINE.OUTPUT_SIZE), got {sorted(set(sizes))}")
+            images = ops.warp_affine_u8(raws, [x["warp"] for x in batched_inputs], sizes[0], device=self.device)
+        else:
+            images = ops.resize_u8(raws, sizes, device=self.device)
         return ops.colour_jitter_u8(images, [x.get("jitter") for x in batched_inputs])
 
     def _raw_ragged(self, batched_inputs, resized, flip):

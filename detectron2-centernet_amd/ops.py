@@ -891,7 +891,15 @@ def resize_u8_prepare(images, sizes, outs=None, device=None):
         d["blk0"] = blocks
         blocks += -(-nw // RESIZE_TW) * -(-nh // RESIZE_RB)
     assert blocks < 2 ** 31 and words < 2 ** 31
-    # the call's upload: [descriptors][tables][host images], each part 16-byte aligned
+    dev, tab_at = _u8_upload(desc, tables, words, views, device)
+    return ResizeLaunch(dev, desc, tab_at, blocks, outs)
+
+
+def _u8_upload(desc, tables, words, views, device, first=None):
+    """the one upload of a resize / warp call: [descriptors][int32 tables][host images], each part 16-byte aligned, through
+    the pinned arena.  Fills desc["src"] (device images: their pointer; host images: where they land), plus first[i] bytes
+    where given (a source read from another element than [0, 0, 0]).  Returns the device buffer and the byte offset of the
+    tables in it."""
     tab_at = round_up(desc.nbytes, 16)
     total = round_up(tab_at + 4 * max(words, 1), 16)
     host_at = []
@@ -906,14 +914,97 @@ def resize_u8_prepare(images, sizes, outs=None, device=None):
         if host is not None:
             staged[host_at[i]:host_at[i] + host[0].size] = host[0]
             ptr = dev.data_ptr() + host_at[i] + org
-        desc["src"][i] = ptr
+        desc["src"][i] = ptr + (first[i] if first is not None else 0)
     if tables:
         staged[tab_at:tab_at + 4 * words] = np.concatenate(tables).view(np.uint8)
     staged[:desc.nbytes] = desc.view(np.uint8)
     with torch.cuda.device(device):
         dev.copy_(arena[:total], non_blocking=True)
         _RESIZE_ARENA.uploaded()
-    return ResizeLaunch(dev, desc, tab_at, blocks, outs)
+    return dev, tab_at
+
+
+# ---------------------------------------------------------------------------------- uint8 affine warp (csrc/warp.hip)
+WARP_TW, WARP_RB = 64, 8      # output columns / rows of one block (csrc/warp.hip)
+# ctdet_warp_desc as a numpy record
+WARP_DESC_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8")]
+                           + [(n, "<i8") for n in ("src_row", "src_pix", "src_chan", "dst_row", "dst_pix", "dst_chan")]
+                           + [(n, "<i4") for n in ("H", "W", "out_h", "out_w", "ax", "bx", "x0", "y0", "blk0", "pad_")])
+assert WARP_DESC_DTYPE.itemsize == C.sizeof(_lib.WarpDesc)
+
+
+class WarpLaunch:
+    """one prepared warp of a list of images (warp_affine_u8_prepare): the uploaded descriptors, tables and host images, and
+    the destinations.  launch() may be repeated: it reads the same sources and writes the same destinations again."""
+
+    def __init__(self, dev, desc, tab_at, blocks, outs):
+        self.dev, self.desc, self.tab_at, self.blocks, self.outs = dev, desc, tab_at, blocks, outs
+
+    def launch(self):
+        with torch.cuda.device(self.dev.device):
+            rc = _lib.lib().ctdet_warp_affine_u8_batch(C.c_void_p(self.dev.data_ptr()), len(self.desc), self.blocks,
+                                                       C.c_void_p(self.dev.data_ptr() + self.tab_at), _stream())
+        _lib.check(rc, "ctdet_warp_affine_u8_batch")
+        return self.outs
+
+
+def warp_affine_u8(images, warps, out_hw, outs=None, device=None):
+    """The 8-bit bilinear affine warp of data.warp.warp_affine_u8_reference (what data.transforms.AffineTransform.apply_image
+    computes on the host) of a list of 3-channel images on the device, byte for byte, in ONE launch whatever their sizes.
+
+    images: logical [3, H, W] uint8 views with any strides, as ops.resize_u8 takes them; host images travel inside this
+      call's single upload.  Sources above data.warp.MAX_SOURCE_SIDE per side are refused.
+    warps: per image a float64 [2, 4] array / tensor (data.warp.pack_warp: the inverse matrix, destination to source pixel
+      index, and the flip flag) or an (M [2, 3], flip) pair.  A flipped image is read mirrored: no copy is made.
+    out_hw: (out_h, out_w) of every destination.  outs: device uint8 views [3, out_h, out_w] with any strides; None: fresh
+      CHW tensors.  Returns outs.
+    One host-to-device copy per call carries the descriptors, the four int32 tables of every image (data.warp.warp_tables;
+      a table entry outside int32 is refused) and the host images."""
+    if len(images) == 0:
+        return []
+    return warp_affine_u8_prepare(images, warps, out_hw, outs, device).launch()
+
+
+def warp_affine_u8_prepare(images, warps, out_hw, outs=None, device=None):
+    """everything of warp_affine_u8 but the launch: a WarpLaunch"""
+    from .data import warp as W
+    n = len(images)
+    assert n >= 1 and n == len(warps) and (outs is None or len(outs) == n)
+    if device is None:
+        device = outs[0].device if outs is not None else next((im.device for im in images if isinstance(im, torch.Tensor) and im.is_cuda), None)
+    if (device is None and not torch.cuda.is_available()) or (device is not None and torch.device(device).type != "cuda"):
+        raise NotImplementedError("warp_affine_u8 has no CPU implementation: the host form is data.warp.warp_affine_u8_reference")
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    out_h, out_w = int(out_hw[0]), int(out_hw[1])
+    assert out_h >= 1 and out_w >= 1, out_hw
+    views = [_u8_view(im) for im in images]
+    if outs is None:
+        outs = [torch.empty(3, out_h, out_w, dtype=torch.uint8, device=device) for _ in range(n)]
+    desc = np.zeros(n, dtype=WARP_DESC_DTYPE)
+    tables, first, words, blocks = [], [], 0, 0
+    for i, ((ptr, host, org, H, Wd, st), warp, out) in enumerate(zip(views, warps, outs)):
+        if not (H <= W.MAX_SOURCE_SIDE and Wd <= W.MAX_SOURCE_SIDE):
+            raise ValueError(f"image {i}: warp_affine_u8 takes sources of at most {W.MAX_SOURCE_SIDE} pixels per side, got {H}x{Wd}")
+        assert H >= 1 and Wd >= 1, (H, Wd)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (3, out_h, out_w), (
+            f"image {i}: the destination must be a device uint8 view [3, {out_h}, {out_w}], got {tuple(out.shape)} {out.dtype} on {out.device}")
+        M, flip = W.unpack_warp(warp.cpu() if isinstance(warp, torch.Tensor) else warp)
+        d = desc[i]
+        d["dst"] = out.data_ptr()
+        d["dst_row"], d["dst_pix"], d["dst_chan"] = out.stride(1), out.stride(2), out.stride(0)
+        # a mirrored source is read from its last column backwards
+        d["src_row"], d["src_pix"], d["src_chan"] = st[0], (-st[1] if flip else st[1]), st[2]
+        first.append((Wd - 1) * st[1] if flip else 0)
+        d["H"], d["W"], d["out_h"], d["out_w"] = H, Wd, out_h, out_w
+        d["ax"], d["bx"], d["x0"], d["y0"] = words, words + out_w, words + 2 * out_w, words + 2 * out_w + out_h
+        tables.extend(W.warp_tables(M, out_h, out_w))      # ax, bx, x0, y0: refuses an entry outside int32
+        words += 2 * (out_w + out_h)
+        d["blk0"] = blocks
+        blocks += -(-out_w // WARP_TW) * -(-out_h // WARP_RB)
+    assert blocks < 2 ** 31 and words < 2 ** 31
+    dev, tab_at = _u8_upload(desc, tables, words, views, device, first)
+    return WarpLaunch(dev, desc, tab_at, blocks, outs)
 
 
 # ---------------------------------------------------------------------------------- uint8 colour jitter (csrc/jitter.hip)

@@ -682,6 +682,31 @@ int32_t ctdet_resize_bilinear_u8(const ctdet_resize_desc* desc, const int32_t* t
 int32_t ctdet_resize_bilinear_u8_batch(const ctdet_resize_desc* descs_dev, int32_t n, int32_t total_blocks,
                                        const int32_t* tables_dev, void* stream);
 
+/* ---- uint8 bilinear affine warp, data/warp.py's arithmetic byte for byte ------------------------------------------------
+ * The training mapper's AffineTransform (INPUT.AFFINE) on 3-channel uint8 images.  Destination pixel (x, y)
+ * reads the source at the 10-bit fixed-point coordinate (x0[y] + ax[x], y0[y] + bx[x]), the sums formed in 64 bits; per
+ * coordinate v: V = v >> 5, first tap V >> 5 (arithmetic), phase f = V & 31.  The four taps weigh 32*(32-fx)(32-fy),
+ * 32*fx(32-fy), 32*(32-fx)fy, 32*fx*fy; a tap outside [0, H) x [0, W) contributes 0; out = (sum + 16384) >> 15.  ax, bx
+ * (out_w entries) and x0, y0 (out_h entries) are int32 tables in a DEVICE buffer the caller fills (data.warp.warp_tables).
+ * Addresses as in ctdet_resize_desc, strides of either sign: a mirrored source is src = its last column, src_pix negated.
+ * Every tap address is clamped into the source, whatever the tables hold.  Only the out_h x out_w x 3 bytes of the
+ * destination window are written.  Source and destination must not overlap.
+ *
+ * ctdet_warp_affine_u8_batch: n images of any sizes in ONE launch, `descs_dev` in DEVICE memory, sorted by blk0 = the number
+ *   of blocks of the descriptors before it, ceil(out_w / 64) * ceil(out_h / 8) each; total_blocks = their sum (every
+ *   descriptor has at least one block, so total_blocks < n is refused; blocks no descriptor covers do nothing).  n = 0
+ *   launches nothing.  Graph-capturable, no LDS. */
+typedef struct ctdet_warp_desc {
+  const void* src; void* dst;
+  int64_t src_row, src_pix, src_chan;   /* byte strides of the source */
+  int64_t dst_row, dst_pix, dst_chan;   /* byte strides of the destination */
+  int32_t H, W, out_h, out_w;
+  int32_t ax, bx, x0, y0;               /* offsets (int32 elements) of the four tables in tables_dev */
+  int32_t blk0, pad_;
+} ctdet_warp_desc;
+int32_t ctdet_warp_affine_u8_batch(const ctdet_warp_desc* descs_dev, int32_t n, int32_t total_blocks,
+                                   const int32_t* tables_dev, void* stream);
+
 /* ---- uint8 colour jitter, the host mapper's arithmetic byte for byte ---------------------------------------------------
  * The training mapper's RandomContrast, RandomBrightness, RandomSaturation and RandomLighting (in that order, each a blend on
  * the uint8 result of the one before), in place on 3-channel uint8 windows.  Per byte of a transform that is on

@@ -19,6 +19,12 @@ plus jitter for the batch.  It is printed as holding or not.
 
     python tools/bench_train_input.py [--out profiles/NAME.txt] [--modes f16x3,f16] [--no-step]
 
+`--affine` runs the INPUT.AFFINE leg alone: the device time of the warp launch (ops.warp_affine_u8) for a
+batch of 16 from 480x640 and from 1080x1920 sources next to the resize launch on the same inputs, and DefaultTrainer images/s
+on raw records with INPUT.AFFINE off and on, with the share of steps that replayed a captured graph.  No threshold is set.
+
+    python tools/bench_train_input.py --affine [--out profiles/NAME.txt] [--modes f16x3] [--steps 40] [--warmup 10]
+
 Needs a GPU: there is no CPU fallback, a time taken without one would mean nothing."""
 import argparse
 import json
@@ -124,22 +130,26 @@ def device_times(torch, ops, dev, raw, host, reps):
     torch.cuda.synchronize()
     for im, h in zip(images, host):
         assert torch.equal(im.cpu(), h["image"]), "the device pipeline differs from the host pipeline"
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    out = []
-    for fn in (plan.launch, jit.launch_sum, jit.launch_jitter):      # repeated in place: the same work on other bytes
-        for _ in range(5):
-            fn()
-        best = None
-        for _ in range(3):
-            e0.record()
-            for _ in range(reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ms = e0.elapsed_time(e1) / reps
-            best = ms if best is None else min(best, ms)
-        out.append(best)
+    # repeated in place: the same work on other bytes
+    out = [launch_ms(torch, fn, reps) for fn in (plan.launch, jit.launch_sum, jit.launch_jitter)]
     return out, jit.n, jit.sums.numel()
+
+
+def launch_ms(torch, fn, reps):
+    """device ms of one call of `fn`: HIP events around `reps` back-to-back calls after 5 warm-up calls, best of three"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(5):
+        fn()
+    best = None
+    for _ in range(3):
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        ms = e0.elapsed_time(e1) / reps
+        best = ms if best is None else min(best, ms)
+    return best
 
 
 def staging_times(torch, dev, raw, host, reps=20):
@@ -181,8 +191,128 @@ def step_times(torch, dev, mode, raw, host, steps, warmup):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ --affine
+AFFINE_SOURCES = ((480, 640), (1080, 1920))
+AFFINE_LEGS = (("AFFINE off, MIN_SIZE_TRAIN (512,)", False, (MIN_SIZE,)), ("AFFINE off, MIN_SIZE_TRAIN (448, 512, 576)", False, (448, 512, 576)),
+               ("AFFINE on, OUTPUT_SIZE (512, 512)", True, (MIN_SIZE,)))
+
+
+def affine_cfg(affine, sizes=(MIN_SIZE,)):
+    cfg = make_cfg(True)
+    cfg.INPUT.MIN_SIZE_TRAIN = sizes
+    cfg.INPUT.AFFINE.ENABLED = affine
+    return cfg
+
+
+def affine_device_times(torch, ops, dev, reps):
+    """per source size: device ms of the warp launch and of the resize launch for BATCH device-resident raw images, the
+    warps drawn by the sampler itself (seeded); the warp's bytes are checked against the host reference first"""
+    from detectron2_centernet_amd.data import transforms as T
+    from detectron2_centernet_amd.data.warp import warp_affine_u8_reference
+    crop = T.RandomAffineCrop(affine_cfg(True))
+    resize = T.ResizeShortestEdge((MIN_SIZE,), 1333, "choice")
+    out = {}
+    for h, w in AFFINE_SOURCES:
+        rng = np.random.RandomState(h)
+        imgs = [rng.randint(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(BATCH)]
+        np.random.seed(7)
+        tfms = [crop.get_transform(im) for im in imgs]
+        srcs = [torch.from_numpy(im).to(dev).permute(2, 0, 1) for im in imgs]
+        plan = ops.warp_affine_u8_prepare(srcs, [(t.Minv, t.flip) for t in tfms], (crop.out_h, crop.out_w))
+        got = plan.launch()
+        for k in (0, BATCH - 1):
+            assert np.array_equal(got[k].permute(1, 2, 0).cpu().numpy(), tfms[k].apply_image(imgs[k])), "the device warp differs from the host's"
+        new = resize.output_size(h, w, MIN_SIZE, 1333)
+        rplan = ops.resize_u8_prepare(srcs, [new] * BATCH)
+        out[(h, w)] = (launch_ms(torch, plan.launch, reps), launch_ms(torch, rplan.launch, reps), new, sum(t.flip for t in tfms))
+    return out
+
+
+def affine_trainer_leg(torch, dev, dicts, affine, sizes, mode, steps, warmup):
+    """DefaultTrainer.train() on raw records (INPUT.DEVICE_AUGMENT) mapped once by the real mapper and fed from memory:
+    images/s (host clock, synchronised) and the share of the timed steps that replayed a captured graph"""
+    import itertools
+
+    import bench
+    from detectron2_centernet_amd.data import TrafficLightDatasetMapper
+    from detectron2_centernet_amd.engine import DefaultTrainer, hooks
+    mapper = TrafficLightDatasetMapper(affine_cfg(affine, sizes), is_train=True)
+    np.random.seed(3)
+    batches = [[mapper(d) for d in dicts[i:i + BATCH]] for i in range(0, N_IMAGES, BATCH)]
+    model, cfg = bench.build_model(mode, dev, seed=1, calibrate=False)
+    clock, replays = {}, [0]
+    real_replay = torch.cuda.CUDAGraph.replay
+
+    def counted(self):
+        replays[0] += 1
+        return real_replay(self)
+
+    class Trainer(DefaultTrainer):
+        @classmethod
+        def build_model(cls, cfg):
+            return model
+
+        @classmethod
+        def build_train_loader(cls, cfg):
+            return itertools.cycle(batches)
+
+        @classmethod
+        def test(cls, cfg, model, evaluators=None):
+            return {}
+
+    def tick(trainer):
+        if trainer.iter in (warmup - 1, trainer.max_iter - 2):
+            torch.cuda.synchronize()
+            clock[trainer.iter] = (time.perf_counter(), replays[0])
+
+    cfg.SOLVER.IMS_PER_BATCH = BATCH
+    cfg.SOLVER.MAX_ITER = warmup + steps + 1
+    cfg.SOLVER.CHECKPOINT_PERIOD = 0
+    cfg.TEST.EVAL_PERIOD = 0
+    cfg.OUTPUT_DIR = tempfile.mkdtemp(prefix="ctdet_affine_")
+    trainer = Trainer(cfg)
+    trainer.register_hooks([hooks.CallbackHook(after_step=tick)])
+    torch.cuda.CUDAGraph.replay = counted
+    try:
+        trainer.train()
+    finally:
+        torch.cuda.CUDAGraph.replay = real_replay
+    (t0, r0), (t1, r1) = clock[warmup - 1], clock[trainer.max_iter - 2]
+    return steps * BATCH / (t1 - t0), (r1 - r0) / steps, sorted({tuple(r["resize_hw"]) for b in batches for r in b})
+
+
+def affine_main(args, say, rec):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_train_input needs a ROCm GPU: nothing here is measurable without one")
+    from detectron2_centernet_amd import ops
+    from detectron2_centernet_amd.data import DatasetCatalog
+    dev = torch.device("cuda:0")
+    say(f"# tools/bench_train_input.py --affine on {torch.cuda.get_device_name(0)}; batch {BATCH}, numpy {np.__version__}")
+    say("device time of ONE launch for the batch, device-resident HWC sources (HIP events):")
+    for (h, w), (t_warp, t_resize, new, flips) in affine_device_times(torch, ops, dev, args.reps).items():
+        rec.update({f"warp_{h}x{w}_us": t_warp * 1e3, f"resize_{h}x{w}_us": t_resize * 1e3})
+        say(f"  {h}x{w}: warp to 512x512 ({flips} of {BATCH} flipped) {t_warp * 1e3:.1f} us; resize to {new[0]}x{new[1]} {t_resize * 1e3:.1f} us")
+    if not args.no_step:
+        with tempfile.TemporaryDirectory(prefix="ctdet_train_input_") as root:
+            dicts = write_dataset(root)
+            if DATASET not in DatasetCatalog:
+                DatasetCatalog.register(DATASET, lambda: dicts)
+            say(f"DefaultTrainer.train(), DLA-34, batch {BATCH}, raw records ({SRC_HW[0]}x{SRC_HW[1]} JPEGs) fed from memory, {args.steps} steps "
+                f"after {args.warmup} (host clock, synchronised):")
+            for mode in [m for m in args.modes.split(",") if m]:
+                for name, affine, sizes in AFFINE_LEGS:
+                    rate, share, hws = affine_trainer_leg(torch, dev, dicts, affine, sizes, mode, args.steps, args.warmup)
+                    key = f"{mode}_{'affine' if affine else 'resize_' + '_'.join(map(str, sizes))}"
+                    rec.update({f"trainer_{key}_img_s": rate, f"trainer_{key}_graph_share": share})
+                    say(f"  {mode:6s} {name:44s} {rate:7.1f} img/s, {share * 100:5.1f} % of the steps replayed a captured graph; "
+                        f"sizes after mapping {hws}")
+    say(json.dumps({"bench_train_input_affine": rec}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--affine", action="store_true", help="the INPUT.AFFINE leg alone (DESIGN.md 7.12)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--batches", type=int, default=100)
@@ -197,6 +327,13 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
+    if args.affine:
+        affine_main(args, say, rec)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     import PIL
     from detectron2_centernet_amd.data import DatasetCatalog, TrafficLightDatasetMapper
     with tempfile.TemporaryDirectory(prefix="ctdet_train_input_") as root:
