@@ -89,13 +89,18 @@ _C.INPUT.DEVICE_AUGMENT = False
 # replaces ResizeShortestEdge by one affine warp to OUTPUT_SIZE = (out_h, out_w), each a multiple of
 # MODEL.CENTERNET.SIZE_DIVISIBILITY: the source window has side max(h, w) * one of SCALES, its centre is drawn at least
 # BORDER pixels from the edges (halved until it fits) and the image is mirrored with FLIP_PROB.  With INPUT.DEVICE_AUGMENT
-# the warp runs on the device (ops.warp_affine_u8).  The test-time mapper ignores these keys.
+# the warp runs on the device (ops.warp_affine_u8).  The test-time mapper ignores these keys, TEST_MODE apart.
 _C.INPUT.AFFINE = CN()
 _C.INPUT.AFFINE.ENABLED = False
 _C.INPUT.AFFINE.OUTPUT_SIZE = (512, 512)
 _C.INPUT.AFFINE.SCALES = (0.6, 0.7, 0.8, 0.9, 1.0, 1.1, 1.2, 1.3)
 _C.INPUT.AFFINE.BORDER = 128
 _C.INPUT.AFFINE.FLIP_PROB = 0.5
+# CenterNet's TEST input, independent of ENABLED, which stays training-only: "" = off (ResizeShortestEdge);
+# "fix_res" = the test-time mapper letterboxes every image to OUTPUT_SIZE by one affine warp; "keep_res" = it pads every image
+# to the next multiple of MODEL.CENTERNET.SIZE_DIVISIBILITY (a power of two) above its size.  The boxes come back through the
+# inverse map (ops.postprocess_affine).  The training mapper ignores the key.
+_C.INPUT.AFFINE.TEST_MODE = ""
 
 _C.DATASETS = CN()
 _C.DATASETS.TRAIN = ()

@@ -509,6 +509,16 @@ int32_t ctdet_postprocess(const float* boxes, const float* scores, const int32_t
                             out_classes, counts, (hipStream_t)stream);
 }
 
+int32_t ctdet_postprocess_affine(const float* boxes, const float* scores, const int32_t* classes, int32_t B, int32_t K,
+                                 int32_t max_det, float score_thresh, const float* img_params6, float* out_boxes,
+                                 float* out_scores, int32_t* out_classes, int32_t* counts, void* stream) {
+  CTDET_CHECK(boxes && scores && classes && img_params6 && out_boxes && out_scores && out_classes && counts,
+              "postprocess_affine: null pointer");
+  CTDET_CHECK(B >= 0 && K >= 1, "postprocess_affine: bad shape B=%d K=%d", B, K);
+  return launch_postprocess_affine(boxes, scores, classes, B, K, max_det, score_thresh, img_params6, out_boxes, out_scores,
+                                   out_classes, counts, (hipStream_t)stream);
+}
+
 int32_t ctdet_decode_status(const void* workspace, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, void* stream) {
   long words = 0;
   int below = 0;

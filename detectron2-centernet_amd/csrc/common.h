@@ -334,6 +334,11 @@ int launch_postprocess(const float* boxes, const float* scores, const int* class
                        float thresh, const float* img_params, float* out_boxes, float* out_scores, int* out_classes,
                        int* counts, hipStream_t s);
 
+// unwarp.hip
+int launch_postprocess_affine(const float* boxes, const float* scores, const int* classes, int B, int K, int max_det,
+                              float thresh, const float* img_params6, float* out_boxes, float* out_scores, int* out_classes,
+                              int* counts, hipStream_t s);
+
 // train_ops.hip
 int launch_gaussian_radius(const int* hw, int n, double* out_r, int* out_i, hipStream_t s);
 int launch_gaussian_targets(const float* boxes, const int64_t* classes, const int* counts, int B, int Nmax, int H,

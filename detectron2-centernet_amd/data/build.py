@@ -101,7 +101,8 @@ def build_detection_test_loader(cfg, dataset_name, mapper=None, rank=0, world_si
     """loader over `dataset_name` for inference (data/build.py:358-403): every record once and in order (InferenceSampler),
     nothing filtered, lists of TEST.BATCH_SIZE mapped samples (the last one shorter).  The default mapper is
     TrafficLightDatasetMapper(cfg, False): with INPUT.DEVICE_RESIZE its records carry the raw image and the model resizes
-    the batch on the device."""
+    the batch on the device; with INPUT.AFFINE.TEST_MODE they are CenterNet's warped test input (fix_res: one size for the
+    whole set, so every full batch replays one captured engine)."""
     dicts = list(DatasetCatalog.get(dataset_name))
     assert len(dicts), f"dataset '{dataset_name}' is empty"
     mapper = mapper if mapper is not None else TrafficLightDatasetMapper(cfg, False)

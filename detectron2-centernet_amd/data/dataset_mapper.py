@@ -18,7 +18,12 @@ coordinate).  CenterNet.stage_raw_train turns a batch of them into the bytes the
 INPUT.AFFINE.ENABLED (training only, not in the reference): CenterNet's random scale-and-crop sampler (T.RandomAffineCrop,
 data/warp.py) takes ResizeShortestEdge's place as the first augmentation; every image leaves it at INPUT.AFFINE.OUTPUT_SIZE.
 Its draws come first, the jitters' follow as before.  A raw record then also carries "warp" (float64 [2, 4] tensor,
-data.warp.pack_warp: the inverse matrix and the flip flag) and "resize_hw" is the output size."""
+data.warp.pack_warp: the inverse matrix and the flip flag) and "resize_hw" is the output size.
+
+INPUT.AFFINE.TEST_MODE (test time only, not in the reference): "fix_res" / "keep_res" put CenterNet's test warp
+(data.warp.test_params) in ResizeShortestEdge's place.  The record carries "warp" (never flipped) and the original "height" /
+"width"; "image" holds the bytes of data.warp.warp_affine_u8_reference, or, with INPUT.DEVICE_RESIZE, "image_raw" / "resize_hw"
+leave the warp to the model (ops.warp_affine_u8).  The model maps the boxes back through the inverse map."""
 import copy
 
 import numpy as np
@@ -27,6 +32,7 @@ import torch
 from . import detection_utils as du
 from . import transforms as T
 from .jitter import JITTER_ORDER, empty_spec
+from . import warp as W
 from .warp import pack_warp
 
 # colour jitters of the training pipeline (:36-43 of the reference mapper): (augmentation, constructor arguments)
@@ -68,6 +74,12 @@ class TrafficLightDatasetMapper:
                                       "resize on the host (build the training mapper with INPUT.DEVICE_RESIZE False; "
                                       "INPUT.DEVICE_AUGMENT moves the training resize and the jitters to the device)")
         self.device_augment = bool(getattr(cfg.INPUT, "DEVICE_AUGMENT", False)) and is_train      # test time: ignored
+        # CenterNet's test input (INPUT.AFFINE.TEST_MODE): read at test time alone, checked there by name
+        affine = getattr(cfg.INPUT, "AFFINE", None)
+        self.test_mode = "" if (is_train or affine is None) else getattr(affine, "TEST_MODE", "")
+        if self.test_mode != "":
+            self.test_out_hw, self.test_div = tuple(affine.OUTPUT_SIZE), int(cfg.MODEL.CENTERNET.SIZE_DIVISIBILITY)
+            W.check_test_mode(self.test_mode, self.test_out_hw, self.test_div)
         self.img_format = cfg.INPUT.FORMAT
         self.augmentation = bulb_traffic_light_augmentation(cfg, is_train)
         if self.device_augment:
@@ -110,10 +122,31 @@ class TrafficLightDatasetMapper:
             record["instances"] = self._targets(annotations, T.TransformList([resize]), hw)
         return record
 
+    def _affine_test_record(self, record):
+        """INPUT.AFFINE.TEST_MODE: the image through CenterNet's test warp (data.warp.test_params), on the host ("image") or
+        left to the model ("image_raw" / "resize_hw", INPUT.DEVICE_RESIZE); either way the record carries "warp" and the
+        original "height" / "width", from which the model maps the boxes back"""
+        pixels = du.read_image(record["file_name"], format=self.img_format)
+        du.check_image_size(record, pixels)
+        h, w = pixels.shape[:2]
+        M, out_h, out_w = W.test_params(h, w, self.test_mode, self.test_out_hw, self.test_div)
+        record["warp"] = torch.from_numpy(pack_warp(M, False))
+        record["height"], record["width"] = h, w
+        if self.device_resize:
+            record["image_raw"] = np.ascontiguousarray(pixels)
+            record["resize_hw"] = (out_h, out_w)
+        else:
+            warped = W.warp_affine_u8_reference(np.ascontiguousarray(pixels), M, out_h, out_w)
+            record["image"] = torch.as_tensor(np.ascontiguousarray(warped.transpose(2, 0, 1)))
+        record.pop("annotations", None)
+        return record
+
     def __call__(self, dataset_dict):
         record = copy.deepcopy(dataset_dict)       # the caller's dict (shared by every epoch) is never modified
         if self.device_augment:
             return self._raw_train_record(record)
+        if self.test_mode:
+            return self._affine_test_record(record)
         if self.device_resize:
             pixels = du.read_image(record["file_name"], format=self.img_format)
             du.check_image_size(record, pixels)

@@ -8,6 +8,10 @@ size); the warp arithmetic is restated from OpenCV's 8-bit INTER_LINEAR warpAffi
 phases, 15-bit weights).  cv2 is not a dependency and parity with either is unpinned, the standing the fvcore transforms
 have in data/transforms.py.
 
+The test side (INPUT.AFFINE.TEST_MODE) is here too, on the same standing: CenterNet's fix_res / keep_res test
+input as a map (`test_params`), the way of its boxes back into the original image (`unwarp_params`) and the numpy oracle
+csrc/unwarp.hip is held to bit for bit (`unwarp_boxes_reference`).
+
 Coordinates are pixel indices: destination pixel (x, y) reads the source at M @ (x, y, 1), M the 2x3 inverse matrix.  With
 `flip` the source is read mirrored -- column j of the image M speaks of is column W - 1 - j of the stored one."""
 import numpy as np
@@ -100,6 +104,90 @@ def forward_coords(coords, M, flip, w):
     if flip:
         coords[:, 0] = w - 1 - coords[:, 0]
     return (coords - M[:, 2]) @ np.linalg.inv(M[:, :2]).T
+
+
+# ------------------------------------------------------------------------- the test input (INPUT.AFFINE.TEST_MODE, 7.13)
+TEST_MODES = ("", "fix_res", "keep_res")
+
+
+def check_test_mode(mode, out_hw, divisibility):
+    """refuses, by name, a TEST_MODE that is none of TEST_MODES, a fix_res OUTPUT_SIZE that is no positive multiple of the
+    size divisibility and a keep_res divisibility that is no power of two; returns the mode"""
+    if mode not in TEST_MODES:
+        raise ValueError(f"INPUT.AFFINE.TEST_MODE {mode!r}: one of {', '.join(repr(m) for m in TEST_MODES)}")
+    D = int(divisibility)
+    if mode == "fix_res":
+        oh, ow = (int(v) for v in out_hw)
+        if oh < 1 or ow < 1 or (D > 0 and (oh % D or ow % D)):
+            raise ValueError(f"INPUT.AFFINE.OUTPUT_SIZE {tuple(out_hw)}: (out_h, out_w), each a positive multiple of "
+                             f"MODEL.CENTERNET.SIZE_DIVISIBILITY ({D})")
+    if mode == "keep_res" and (D < 1 or D & (D - 1)):
+        raise ValueError(f"INPUT.AFFINE.TEST_MODE 'keep_res' pads to (side | (D - 1)) + 1: MODEL.CENTERNET.SIZE_DIVISIBILITY "
+                         f"must be a power of two, got {D}")
+    return mode
+
+
+def test_params(h, w, mode, out_hw=None, divisibility=32):
+    """(M, out_h, out_w) of CenterNet's test input for an h x w source: the inverse matrix (inverse_matrix, never flipped) and
+    the size of the network input.
+      "fix_res": letterbox to out_hw -- the window of side max(h, w) around the image's centre (w / 2, h / 2) lands on the
+        output's width;
+      "keep_res": out = (side | (D - 1)) + 1 per side, CenterNet's rule, which pads even a side that is a multiple of D; the
+        window's side is out_w (scale 1) and the centre (w // 2, h // 2), so the map is an integer shift and the warp a copy
+        of the source into a zero frame."""
+    h, w = int(h), int(w)
+    assert h >= 1 and w >= 1, (h, w)
+    check_test_mode(mode, out_hw, divisibility)
+    if mode == "fix_res":
+        out_h, out_w = (int(v) for v in out_hw)
+        s, cx, cy = float(max(h, w)), w / 2, h / 2
+    elif mode == "keep_res":
+        D = int(divisibility)
+        out_h, out_w = (h | (D - 1)) + 1, (w | (D - 1)) + 1
+        s, cx, cy = float(out_w), w // 2, h // 2
+    else:
+        raise ValueError("test_params: INPUT.AFFINE.TEST_MODE is off ('')")
+    return inverse_matrix(s, cx, cy, False, w, out_h, out_w), out_h, out_w
+
+
+test_params.__test__ = False      # a definition, not a test (its name is the one DESIGN.md 7.13 gives it)
+
+
+def unwarp_params(M, orig_hw):
+    """float32 [6] = (sx, sy, tx, ty, orig_w, orig_h): the map of a box coordinate of the network input back into the
+    orig_h x orig_w source, x' = x * sx + tx, y' = y * sy + ty, and the frame it is clipped to.  M is the (axis-aligned)
+    inverse matrix of the warp; computed in float64 and cast once."""
+    M = np.asarray(M, dtype=np.float64)
+    assert M.shape == (2, 3) and np.isfinite(M).all() and M[0, 1] == 0 and M[1, 0] == 0, f"an axis-aligned [2, 3] map, got {M.tolist()}"
+    return np.array([M[0, 0], M[1, 1], M[0, 2], M[1, 2], float(orig_hw[1]), float(orig_hw[0])], dtype=np.float64).astype(np.float32)
+
+
+def unwarp_boxes_reference(boxes, scores, classes, max_det, thresh, params):
+    """the numpy float32 oracle of dec_postprocess_affine_kernel (csrc/unwarp.hip, ops.postprocess_affine) for ONE image:
+    boxes f32 [K, 4] XYXY in network-input pixels, scores f32 [K], classes [K], params = unwarp_params(...) ->
+    (boxes [n, 4], scores [n], classes [n]).
+
+    The box map is the inverse of the training box rule forward_coords(., M, False, w): a source point that
+    forward_coords sends to (x, y) comes back as (x * sx + tx, y * sy + ty).  Its arithmetic is x' = f32(f32(x * sx) + tx)
+    -- two roundings, never a fused multiply-add -- and y' alike with sy, ty.  The rest is dec_postprocess_kernel's rule, word
+    for word: clip to [0, orig_w] x [0, orig_h], a NaN coordinate handed on; keep row k only if score > thresh (strictly, in
+    f32), x2 - x1 > 0, y2 - y1 > 0 and k < max_det; the kept rows stay in order."""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    scores = np.asarray(scores, dtype=np.float32).reshape(-1)
+    classes = np.asarray(classes).reshape(-1)
+    p = np.asarray(params, dtype=np.float32).reshape(6)
+    assert len(scores) == len(classes) == len(boxes)
+    n = max(0, min(len(boxes), int(max_det)))
+    boxes, scores, classes = boxes[:n], scores[:n], classes[:n]
+    with np.errstate(invalid="ignore", over="ignore"):
+        scale = np.array([p[0], p[1], p[0], p[1]], dtype=np.float32)
+        shift = np.array([p[2], p[3], p[2], p[3]], dtype=np.float32)
+        hi = np.array([p[4], p[5], p[4], p[5]], dtype=np.float32)
+        prod = (boxes * scale).astype(np.float32)            # rounded once ...
+        moved = (prod + shift).astype(np.float32)            # ... and once more
+        clipped = np.where(np.isnan(moved), moved, np.minimum(np.maximum(moved, np.float32(0)), hi)).astype(np.float32)
+        keep = (scores > np.float32(thresh)) & ((clipped[:, 2] - clipped[:, 0]) > 0) & ((clipped[:, 3] - clipped[:, 1]) > 0)
+    return clipped[keep], scores[keep], classes[keep]
 
 
 # --------------------------------------------------------------------------------------------------- the record's "warp"

@@ -20,6 +20,7 @@ import torch
 from ..checkpoint import DetectionCheckpointer
 from ..data import MetadataCatalog, TrafficLightDatasetMapper, build_detection_test_loader, build_detection_train_loader
 from ..data import transforms as T
+from ..data import warp as warp_defs
 from ..evaluation import COCOEvaluator, DatasetEvaluator, inference_on_dataset, print_csv_format, verify_results
 from ..modeling.meta_arch.build import build_model
 from ..solver import build_lr_scheduler, build_optimizer
@@ -97,6 +98,10 @@ class DefaultPredictor:
 
     def __init__(self, cfg):
         self.cfg = cfg.clone()      # cfg can be modified by the model
+        # INPUT.AFFINE.TEST_MODE: CenterNet's test warp in the resize's place (data.warp.test_params), on the device as well;
+        # a bad value is refused before the model is built
+        self.test_mode = warp_defs.check_test_mode(cfg.INPUT.AFFINE.TEST_MODE, cfg.INPUT.AFFINE.OUTPUT_SIZE,
+                                                   cfg.MODEL.CENTERNET.SIZE_DIVISIBILITY)
         self.model = build_model(self.cfg)
         self.model.eval()
         if len(cfg.DATASETS.TEST):
@@ -115,6 +120,12 @@ class DefaultPredictor:
             if self.input_format == "RGB":
                 original_image = original_image[:, :, ::-1]      # a view: the device resize reads channel stride -1
             height, width = original_image.shape[:2]
+            if self.test_mode:
+                M, out_h, out_w = warp_defs.test_params(height, width, self.test_mode, self.cfg.INPUT.AFFINE.OUTPUT_SIZE,
+                                                        self.cfg.MODEL.CENTERNET.SIZE_DIVISIBILITY)
+                inputs = {"image_raw": original_image, "resize_hw": (out_h, out_w), "warp": warp_defs.pack_warp(M, False),
+                          "height": height, "width": width}
+                return self.model([inputs])[0]
             size = int(self.aug.short_edge_length[0])
             resize_hw = self.aug.output_size(height, width, size, self.aug.max_size) if size else (height, width)
             inputs = {"image_raw": original_image, "resize_hw": resize_hw, "height": height, "width": width}

@@ -58,9 +58,10 @@ MAX_ENGINES = 16   # captured eval graphs kept per model (least recently used go
 SIGMOID_CLAMP = (ops.SIGMOID_CLAMP_FLOOR, 1.0 - ops.SIGMOID_CLAMP_FLOOR)
 
 
-def _engine_key(fused_base, B, H, W, Hp, Wp, img_dtype, flip=False):
+def _engine_key(fused_base, B, H, W, Hp, Wp, img_dtype, flip=False, affine=False):
     key = (B, Hp, Wp, img_dtype) if fused_base else (B, H, W, Hp, Wp, img_dtype)
-    return key + ("flip",) if flip else key      # a plain and a flip-test engine of one shape live side by side
+    key = key + ("flip",) if flip else key      # a plain and a flip-test engine of one shape live side by side
+    return key + ("affine",) if affine else key      # ... and so does the engine of affine-warped inputs (see _EvalEngine)
 
 
 class _EvalEngine:
@@ -77,21 +78,25 @@ class _EvalEngine:
     half is produced by the kernels that read the images (fused DLA base / preprocess), never as a copy of the batch.  The
     decode merges inside its one pass over the maps: hm = (hm[b] + mirror(hm[b+B])) * 0.5 on the sigmoid-and-clamped maps,
     wh = (wh[b] + mirror(wh[b+B])) * 0.5, reg = reg[b]; peak NMS, top-K, decode and everything after run once, on B images
-    (img_params, _post() and the handles are those of a plain engine; the finite flag covers both halves)."""
+    (img_params, _post() and the handles are those of a plain engine; the finite flag covers both halves).
 
-    def __init__(self, model, B, H, W, Hp, Wp, img_dtype, use_graph=True, flip=False):
+    affine: the engine of a batch whose network input is an affine warp of the original image (INPUT.AFFINE.TEST_MODE, DESIGN.md
+    7.13).  Everything up to the decode is a plain (or flip) engine's; img_params is [B, 6] -- data.warp.unwarp_params per image
+    -- and _post() maps the boxes back with ops.postprocess_affine in ops.postprocess's place."""
+
+    def __init__(self, model, B, H, W, Hp, Wp, img_dtype, use_graph=True, flip=False, affine=False):
         import weakref
         self._model = weakref.ref(model)
         dev = model.device
-        self.B, self.img_dtype, self.flip = B, img_dtype, bool(flip)
+        self.B, self.img_dtype, self.flip, self.affine = B, img_dtype, bool(flip), bool(affine)
         NB = 2 * B if flip else B            # images the network runs on
         self._mirror = "both" if flip else False
-        self.img_params = torch.zeros(B, 4, dtype=torch.float32, device=dev)
+        self.img_params = torch.zeros(B, 6 if affine else 4, dtype=torch.float32, device=dev)
         # DLA-34: normalisation + base_layer + level0 + level1 run as one kernel straight from the image batch
         self.fused_base = model.backbone_type == "dla34" and model.backbone.images_fusable(model._ctx, Hp, Wp)
         # the base kernel runs outside the captured graph and reads the caller's image batch in place, whatever its
         # unpadded size: the graph only depends on the padded size
-        self.key = _engine_key(self.fused_base, B, H, W, Hp, Wp, img_dtype, flip)
+        self.key = _engine_key(self.fused_base, B, H, W, Hp, Wp, img_dtype, flip, affine)
         self.images = torch.zeros(B, 3, H, W, dtype=img_dtype, device=dev)
         # otherwise: normalised input with a 3-pixel zero frame (the 7x7 stem's padding), cleared once, interior rewritten
         # per call
@@ -212,7 +217,8 @@ class _EvalEngine:
         m = self.model
         boxes, scores, classes, _ = self.dec
         max_det = min(m.max_detections_per_image, m.topk_candidates)
-        boxes, scores, classes, counts = ops.postprocess(boxes, scores, classes, max_det, m.score_threshold, self.img_params)
+        post = ops.postprocess_affine if self.affine else ops.postprocess
+        boxes, scores, classes, counts = post(boxes, scores, classes, max_det, m.score_threshold, self.img_params)
         return boxes, scores, classes, torch.where(self.finite, counts, torch.full_like(counts, -1))
 
     def __call__(self, images=None):
@@ -349,11 +355,12 @@ class CenterNet(nn.Module):
             self._engines = {}
         return super().train(mode)
 
-    def _engine(self, B, H, W, Hp, Wp, img_dtype, flip=False):
+    def _engine(self, B, H, W, Hp, Wp, img_dtype, flip=False, affine=False):
         """the captured engine of this input geometry (least recently used ones beyond MAX_ENGINES are destroyed here, before
-        a new one is built, i.e. never inside a stream capture); flip: the flip-test engine (see _EvalEngine)"""
+        a new one is built, i.e. never inside a stream capture); flip: the flip-test engine, affine: the engine of
+        affine-warped inputs (see _EvalEngine)"""
         fused = self.backbone_type == "dla34" and self.backbone.images_fusable(self._ctx, Hp, Wp)
-        key = _engine_key(fused, B, H, W, Hp, Wp, img_dtype, flip)
+        key = _engine_key(fused, B, H, W, Hp, Wp, img_dtype, flip, affine)
         eng = self._engines.get(key)
         if eng is not None:
             self._engines[key] = self._engines.pop(key)      # most recently used last
@@ -362,7 +369,7 @@ class CenterNet(nn.Module):
             old = self._engines.pop(next(iter(self._engines)))
             del old
         eng = self._engines[key] = _EvalEngine(self, B, H, W, Hp, Wp, img_dtype, self.use_hip_graph and not ops.RANGE_CHECK,
-                                               flip=flip)
+                                               flip=flip, affine=affine)
         return eng
 
     # ------------------------------------------------------------------ network (NHWC, HIP kernels)
@@ -506,7 +513,7 @@ class CenterNet(nn.Module):
             return self._forward_eval_ragged(batched_inputs, imgs, sizes, Hp, Wp, flip)
         H, W = sizes[0]
         img_dtype = torch.uint8 if imgs[0].dtype == torch.uint8 else torch.float32
-        eng = self._engine(B, H, W, Hp, Wp, img_dtype, flip)
+        eng = self._engine(B, H, W, Hp, Wp, img_dtype, flip, affine=_is_affine_batch(batched_inputs))
         stage = eng.staging(H, W)
         for b, im in enumerate(imgs):
             stage[b].copy_(im if im.dtype == img_dtype else im.to(img_dtype), non_blocking=True)
@@ -531,7 +538,7 @@ class CenterNet(nn.Module):
         Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
         H, W = sizes[0]
         img_dtype = torch.uint8 if imgs[0].dtype == torch.uint8 else torch.float32
-        eng = self._engine(len(imgs), H, W, Hp, Wp, img_dtype, flip)
+        eng = self._engine(len(imgs), H, W, Hp, Wp, img_dtype, flip, affine=_is_affine_batch(batched_inputs))
         stage = eng.staging(H, W)
         for b, im in enumerate(imgs):
             stage[b].copy_(im if im.dtype == img_dtype else im.to(img_dtype), non_blocking=True)
@@ -542,7 +549,10 @@ class CenterNet(nn.Module):
         tensor) and "resize_hw".  The raw images go to the device in one pinned copy and ONE launch (ops.resize_u8) resizes
         them, to the bytes the host mapper's Pillow resize gives.  All targets equal: straight into the staging batch of the
         captured engine -> (engine, batched_inputs, sizes), what _launch_eval takes.  Otherwise: the list of resized [3,h,w]
-        device tensors, for the ragged path."""
+        device tensors, for the ragged path.
+        Records that also carry "warp" (INPUT.AFFINE.TEST_MODE) go through ops.warp_affine_u8 in the resize's place -- one
+        launch into the staging batch of the affine engine when "resize_hw" is one size (fix_res), one launch per distinct size
+        otherwise (keep_res); a batch is warped or resized as a whole."""
         if self.device.type != "cuda":
             raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
         missing = [i for i, x in enumerate(batched_inputs) if "image_raw" not in x or "resize_hw" not in x]
@@ -554,13 +564,27 @@ class CenterNet(nn.Module):
             assert raw.ndim == 3 and raw.shape[2] == 3, f"image_raw is uint8 [H, W, 3], got {tuple(raw.shape)}"
             raws.append(raw.permute(2, 0, 1) if isinstance(raw, torch.Tensor) else raw.transpose(2, 0, 1))
         sizes = [(int(x["resize_hw"][0]), int(x["resize_hw"][1])) for x in batched_inputs]
+        affine = _is_affine_batch(batched_inputs)
         if any(s != sizes[0] for s in sizes):
+            if affine:      # keep_res over several source sizes: one warp launch per distinct size
+                out = [None] * len(raws)
+                for hw in sorted(set(sizes)):
+                    idx = [i for i, s in enumerate(sizes) if s == hw]
+                    warped = ops.warp_affine_u8([raws[i] for i in idx], [batched_inputs[i]["warp"] for i in idx], hw,
+                                                device=self.device)
+                    for i, im in zip(idx, warped):
+                        out[i] = im
+                return out
             return ops.resize_u8(raws, sizes, device=self.device)
         H, W = sizes[0]
         Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
-        eng = self._engine(len(raws), H, W, Hp, Wp, torch.uint8, flip)
+        eng = self._engine(len(raws), H, W, Hp, Wp, torch.uint8, flip, affine=affine)
         stage = eng.staging(H, W)
-        ops.resize_u8(raws, sizes, outs=[stage[b] for b in range(len(raws))])
+        outs = [stage[b] for b in range(len(raws))]
+        if affine:      # ONE warp launch in the resize's place, straight into the staging batch
+            ops.warp_affine_u8(raws, [x["warp"] for x in batched_inputs], sizes[0], outs=outs)
+        else:
+            ops.resize_u8(raws, sizes, outs=outs)
         return eng, batched_inputs, sizes
 
     def stage_raw_train(self, batched_inputs):
@@ -623,6 +647,13 @@ class CenterNet(nn.Module):
         return self._launch_eval(eng, batched_inputs, sizes).result()
 
     def _launch_eval(self, eng, batched_inputs, sizes, images=None, read_back=True):
+        if eng.affine:
+            out_sizes, params, pkey = _affine_params(batched_inputs)
+            if getattr(eng, "_params_key", None) != pkey:      # the unwarp parameters change only with the warps or the sizes
+                eng.img_params.copy_(params, non_blocking=False)
+                eng._params_key = pkey
+            boxes, scores, classes, counts = eng(images)
+            return _EvalHandle(boxes, scores, classes, counts, out_sizes, read_back)
         out_sizes = tuple((inp.get("height", size[0]), inp.get("width", size[1])) for inp, size in zip(batched_inputs, sizes))
         pkey = (out_sizes, tuple(sizes))
         if getattr(eng, "_params_key", None) != pkey:  # rescale parameters change only with the requested sizes
@@ -647,15 +678,20 @@ class CenterNet(nn.Module):
         hm, wh, reg = self._network_outputs(x, apply_sigmoid=True)
         boxes, scores, classes, _ = ops.decode(hm, wh, reg, self.topk_candidates, self.backbone.down_ratio,
                                                heat_floor=ops.SIGMOID_CLAMP_FLOOR, flip=flip)
-        params = torch.empty(B, 4, dtype=torch.float32)
-        out_sizes = []
-        for b, (inp, size) in enumerate(zip(batched_inputs, sizes)):
-            oh, ow = inp.get("height", size[0]), inp.get("width", size[1])
-            out_sizes.append((oh, ow))
-            params[b, 0], params[b, 1], params[b, 2], params[b, 3] = ow / size[1], oh / size[0], ow, oh
         max_det = min(self.max_detections_per_image, self.topk_candidates)
-        boxes, scores, classes, counts = ops.postprocess(boxes, scores, classes, max_det, self.score_threshold,
-                                                         params.to(dev))
+        if _is_affine_batch(batched_inputs):
+            out_sizes, params, _ = _affine_params(batched_inputs)
+            boxes, scores, classes, counts = ops.postprocess_affine(boxes, scores, classes, max_det, self.score_threshold,
+                                                                    params.to(dev))
+        else:
+            params = torch.empty(B, 4, dtype=torch.float32)
+            out_sizes = []
+            for b, (inp, size) in enumerate(zip(batched_inputs, sizes)):
+                oh, ow = inp.get("height", size[0]), inp.get("width", size[1])
+                out_sizes.append((oh, ow))
+                params[b, 0], params[b, 1], params[b, 2], params[b, 3] = ow / size[1], oh / size[0], ow, oh
+            boxes, scores, classes, counts = ops.postprocess(boxes, scores, classes, max_det, self.score_threshold,
+                                                             params.to(dev))
         counts = counts.tolist()
         results = []
         for b in range(B):
@@ -770,6 +806,36 @@ class CenterNet(nn.Module):
     def inference_single_image(self, output, image_size):
         """centernet.py:236-266 (batch of one)."""
         return self.inference(output, [image_size])[0]
+
+
+def _is_affine_batch(batched_inputs):
+    """does the batch carry "warp" (the records of a test-time mapper built with INPUT.AFFINE.TEST_MODE)?  All of its records
+    or none: a batch is warped or resized as a whole"""
+    warped = [i for i, x in enumerate(batched_inputs) if "warp" in x]
+    if warped and len(warped) != len(batched_inputs):
+        plain = next(i for i, x in enumerate(batched_inputs) if "warp" not in x)
+        raise KeyError(f"record {plain} of a batch lacks 'warp' and record {warped[0]} has it: a batch is warped "
+                       f"(INPUT.AFFINE.TEST_MODE) or resized as a whole")
+    return bool(warped)
+
+
+def _affine_params(batched_inputs):
+    """(out_sizes, f32 [B, 6] host tensor of data.warp.unwarp_params, a key that changes when either does) of an affine batch:
+    the boxes come back into the record's original "height" x "width" through its "warp" """
+    from ...data import warp as warp_defs
+    out_sizes, rows, key = [], [], []
+    for i, inp in enumerate(batched_inputs):
+        if "height" not in inp or "width" not in inp:
+            raise KeyError(f"record {i} carries 'warp' but not 'height' / 'width': the frame its boxes are mapped back into")
+        warp = inp["warp"]
+        M, flip = warp_defs.unpack_warp(warp.cpu() if isinstance(warp, torch.Tensor) else warp)
+        if flip:
+            raise ValueError(f"record {i}: a test-time 'warp' is never flipped (TEST.AUG.FLIP mirrors the network input instead)")
+        hw = (int(inp["height"]), int(inp["width"]))
+        out_sizes.append(hw)
+        rows.append(warp_defs.unwarp_params(M, hw))
+        key.append((hw, tuple(M.ravel().tolist())))
+    return tuple(out_sizes), torch.from_numpy(np.stack(rows)), tuple(key)
 
 
 class _Done:

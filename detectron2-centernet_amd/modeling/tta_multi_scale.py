@@ -16,6 +16,7 @@ import itertools
 import torch
 
 from .. import ops
+from .tta_device_resize import refuse_multi_scale_over_warped
 from .tta_device_resize import CenterNetWithTTA as _SinglePassTTA
 
 __all__ = ["CenterNetWithTTA"]
@@ -36,6 +37,7 @@ class CenterNetWithTTA(_SinglePassTTA):
     by per-class Gaussian soft-NMS (SIGMA, MIN_SCORE) and cut to TEST.DETECTIONS_PER_IMAGE, best score first."""
 
     def __init__(self, cfg, model):
+        refuse_multi_scale_over_warped(cfg)      # INPUT.AFFINE.TEST_MODE: no test sizes, no merge (DESIGN.md 7.13)
         sizes = tuple(cfg.TEST.AUG.MIN_SIZES)
         self.soft_nms = bool(cfg.TEST.SOFT_NMS.ENABLED)
         # the single-pass wrapper checks the model, reads FLIP and owns the one-size resize; it is never shown several sizes

@@ -1598,6 +1598,33 @@ def postprocess(boxes, scores, classes, max_det, score_thresh, img_params):
     return ob, os_, oc, counts
 
 
+def postprocess_affine(boxes, scores, classes, max_det, score_thresh, img_params6, out=None):
+    """ops.postprocess for a batch whose network input was an affine warp of the original image (INPUT.AFFINE.TEST_MODE,
+    DESIGN.md 7.13): threshold + unwarp + clip + drop-empty, order preserving.  img_params6 f32 [B,6] on device = (sx, sy, tx,
+    ty, orig_w, orig_h), data.warp.unwarp_params per image; x' = f32(f32(x * sx) + tx), bit for bit
+    data.warp.unwarp_boxes_reference.  Returns compacted (boxes, scores, classes, counts[B] i32): fresh tensors, or `out`, a
+    tuple of four the caller owns (rows behind counts[b] are left as they were)."""
+    _require_cuda(boxes, scores, classes, img_params6)
+    B, K = scores.shape
+    assert boxes.dtype == scores.dtype == img_params6.dtype == torch.float32 and classes.dtype == torch.int32
+    assert tuple(boxes.shape) == (B, K, 4) and tuple(classes.shape) == (B, K), (tuple(boxes.shape), tuple(classes.shape))
+    assert tuple(img_params6.shape) == (B, 6) and img_params6.is_contiguous(), (
+        f"postprocess_affine: img_params6 is a contiguous f32 [{B}, 6] tensor, got {tuple(img_params6.shape)}")
+    assert boxes.is_contiguous() and scores.is_contiguous() and classes.is_contiguous()
+    if out is None:
+        out = (torch.empty_like(boxes), torch.empty_like(scores), torch.empty_like(classes),
+               torch.empty(B, dtype=torch.int32, device=boxes.device))
+    ob, os_, oc, counts = out
+    _require_cuda(ob, os_, oc, counts)
+    for t, like in ((ob, boxes), (os_, scores), (oc, classes)):
+        assert t.shape == like.shape and t.dtype == like.dtype and t.is_contiguous(), "postprocess_affine: out mirrors the inputs"
+    assert tuple(counts.shape) == (B,) and counts.dtype == torch.int32 and counts.is_contiguous()
+    rc = _lib.lib().ctdet_postprocess_affine(_ptr(boxes), _ptr(scores), _ptr(classes), B, K, int(max_det), float(score_thresh),
+                                             _ptr(img_params6), _ptr(ob), _ptr(os_), _ptr(oc), _ptr(counts), _stream())
+    _lib.check(rc, "ctdet_postprocess_affine")
+    return ob, os_, oc, counts
+
+
 def soft_nms_merge(passes, num_classes, sigma, min_score, max_det):
     """Multi-scale test augmentation's merge: per-class Gaussian soft-NMS over the union of the passes'
     detections, then the per-image cap, on the device.  passes: a list of (boxes f32 [B,K_s,4], scores f32 [B,K_s], classes

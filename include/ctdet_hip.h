@@ -370,6 +370,15 @@ int32_t ctdet_decode_flip(const float* heat, int32_t heat_stride, const float* w
 int32_t ctdet_postprocess(const float* boxes, const float* scores, const int32_t* classes, int32_t B, int32_t K,
                           int32_t max_det, float score_thresh, const float* img_params, float* out_boxes,
                           float* out_scores, int32_t* out_classes, int32_t* counts, void* stream);
+/* ctdet_postprocess for a batch whose network input was an affine warp of the original image (INPUT.AFFINE.TEST_MODE, an
+ * addition within ABI 8; no counterpart in the reference, CenterNet's ctdet_post_process): the same threshold, clip, drop
+ * and ordered compaction, with the box map  x' = f32(f32(x * sx) + tx),  y' = f32(f32(y * sy) + ty)  -- the product rounded,
+ * then the sum: never a fused multiply-add -- in the place of the scale.  img_params6 f32 [B,6] = {sx, sy, tx, ty, orig_w,
+ * orig_h}; boxes clip to [0, orig_w] x [0, orig_h].  Kernel label: dec_postprocess_affine_kernel.  B = 0 launches nothing;
+ * K < 1 or a null pointer: -EINVAL.  Rows behind counts[b] are unspecified. */
+int32_t ctdet_postprocess_affine(const float* boxes, const float* scores, const int32_t* classes, int32_t B, int32_t K,
+                                 int32_t max_det, float score_thresh, const float* img_params6, float* out_boxes,
+                                 float* out_scores, int32_t* out_classes, int32_t* counts, void* stream);
 /* reads back the per-image status words of the last decode on this workspace (device->host copy + sync):
  * returns 0 if every image decoded exactly, -75 (EOVERFLOW) if a candidate buffer overflowed (cannot happen for a
  * workspace of the queried size), -22 (EINVAL) if a positive heat value lay below the promised heat_floor.

@@ -17,6 +17,14 @@ Per case:
 
     python tools/bench_resize.py [--out profiles/NAME.txt] [--modes f16x3,f16] [--no-eval]
 
+--affine-test runs another leg alone: evaluation.inference_on_dataset over a set that mixes 480x640, 640x480,
+427x640 and 375x500 sources, DLA-34 f16x3, TEST.BATCH_SIZE 16, raw records, once per test input -- ResizeShortestEdge
+(MIN_SIZE_TEST 512), INPUT.AFFINE.TEST_MODE fix_res 512x512 and keep_res: images/s and the share of batches that replayed a
+captured engine; then the device time of ctdet_postprocess_affine against ctdet_postprocess at B = 64, K = 100.  The three
+inputs feed different pixel counts: the images/s are what a user of each setting gets, no like-for-like comparison.
+
+    python tools/bench_resize.py --affine-test [--out profiles/NAME.txt] [--batches 40] [--reps 200]
+
 Needs a GPU: there is no CPU fallback, a time taken without one would mean nothing."""
 import argparse
 import json
@@ -139,8 +147,137 @@ def eval_times(torch, dev, mode, hw, new, steps, warmup):
     return out
 
 
+# ------------------------------------------------------------------------------- --affine-test
+AT_SOURCES = ((480, 640), (640, 480), (427, 640), (375, 500))      # (h, w): a COCO-like mix
+AT_BATCH = 16
+AT_LEGS = (("ResizeShortestEdge 512", ""), ("fix_res 512x512", "fix_res"), ("keep_res", "keep_res"))
+AT_DATASET = "bench_affine_test_mixed"
+
+
+def _at_dataset(root, batches):
+    """batches * AT_BATCH JPEGs, the four source sizes in rotation (every batch holds all four)"""
+    from PIL import Image
+    rng = np.random.RandomState(5)
+    dicts = []
+    for i in range(batches * AT_BATCH):
+        h, w = AT_SOURCES[i % len(AT_SOURCES)]
+        path = os.path.join(root, f"{i:04d}.jpg")
+        Image.fromarray(rng.randint(0, 256, (h // 8, w // 8, 3), dtype=np.uint8)).resize((w, h), Image.BILINEAR).save(path, quality=90)
+        dicts.append({"file_name": path, "image_id": i, "height": h, "width": w})
+    return dicts
+
+
+def _at_leg(torch, model, cfg, mode):
+    """(images/s, share of batches that replayed a captured graph, sizes after mapping) of inference_on_dataset over the mixed
+    set: raw records of the test loader, mapped once and fed from memory (no decode in the time)"""
+    from detectron2_centernet_amd.data import build_detection_test_loader
+    from detectron2_centernet_amd.evaluation import inference_on_dataset
+    c = cfg.clone()
+    c.INPUT.MIN_SIZE_TEST, c.INPUT.DEVICE_RESIZE, c.TEST.BATCH_SIZE = 512, True, AT_BATCH
+    c.INPUT.AFFINE.TEST_MODE, c.INPUT.AFFINE.OUTPUT_SIZE = mode, (512, 512)
+    batches = list(build_detection_test_loader(c, AT_DATASET, num_workers=0))
+    assert all(len(b) == AT_BATCH and "image_raw" in b[0] and (("warp" in b[0]) == bool(mode)) for b in batches)
+    replays = [0]
+    real_replay = torch.cuda.CUDAGraph.replay
+
+    def counted(self):
+        replays[0] += 1
+        return real_replay(self)
+    model._engines = {}
+    torch.cuda.CUDAGraph.replay = counted
+    try:
+        inference_on_dataset(model, batches, None)
+    finally:
+        torch.cuda.CUDAGraph.replay = real_replay
+    timing = inference_on_dataset.last_timing
+    sizes = sorted({tuple(r["resize_hw"]) for b in batches for r in b})
+    return AT_BATCH / timing["total_s_per_iter"], replays[0] / len(batches), sizes, len(batches), timing["iters"]
+
+
+def _at_post_times(torch, ops, dev, reps, B=64, K=100):
+    """per launch of ctdet_postprocess_affine / ctdet_postprocess, HIP events, warm-up, best of three, the two alternating:
+    (a) `reps` launches captured in one graph, ten replays per timing -- the device's time, the host's launch cost left out;
+    (b) `reps` calls of the Python wrapper back to back -- what a caller pays, launch-bound for a kernel this small"""
+    g = torch.Generator().manual_seed(3)
+    xy = torch.rand(B, K, 2, generator=g) * 400
+    boxes = torch.cat([xy, xy + torch.rand(B, K, 2, generator=g) * 100 + 1], 2).to(dev)
+    scores, classes = torch.rand(B, K, generator=g).to(dev), torch.randint(0, 80, (B, K), generator=g, dtype=torch.int32).to(dev)
+    p4 = torch.tensor([[1.25, 1.25, 640.0, 480.0]] * B, device=dev)
+    p6 = torch.tensor([[1.25, 1.25, 0.0, -80.0, 640.0, 480.0]] * B, device=dev)
+    legs = (("ctdet_postprocess_affine", ops.postprocess_affine, p6), ("ctdet_postprocess", ops.postprocess, p4))
+    graphs = {}
+    for name, fn, params in legs:
+        for _ in range(10):
+            fn(boxes, scores, classes, K, 0.3, params)
+        torch.cuda.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name]):
+            for _ in range(reps):
+                fn(boxes, scores, classes, K, 0.3, params)
+        for _ in range(3):
+            graphs[name].replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = {}
+    for _ in range(3):
+        for name, fn, params in legs:
+            e0.record()
+            for _ in range(10):
+                graphs[name].replay()
+            e1.record()
+            e1.synchronize()
+            t = e0.elapsed_time(e1) / (10 * reps) * 1e-3
+            out[name + "_graph"] = min(out.get(name + "_graph", t), t)
+            e0.record()
+            for _ in range(reps):
+                fn(boxes, scores, classes, K, 0.3, params)
+            e1.record()
+            e1.synchronize()
+            t = e0.elapsed_time(e1) / reps * 1e-3
+            out[name + "_call"] = min(out.get(name + "_call", t), t)
+    return out
+
+
+def affine_test_main(args, say):
+    """the --affine-test leg: one MI355X, DLA-34 f16x3, TEST.BATCH_SIZE 16, raw records of a set that mixes four source sizes"""
+    import tempfile
+
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_resize needs a ROCm GPU: nothing here is measurable without one")
+    import bench
+    from detectron2_centernet_amd import ops
+    from detectron2_centernet_amd.data import DatasetCatalog
+    dev = torch.device("cuda:0")
+    rec = {}
+    say(f"# tools/bench_resize.py --affine-test on {torch.cuda.get_device_name(0)}; DLA-34 f16x3, TEST.BATCH_SIZE {AT_BATCH}, raw records")
+    say("sources (h x w) in rotation: " + ", ".join(f"{h}x{w}" for h, w in AT_SOURCES))
+    model, cfg = bench.build_model("f16x3", dev, seed=1)
+    model.eval()
+    with tempfile.TemporaryDirectory(prefix="ctdet_affine_test_") as root:
+        dicts = _at_dataset(root, args.batches)
+        if AT_DATASET not in DatasetCatalog:
+            DatasetCatalog.register(AT_DATASET, lambda: dicts)
+        say("inference_on_dataset, records mapped once and fed from memory (host clock over the timed batches):")
+        for name, mode in AT_LEGS:
+            rate, share, sizes, n, timed = _at_leg(torch, model, cfg, mode)
+            key = mode or "resize_shortest_edge"
+            rec.update({f"{key}_img_s": rate, f"{key}_graph_share": share})
+            say(f"  {name:24s} {rate:8.1f} img/s, {share * 100:5.1f} % of the {n} batches replayed a captured engine "
+                f"({timed} timed); sizes after mapping {sizes}")
+    t = _at_post_times(torch, ops, dev, args.reps)
+    rec.update({k + "_us": v * 1e6 for k, v in t.items()})
+    say("per launch at B = 64, K = 100 (HIP events, warm-up, best of three, the two alternating):")
+    for name in ("ctdet_postprocess_affine", "ctdet_postprocess"):
+        say(f"  {name:26s} {t[name + '_graph'] * 1e6:6.2f} us in a captured graph of {args.reps} launches (device time), "
+            f"{t[name + '_call'] * 1e6:6.2f} us per call of the Python wrapper back to back")
+    say(json.dumps({"bench_affine_test": rec}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--affine-test", action="store_true", help="the INPUT.AFFINE.TEST_MODE leg alone (DESIGN.md 7.13)")
+    ap.add_argument("--batches", type=int, default=40, help="--affine-test: batches of the mixed set")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--steps", type=int, default=10)
@@ -154,6 +291,14 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
+
+    if args.affine_test:
+        affine_test_main(args, say)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
 
     host = [host_times(hw, new) for hw, new in CASES]      # before the GPU is touched: the workers are forked
 
