@@ -26,6 +26,7 @@ class DetectionCheckpointer:
         self.save_dir = save_dir
         self.save_to_disk = is_main_process() if save_to_disk is None else save_to_disk
         self.checkpointables = dict(checkpointables)
+        self.loaded = []         # the checkpointables the last `load` found in its file
         self.logger = logging.getLogger(__name__)
 
     # ---- save (fvcore Checkpointer.save) ----
@@ -60,6 +61,7 @@ class DetectionCheckpointer:
 
     # ---- load ----
     def load(self, path, checkpointables=None):
+        self.loaded = []
         if not path:
             self.logger.info("No checkpoint found. Initializing model from scratch")
             return {}
@@ -74,6 +76,7 @@ class DetectionCheckpointer:
         for key in self.checkpointables if checkpointables is None else checkpointables:
             if key in checkpoint:
                 self.checkpointables[key].load_state_dict(checkpoint.pop(key))
+                self.loaded.append(key)
         return checkpoint                                  # remaining entries, e.g. "iteration"
 
     def _load_model(self, checkpoint):

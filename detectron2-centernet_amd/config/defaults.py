@@ -140,6 +140,15 @@ _C.SOLVER.ADAM = CN()
 _C.SOLVER.ADAM.BETAS = (0.9, 0.999)
 _C.SOLVER.ADAM.EPS = 1e-8
 _C.SOLVER.ADAM.AMSGRAD = False
+# not in the reference: an exponential moving average of the weights and of the BatchNorm running statistics, updated behind
+# every optimizer step by HIP kernels (solver/ema.py).  e += (1 - d) * (p - e) with d = DECAY, under WARMUP
+# d = min(DECAY, (1 + t) / (10 + t)) at update t.  EVAL: the trainer's evaluations and `train_net.py --eval-only` score the
+# averaged weights.  Checkpoints carry them under "ema"
+_C.SOLVER.EMA = CN()
+_C.SOLVER.EMA.ENABLED = False
+_C.SOLVER.EMA.DECAY = 0.9998
+_C.SOLVER.EMA.WARMUP = True
+_C.SOLVER.EMA.EVAL = True
 
 _C.TEST = CN()
 _C.TEST.EXPECTED_RESULTS = []

@@ -867,6 +867,31 @@ int32_t ctdet_adam_runs(float* param, const float* grad, float* exp_avg, float* 
                           clip_type, clip_value, coefs, (hipStream_t)stream);
 }
 
+int32_t ctdet_ema_advance(int64_t* updates_dev, float* weight_dev, double decay, int32_t warmup, void* stream) {
+  CTDET_CHECK(updates_dev && weight_dev, "ema_advance: null pointer");
+  CTDET_CHECK(decay >= 0.0 && decay < 1.0, "ema_advance: decay %g outside [0, 1)", decay);
+  return launch_ema_advance((long long*)updates_dev, weight_dev, decay, warmup != 0, (hipStream_t)stream);
+}
+
+#define CTDET_EMA_SEGMENTS(what)                                                                               \
+  CTDET_CHECK(nseg >= 0 && max_len >= 0, what ": nseg=%d max_len=%lld", nseg, (long long)max_len);             \
+  if (nseg == 0) return 0
+
+int32_t ctdet_ema_lerp_segments(const float* const* live_ptrs_dev, float* ema, const int64_t* seg_start_dev, int32_t nseg,
+                                int64_t max_len, const float* weight_dev, void* stream) {
+  CTDET_EMA_SEGMENTS("ema_lerp_segments");
+  CTDET_CHECK(live_ptrs_dev && ema && seg_start_dev && weight_dev, "ema_lerp_segments: null pointer");
+  return launch_ema_lerp_segments(live_ptrs_dev, ema, (const long*)seg_start_dev, nseg, (long)max_len, weight_dev,
+                                  (hipStream_t)stream);
+}
+
+int32_t ctdet_ema_swap_segments(float* const* live_ptrs_dev, float* ema, const int64_t* seg_start_dev, int32_t nseg,
+                                int64_t max_len, void* stream) {
+  CTDET_EMA_SEGMENTS("ema_swap_segments");
+  CTDET_CHECK(live_ptrs_dev && ema && seg_start_dev, "ema_swap_segments: null pointer");
+  return launch_ema_swap_segments(live_ptrs_dev, ema, (const long*)seg_start_dev, nseg, (long)max_len, (hipStream_t)stream);
+}
+
 int32_t ctdet_resize_bilinear_u8(const ctdet_resize_desc* d, const int32_t* tables_dev, void* stream) {
   CTDET_CHECK(d && d->src && d->dst, "resize_bilinear_u8: null pointer");
   CTDET_CHECK(d->H >= 1 && d->W >= 1 && d->new_h >= 1 && d->new_w >= 1, "resize_bilinear_u8: %dx%d -> %dx%d", d->H, d->W,

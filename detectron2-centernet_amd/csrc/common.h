@@ -366,6 +366,12 @@ int launch_adam_runs(float* p, const float* g, float* m, float* v, float* vmax, 
                      double beta1, double beta2, double eps, int decoupled, int amsgrad, int clip_type, float clip_value,
                      const float* coefs, hipStream_t s);
 
+// ema.hip
+int launch_ema_advance(long long* updates, float* weight, double decay, int warmup, hipStream_t s);
+int launch_ema_lerp_segments(const float* const* live_ptrs, float* ema, const long* seg_start, int nseg, long max_len,
+                             const float* weight, hipStream_t s);
+int launch_ema_swap_segments(float* const* live_ptrs, float* ema, const long* seg_start, int nseg, long max_len, hipStream_t s);
+
 // train_bwd.hip
 size_t chan_reduce_workspace_bytes(int C);                   // BnArgs::workspace
 int launch_bn_train_fwd(const BnArgs& a, hipStream_t s);

@@ -9,6 +9,7 @@ the records of a mapper built with INPUT.DEVICE_RESIZE); the RGB reversal is a v
 kernel reads as it is, so the host touches the pixels once, for the pinned upload.  The result equals what the host resize
 gives: the resized bytes are identical (ops.resize_u8)."""
 import argparse
+import contextlib
 import logging
 import os
 import sys
@@ -155,6 +156,8 @@ class DefaultTrainer(SimpleTrainer):
         super().__init__(model, data_loader, cfg, optimizer=optimizer, route_records=True)
         self.scheduler = self.build_lr_scheduler(cfg, optimizer)
         self.checkpointer = DetectionCheckpointer(model, cfg.OUTPUT_DIR, optimizer=optimizer, scheduler=self.scheduler)
+        if self.ema is not None:      # SOLVER.EMA (built by SimpleTrainer): checkpoints carry it under "ema"
+            self.checkpointer.checkpointables["ema"] = self.ema
         self.start_iter = 0
         self.max_iter = cfg.SOLVER.MAX_ITER
         self.cfg = cfg
@@ -162,10 +165,19 @@ class DefaultTrainer(SimpleTrainer):
         self.register_hooks(self.build_hooks())
 
     def resume_or_load(self, resume=True):
-        """resume and a checkpoint in OUTPUT_DIR: model, optimizer and scheduler from it, and training goes on at the
-        iteration after the one it stores.  Otherwise: MODEL.WEIGHTS into the model only, from iteration 0."""
+        """resume and a checkpoint in OUTPUT_DIR: model, optimizer, scheduler and (SOLVER.EMA) the averaged weights from it,
+        and training goes on at the iteration after the one it stores.  Otherwise: MODEL.WEIGHTS into the model only, from
+        iteration 0.  The EMA restarts from the loaded weights whenever it did not come out of the checkpoint: it was copied
+        from the initialisation before the weights arrived."""
         checkpoint = self.checkpointer.resume_or_load(self.cfg.MODEL.WEIGHTS, resume=resume)
-        if resume and self.checkpointer.has_checkpoint():
+        resuming = resume and self.checkpointer.has_checkpoint()
+        if self.ema is not None and "ema" not in self.checkpointer.loaded:
+            if resuming:
+                logging.getLogger(__name__).warning(
+                    "SOLVER.EMA is enabled, but %s carries no \"ema\" entry: the average restarts from the loaded weights",
+                    self.checkpointer.get_checkpoint_file())
+            self.ema.reset()
+        if resuming:
             self.start_iter = checkpoint.get("iteration", -1) + 1
             self.iter = self.start_iter
 
@@ -182,7 +194,10 @@ class DefaultTrainer(SimpleTrainer):
         ]
 
         def test_and_save_results():
-            self._last_eval_results = self.test(self.cfg, self.model)
+            # SOLVER.EMA.EVAL: the averaged weights are exchanged into the model for the evaluation and back after it
+            swapped = self.ema.swapped() if self.ema is not None and cfg.SOLVER.EMA.EVAL else contextlib.nullcontext()
+            with swapped:
+                self._last_eval_results = self.test(self.cfg, self.model)
             return self._last_eval_results
 
         # evaluation after the checkpoint: if it fails, the checkpoint is there to debug with

@@ -8,7 +8,7 @@ import weakref
 import torch
 
 from .. import ops_train
-from ..solver import build_lr_scheduler, build_optimizer
+from ..solver import build_lr_scheduler, build_model_ema, build_optimizer
 from ..utils import comm
 from ..utils.events import EventStorage
 from . import graph_nodes, train_step
@@ -109,9 +109,12 @@ class SimpleTrainer(TrainerBase):
     Per-iteration metrics are kept on the device and only fetched when `metrics()` is called: the reference does a
     `.item()` sync plus a Gloo pickle gather every step (train_loop.py:261-290), which this build avoids."""
 
-    def __init__(self, model, data_loader, cfg, optimizer=None, process_group=None, route_records=False):
+    ema = None      # SOLVER.EMA: the solver.ema.ModelEMA attached to the optimizer, when enabled
+
+    def __init__(self, model, data_loader, cfg, optimizer=None, process_group=None, route_records=False, ema=None):
         """route_records: `run_step` sends a record batch whose images share one size to the captured step of
-        `run_step_tensors` (see `_record_tensors`); off, every record batch takes the eager path"""
+        `run_step_tensors` (see `_record_tensors`); off, every record batch takes the eager path.
+        ema: a solver.ema.ModelEMA over `optimizer`; None: built from SOLVER.EMA (nothing when it is disabled)"""
         super().__init__()
         model.train()
         self.route_records = bool(route_records)
@@ -124,6 +127,16 @@ class SimpleTrainer(TrainerBase):
         self.reducer = BucketedReducer(self.optimizer, process_group=process_group, comm=self._rccl_comm(process_group))
         ops_train.set_world_size(self.reducer.world)
         self.reducer.broadcast_parameters([b for b in model.buffers() if b.dtype.is_floating_point])
+        # SOLVER.EMA: attached to the optimizer, whose step updates it -- inside the captured single-GPU step, behind the eager
+        # optimizer.step() of the data-parallel one; no collective: every rank applies the same update to the same values.
+        # Built behind the broadcast, so that it starts from rank 0's weights on every rank
+        if ema is None:
+            ema = build_model_ema(cfg, model, self.optimizer)
+        elif self.reducer.world > 1:
+            ema.reset()
+        self.ema = ema
+        if ema is not None:
+            self.optimizer.ema = ema
         self.scheduler = build_lr_scheduler(cfg, self.optimizer)     # SOLVER.LR_SCHEDULER_NAME (solver/build.py:140-165)
         ops_train.SYNC_BN_GROUP = process_group                       # SyncBatchNorm's collectives go over the trainer's group
         self.iter = 0

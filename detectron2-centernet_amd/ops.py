@@ -1826,3 +1826,41 @@ def adam_runs_(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, run_end, run_lr
                                     float(beta1), float(beta2), float(eps), int(bool(decoupled)), int(bool(amsgrad)),
                                     int(clip_type), float(clip_value), _ptr(coefs), _stream())
     _lib.check(rc, "ctdet_adam_runs")
+
+
+def ema_advance_(updates, weight, decay, warmup):
+    """the first launch of an EMA update: t = updates[0], updates[0] = t + 1 (i64, device) and weight[0] = 1 - d with
+    d = min(decay, (1 + t) / (10 + t)) under warm-up, else decay (see ctdet_ema_advance) -- a kernel, so that a captured step
+    keeps counting when it is replayed"""
+    _require_cuda(updates, weight)
+    assert updates.dtype == torch.int64 and updates.numel() == 1
+    assert weight.dtype == torch.float32 and weight.numel() == 1
+    rc = _lib.lib().ctdet_ema_advance(_ptr(updates), _ptr(weight), float(decay), int(bool(warmup)), _stream())
+    _lib.check(rc, "ctdet_ema_advance")
+
+
+def _ema_tables(live_ptrs, ema, seg_start):
+    _require_cuda(live_ptrs, ema, seg_start)
+    assert live_ptrs.dtype == torch.int64 and seg_start.dtype == torch.int64 and live_ptrs.is_contiguous()
+    assert seg_start.is_contiguous() and seg_start.numel() == live_ptrs.numel() + 1
+    assert ema.dtype == torch.float32 and ema.is_contiguous()
+
+
+def ema_lerp_segments_(live_ptrs, ema, seg_start, max_len, weight):
+    """ema[seg_start[s] + i] += weight[0] * (live[s][i] - ema[seg_start[s] + i]) in torch's lerp_ form, over the device tables
+    `live_ptrs` (i64 addresses of f32 data, one per segment) and `seg_start` (i64, one more entry than segments); `max_len`
+    bounds the segment lengths (see ctdet_ema_lerp_segments)"""
+    _ema_tables(live_ptrs, ema, seg_start)
+    _require_cuda(weight)
+    assert weight.dtype == torch.float32 and weight.numel() == 1
+    rc = _lib.lib().ctdet_ema_lerp_segments(_ptr(live_ptrs), _ptr(ema), _ptr(seg_start), live_ptrs.numel(), int(max_len),
+                                            _ptr(weight), _stream())
+    _lib.check(rc, "ctdet_ema_lerp_segments")
+
+
+def ema_swap_segments_(live_ptrs, ema, seg_start, max_len):
+    """exchanges live[s][i] and ema[seg_start[s] + i] bit for bit over the same tables (see ctdet_ema_swap_segments)"""
+    _ema_tables(live_ptrs, ema, seg_start)
+    rc = _lib.lib().ctdet_ema_swap_segments(_ptr(live_ptrs), _ptr(ema), _ptr(seg_start), live_ptrs.numel(), int(max_len),
+                                            _stream())
+    _lib.check(rc, "ctdet_ema_swap_segments")

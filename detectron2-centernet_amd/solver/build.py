@@ -147,6 +147,7 @@ class FlatOptimizer:
         # zero-initialised scratch for the atomically accumulated weight gradients (ops_train.ZeroArena): a little larger
         # than the parameter count (channel padding), cleared together with the gradient buffer
         self._arena = self._packs = None
+        self.ema = None       # a solver.ema.ModelEMA, attached by its owner: updated behind every step (_after_update)
         if torch.device(device).type == "cuda":
             from .. import ops_train
             self._arena = ops_train.ARENA = ops_train.ZeroArena(int(total * 1.25) + (1 << 20), torch.device(device))
@@ -181,6 +182,8 @@ class FlatOptimizer:
                                  self.grad_norms, self.clip_coefs)
 
     def _after_update(self):
+        if self.ema is not None:      # SOLVER.EMA: launches only, so inside the captured single-GPU step
+            self.ema.update()
         for p in self.params:  # raw-pointer update: tell autograd / the packed-weight caches the values changed
             torch.autograd.graph.increment_version(p)
         if self._packs is not None:   # the f16 operands of every conv weight the last step used, in one launch
@@ -379,3 +382,13 @@ def build_optimizer(cfg, model):
     adam = cfg.SOLVER.ADAM
     return FlatAdam(param_groups(cfg, model), cfg.SOLVER.BASE_LR, betas=adam.BETAS, eps=adam.EPS, decoupled=name == "ADAMW",
                     amsgrad=adam.AMSGRAD, clip=clip_from_cfg(cfg))
+
+
+def build_model_ema(cfg, model, optimizer):
+    """SOLVER.EMA -> a ModelEMA over `optimizer`'s flat buffer (solver/ema.py), or None when it is disabled.  The caller
+    attaches it (`optimizer.ema = ema`) and registers it with the checkpointer"""
+    e = cfg.SOLVER.get("EMA", None)
+    if e is None or not e.get("ENABLED", False):
+        return None
+    from .ema import ModelEMA
+    return ModelEMA(model, optimizer, decay=e.DECAY, warmup=e.WARMUP)

@@ -475,6 +475,25 @@ int32_t ctdet_adam_runs(float* param, const float* grad, float* exp_avg, float* 
                         int32_t decoupled, int32_t amsgrad, int32_t clip_type, float clip_value, const float* coefs,
                         void* stream);
 
+/* Exponential moving average of the weights (SOLVER.EMA).  ctdet_ema_advance, one thread: t = updates_dev[0] (i64),
+ * updates_dev[0] = t + 1, d = warmup ? min(decay, (1 + t) / (10 + t)) : decay in f64, weight_dev[0] = (float)(1 - d) -- a
+ * device counter, so that a captured step keeps counting when it is replayed.  decay in [0, 1), else -22. */
+int32_t ctdet_ema_advance(int64_t* updates_dev, float* weight_dev, double decay, int32_t warmup, void* stream);
+
+/* ema[seg_start[s] + i] = fmaf(w, live_ptrs[s][i] - e, e) with e the old value and w = weight_dev[0], for every segment s
+ * in [0, nseg) and i in [0, seg_start[s + 1] - seg_start[s]): live_ptrs_dev is a device table of nseg device pointers,
+ * seg_start_dev a device i64 table of nseg + 1 ascending offsets into `ema` (a segment may be empty), max_len an upper bound
+ * of the segment lengths that only sizes the grid.  float4 accesses where a segment starts 16-byte aligned on both sides,
+ * scalar ones otherwise.  NaN and Inf follow the formula.  nseg == 0 is a no-op; nseg < 0, max_len < 0 or a null pointer
+ * with nseg > 0: -22. */
+int32_t ctdet_ema_lerp_segments(const float* const* live_ptrs_dev, float* ema, const int64_t* seg_start_dev, int32_t nseg,
+                                int64_t max_len, const float* weight_dev, void* stream);
+
+/* Exchanges live_ptrs[s][i] and ema[seg_start[s] + i] over the same tables, bit for bit (moved as integers: NaN payloads and
+ * -0 survive); two calls give back the original bits.  Same refusals. */
+int32_t ctdet_ema_swap_segments(float* const* live_ptrs_dev, float* ema, const int64_t* seg_start_dev, int32_t nseg,
+                                int64_t max_len, void* stream);
+
 /* ---- training-side entry points (f32 statistics and weight gradients; activations and activation gradients f16 --
  * the throughput mode -- or f32 -- the reference's precision -- selected by `dtype` (ctdet_dtype) / the descriptor's
  * compute_dtype).  Input gradients of plain convs are ctdet_conv2d_fwd calls with transposed/flipped weights (in_dil

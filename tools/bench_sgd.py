@@ -10,7 +10,10 @@ the same round.  Not part of the product or of the tests.
   --lib PATH     an additional "plain" case through another build of libctdet_hip.so (the plain case calls
                  ctdet_sgd_momentum_runs alone, which every build of ABI 8 has): A/B of the plain path against a parent build
   --train-step   instead: the f16x3 DLA-34 training step (16 x 512^2, engine/bench_train.py's step), a fresh trainer per leg,
-                 legs alternating: SGD with norm clipping off / on, or with --adam SGD / ADAM (no clipping)"""
+                 legs alternating: SGD with norm clipping off / on, or with --adam SGD / ADAM (no clipping), or with --ema SGD
+                 with SOLVER.EMA off / on
+  --ema          instead: the EMA update alone (advance + the lerp over the flat parameters + the lerp over the BatchNorm
+                 statistics) next to the plain SGD launch, on the same layout; 12 B per parameter (e and p read, e written)"""
 import argparse
 import ctypes
 import os
@@ -32,6 +35,7 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--lib", default=None)
 ap.add_argument("--train-step", action="store_true")
 ap.add_argument("--adam", action="store_true", help="--train-step: the legs are SGD / ADAM instead of norm clipping off / on")
+ap.add_argument("--ema", action="store_true", help="the EMA update alone; with --train-step: the legs are SOLVER.EMA off / on")
 ap.add_argument("--steps", type=int, default=40, help="--train-step: timed steps per leg")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -60,7 +64,9 @@ def train_step_legs():
         model, cfg = bench.build_model("f16x3", dev, seed=1)
         model.train()
         cfg.SOLVER.IMS_PER_BATCH = 16
-        if on and a.adam:
+        if a.ema:
+            cfg.SOLVER.EMA.ENABLED = on
+        elif on and a.adam:
             cfg.SOLVER.OPTIMIZER = "ADAM"
             cfg.SOLVER.BASE_LR = 1.25e-4 * 16 / 32
         elif on:
@@ -68,6 +74,11 @@ def train_step_legs():
             cfg.SOLVER.CLIP_GRADIENTS.CLIP_TYPE, cfg.SOLVER.CLIP_GRADIENTS.CLIP_VALUE = "norm", 1.0
         tr = SimpleTrainer(model, None, cfg)
         ms = timed(lambda: tr.run_step_tensors(*batch), 8, a.steps) / 1e3
+        if a.ema:
+            print(f"train step f16x3 16x512^2, SOLVER.EMA {'on ' if on else 'off'}: {ms:.3f} ms / step  ({tr.graph_state}"
+                  f"{f', {int(tr.ema.updates)} updates' if on else ''})", flush=True)
+            del tr, model
+            continue
         if a.adam:
             print(f"train step f16x3 16x512^2, {type(tr.optimizer).__name__:8s}: {ms:.3f} ms / step  ({tr.graph_state}"
                   f"{f', step count {int(tr.optimizer.step_count)}' if on else ''})", flush=True)
@@ -79,9 +90,43 @@ def train_step_legs():
         del tr, model
 
 
+def ema_cases():
+    """the EMA update on DLA-34's layout, alternating with the plain SGD launch as the yardstick of the same round"""
+    from detectron2_centernet_amd.solver.ema import ModelEMA
+
+    model, cfg = bench.build_model("f16x3", dev, calibrate=False)
+    model.train()
+    opt = FlatSGD(param_groups(cfg, model), 0.01, 0.9)
+    ema = ModelEMA(model, opt)
+    n, ns = opt.flat_param.numel(), sum(k for _, _, k, _ in ema.table.buffers)
+    grad = torch.randn(n, generator=torch.Generator().manual_seed(0)).to(dev) * 1e-3
+
+    def plain():
+        ops.sgd_momentum_runs_(opt.flat_param, grad, opt.flat_mom, opt._run_end, opt._run_lr_index, opt._run_wd, opt._lr_table,
+                               0.9, False)
+
+    def params_only():
+        ops.ema_lerp_segments_(ema._param_ptrs, ema.ema_param, ema._param_start, n, ema.weight)
+
+    def stats_only():
+        ops.ema_lerp_segments_(ema._stat_ptrs, ema.ema_stats, ema._stat_start, ema._stat_max, ema.weight)
+
+    cases = [("plain SGD launch", plain, 20 * n), ("EMA update (3 launches)", ema.update, 12 * (n + ns)),
+             ("EMA lerp, parameters alone", params_only, 12 * n), ("EMA lerp, statistics alone", stats_only, 12 * ns)]
+    print(f"{n} parameters in one segment, {ns} statistics in {ema._stat_ptrs.numel()} segments; {a.warm} warm + {a.reps} timed "
+          "launches per case and round")
+    for r in range(a.rounds):
+        for name, f, by in cases:
+            us = timed(f, a.warm, a.reps)
+            print(f"round {r}  {name:28s} {us:8.2f} us  {by / us / 1e3:8.1f} GB/s  {by / HBM_PEAK * 1e6 / us * 100:5.1f} % of the "
+                  f"HBM bound ({by / 1e6:.1f} MB)", flush=True)
+
+
 def main():
     if a.train_step:
         return train_step_legs()
+    if a.ema:
+        return ema_cases()
     model, cfg = bench.build_model("f16x3", dev, calibrate=False)
     groups = param_groups(cfg, model)
     variants = {"plain": (False, None), "nesterov": (True, None), "value": (False, ("value", 0.01)),

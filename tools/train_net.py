@@ -5,7 +5,8 @@
 
 Trains to OUTPUT_DIR (checkpoints, metrics.json, log.txt, config.yaml), or with --eval-only scores MODEL.WEIGHTS (with
 --resume: the last checkpoint of OUTPUT_DIR) on DATASETS.TEST.  With TEST.AUG.ENABLED the model is tested through
-CenterNetWithTTA.  The configs' "bulb_train" / "bulb_val" are not distributed: with CTDET_SYNTHETIC_SET="train images,test images,size" in the
+CenterNetWithTTA.  With SOLVER.EMA.ENABLED and SOLVER.EMA.EVAL, --eval-only scores the averaged weights a checkpoint carries
+under "ema" (a checkpoint without them: its "model", with a warning).  The configs' "bulb_train" / "bulb_val" are not distributed: with CTDET_SYNTHETIC_SET="train images,test images,size" in the
 environment (e.g. "64,16,512") a dataset the config names but nothing has registered is replaced by the synthetic set, written
 once as PNG files under OUTPUT_DIR/synthetic; without it an unregistered name is an error."""
 import json
@@ -23,6 +24,7 @@ from detectron2_centernet_amd.config import get_cfg  # noqa: E402
 from detectron2_centernet_amd.data.catalog import DatasetCatalog, register_synthetic_files  # noqa: E402
 from detectron2_centernet_amd.engine import DefaultTrainer, default_argument_parser, default_setup, launch  # noqa: E402
 from detectron2_centernet_amd.evaluation import verify_results  # noqa: E402
+from detectron2_centernet_amd.solver.ema import ModelEMA  # noqa: E402
 from detectron2_centernet_amd.utils import comm  # noqa: E402
 
 # CTDET_SYNTHETIC_SET="train images,test images,size" (e.g. "64,16,512"): opt-in -- with it, a dataset of the config that
@@ -82,7 +84,15 @@ def main(args):
     cfg = setup(args)
     if args.eval_only:
         model = Trainer.build_model(cfg)
-        DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
+        rest = DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
+        if cfg.SOLVER.EMA.ENABLED and cfg.SOLVER.EMA.EVAL:
+            if "ema" in rest:
+                ModelEMA.load_into_model(model, rest["ema"])
+                logging.getLogger(__name__).info("SOLVER.EMA.EVAL: evaluating the checkpoint's averaged weights (%d updates)",
+                                                 rest["ema"]["updates"])
+            else:
+                logging.getLogger(__name__).warning("SOLVER.EMA.EVAL: the checkpoint carries no \"ema\" entry; evaluating "
+                                                    "its \"model\" weights")
         res = Trainer.test(cfg, model)
         if comm.is_main_process():
             with open(os.path.join(cfg.OUTPUT_DIR, "eval_results.json"), "w") as f:      # the figures at full precision
