@@ -115,6 +115,8 @@ SIGNATURES = {
     "ctdet_ema_advance": (_i32, [_vp, _vp, _f64, _i32, _vp]),
     "ctdet_ema_lerp_segments": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp]),
     "ctdet_ema_swap_segments": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
+    "ctdet_precise_bn_merge_segments": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp]),
+    "ctdet_precise_bn_finish_segments": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _i64, _vp]),
     "ctdet_cocoeval_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
     "ctdet_cocoeval_iou": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ctdet_cocoeval_match": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _i32,

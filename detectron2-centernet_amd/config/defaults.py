@@ -166,6 +166,11 @@ _C.TEST.AUG.FLIP = True
 _C.TEST.SOFT_NMS = CN({"ENABLED": False})
 _C.TEST.SOFT_NMS.SIGMA = 0.5
 _C.TEST.SOFT_NMS.MIN_SCORE = 0.001
+# detectron2/config/defaults.py:640-642: before every evaluation period's checkpoint and after the last iteration, recompute
+# the BatchNorm running statistics as the true mean and population variance over NUM_ITER training batches
+# (engine/precise_bn.py, hooks.PreciseBN).  With SOLVER.EMA.EVAL they are measured for the averaged weights
+_C.TEST.PRECISE_BN = CN({"ENABLED": False})
+_C.TEST.PRECISE_BN.NUM_ITER = 200
 
 _C.OUTPUT_DIR = "./output"
 _C.SEED = -1

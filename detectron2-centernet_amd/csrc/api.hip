@@ -892,6 +892,32 @@ int32_t ctdet_ema_swap_segments(float* const* live_ptrs_dev, float* ema, const i
   return launch_ema_swap_segments(live_ptrs_dev, ema, (const long*)seg_start_dev, nseg, (long)max_len, (hipStream_t)stream);
 }
 
+#define CTDET_PRECISE_BN_SEGMENTS(what)                                                                                     \
+  CTDET_CHECK(nseg >= 0 && max_len >= 0 && total >= 0, what ": nseg=%d max_len=%lld total=%lld", nseg, (long long)max_len, \
+              (long long)total);                                                                                            \
+  if (nseg == 0) return 0
+
+int32_t ctdet_precise_bn_merge_segments(const float* const* mean_ptrs_dev, const float* const* var_ptrs_dev,
+                                        const int64_t* seg_start_dev, const int64_t* rows_dev, int32_t nseg, int64_t max_len,
+                                        double* state, int64_t total, void* stream) {
+  CTDET_PRECISE_BN_SEGMENTS("precise_bn_merge_segments");
+  CTDET_CHECK(mean_ptrs_dev && var_ptrs_dev && seg_start_dev && rows_dev && state, "precise_bn_merge_segments: null pointer");
+  CTDET_CHECK(((uintptr_t)state & 7) == 0, "precise_bn_merge_segments: state must be 8-byte aligned");
+  return launch_precise_bn_merge(mean_ptrs_dev, var_ptrs_dev, (const long*)seg_start_dev, (const long*)rows_dev, nseg,
+                                 (long)max_len, state, (long)total, (hipStream_t)stream);
+}
+
+int32_t ctdet_precise_bn_finish_segments(float* const* mean_ptrs_dev, float* const* var_ptrs_dev, const int64_t* seg_start_dev,
+                                         int32_t nseg, int64_t max_len, const double* slots, int32_t world, int64_t total,
+                                         void* stream) {
+  CTDET_PRECISE_BN_SEGMENTS("precise_bn_finish_segments");
+  CTDET_CHECK(world >= 1, "precise_bn_finish_segments: world=%d", world);
+  CTDET_CHECK(mean_ptrs_dev && var_ptrs_dev && seg_start_dev && slots, "precise_bn_finish_segments: null pointer");
+  CTDET_CHECK(((uintptr_t)slots & 7) == 0, "precise_bn_finish_segments: slots must be 8-byte aligned");
+  return launch_precise_bn_finish(mean_ptrs_dev, var_ptrs_dev, (const long*)seg_start_dev, nseg, (long)max_len, slots, world,
+                                  (long)total, (hipStream_t)stream);
+}
+
 int32_t ctdet_resize_bilinear_u8(const ctdet_resize_desc* d, const int32_t* tables_dev, void* stream) {
   CTDET_CHECK(d && d->src && d->dst, "resize_bilinear_u8: null pointer");
   CTDET_CHECK(d->H >= 1 && d->W >= 1 && d->new_h >= 1 && d->new_w >= 1, "resize_bilinear_u8: %dx%d -> %dx%d", d->H, d->W,

@@ -372,6 +372,12 @@ int launch_ema_lerp_segments(const float* const* live_ptrs, float* ema, const lo
                              const float* weight, hipStream_t s);
 int launch_ema_swap_segments(float* const* live_ptrs, float* ema, const long* seg_start, int nseg, long max_len, hipStream_t s);
 
+// precise_bn.hip
+int launch_precise_bn_merge(const float* const* mean_ptrs, const float* const* var_ptrs, const long* seg_start, const long* rows,
+                            int nseg, long max_len, double* state, long total, hipStream_t s);
+int launch_precise_bn_finish(float* const* mean_ptrs, float* const* var_ptrs, const long* seg_start, int nseg, long max_len,
+                             const double* slots, int world, long total, hipStream_t s);
+
 // train_bwd.hip
 size_t chan_reduce_workspace_bytes(int C);                   // BnArgs::workspace
 int launch_bn_train_fwd(const BnArgs& a, hipStream_t s);

@@ -29,6 +29,7 @@ from ..utils import comm
 from ..utils.events import CommonMetricPrinter, JSONWriter, TensorboardXWriter, tensorboard_available
 from ..utils.logger import setup_logger
 from . import hooks
+from .precise_bn import get_bn_modules
 from .train_loop import SimpleTrainer
 
 __all__ = ["default_argument_parser", "default_setup", "DefaultPredictor", "DefaultTrainer"]
@@ -182,16 +183,23 @@ class DefaultTrainer(SimpleTrainer):
             self.iter = self.start_iter
 
     def build_hooks(self):
-        """timer, learning rate, checkpoints, evaluation, writers -- the reference's order (PreciseBN is not built).  Every
-        rank runs the same hooks, because the hooks that act flush the metric ring and a flush of several ranks is a
-        collective; only the main process writes: the checkpointer saves nothing elsewhere, and the other ranks' writer
-        hook has no writers."""
+        """timer, learning rate, (TEST.PRECISE_BN) precise BatchNorm statistics, checkpoints, evaluation, writers -- the
+        reference's order.  Every rank runs the same hooks, because the hooks that act flush the metric ring and a flush of
+        several ranks is a collective (PreciseBN's merge of the ranks' statistics is one too); only the main process writes:
+        the checkpointer saves nothing elsewhere, and the other ranks' writer hook has no writers."""
         cfg = self.cfg
         ret = [
             hooks.IterationTimer(),
             hooks.LRScheduler(self.optimizer, self.scheduler),
+            # TEST.PRECISE_BN, before the checkpointer so that the files carry the precise statistics.  With SOLVER.EMA.EVAL
+            # it runs inside the exchange: the statistics are measured for the averaged weights and go back into the EMA
+            # with them ("ema" in the checkpoint); the live running statistics stay what training made them
+            hooks.PreciseBN(cfg.TEST.EVAL_PERIOD, self.model, self.build_train_loader(cfg), cfg.TEST.PRECISE_BN.NUM_ITER,
+                            around=self.ema.swapped if self.ema is not None and cfg.SOLVER.EMA.EVAL else None)
+            if cfg.TEST.PRECISE_BN.ENABLED and get_bn_modules(self.model) else None,
             hooks.PeriodicCheckpointer(self.checkpointer, cfg.SOLVER.CHECKPOINT_PERIOD),
         ]
+        ret = [h for h in ret if h is not None]
 
         def test_and_save_results():
             # SOLVER.EMA.EVAL: the averaged weights are exchanged into the model for the evaluation and back after it

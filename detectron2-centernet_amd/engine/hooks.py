@@ -10,17 +10,21 @@ Two things differ from the reference, both because of how SimpleTrainer works he
     update kernel reads the rate from a device table the scheduler writes); a hook that stepped it again would run the
     schedule at double speed.
 
-Not built: AutogradProfiler, PreciseBN."""
+Not built: AutogradProfiler."""
+import contextlib
 import datetime
+import itertools
 import logging
 import time
 
 from ..evaluation.testing import flatten_results_dict
 from ..utils import comm
-from ..utils.events import EventWriter
+from ..utils.events import EventStorage, EventWriter
+from .precise_bn import get_bn_modules, update_bn_stats
 from .train_loop import HookBase
 
-__all__ = ["CallbackHook", "IterationTimer", "PeriodicWriter", "PeriodicCheckpointer", "LRScheduler", "EvalHook"]
+__all__ = ["CallbackHook", "IterationTimer", "PeriodicWriter", "PeriodicCheckpointer", "LRScheduler", "EvalHook",
+           "PreciseBN"]
 
 
 def _flush(trainer):
@@ -211,3 +215,51 @@ class EvalHook(HookBase):
 
     def after_train(self):
         del self._func      # likely a closure over the trainer
+
+
+class PreciseBN(HookBase):
+    """every `period` iterations (0: never during training) and after the last one: the running statistics of the model's
+    BatchNorm layers in training mode are recomputed as the true mean and population variance over `num_iter` batches of
+    `data_loader` (engine/precise_bn.py::update_bn_stats).  One iterator over the loader stays alive across runs.
+
+    around: a callable returning a context manager that every run happens inside -- DefaultTrainer passes the EMA's
+    `swapped`, so that the statistics are measured for, and stored with, the averaged weights."""
+
+    def __init__(self, period, model, data_loader, num_iter, around=None):
+        self._logger = logging.getLogger(__name__)
+        if len(get_bn_modules(model)) == 0:
+            self._logger.info("PreciseBN is disabled because model does not contain BN layers in training mode.")
+            self._disabled = True
+            return
+        self._model = model
+        self._data_loader = data_loader
+        self._num_iter = num_iter
+        self._period = period
+        self._around = around
+        self._disabled = False
+        self._data_iter = None
+
+    def after_step(self):
+        next_iter = self.trainer.iter + 1
+        is_final = next_iter == self.trainer.max_iter
+        if is_final or (self._period > 0 and next_iter % self._period == 0):
+            self.update_stats()
+
+    def update_stats(self):
+        """update the model with precise statistics; may be called by hand"""
+        if self._disabled:
+            return
+        if self._data_iter is None:
+            self._data_iter = iter(self._data_loader)
+
+        def data_loader():
+            for num_iter in itertools.count(1):
+                if num_iter % 100 == 0:
+                    self._logger.info("Running precise-BN ... {}/{} iterations.".format(num_iter, self._num_iter))
+                yield next(self._data_iter)      # this way the same iterator is reused
+
+        with EventStorage():      # events of these forwards go into a storage that is thrown away
+            self._logger.info("Running precise-BN for {} iterations...  ".format(self._num_iter)
+                              + "Note that this could produce different statistics every time.")
+            with (self._around() if self._around is not None else contextlib.nullcontext()):
+                update_bn_stats(self._model, data_loader(), self._num_iter)

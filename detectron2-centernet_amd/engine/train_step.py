@@ -18,13 +18,17 @@ from ..ops_train import (BNActFn, ConvFn, ConvTransposeFn, DCNFn, DeformConvFn, 
 
 
 _COUNTERS = []
+_STATS_WALK = None      # a list while engine/precise_bn.py collects statistics: (module, rows) of every BatchNorm, in call order
 
 
-def _count(bn):
+def _count(bn, y):
     """nn.BatchNorm2d increments num_batches_tracked per forward (torch/nn/modules/batchnorm.py); 59 one-element launches per
-    step here -- the counters are collected and advanced by ONE foreach launch at the end of the forward"""
+    step here -- the counters are collected and advanced by ONE foreach launch at the end of the forward.  y: the NHWC map
+    the layer normalises; its rows B * h * w are what a PreciseBN collection records next to the module"""
     if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
         _COUNTERS.append(bn.num_batches_tracked)
+    if _STATS_WALK is not None:
+        _STATS_WALK.append((bn, y.shape[0] * y.shape[1] * y.shape[2]))
 
 
 def _flush_counters():
@@ -35,7 +39,7 @@ def _flush_counters():
 
 def conv_bn(x, conv, bn, relu=True, res=None):
     y = ConvFn.apply(x, conv.weight, None, conv.stride[0], conv.padding[0], False, False)
-    _count(bn)
+    _count(bn, y)
     return BNActFn.apply(y, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu)
 
 
@@ -85,7 +89,7 @@ def dla_base(m, x):
 def deform_conv_v2(m, x):
     dcn, bn = m.conv, m.actf[0]
     y = DeformConvFn.apply(x, dcn.conv_offset_mask.weight, dcn.conv_offset_mask.bias, dcn.weight, dcn.bias)
-    _count(bn)
+    _count(bn, y)
     return BNActFn.apply(y, bn.weight, bn.bias, None, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True)
 
 
@@ -127,7 +131,7 @@ def _bn_conv(x, conv, relu, res=None):
     BNActFn -- or SyncBNActFn, whose statistics span every rank, when a SyncBatchNorm runs with more than one rank"""
     bn = conv.norm
     y = ConvFn.apply(x, conv.weight, None, conv.stride[0], conv.padding[0], False, False)
-    _count(bn)
+    _count(bn, y)
     fn = SyncBNActFn if isinstance(bn, torch.nn.SyncBatchNorm) and sync_bn_world()[1] > 1 else BNActFn
     return fn.apply(y, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu)
 
@@ -147,7 +151,7 @@ def _resnet_deform_conv(x, m):
     bn = conv.norm
     if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
         y = DCNFn.apply(x, om, conv.weight, None, m.mask_mode)
-        _count(bn)
+        _count(bn, y)
         fn = SyncBNActFn if isinstance(bn, torch.nn.SyncBatchNorm) and sync_bn_world()[1] > 1 else BNActFn
         return fn.apply(y, bn.weight, bn.bias, None, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True)
     scale, bias = hipnn.fold_bn(bn)
@@ -278,7 +282,7 @@ def deconv_layers(model, y):
     for i in range(0, len(mods), 3):
         up, bn = mods[i], mods[i + 1]
         y = ConvTransposeFn.apply(y, up.weight, up.stride[0], up.padding[0])
-        _count(bn)
+        _count(bn, y)
         y = BNActFn.apply(y.contiguous(), bn.weight, bn.bias, None, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True)
     return y
 
@@ -309,6 +313,41 @@ def centernet_train_forward(model, batched_inputs):
     return train_forward_tensors(model, images.nhwc, targets)
 
 
+def feature_map(model, x_nhwc):
+    """the map the heads read: the backbone in training mode and, behind ResNet / VoVNet, the deconv layers -- every
+    BatchNorm of the model"""
+    if model.backbone_type == "resnet":
+        return deconv_layers(model, resnet_features(model.backbone, x_nhwc, model._ctx))
+    if model.backbone_type == "vovnet":
+        return deconv_layers(model, vovnet_features(model.backbone, x_nhwc, model._ctx))
+    if model.backbone_type != "dla34":
+        raise NotImplementedError(f"training of the '{model.backbone_type}' backbone is not built (inference only)")
+    return dla34(model.backbone, x_nhwc)[-1]
+
+
+def stats_forward_tensors(model, x_nhwc):
+    """the training forward as far as the BatchNorm layers reach: no heads, no targets, no losses.  For PreciseBN
+    (engine/precise_bn.py), under torch.no_grad(): every layer updates its running statistics with its momentum on the way"""
+    from .. import ops_train
+    ops_train.F32_COMPUTE = ops.F16X3 if model._ctx.compute == ops.F16X3 else ops.F32
+    _COUNTERS.clear()
+    y = feature_map(model, x_nhwc)
+    _flush_counters()
+    return y
+
+
+def centernet_stats_forward(model, batched_inputs):
+    """`stats_forward_tensors` on a record batch, staged as centernet_train_forward stages it (raw records through
+    CenterNet.stage_raw_train)"""
+    if model.device.type != "cuda":
+        raise NotImplementedError("the CenterNet HIP path has no CPU implementation (MODEL.DEVICE must be cuda)")
+    if any("image_raw" in x for x in batched_inputs):
+        staged = model.stage_raw_train(batched_inputs)
+        batched_inputs = [dict(x, image=im) for x, im in zip(batched_inputs, staged)]
+    images, _ = model.preprocess_image(batched_inputs)
+    return stats_forward_tensors(model, images.nhwc)
+
+
 STEP_CHECK = int(os.environ.get("CTDET_TRAIN_CHECK", "0"))    # 1: host check after every step; 2: device-side log, no syncs
 STEP_STATS = {}
 
@@ -318,14 +357,7 @@ def train_forward_tensors(model, x_nhwc, targets):
     # how the autograd nodes contract f32 tensors (each node remembers it for its backward pass)
     ops_train.F32_COMPUTE = ops.F16X3 if model._ctx.compute == ops.F16X3 else ops.F32
     _COUNTERS.clear()        # counters collected by a forward that did not reach its flush (an exception, a partial walk) are dropped
-    if model.backbone_type == "resnet":
-        y = deconv_layers(model, resnet_features(model.backbone, x_nhwc, model._ctx))
-    elif model.backbone_type == "vovnet":
-        y = deconv_layers(model, vovnet_features(model.backbone, x_nhwc, model._ctx))
-    elif model.backbone_type != "dla34":
-        raise NotImplementedError(f"training of the '{model.backbone_type}' backbone is not built (inference only)")
-    else:
-        y = dla34(model.backbone, x_nhwc)[-1]
+    y = feature_map(model, x_nhwc)
     z = heads(model, y)
     _flush_counters()
     C = model.num_classes

@@ -1864,3 +1864,73 @@ def ema_swap_segments_(live_ptrs, ema, seg_start, max_len):
     rc = _lib.lib().ctdet_ema_swap_segments(_ptr(live_ptrs), _ptr(ema), _ptr(seg_start), live_ptrs.numel(), int(max_len),
                                             _stream())
     _lib.check(rc, "ctdet_ema_swap_segments")
+
+
+def _precise_bn_tables(mean_ptrs, var_ptrs, seg_start, buf, lead):
+    """the checks the two PreciseBN wrappers share; `buf` is the f64 state / slot buffer whose leading dimensions are `lead`"""
+    for name, t in (("mean_ptrs", mean_ptrs), ("var_ptrs", var_ptrs), ("seg_start", seg_start)):
+        if t.dtype != torch.int64:
+            raise TypeError(f"precise_bn: {name} must be int64, got {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"precise_bn: {name} must be a contiguous vector")
+    if buf.dtype != torch.float64:
+        raise TypeError(f"precise_bn: the state must be float64, got {buf.dtype}")
+    nseg = mean_ptrs.numel()
+    if var_ptrs.numel() != nseg or seg_start.numel() != nseg + 1:
+        raise ValueError(f"precise_bn: {nseg} mean pointers go with {nseg} variance pointers and {nseg + 1} offsets, got "
+                         f"{var_ptrs.numel()} and {seg_start.numel()}")
+    if buf.dim() != len(lead) + 1 or tuple(buf.shape[:-1]) != tuple(lead) or not buf.is_contiguous():
+        raise ValueError(f"precise_bn: the state must be a contiguous [{', '.join(map(str, lead))}, total] tensor, got "
+                         f"{tuple(buf.shape)}")
+    _require_cuda(mean_ptrs, var_ptrs, seg_start, buf)
+    if len({t.device for t in (mean_ptrs, var_ptrs, seg_start, buf)}) != 1:
+        raise ValueError("precise_bn: the tables and the state must live on one device")
+    return nseg, buf.shape[-1]
+
+
+def precise_bn_rows(rows):
+    """the per-segment row counts of one batch as a CPU int64 vector; a count below 2 raises ValueError naming its index (a
+    batch statistic over one row has no unbiased variance: torch refuses a training-mode BatchNorm over one value per channel
+    for the same reason)"""
+    if not isinstance(rows, torch.Tensor):
+        rows = torch.tensor([r.__index__() for r in rows], dtype=torch.int64)      # integers only: a float has no __index__
+    rows = rows.cpu()
+    if rows.dtype != torch.int64:
+        raise TypeError(f"precise_bn: rows must be int64, got {rows.dtype}")
+    rows = rows.reshape(-1)
+    bad = (rows < 2).nonzero()
+    if bad.numel():
+        i = int(bad[0])
+        raise ValueError(f"precise_bn: rows[{i}] = {int(rows[i])}: every segment needs at least 2 rows per batch")
+    return rows
+
+
+def precise_bn_merge_(mean_ptrs, var_ptrs, seg_start, rows, max_len, state, rows_dev=None):
+    """folds one batch into the f64 state [3, total] = (n, mean, M2) per channel (see ctdet_precise_bn_merge_segments): segment
+    s reads its batch mean from the f32 data at address mean_ptrs[s], its unbiased batch variance at var_ptrs[s] and its row
+    count from rows[s].  `mean_ptrs` / `var_ptrs` / `seg_start` are device int64 tables as for ema_lerp_segments_.  `rows`: the
+    host's counts (a sequence or CPU int64 tensor), checked here; `rows_dev`: their device copy where the caller keeps one
+    (None: uploaded here)."""
+    rows = precise_bn_rows(rows)
+    if rows.numel() != mean_ptrs.numel():
+        raise ValueError(f"precise_bn_merge_: {mean_ptrs.numel()} segments, {rows.numel()} row counts")
+    nseg, total = _precise_bn_tables(mean_ptrs, var_ptrs, seg_start, state, (3,))
+    if rows_dev is None:
+        rows_dev = rows.to(state.device)
+    if rows_dev.dtype != torch.int64 or rows_dev.numel() != nseg or not rows_dev.is_contiguous() or rows_dev.device != state.device:
+        raise ValueError("precise_bn_merge_: rows_dev must be the contiguous int64 device copy of rows")
+    rc = _lib.lib().ctdet_precise_bn_merge_segments(_ptr(mean_ptrs), _ptr(var_ptrs), _ptr(seg_start), _ptr(rows_dev), nseg,
+                                                    int(max_len), _ptr(state), total, _stream())
+    _lib.check(rc, "ctdet_precise_bn_merge_segments")
+
+
+def precise_bn_finish_(mean_ptrs, var_ptrs, seg_start, max_len, slots):
+    """combines the rank slots of the f64 buffer [world, 3, total] in rank order and writes (float)mean to the f32 data at
+    mean_ptrs[s], the population variance (float)(M2 / n) at var_ptrs[s]; channels without rows keep their values (see
+    ctdet_precise_bn_finish_segments).  The written tensors are raw addresses: the caller bumps their versions."""
+    if slots.dim() != 3:
+        raise ValueError(f"precise_bn_finish_: slots must be [world, 3, total], got {tuple(slots.shape)}")
+    nseg, total = _precise_bn_tables(mean_ptrs, var_ptrs, seg_start, slots, (slots.shape[0], 3))
+    rc = _lib.lib().ctdet_precise_bn_finish_segments(_ptr(mean_ptrs), _ptr(var_ptrs), _ptr(seg_start), nseg, int(max_len),
+                                                     _ptr(slots), slots.shape[0], total, _stream())
+    _lib.check(rc, "ctdet_precise_bn_finish_segments")

@@ -494,6 +494,27 @@ int32_t ctdet_ema_lerp_segments(const float* const* live_ptrs_dev, float* ema, c
 int32_t ctdet_ema_swap_segments(float* const* live_ptrs_dev, float* ema, const int64_t* seg_start_dev, int32_t nseg,
                                 int64_t max_len, void* stream);
 
+/* PreciseBN (TEST.PRECISE_BN): population BatchNorm statistics over many batches.  state is f64 [3][total]: per channel the
+ * row count n, the mean mu and the sum of squared deviations M2; all zeros when fresh.  The tables are the EMA's kind:
+ * mean_ptrs_dev / var_ptrs_dev device tables of nseg device pointers (a layer's running_mean / running_var), seg_start_dev a
+ * device i64 table of nseg + 1 ascending offsets into the channels of `state` (a segment may be empty), max_len an upper
+ * bound of the segment lengths that only sizes the grid.  Merge reads running_mean as the batch mean m and running_var as
+ * the unbiased batch variance u -- what ctdet_bn_train_fwd / ctdet_bn_sync_fwd leave at momentum 1 -- and rows_dev[s] (i64)
+ * as the batch's row count M of segment s, and folds them in by Chan's step in f64:
+ *   M2_b = u (M - 1);  n' = n + M;  d = m - mu;  mu += d M / n';  M2 += M2_b + d^2 n M / n';  n = n'
+ * (n == 0: mu = m and M2 = M2_b exactly).  The live buffers are only read.  One thread per channel, no atomics.
+ * nseg == 0 is a no-op; nseg < 0, max_len < 0, total < 0, or a null pointer with nseg > 0: -22.  state: 8-byte aligned. */
+int32_t ctdet_precise_bn_merge_segments(const float* const* mean_ptrs_dev, const float* const* var_ptrs_dev,
+                                        const int64_t* seg_start_dev, const int64_t* rows_dev, int32_t nseg, int64_t max_len,
+                                        double* state, int64_t total, void* stream);
+
+/* Combines the rank slots of slots[world][3][total] (f64, each laid out as `state`) in rank order by the same step -- a slot
+ * with n == 0 contributes nothing -- and writes running_mean = (float)mu, running_var = (float)(M2 / n): the population
+ * (biased) variance.  A channel whose total n is 0 is left untouched.  Same refusals; world < 1: -22. */
+int32_t ctdet_precise_bn_finish_segments(float* const* mean_ptrs_dev, float* const* var_ptrs_dev, const int64_t* seg_start_dev,
+                                         int32_t nseg, int64_t max_len, const double* slots, int32_t world, int64_t total,
+                                         void* stream);
+
 /* ---- training-side entry points (f32 statistics and weight gradients; activations and activation gradients f16 --
  * the throughput mode -- or f32 -- the reference's precision -- selected by `dtype` (ctdet_dtype) / the descriptor's
  * compute_dtype).  Input gradients of plain convs are ctdet_conv2d_fwd calls with transposed/flipped weights (in_dil
