@@ -185,6 +185,34 @@ def metrics_lib():
     return _metrics_lib
 
 
+# libctdet_voceval.so (include/ctdet_voceval.h): the Pascal VOC scorer, loaded when VOCevalHIP first scores
+VOCEVAL_LIB_PATH = os.path.join(_HERE, "lib", "libctdet_voceval.so")
+VOCEVAL_SIGNATURES = {
+    "ctdet_voceval_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "ctdet_voceval_match": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp]),
+    "ctdet_voceval_ap": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+_voceval_lib = None
+
+
+def voceval_lib():
+    """Loads libctdet_voceval.so once (after libctdet_hip.so, which it links against); raises if it has not been built"""
+    global _voceval_lib
+    if _voceval_lib is None:
+        lib()
+        if not os.path.exists(VOCEVAL_LIB_PATH):
+            raise RuntimeError(f"{VOCEVAL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C detectron2-centernet_amd/csrc`). There is no CPU fallback.")
+        l = C.CDLL(VOCEVAL_LIB_PATH)
+        for name, (res, args) in VOCEVAL_SIGNATURES.items():
+            fn = getattr(l, name)
+            fn.restype = res
+            fn.argtypes = args
+        _voceval_lib = l
+    return _voceval_lib
+
+
 def check(rc, what):
     if rc != 0:
         msg = lib().ctdet_last_error()

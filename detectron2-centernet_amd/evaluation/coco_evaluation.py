@@ -62,6 +62,22 @@ def load_coco_ground_truth(dataset):
     return gt, [c["name"] for c in cats], "annotations" in dataset
 
 
+def gather_detections(local, distributed=True):
+    """every rank's (image ids, counts, boxes, scores, classes) on the main process, concatenated in rank order; None on
+    the other ranks.  A single process keeps its device tensors; gathered arrays travel as numpy."""
+    if not distributed or comm.get_world_size() == 1:
+        return local
+    comm.synchronize()
+    mine = tuple(local[:2]) + tuple(None if t is None else t.cpu().numpy() for t in local[2:])
+    shards = comm.gather(mine, dst=0)
+    if not comm.is_main_process():
+        return None
+    shards = [s for s in shards if len(s[0])]
+    ids, counts = [i for s in shards for i in s[0]], [c for s in shards for c in s[1]]
+    arrays = [np.concatenate([s[j] for s in shards]) if shards else None for j in (2, 3, 4)]
+    return (ids, counts) + tuple(arrays)
+
+
 class COCOEvaluator(DatasetEvaluator):
     def __init__(self, dataset_name, cfg=None, distributed=True, output_dir=None, *, tasks=None):
         self._logger = logging.getLogger(__name__)
@@ -125,19 +141,7 @@ class COCOEvaluator(DatasetEvaluator):
                 torch.cat(self._classes).to(torch.int32))
 
     def _gather(self, local):
-        """every rank's (image ids, counts, boxes, scores, classes) on the main process, concatenated in rank order; None on
-        the other ranks.  A single process keeps its device tensors; gathered arrays travel as numpy."""
-        if not self._distributed or comm.get_world_size() == 1:
-            return local
-        comm.synchronize()
-        mine = tuple(local[:2]) + tuple(None if t is None else t.cpu().numpy() for t in local[2:])
-        shards = comm.gather(mine, dst=0)
-        if not comm.is_main_process():
-            return None
-        shards = [s for s in shards if len(s[0])]
-        ids, counts = [i for s in shards for i in s[0]], [c for s in shards for c in s[1]]
-        arrays = [np.concatenate([s[j] for s in shards]) if shards else None for j in (2, 3, 4)]
-        return (ids, counts) + tuple(arrays)
+        return gather_detections(local, self._distributed)
 
     def evaluate(self):
         merged = self._gather(self._local())

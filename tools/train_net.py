@@ -6,7 +6,9 @@
 Trains to OUTPUT_DIR (checkpoints, metrics.json, log.txt, config.yaml), or with --eval-only scores MODEL.WEIGHTS (with
 --resume: the last checkpoint of OUTPUT_DIR) on DATASETS.TEST.  With TEST.AUG.ENABLED the model is tested through
 CenterNetWithTTA.  With SOLVER.EMA.ENABLED and SOLVER.EMA.EVAL, --eval-only scores the averaged weights a checkpoint carries
-under "ema" (a checkpoint without them: its "model", with a warning).  The configs' "bulb_train" / "bulb_val" are not distributed: with CTDET_SYNTHETIC_SET="train images,test images,size" in the
+under "ema" (a checkpoint without them: its "model", with a warning).  The Pascal VOC splits ("voc_2007_test", ...) are
+registered from $DETECTRON2_DATASETS (default "datasets") where VOC2007 / VOC2012 exist there, and scored by
+PascalVOCDetectionEvaluator.  The configs' "bulb_train" / "bulb_val" are not distributed: with CTDET_SYNTHETIC_SET="train images,test images,size" in the
 environment (e.g. "64,16,512") a dataset the config names but nothing has registered is replaced by the synthetic set, written
 once as PNG files under OUTPUT_DIR/synthetic; without it an unregistered name is an error."""
 import json
@@ -21,6 +23,7 @@ if ROOT not in sys.path:
 import detectron2_centernet_amd  # noqa: E402,F401
 from detectron2_centernet_amd.checkpoint import DetectionCheckpointer  # noqa: E402
 from detectron2_centernet_amd.config import get_cfg  # noqa: E402
+from detectron2_centernet_amd.data import register_all_pascal_voc  # noqa: E402
 from detectron2_centernet_amd.data.catalog import DatasetCatalog, register_synthetic_files  # noqa: E402
 from detectron2_centernet_amd.engine import DefaultTrainer, default_argument_parser, default_setup, launch  # noqa: E402
 from detectron2_centernet_amd.evaluation import verify_results  # noqa: E402
@@ -76,6 +79,8 @@ def setup(args):
     cfg.merge_from_list(args.opts)
     cfg.freeze()
     default_setup(cfg, args)
+    # the Pascal VOC splits (voc_2007_*, voc_2012_*) whose VOC2007 / VOC2012 directory exists under the datasets root
+    register_all_pascal_voc(os.getenv("DETECTRON2_DATASETS", "datasets"))
     register_missing_datasets(cfg)
     return cfg
 
