@@ -138,26 +138,34 @@ SIGNATURES = {
     "ctdet_comm_destroy": (_i32, [_vp]),
 }
 
-_lib = None
+_loaded = {}   # id(signature table) -> CDLL: one library per table, loaded once
 
 
-def lib():
-    """Loads the shared library once; raises if it has not been built (no fallback)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
+def _load(path, signatures, after_main):
+    """CDLL of `path` with every signature bound, loaded once; raises if it has not been built (no fallback).  after_main:
+    a library that links against libctdet_hip.so, which is loaded first; the main library itself takes CTDET_TUNE_FLAGS"""
+    l = _loaded.get(id(signatures))
+    if l is None:
+        if after_main:
+            lib()
+        if not os.path.exists(path):
             raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C detectron2-centernet_amd/csrc`). There is no CPU fallback for the HIP path.")
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
+                f"detectron2-centernet_amd/csrc`). There is no CPU fallback{'' if after_main else ' for the HIP path'}.")
+        l = C.CDLL(path)
+        for name, (res, args) in signatures.items():
             fn = getattr(l, name)  # AttributeError if the .so is stale
             fn.restype = res
             fn.argtypes = args
-        _lib = l
-        if os.environ.get("CTDET_TUNE_FLAGS"):      # kernel-selection bits for a whole process (A/B runs of bench.py's ranks)
+        _loaded[id(signatures)] = l
+        if not after_main and os.environ.get("CTDET_TUNE_FLAGS"):      # kernel-selection bits for a whole process (A/B runs of bench.py's ranks)
             l.ctdet_set_tuning_flags(int(os.environ["CTDET_TUNE_FLAGS"], 0))
-    return _lib
+    return l
+
+
+def lib():
+    """Loads libctdet_hip.so once; raises if it has not been built (no fallback)."""
+    return _load(LIB_PATH, SIGNATURES, False)
 
 
 # libctdet_metrics.so (include/ctdet_metrics.h): the training loop's metric push, loaded when a metric ring is first built
@@ -165,24 +173,11 @@ METRICS_LIB_PATH = os.path.join(_HERE, "lib", "libctdet_metrics.so")
 METRICS_SIGNATURES = {
     "ctdet_metric_push": (_i32, [_vp, _i32, _f32, _vp, _i32, _i32, _vp, _i64, _vp]),
 }
-_metrics_lib = None
 
 
 def metrics_lib():
     """Loads libctdet_metrics.so once (after libctdet_hip.so, which it links against); raises if it has not been built"""
-    global _metrics_lib
-    if _metrics_lib is None:
-        lib()
-        if not os.path.exists(METRICS_LIB_PATH):
-            raise RuntimeError(f"{METRICS_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C detectron2-centernet_amd/csrc`). There is no CPU fallback.")
-        l = C.CDLL(METRICS_LIB_PATH)
-        for name, (res, args) in METRICS_SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        _metrics_lib = l
-    return _metrics_lib
+    return _load(METRICS_LIB_PATH, METRICS_SIGNATURES, True)
 
 
 # libctdet_voceval.so (include/ctdet_voceval.h): the Pascal VOC scorer, loaded when VOCevalHIP first scores
@@ -193,24 +188,11 @@ VOCEVAL_SIGNATURES = {
                                    _vp, _vp]),
     "ctdet_voceval_ap": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
-_voceval_lib = None
 
 
 def voceval_lib():
     """Loads libctdet_voceval.so once (after libctdet_hip.so, which it links against); raises if it has not been built"""
-    global _voceval_lib
-    if _voceval_lib is None:
-        lib()
-        if not os.path.exists(VOCEVAL_LIB_PATH):
-            raise RuntimeError(f"{VOCEVAL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C detectron2-centernet_amd/csrc`). There is no CPU fallback.")
-        l = C.CDLL(VOCEVAL_LIB_PATH)
-        for name, (res, args) in VOCEVAL_SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        _voceval_lib = l
-    return _voceval_lib
+    return _load(VOCEVAL_LIB_PATH, VOCEVAL_SIGNATURES, True)
 
 
 def check(rc, what):

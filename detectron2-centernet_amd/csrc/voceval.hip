@@ -22,12 +22,15 @@
 //     give the envelope at every true positive -- the only positions where recall changes -- and the area sum is taken by one
 //     thread in position order.
 //   * built as a library of its own, libctdet_voceval.so (csrc/Makefile), which the evaluator loads when it first scores: the
-//     hot-path library's binary is not touched by it.  Error text and kernel labels go through the plumbing of libctdet_hip.so
+//     hot-path library does not grow by it.  Error text and kernel labels go through the plumbing of libctdet_hip.so
 //     (ctdet_set_error / ctdet_last_error, CTDET_KERNEL), against which this library links.
 //   * the only atomics are integer (non-difficult ground truths per class, the status bits): two runs are bit-identical.
-#include "common.h"
+//   * eval_common.h holds the scaffolding a box-AP scorer needs whatever its rule: the score key, the lower bound that cuts
+//     the sorted keys into segments, the packed workgroup scan, the in-LDS suffix maximum, the rocprim sort call, the
+//     workspace rounding and the common range checks.  The matcher and the AP passes are this scorer's own.  cocoeval.hip
+//     still carries its own copies of those pieces: it is part of the hot-path library, whose binary stays as it is.
+#include "eval_common.h"
 #include "../../include/ctdet_voceval.h"
-#include <rocprim/device/device_radix_sort.hpp>
 #include <float.h>
 #include <limits.h>
 
@@ -57,9 +60,7 @@ __device__ __forceinline__ int ve_invalid(const VeMatchArgs& a, long i) {
 }
 
 __global__ void __launch_bounds__(256) ve_clear_kernel(int* __restrict__ npos, int n, int* __restrict__ status) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) npos[i] = 0;
-  if (i == 0) status[0] = 0;
+  eval_clear(npos, n, status);
 }
 
 // order-S keys: ascending key = descending rint(score * 1000); equal quantised scores (-0 == +0 included) give equal keys
@@ -68,10 +69,7 @@ __global__ void __launch_bounds__(256) ve_key_score_kernel(VeMatchArgs a) {
   if (i >= a.N) return;
   const int st = ve_invalid(a, i);
   if (st) atomicOr(a.status, st);
-  const double r = rint((double)a.scores[i] * 1000.0) + 0.0;
-  uint64_t u = (uint64_t)__double_as_longlong(r);
-  u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-  a.keys64[i] = ~u;
+  a.keys64[i] = eval_score_key(rint((double)a.scores[i] * 1000.0));
   a.vals[i] = (uint32_t)i;
 }
 
@@ -91,13 +89,7 @@ __global__ void __launch_bounds__(256) ve_key_group_kernel(VeMatchArgs a, int by
 __global__ void __launch_bounds__(256) ve_offsets_kernel(const uint32_t* __restrict__ keys, long N, int n, int* __restrict__ off) {
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
   if (c > n) return;
-  long lo = 0, hi = N;
-  while (lo < hi) {
-    const long mid = (lo + hi) >> 1;
-    if ((long)keys[mid] < c) lo = mid + 1;
-    else hi = mid;
-  }
-  off[c] = (int)lo;
+  off[c] = eval_lower_bound(keys, N, c, [](uint32_t k) { return (long)k; });
 }
 
 __global__ void __launch_bounds__(64) ve_match_kernel(VeMatchArgs a) {
@@ -169,27 +161,6 @@ struct VeApArgs {
   double* ap07; double* ap12; double* rec; double* prec;
 };
 
-// inclusive scan over the workgroup of two counters <= VE_NT packed into one word (16 bits each); `tot` = the sum
-__device__ __forceinline__ uint32_t ve_scan2(uint32_t v, uint32_t* wsum, uint32_t& tot) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  __syncthreads();     // the previous round's readers of wsum are done
-  if (lane == 63) wsum[wv] = v;
-  __syncthreads();
-  tot = 0;
-#pragma unroll
-  for (int w = 0; w < VE_NT / 64; ++w) {
-    const uint32_t s = wsum[w];
-    tot += s;
-    if (w < wv) v += s;
-  }
-  return v;
-}
-
 __global__ void __launch_bounds__(VE_NT) ve_ap_kernel(VeApArgs a) {
   __shared__ double sm[VE_NT];
   __shared__ double pmax[VE_NT / 64][VE_POINTS];
@@ -214,7 +185,7 @@ __global__ void __launch_bounds__(VE_NT) ve_ap_kernel(VeApArgs a) {
       tp = f == 1; fp = f == 2;
     }
     uint32_t tot;
-    const uint32_t sc = ve_scan2(tp | (fp << 16), wsum, tot);
+    const uint32_t sc = eval_scan_packed<VE_NT>(tp | (fp << 16), wsum, tot);     // two 16-bit counters
     double prec = 0.0;
     if (j < s1) {
       const int itp = ctp + (int)(sc & 0xFFFFu), ifp = cfp + (int)(sc >> 16);
@@ -276,16 +247,9 @@ __global__ void __launch_bounds__(VE_NT) ve_ap_kernel(VeApArgs a) {
       tp = f == 1; fp = f == 2;
     }
     uint32_t tot;
-    const uint32_t sc = ve_scan2(tp | (fp << 16), wsum, tot);
+    const uint32_t sc = eval_scan_packed<VE_NT>(tp | (fp << 16), wsum, tot);     // two 16-bit counters
     const int itp = ctp + (int)(sc & 0xFFFFu), ifp = cfp + (int)(sc >> 16);
-    sm[tid] = j < s1 ? (double)itp / fmax((double)(itp + ifp), DBL_EPSILON) : 0.0;
-    __syncthreads();
-    for (int o = 1; o < VE_NT; o <<= 1) {
-      const double v = tid + o < VE_NT ? sm[tid + o] : 0.0;
-      __syncthreads();
-      sm[tid] = fmax(sm[tid], v);
-      __syncthreads();
-    }
+    eval_suffix_max<VE_NT>(sm, j < s1 ? (double)itp / fmax((double)(itp + ifp), DBL_EPSILON) : 0.0, 0.0);
     const double env = fmax(sm[tid], cmax[c]);
     __syncthreads();
     // recall changes exactly at a true positive: (tp / npos - (tp - 1) / npos) * envelope; 0 elsewhere, which adds nothing
@@ -301,50 +265,29 @@ __global__ void __launch_bounds__(VE_NT) ve_ap_kernel(VeApArgs a) {
 
 // ---- workspace: chunk values f64 [T * (N / 256 + K + 1)] (first: the AP call finds them without knowing NG or I), score keys
 // u64 [N] x 2, values / order S u32 [N] x 2, group keys u32 [N] x 2, cell order u32 [N], cell offsets i32 [I*K + 2], taken
-// words u32 [NG], then the sort's own temporary storage (bounded here, checked against rocprim's answer at the call)
-static inline size_t ve_up(size_t v) { return (v + 255) & ~(size_t)255; }
+// words u32 [NG], then the sort block
 struct VeWs { size_t chunk, keys64, keys64_sorted, vals, order_s, keys32, keys32_sorted, cell_order, off, taken, sort, total; };
 static long ve_chunk_stride(long N, long K) { return N / VE_NT + K + 1; }
 static VeWs ve_layout(long N, long NG, long I, long K, long T) {
   VeWs w;
   size_t p = 0;
-  w.chunk = p; p += ve_up((size_t)T * (size_t)ve_chunk_stride(N, K) * 8);
-  w.keys64 = p; p += ve_up((size_t)N * 8);
-  w.keys64_sorted = p; p += ve_up((size_t)N * 8);
-  w.vals = p; p += ve_up((size_t)N * 4);
-  w.order_s = p; p += ve_up((size_t)N * 4);
-  w.keys32 = p; p += ve_up((size_t)N * 4);
-  w.keys32_sorted = p; p += ve_up((size_t)N * 4);
-  w.cell_order = p; p += ve_up((size_t)N * 4);
-  w.off = p; p += ve_up((size_t)(I * K + 2) * 4);
-  w.taken = p; p += ve_up((size_t)NG * 4);
-  w.sort = p; p += ve_up((size_t)N * 16 + ((size_t)16 << 20));
+  w.chunk = p; p += eval_up((size_t)T * (size_t)ve_chunk_stride(N, K) * 8);
+  w.keys64 = p; p += eval_up((size_t)N * 8);
+  w.keys64_sorted = p; p += eval_up((size_t)N * 8);
+  w.vals = p; p += eval_up((size_t)N * 4);
+  w.order_s = p; p += eval_up((size_t)N * 4);
+  w.keys32 = p; p += eval_up((size_t)N * 4);
+  w.keys32_sorted = p; p += eval_up((size_t)N * 4);
+  w.cell_order = p; p += eval_up((size_t)N * 4);
+  w.off = p; p += eval_up((size_t)(I * K + 2) * 4);
+  w.taken = p; p += eval_up((size_t)NG * 4);
+  w.sort = p; p += eval_sort_bytes(N);
   w.total = p;
   return w;
 }
 
-static int ve_bits(unsigned long v) { int b = 1; while ((v >> b) && b < 32) ++b; return b; }
-
-template <typename Key>
-static int ve_sort(const VeWs& w, char* ws, const Key* kin, Key* kout, const uint32_t* vin, uint32_t* vout, long N, int bits,
-                   hipStream_t s) {
-  size_t need = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, (size_t)N, 0u, (unsigned)bits, s);
-  CTDET_CHECK(e == hipSuccess, "voceval: sort size query failed: %s", hipGetErrorString(e));
-  const size_t have = w.total - w.sort;
-  CTDET_CHECK(need <= have, "voceval: the sort needs %zu bytes of temporary storage, the workspace formula provides %zu", need,
-              have);
-  e = rocprim::radix_sort_pairs(ws + w.sort, need, kin, kout, vin, vout, (size_t)N, 0u, (unsigned)bits, s);
-  CTDET_CHECK(e == hipSuccess, "voceval: sort failed: %s", hipGetErrorString(e));
-  return 0;
-}
-
 static int ve_check_dims(const char* what, int64_t N, int64_t NG, int32_t I, int32_t K, int32_t T) {
-  CTDET_CHECK(N >= 0 && N < (1LL << 31) - 1024, "%s: N=%lld out of range", what, (long long)N);
-  CTDET_CHECK(NG >= 0 && NG < (1LL << 31), "%s: %lld ground truths out of range", what, (long long)NG);
-  // one 64-thread workgroup per cell: a grid holds fewer than 2^32 threads
-  CTDET_CHECK(I >= 1 && K >= 1 && (int64_t)I * K < (1LL << 26), "%s: I=%d images x K=%d classes out of range (I*K < 2^26)", what,
-              I, K);
+  if (const int rc = eval_check_dims(what, "classes", N, NG, I, K)) return rc;
   CTDET_CHECK(T >= 1 && T <= 32, "%s: T=%d thresholds (1..32: one bit of a ground truth's taken word each)", what, T);
   return 0;
 }
@@ -376,7 +319,7 @@ int32_t ctdet_voceval_match(const float* boxes, const float* scores, const int32
   CTDET_CHECK(N <= 0 || flags, "voceval_match: null pointer flags");
   const int rc = ve_check_dims("voceval_match", N, NG, I, K, T);
   if (rc) return rc;
-  CTDET_CHECK(((uintptr_t)workspace & 255) == 0, "voceval_match: workspace must be 256-byte aligned");
+  EVAL_CHECK_WORKSPACE("voceval_match", workspace);
   CTDET_KERNEL("ve_match_kernel<wave per cell,%d thresholds>", T);
   hipStream_t s = (hipStream_t)stream;
   const VeWs w = ve_layout(N, NG, I, K, T);
@@ -390,21 +333,23 @@ int32_t ctdet_voceval_match(const float* boxes, const float* scores, const int32
   const uint32_t* k32s = (const uint32_t*)(ws + w.keys32_sorted);
   const int ncell = I * K;
   const unsigned nb = (unsigned)((N + 255) / 256);
+  const auto sort = [&](auto* kin, auto* kout, const uint32_t* vin, uint32_t* vout, int bits) {     // tmp: the sort block
+    return eval_sort("voceval", kin, kout, vin, vout, N, bits, ws + w.sort, w.total - w.sort, s);
+  };
   hipLaunchKernelGGL(ve_clear_kernel, dim3((K + 255) / 256), dim3(256), 0, s, npos, K, status);
   if (N) {
     hipLaunchKernelGGL(ve_key_score_kernel, dim3(nb), dim3(256), 0, s, a);
-    int src = ve_sort<uint64_t>(w, ws, a.keys64, (uint64_t*)(ws + w.keys64_sorted), a.vals, (uint32_t*)(ws + w.order_s), N, 64, s);
+    int src = sort(a.keys64, (uint64_t*)(ws + w.keys64_sorted), a.vals, (uint32_t*)(ws + w.order_s), 64);
     if (src) return src;
     hipLaunchKernelGGL(ve_key_group_kernel, dim3(nb), dim3(256), 0, s, a, 0);
-    src = ve_sort<uint32_t>(w, ws, a.keys32, (uint32_t*)(ws + w.keys32_sorted), a.order_s, (uint32_t*)order, N,
-                            ve_bits((unsigned long)K), s);
+    src = sort(a.keys32, (uint32_t*)(ws + w.keys32_sorted), a.order_s, (uint32_t*)order, eval_bits((unsigned long)K));
     if (src) return src;
   }
   hipLaunchKernelGGL(ve_offsets_kernel, dim3((K + 1 + 255) / 256), dim3(256), 0, s, k32s, (long)N, K, cls_off);
   if (N) {
     hipLaunchKernelGGL(ve_key_group_kernel, dim3(nb), dim3(256), 0, s, a, 1);
-    const int src = ve_sort<uint32_t>(w, ws, a.keys32, (uint32_t*)(ws + w.keys32_sorted), a.order_s,
-                                      (uint32_t*)(ws + w.cell_order), N, ve_bits((unsigned long)ncell), s);
+    const int src = sort(a.keys32, (uint32_t*)(ws + w.keys32_sorted), a.order_s, (uint32_t*)(ws + w.cell_order),
+                         eval_bits((unsigned long)ncell));
     if (src) return src;
   }
   hipLaunchKernelGGL(ve_offsets_kernel, dim3((ncell + 1 + 255) / 256), dim3(256), 0, s, k32s, (long)N, ncell, a.dt_off);
@@ -427,7 +372,7 @@ int32_t ctdet_voceval_ap(const int32_t* order, const int32_t* cls_off, const uin
   const int rc = ve_check_dims("voceval_ap", N, 0, 1, K, T);
   if (rc) return rc;
   CTDET_CHECK((int64_t)K * T < (1LL << 31), "voceval_ap: K*T too large");
-  CTDET_CHECK(((uintptr_t)workspace & 255) == 0, "voceval_ap: workspace must be 256-byte aligned");
+  EVAL_CHECK_WORKSPACE("voceval_ap", workspace);
   CTDET_KERNEL("ve_ap_kernel<workgroup per (k,t),two passes>");
   // the chunk values lead the layout and their size depends on N, K and T alone: the workspace of the match call serves
   VeApArgs a;

@@ -17,9 +17,9 @@ import torch
 from ..data.catalog import DatasetCatalog, MetadataCatalog
 from ..structures import BoxMode
 from ..utils import comm
+from .box_scoring import BoxEvaluator
 from .coco_results import coco_records
 from .cocoeval import COCOevalHIP, derive_coco_results, prepare_ground_truth
-from .evaluator import DatasetEvaluator
 
 
 def convert_to_coco_dict(dataset_name):
@@ -78,7 +78,7 @@ def gather_detections(local, distributed=True):
     return (ids, counts) + tuple(arrays)
 
 
-class COCOEvaluator(DatasetEvaluator):
+class COCOEvaluator(BoxEvaluator):
     def __init__(self, dataset_name, cfg=None, distributed=True, output_dir=None, *, tasks=None):
         self._logger = logging.getLogger(__name__)
         tasks = tuple(tasks) if tasks is not None else self._tasks_from_config(cfg)
@@ -113,32 +113,10 @@ class COCOEvaluator(DatasetEvaluator):
             tasks = tasks + ("keypoints",)
         return tasks
 
-    def reset(self):
-        self._image_ids, self._counts, self._boxes, self._scores, self._classes = [], [], [], [], []
-
-    def process(self, inputs, outputs):
-        for inp, out in zip(inputs, outputs):
-            if "proposals" in out:
-                raise NotImplementedError("COCOEvaluator: box proposals ('proposals' outputs) are not scored")
-            if "instances" not in out:
-                continue
-            inst = out["instances"]
-            boxes, scores, classes = inst.pred_boxes.tensor, inst.scores, inst.pred_classes
-            if not (boxes.is_cuda and scores.is_cuda and classes.is_cuda):
-                raise NotImplementedError("COCOEvaluator: the Instances must be on the GPU; scoring runs in HIP kernels and "
-                                          "there is no CPU fallback")
-            self._image_ids.append(inp["image_id"])
-            self._counts.append(int(scores.shape[0]))
-            self._boxes.append(boxes.detach())
-            self._scores.append(scores.detach())
-            self._classes.append(classes.detach())
-
-    def _local(self):
-        """this rank's detections, concatenated on the device: (image ids, counts, boxes, scores, classes)"""
-        if not self._boxes:
-            return [], [], None, None, None
-        return (self._image_ids, self._counts, torch.cat(self._boxes).float().reshape(-1, 4), torch.cat(self._scores).float(),
-                torch.cat(self._classes).to(torch.int32))
+    def _instances(self, out):
+        if "proposals" in out:
+            raise NotImplementedError("COCOEvaluator: box proposals ('proposals' outputs) are not scored")
+        return out.get("instances")
 
     def _gather(self, local):
         return gather_detections(local, self._distributed)
@@ -151,13 +129,7 @@ class COCOEvaluator(DatasetEvaluator):
         if len(ids) == 0:
             self._logger.warning("[COCOEvaluator] Did not receive valid predictions.")
             return {}
-        img_index = {v: i for i, v in enumerate(self._gt["image_ids"])}
-        unknown = [i for i in ids if i not in img_index]
-        if unknown and self._do_evaluation:
-            raise ValueError(f"COCOEvaluator: predictions for image ids that are not in the ground-truth set: {unknown[:5]}")
-        if not isinstance(boxes, torch.Tensor):
-            dev = torch.device("cuda", torch.cuda.current_device())
-            boxes, scores, classes = (torch.as_tensor(a).to(dev) for a in (boxes, scores, classes))
+        boxes, scores, classes = self._checked(ids, boxes, scores, classes, "the ground-truth set", refuse=self._do_evaluation)
         self._results = OrderedDict()
         self._eval_predictions(ids, counts, boxes, scores, classes)
         return copy.deepcopy(self._results)
@@ -174,12 +146,10 @@ class COCOEvaluator(DatasetEvaluator):
         if not self._do_evaluation:
             self._logger.info("Annotations are not available for evaluation.")
             return
-        img_index = {v: i for i, v in enumerate(self._gt["image_ids"])}
         self._logger.info("Evaluating predictions with the HIP COCO scorer...")
         stats, precision = None, None
         if int(scores.numel()) > 0:
-            image = torch.as_tensor(np.repeat(np.array([img_index[i] for i in ids], dtype=np.int32),
-                                              np.array(counts, dtype=np.int64))).to(dev)
+            image = self._image_of(ids, counts, dev)
             lut = torch.tensor(self._lut + [-1], dtype=torch.int32, device=dev)
             cls = lut[classes.long().clamp(min=-1, max=len(self._lut) - 1)]      # out of range -> -1: the scorer reports it
             cls = torch.where((classes < 0) | (classes >= len(self._lut)), torch.full_like(cls, -1), cls)

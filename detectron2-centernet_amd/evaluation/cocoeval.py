@@ -3,13 +3,13 @@ library (ctdet_cocoeval_match / ctdet_cocoeval_accumulate, csrc/cocoeval.hip) th
 (detectron2/evaluation/fast_eval_api.py) drives `detectron2._C.COCOevalEvaluateImages` / `COCOevalAccumulate`.  The result is
 pinned to that native scorer (precision = tp / (tp + fp); DESIGN.md 7.7 holds the definition).  "bbox" with useCats = 1 only;
 there is no CPU fallback: detections on the CPU are refused by name."""
-import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from .. import _lib
+from .box_scoring import DeviceScorer, cells_csr, ptr as _ptr
 
 
 class Params:
@@ -35,15 +35,12 @@ def prepare_ground_truth(image_ids, cat_ids, annotations):
     img_index, cat_index = {v: i for i, v in enumerate(image_ids)}, {v: i for i, v in enumerate(cat_ids)}
     I, K, n = len(image_ids), len(cat_ids), len(annotations)
     cell = np.array([img_index[a["image_id"]] * K + cat_index[a["category_id"]] for a in annotations], dtype=np.int64)
-    order = np.argsort(cell, kind="stable")
+    order, off, image, classes = cells_csr(cell, I, K)
     boxes = np.array([annotations[j]["bbox"] for j in order], dtype=np.float64).reshape(n, 4)
     area = np.array([annotations[j]["area"] for j in order], dtype=np.float64)
     crowd = np.array([int(annotations[j].get("iscrowd", 0)) for j in order], dtype=np.uint8)
-    off = np.zeros(I * K + 1, dtype=np.int32)
-    np.cumsum(np.bincount(cell, minlength=I * K), out=off[1:])
     return {"image_ids": image_ids, "cat_ids": cat_ids, "boxes": boxes, "area": area, "crowd": crowd, "off": off,
-            "image": (cell[order] // K).astype(np.int32) if K else cell.astype(np.int32),
-            "classes": (cell[order] % K).astype(np.int32) if K else cell.astype(np.int32)}
+            "image": image, "classes": classes}
 
 
 def summarize_stats(precision, recall, params):
@@ -66,11 +63,7 @@ def summarize_stats(precision, recall, params):
                      one(0, areaRng="large", maxDets=md[2])])
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-class COCOevalHIP:
+class COCOevalHIP(DeviceScorer):
     """evaluate() / accumulate() / summarize() with `eval` = {"params", "counts", "precision", "recall", "scores"} and `stats`
     shaped as the reference's COCOeval_opt leaves them.
 
@@ -80,34 +73,25 @@ class COCOevalHIP:
     def __init__(self, gt, boxes, scores, classes, image, iouType="bbox"):
         self.params = Params(iouType)
         self.params.imgIds, self.params.catIds = list(gt["image_ids"]), list(gt["cat_ids"])
-        for name, t in (("boxes", boxes), ("scores", scores), ("classes", classes), ("image", image)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise NotImplementedError(f"COCOevalHIP: `{name}` must be a tensor on the GPU; scoring runs in HIP kernels and "
-                                          "there is no CPU fallback")
-        self._gt = gt
-        self._dt = (boxes.detach().float().reshape(-1, 4).contiguous(), scores.detach().float().contiguous(),
-                    classes.detach().to(torch.int32).contiguous(), image.detach().to(torch.int32).contiguous())
+        super().__init__(gt, boxes, scores, classes, image)
         self.eval, self.stats, self._dev = {}, None, None
 
     # ---- device side
     def _upload(self):
-        p, gt, dev = self.params, self._gt, self._dt[0].device
+        p, gt, dev = self.params, self._gt, self._device
         if int(p.useCats) != 1:
             raise NotImplementedError("COCOevalHIP: useCats = 0 is not built")
         T, A, R, M = len(p.iouThrs), len(p.areaRng), len(p.recThrs), len(p.maxDets)
         I, K, N, NG = len(p.imgIds), len(p.catIds), int(self._dt[1].numel()), int(len(gt["area"]))
         if list(p.maxDets) != sorted(p.maxDets):
             raise ValueError("COCOevalHIP: maxDets must be ascending")
-        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)     # noqa: E731
+        up = self._up
         d = {"T": T, "A": A, "R": R, "M": M, "I": I, "K": K, "N": N, "NG": NG, "max_det": int(p.maxDets[-1]),
-             "gt_boxes": f64(gt["boxes"]), "gt_area": f64(gt["area"]), "gt_crowd": torch.as_tensor(gt["crowd"]).to(dev),
-             "gt_off": torch.as_tensor(gt["off"]).to(dev), "iou_thrs": f64(p.iouThrs), "area_rngs": f64(p.areaRng),
-             "rec_thrs": f64(p.recThrs), "max_dets": torch.tensor(list(p.maxDets), dtype=torch.int32, device=dev)}
-        nbytes = _lib.lib().ctdet_cocoeval_workspace_bytes(N, NG, I, K, A, T)
-        if nbytes == 0:
-            raise RuntimeError(f"cocoeval: {_lib.lib().ctdet_last_error().decode()}")
-        d["ws"] = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        d["ws_ptr"] = (d["ws"].data_ptr() + 255) & ~255
+             "gt_boxes": up(gt["boxes"], True), "gt_area": up(gt["area"], True), "gt_crowd": up(gt["crowd"]),
+             "gt_off": up(gt["off"]), "iou_thrs": up(p.iouThrs, True), "area_rngs": up(p.areaRng, True),
+             "rec_thrs": up(p.recThrs, True), "max_dets": torch.tensor(list(p.maxDets), dtype=torch.int32, device=dev)}
+        d["ws"], d["ws_ptr"] = self._workspace(_lib.lib().ctdet_cocoeval_workspace_bytes(N, NG, I, K, A, T),
+                                               lambda text: RuntimeError(f"cocoeval: {text}"))
         d["order"] = torch.empty(N, dtype=torch.int32, device=dev)
         d["rank"] = torch.empty(N, dtype=torch.int32, device=dev)
         d["flags"] = torch.empty(N * A * T, dtype=torch.uint8, device=dev)
@@ -121,24 +105,19 @@ class COCOevalHIP:
     def _match(self):
         d = self._dev
         boxes, scores, classes, image = self._dt
-        stream = C.c_void_p(torch.cuda.current_stream(boxes.device).cuda_stream)
-        with torch.cuda.device(boxes.device):
-            _lib.check(_lib.lib().ctdet_cocoeval_match(
-                _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(image), d["N"], _ptr(d["gt_boxes"]), _ptr(d["gt_area"]),
-                _ptr(d["gt_crowd"]), _ptr(d["gt_off"]), d["NG"], d["I"], d["K"], _ptr(d["iou_thrs"]), d["T"],
-                _ptr(d["area_rngs"]), d["A"], d["max_det"], C.c_void_p(d["ws_ptr"]), _ptr(d["order"]), _ptr(d["rank"]),
-                _ptr(d["flags"]), _ptr(d["npig"]), _ptr(d["status"]), stream), "ctdet_cocoeval_match")
+        self._call(_lib.lib().ctdet_cocoeval_match,
+                   _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(image), d["N"], _ptr(d["gt_boxes"]), _ptr(d["gt_area"]),
+                   _ptr(d["gt_crowd"]), _ptr(d["gt_off"]), d["NG"], d["I"], d["K"], _ptr(d["iou_thrs"]), d["T"],
+                   _ptr(d["area_rngs"]), d["A"], d["max_det"], d["ws_ptr"], _ptr(d["order"]), _ptr(d["rank"]),
+                   _ptr(d["flags"]), _ptr(d["npig"]), _ptr(d["status"]))
 
     def _accumulate(self):
         d = self._dev
-        boxes, scores, classes, image = self._dt
-        stream = C.c_void_p(torch.cuda.current_stream(boxes.device).cuda_stream)
-        with torch.cuda.device(boxes.device):
-            _lib.check(_lib.lib().ctdet_cocoeval_accumulate(
-                _ptr(scores), _ptr(classes), _ptr(d["order"]), _ptr(d["rank"]), _ptr(d["flags"]), _ptr(d["npig"]), d["N"],
-                d["K"], d["A"], d["T"], _ptr(d["rec_thrs"]), d["R"], _ptr(d["max_dets"]), d["M"], d["max_det"],
-                C.c_void_p(d["ws_ptr"]),
-                _ptr(d["precision"]), _ptr(d["scores"]), _ptr(d["recall"]), stream), "ctdet_cocoeval_accumulate")
+        scores, classes = self._dt[1:3]
+        self._call(_lib.lib().ctdet_cocoeval_accumulate,
+                   _ptr(scores), _ptr(classes), _ptr(d["order"]), _ptr(d["rank"]), _ptr(d["flags"]), _ptr(d["npig"]), d["N"],
+                   d["K"], d["A"], d["T"], _ptr(d["rec_thrs"]), d["R"], _ptr(d["max_dets"]), d["M"], d["max_det"], d["ws_ptr"],
+                   _ptr(d["precision"]), _ptr(d["scores"]), _ptr(d["recall"]))
 
     # ---- the COCOeval protocol
     def evaluate(self):

@@ -11,11 +11,10 @@ import logging
 from collections import OrderedDict
 
 import numpy as np
-import torch
 
 from ..data.catalog import MetadataCatalog
+from .box_scoring import BoxEvaluator
 from .coco_evaluation import gather_detections
-from .evaluator import DatasetEvaluator
 from .voceval import VOCevalHIP, parse_voc_ground_truth
 
 # the reference's `range(50, 100, 5)`, each divided by 100.0
@@ -37,7 +36,7 @@ def derive_voc_results(ap_table, class_names):
         ("bbox_AP75", dict(zip(names, scaled[t75])))])
 
 
-class PascalVOCDetectionEvaluator(DatasetEvaluator):
+class PascalVOCDetectionEvaluator(BoxEvaluator):
     def __init__(self, dataset_name, distributed=True):
         self._dataset_name, self._distributed = dataset_name, distributed
         meta = MetadataCatalog.get(dataset_name)
@@ -52,29 +51,6 @@ class PascalVOCDetectionEvaluator(DatasetEvaluator):
         self._logger = logging.getLogger(__name__)
         self.reset()
 
-    def reset(self):
-        self._image_ids, self._counts, self._boxes, self._scores, self._classes = [], [], [], [], []
-
-    def process(self, inputs, outputs):
-        for inp, out in zip(inputs, outputs):
-            inst = out["instances"]
-            boxes, scores, classes = inst.pred_boxes.tensor, inst.scores, inst.pred_classes
-            if not (boxes.is_cuda and scores.is_cuda and classes.is_cuda):
-                raise NotImplementedError("PascalVOCDetectionEvaluator: the Instances must be on the GPU; scoring runs in HIP "
-                                          "kernels and there is no CPU fallback")
-            self._image_ids.append(inp["image_id"])
-            self._counts.append(int(scores.shape[0]))
-            self._boxes.append(boxes.detach())
-            self._scores.append(scores.detach())
-            self._classes.append(classes.detach())
-
-    def _local(self):
-        """this rank's detections, concatenated on the device: (image ids, counts, boxes, scores, classes)"""
-        if not self._boxes:
-            return [], [], None, None, None
-        return (self._image_ids, self._counts, torch.cat(self._boxes).float().reshape(-1, 4), torch.cat(self._scores).float(),
-                torch.cat(self._classes).to(torch.int32))
-
     def evaluate(self):
         merged = gather_detections(self._local(), self._distributed)
         if merged is None:
@@ -87,16 +63,8 @@ class PascalVOCDetectionEvaluator(DatasetEvaluator):
             return derive_voc_results(np.zeros((K, T)), self._class_names)
         if self._gt is None:
             self._gt = parse_voc_ground_truth(self._dirname, self._split, self._class_names)
-        img_index = {v: i for i, v in enumerate(self._gt["image_ids"])}
-        unknown = [i for i in ids if i not in img_index]
-        if unknown:
-            raise ValueError(f"PascalVOCDetectionEvaluator: predictions for image ids that are not in ImageSets/Main/"
-                             f"{self._split}.txt: {unknown[:5]}")
-        if not isinstance(boxes, torch.Tensor):
-            dev = torch.device("cuda", torch.cuda.current_device())
-            boxes, scores, classes = (torch.as_tensor(a).to(dev) for a in (boxes, scores, classes))
-        image = torch.as_tensor(np.repeat(np.array([img_index[i] for i in ids], dtype=np.int32),
-                                          np.array(counts, dtype=np.int64))).to(boxes.device)
+        boxes, scores, classes = self._checked(ids, boxes, scores, classes, f"ImageSets/Main/{self._split}.txt")
+        image = self._image_of(ids, counts, boxes.device)
         self.voc_eval = ev = VOCevalHIP(self._gt, boxes, scores, classes, image)
         # a class outside thing_classes or a non-finite score or box is the scorer's ValueError, which names the cause
         table = ev.evaluate([t / 100.0 for t in VOC_THRESHOLDS], self._year)
