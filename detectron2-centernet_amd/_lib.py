@@ -195,6 +195,21 @@ def voceval_lib():
     return _load(VOCEVAL_LIB_PATH, VOCEVAL_SIGNATURES, True)
 
 
+# libctdet_lviseval.so (include/ctdet_lviseval.h): the LVIS scorer, loaded when LVISevalHIP first scores
+LVISEVAL_LIB_PATH = os.path.join(_HERE, "lib", "libctdet_lviseval.so")
+LVISEVAL_SIGNATURES = {
+    "ctdet_lviseval_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "ctdet_lviseval_match": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctdet_lviseval_accumulate": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+}
+
+
+def lviseval_lib():
+    """Loads libctdet_lviseval.so once (after libctdet_hip.so, which it links against); raises if it has not been built"""
+    return _load(LVISEVAL_LIB_PATH, LVISEVAL_SIGNATURES, True)
+
+
 def check(rc, what):
     if rc != 0:
         msg = lib().ctdet_last_error()

@@ -110,6 +110,8 @@ _C.DATALOADER = CN()
 _C.DATALOADER.NUM_WORKERS = 4
 _C.DATALOADER.ASPECT_RATIO_GROUPING = True
 _C.DATALOADER.SAMPLER_TRAIN = "TrainingSampler"
+# frequency threshold of RepeatFactorTrainingSampler: images of a class rarer than this are repeated
+_C.DATALOADER.REPEAT_THRESHOLD = 0.0
 _C.DATALOADER.FILTER_EMPTY_ANNOTATIONS = True
 
 _C.SOLVER = CN()

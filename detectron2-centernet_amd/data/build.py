@@ -1,7 +1,10 @@
 """Training and inference samplers and minimal batched loaders (reference: data/samplers/distributed_sampler.py:12-55
-TrainingSampler, :172-199 InferenceSampler, data/build.py:270-355 build_detection_train_loader / per-GPU batch size, :358-403
+TrainingSampler, :57-170 RepeatFactorTrainingSampler, :172-199 InferenceSampler, data/build.py:270-355 build_detection_train_loader / per-GPU batch size, :358-403
 build_detection_test_loader).  The GPU path takes `list[dict]` batches of unequal image sizes as they come."""
 import itertools
+import math
+from collections import defaultdict
+
 import torch
 
 from .catalog import DatasetCatalog
@@ -26,6 +29,53 @@ class TrainingSampler:
                 yield from torch.randperm(self._size, generator=g).tolist()
             else:
                 yield from range(self._size)
+
+
+def repeat_factors_from_category_frequency(dataset_dicts, repeat_thresh):
+    """f32 [len(dataset_dicts)]: the repeat factor of every image from the frequency of its rarest class (LVIS paper, appendix
+    B.2; reference :86-130).  f(c) = share of the images that hold class c; r(c) = max(1, sqrt(repeat_thresh / f(c))); r(I) =
+    the largest r(c) over the image's classes.  An image without annotations gets 1.0: the reference raises there (max of an
+    empty set), which it can only meet with DATALOADER.FILTER_EMPTY_ANNOTATIONS off; repeating such an image never is this
+    project's choice."""
+    category_freq = defaultdict(int)
+    for d in dataset_dicts:
+        for c in {a["category_id"] for a in d.get("annotations", [])}:
+            category_freq[c] += 1
+    num_images = len(dataset_dicts)
+    category_rep = {c: max(1.0, math.sqrt(repeat_thresh / (n / num_images))) for c, n in category_freq.items()}
+    return torch.tensor([max({category_rep[a["category_id"]] for a in d.get("annotations", [])}, default=1.0)
+                         for d in dataset_dicts], dtype=torch.float32)
+
+
+class RepeatFactorTrainingSampler:
+    """TrainingSampler in which index i appears repeat_factors[i] times per epoch on average (reference :57-170).  Per epoch,
+    on the one seeded generator: `torch.rand(n)` rounds every fractional part up or down (stochastic rounding), the indices
+    are repeated, and with `shuffle` a `randperm` over the repeated list orders them.  Every rank draws the same stream and takes
+    elements rank, rank+W, ...; factors all 1 give TrainingSampler's multiset per epoch (not its order: one more draw)."""
+
+    def __init__(self, repeat_factors, shuffle=True, seed=0, rank=0, world_size=1):
+        repeat_factors = torch.as_tensor(repeat_factors, dtype=torch.float32)
+        assert repeat_factors.ndim == 1 and repeat_factors.numel() > 0
+        self._shuffle, self._seed, self._rank, self._world = shuffle, int(seed), rank, world_size
+        self._int_part = torch.trunc(repeat_factors)
+        self._frac_part = repeat_factors - self._int_part
+
+    def __iter__(self):
+        yield from itertools.islice(self._infinite_indices(), self._rank, None, self._world)
+
+    def _epoch_indices(self, g):
+        rands = torch.rand(len(self._frac_part), generator=g)
+        reps = (self._int_part + (rands < self._frac_part).float()).to(torch.int64)
+        return torch.repeat_interleave(torch.arange(len(reps), dtype=torch.int64), reps)
+
+    def _infinite_indices(self):
+        g = torch.Generator()
+        g.manual_seed(self._seed)
+        while True:
+            indices = self._epoch_indices(g)
+            if self._shuffle:
+                indices = indices[torch.randperm(len(indices), generator=g)]
+            yield from indices.tolist()
 
 
 class InferenceSampler:
@@ -88,7 +138,14 @@ def build_detection_train_loader(cfg, mapper=None, rank=0, world_size=1, seed=0,
     assert total % world_size == 0, f"IMS_PER_BATCH ({total}) must be divisible by the number of workers ({world_size})"
     per_gpu = total // world_size
     mapper = mapper if mapper is not None else TrafficLightDatasetMapper(cfg, True)
-    sampler = TrainingSampler(len(dicts), seed=seed, rank=rank, world_size=world_size)
+    name = cfg.DATALOADER.SAMPLER_TRAIN
+    if name == "TrainingSampler":
+        sampler = TrainingSampler(len(dicts), seed=seed, rank=rank, world_size=world_size)
+    elif name == "RepeatFactorTrainingSampler":
+        factors = repeat_factors_from_category_frequency(dicts, cfg.DATALOADER.REPEAT_THRESHOLD)
+        sampler = RepeatFactorTrainingSampler(factors, seed=seed, rank=rank, world_size=world_size)
+    else:
+        raise ValueError("Unknown training sampler: {}".format(name))
     workers = cfg.DATALOADER.NUM_WORKERS if num_workers is None else num_workers
     batch_sampler = torch.utils.data.BatchSampler(sampler, per_gpu, drop_last=True)
     loader = torch.utils.data.DataLoader(_MapDataset(dicts, mapper), batch_sampler=batch_sampler, num_workers=workers,

@@ -22,8 +22,8 @@ from ..checkpoint import DetectionCheckpointer
 from ..data import MetadataCatalog, TrafficLightDatasetMapper, build_detection_test_loader, build_detection_train_loader
 from ..data import transforms as T
 from ..data import warp as warp_defs
-from ..evaluation import (COCOEvaluator, DatasetEvaluator, PascalVOCDetectionEvaluator, inference_on_dataset, print_csv_format,
-                          verify_results)
+from ..evaluation import (COCOEvaluator, DatasetEvaluator, LVISEvaluator, PascalVOCDetectionEvaluator, inference_on_dataset,
+                          print_csv_format, verify_results)
 from ..modeling.meta_arch.build import build_model
 from ..solver import build_lr_scheduler, build_optimizer
 from ..utils import comm
@@ -264,10 +264,13 @@ class DefaultTrainer(SimpleTrainer):
     def build_evaluator(cls, cfg, dataset_name, output_folder=None):
         if output_folder is None:
             output_folder = os.path.join(cfg.OUTPUT_DIR, "inference")
-        # the dispatch of the reference's training script on the dataset's `evaluator_type`: "pascal_voc" has its own scorer,
-        # every other (or no) type is scored as COCO
-        if MetadataCatalog.get(dataset_name).get("evaluator_type") == "pascal_voc":
+        # the dispatch of the reference's training script on the dataset's `evaluator_type`: "pascal_voc" and "lvis" have
+        # their own scorers, every other (or no) type is scored as COCO
+        evaluator_type = MetadataCatalog.get(dataset_name).get("evaluator_type")
+        if evaluator_type == "pascal_voc":
             return PascalVOCDetectionEvaluator(dataset_name)
+        if evaluator_type == "lvis":
+            return LVISEvaluator(dataset_name, cfg, True, output_folder)
         return COCOEvaluator(dataset_name, cfg, True, output_folder)
 
     @classmethod

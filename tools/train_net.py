@@ -23,7 +23,7 @@ if ROOT not in sys.path:
 import detectron2_centernet_amd  # noqa: E402,F401
 from detectron2_centernet_amd.checkpoint import DetectionCheckpointer  # noqa: E402
 from detectron2_centernet_amd.config import get_cfg  # noqa: E402
-from detectron2_centernet_amd.data import register_all_pascal_voc  # noqa: E402
+from detectron2_centernet_amd.data import register_all_lvis, register_all_pascal_voc  # noqa: E402
 from detectron2_centernet_amd.data.catalog import DatasetCatalog, register_synthetic_files  # noqa: E402
 from detectron2_centernet_amd.engine import DefaultTrainer, default_argument_parser, default_setup, launch  # noqa: E402
 from detectron2_centernet_amd.evaluation import verify_results  # noqa: E402
@@ -81,6 +81,8 @@ def setup(args):
     default_setup(cfg, args)
     # the Pascal VOC splits (voc_2007_*, voc_2012_*) whose VOC2007 / VOC2012 directory exists under the datasets root
     register_all_pascal_voc(os.getenv("DETECTRON2_DATASETS", "datasets"))
+    # ... and the LVIS splits (lvis_v1_*, lvis_v0.5_*) whose json exists under it
+    register_all_lvis(os.getenv("DETECTRON2_DATASETS", "datasets"))
     register_missing_datasets(cfg)
     return cfg
 
