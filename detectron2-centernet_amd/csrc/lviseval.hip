@@ -23,87 +23,64 @@
 //     hot-path library does not grow by it.  Error text and kernel labels go through the plumbing of libctdet_hip.so.
 //   * the only atomics are integer (non-ignored ground truths per (class, area range), the status bits): two runs are
 //     bit-identical.
+//   * what this scorer has in common with the VOC one (voceval.hip) -- the ordering stage around the keys, the checks, the
+//     start of a chunk of the accumulate walk -- is in eval_common.h.  Here are its keys (le_cell: the cut and the drop), its
+//     matcher with le_iou, its accumulate passes and its own workspace blocks (the image offsets, the taken table).
 #include "eval_common.h"
 #include "../../include/ctdet_lviseval.h"
 
 #define LE_LDS_GT 128           // ground truths of a cell whose taken flags (one byte per matcher, <= 64 matchers) stay in LDS
 #define LE_NT 256               // accumulate workgroup = chunk of the class segment
 
+static_assert(CTDET_LVIS_BAD_CLASS == EVAL_BAD_CLASS && CTDET_LVIS_BAD_IMAGE == EVAL_BAD_IMAGE &&
+              CTDET_LVIS_BAD_SCORE == EVAL_BAD_SCORE && CTDET_LVIS_BAD_BOX == EVAL_BAD_BOX, "the public status bits");
+
 struct LeMatchArgs {
-  const float* boxes; const float* scores; const int* classes; const int* image; long N;
-  const double* gt_boxes; const double* gt_area; const uint8_t* gt_ignore; const int* gt_off; const uint8_t* lists; int I, K;
+  EvalDets d;
+  const double* gt_boxes; const double* gt_area; const uint8_t* gt_ignore; const int* gt_off; const uint8_t* lists;
   const double* iou_thrs; int T; const double* area_rngs; int A; int max_det;
-  uint64_t* keys64; uint32_t* vals; const uint32_t* order_s; uint32_t* keys32;
-  const uint32_t* cell_order; const int* img_off; int* dt_off; uint8_t* taken;
+  EvalOrderWs o; const int* img_off; uint8_t* taken;
   uint8_t* flags; int* npig; int* status;
 };
-
-// status bits of a detection that takes no part (0: it does)
-__device__ __forceinline__ int le_invalid(const LeMatchArgs& a, long i) {
-  const int c = a.classes[i], im = a.image[i];
-  int st = 0;
-  if (c < 0 || c >= a.K) st |= CTDET_LVIS_BAD_CLASS;
-  if (im < 0 || im >= a.I) st |= CTDET_LVIS_BAD_IMAGE;
-  if (!isfinite(a.scores[i])) st |= CTDET_LVIS_BAD_SCORE;
-  const float* b = a.boxes + i * 4;
-  if (!(isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]))) st |= CTDET_LVIS_BAD_BOX;
-  return st;
-}
 
 // the (image, class) cell of the detection at position p of S, or -1: invalid, cut (rank >= max_det) or dropped (its class is
 // neither positive -- a cell with ground truth -- nor negative in its image)
 __device__ __forceinline__ long le_cell(const LeMatchArgs& a, long p) {
-  const long i = a.order_s[p];
-  if (le_invalid(a, i)) return -1;
-  const int im = a.image[i];
+  const long i = a.o.order_s[p];
+  if (eval_invalid(a.d, i)) return -1;
+  const int im = a.d.image[i];
   if (p - a.img_off[im] >= a.max_det) return -1;
-  const long cell = (long)im * a.K + a.classes[i];
+  const long cell = (long)im * a.d.K + a.d.classes[i];
   if (a.gt_off[cell + 1] == a.gt_off[cell] && !(a.lists[cell] & CTDET_LVIS_NEG)) return -1;
   return cell;
-}
-
-__global__ void __launch_bounds__(256) le_clear_kernel(int* __restrict__ npig, int n, int* __restrict__ status) {
-  eval_clear(npig, n, status);
 }
 
 // order-S keys: {image | score}; an invalid detection goes behind the last image and raises the status word
 __global__ void __launch_bounds__(256) le_key_image_kernel(LeMatchArgs a) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.N) return;
-  const int st = le_invalid(a, i);
+  if (i >= a.d.N) return;
+  const int st = eval_invalid(a.d, i);
   if (st) atomicOr(a.status, st);
-  const uint32_t im = st ? (uint32_t)a.I : (uint32_t)a.image[i];
-  a.keys64[i] = ((uint64_t)im << 32) | eval_score_key(a.scores[i]);
-  a.vals[i] = (uint32_t)i;
+  const uint32_t im = st ? (uint32_t)a.d.I : (uint32_t)a.d.image[i];
+  a.o.keys64[i] = ((uint64_t)im << 32) | eval_score_key(a.d.scores[i]);
+  a.o.vals[i] = (uint32_t)i;
 }
 
 // keys of the total order, over the positions of S: {class | score}, class K for a detection that takes no part
 __global__ void __launch_bounds__(256) le_key_class_kernel(LeMatchArgs a) {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.N) return;
-  const long i = a.order_s[p];
-  const uint32_t c = le_cell(a, p) < 0 ? (uint32_t)a.K : (uint32_t)a.classes[i];
-  a.keys64[p] = ((uint64_t)c << 32) | eval_score_key(a.scores[i]);
+  if (p >= a.d.N) return;
+  const long i = a.o.order_s[p];
+  const uint32_t c = le_cell(a, p) < 0 ? (uint32_t)a.d.K : (uint32_t)a.d.classes[i];
+  a.o.keys64[p] = ((uint64_t)c << 32) | eval_score_key(a.d.scores[i]);
 }
 
 // keys of the cell order, over the positions of S: the cell, I*K for a detection that takes no part
 __global__ void __launch_bounds__(256) le_key_cell_kernel(LeMatchArgs a) {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.N) return;
+  if (p >= a.d.N) return;
   const long cell = le_cell(a, p);
-  a.keys32[p] = cell < 0 ? (uint32_t)a.I * (uint32_t)a.K : (uint32_t)cell;
-}
-
-// off[c] = first position of the sorted keys whose group (the high word of a 64-bit key, a 32-bit key itself) is >= c, c in [0, n]
-__global__ void __launch_bounds__(256) le_offsets64_kernel(const uint64_t* __restrict__ keys, long N, int n, int* __restrict__ off) {
-  const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c > n) return;
-  off[c] = eval_lower_bound(keys, N, c, [](uint64_t k) { return (long)(k >> 32); });
-}
-__global__ void __launch_bounds__(256) le_offsets32_kernel(const uint32_t* __restrict__ keys, long N, int n, int* __restrict__ off) {
-  const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c > n) return;
-  off[c] = eval_lower_bound(keys, N, c, [](uint32_t k) { return (long)k; });
+  a.o.keys32[p] = cell < 0 ? (uint32_t)a.d.I * (uint32_t)a.d.K : (uint32_t)cell;
 }
 
 // ctdet_cocoeval_iou's formula without a crowd
@@ -119,9 +96,9 @@ __global__ void __launch_bounds__(64) le_match_kernel(LeMatchArgs a) {
   __shared__ uint8_t taken_lds[LE_LDS_GT * 64];
   const int cell = blockIdx.x, lane = threadIdx.x;
   const int g0 = a.gt_off[cell], G = a.gt_off[cell + 1] - g0;
-  const int d0 = a.dt_off[cell], D = a.dt_off[cell + 1] - d0;
+  const int d0 = a.o.dt_off[cell], D = a.o.dt_off[cell + 1] - d0;
   if (G == 0 && D == 0) return;
-  const int k = cell % a.K, AT = a.A * a.T;
+  const int k = cell % a.d.K, AT = a.A * a.T;
   const bool active = lane < AT;
   const int ar = active ? lane / a.T : 0, t = active ? lane % a.T : 0;
   const double lo = a.area_rngs[ar * 2], hi = a.area_rngs[ar * 2 + 1];
@@ -140,8 +117,8 @@ __global__ void __launch_bounds__(64) le_match_kernel(LeMatchArgs a) {
   for (long i = lane; i < (long)G * AT; i += 64) taken[i] = 0;
   __syncthreads();
   for (int d = 0; d < D; ++d) {
-    const long o = a.cell_order[d0 + d];
-    const float x1 = a.boxes[o * 4], y1 = a.boxes[o * 4 + 1], x2 = a.boxes[o * 4 + 2], y2 = a.boxes[o * 4 + 3];
+    const long o = a.o.cell_order[d0 + d];
+    const float x1 = a.d.boxes[o * 4], y1 = a.d.boxes[o * 4 + 1], x2 = a.d.boxes[o * 4 + 2], y2 = a.d.boxes[o * 4 + 3];
     const double dx = (double)x1, dy = (double)y1, dw = (double)(x2 - x1), dh = (double)(y2 - y1);   // w, h in f32, then widened
     const double darea = dw * dh;
     if (!active) continue;
@@ -201,22 +178,14 @@ __global__ void __launch_bounds__(LE_NT) le_accum_kernel(LeAccArgs a) {
   // ---- pass 1: running counts; which position is the first to reach each recall threshold
   for (int base = s0; base < s1; base += LE_NT) {
     const int j = base + tid;
-    uint32_t tp = 0, fp = 0;
-    if (j < s1) {
-      const uint32_t f = a.flags[(long)a.order[j] * AT + col];
-      tp = f == 1; fp = f == 0;
-    }
-    uint32_t tot;
-    const uint32_t sc = eval_scan_packed<LE_NT>(tp | (fp << 16), wsum, tot);     // two 16-bit counters
-    if (j < s1 && (tp || j == s0)) {
-      const int itp = ctp + (int)(sc & 0xFFFFu);
-      const double rec = (double)itp / dnp, prev = (double)(itp - (int)tp) / dnp;
+    const EvalPos at = eval_chunk<LE_NT>(a.order, a.flags, AT, col, 0, j, s1, wsum, ctp, cfp);     // flag 0: a false positive
+    if (j < s1 && (at.tp || j == s0)) {
+      const double rec = (double)at.itp / dnp, prev = (double)(at.itp - (int)at.tp) / dnp;
       for (int r = 0; r < a.R; ++r) {
         const double thr = a.rec_thrs[r];
         if (rec >= thr && (j == s0 || !(prev >= thr))) own[r] = j;
       }
     }
-    ctp += (int)(tot & 0xFFFFu); cfp += (int)(tot >> 16);
   }
   __syncthreads();
   const int total_tp = ctp;
@@ -224,48 +193,29 @@ __global__ void __launch_bounds__(LE_NT) le_accum_kernel(LeAccArgs a) {
   ctp = 0; cfp = 0;
   for (int base = s0; base < s1; base += LE_NT) {
     const int j = base + tid;
-    uint32_t tp = 0, fp = 0;
-    if (j < s1) {
-      const uint32_t f = a.flags[(long)a.order[j] * AT + col];
-      tp = f == 1; fp = f == 0;
-    }
-    uint32_t tot;
-    const uint32_t sc = eval_scan_packed<LE_NT>(tp | (fp << 16), wsum, tot);
-    double prec = -1.0;
-    if (j < s1) {
-      const int itp = ctp + (int)(sc & 0xFFFFu), ifp = cfp + (int)(sc >> 16);
-      prec = (double)itp / ((double)(ifp + itp) + 0x1p-52);
-    }
-    eval_suffix_max<LE_NT>(sm, prec, -1.0);
+    const EvalPos at = eval_chunk<LE_NT>(a.order, a.flags, AT, col, 0, j, s1, wsum, ctp, cfp);
+    eval_suffix_max<LE_NT>(sm, j < s1 ? (double)at.itp / ((double)(at.ifp + at.itp) + 0x1p-52) : -1.0, -1.0);
     for (int r = tid; r < a.R; r += LE_NT) {
       const int o = own[r];
       if (o >= 0 && o < base + LE_NT) env[r] = fmax(env[r], sm[o < base ? 0 : o - base]);
     }
-    ctp += (int)(tot & 0xFFFFu); cfp += (int)(tot >> 16);
   }
   __syncthreads();
   for (int r = tid; r < a.R; r += LE_NT) a.precision[pbase + r * pstride] = own[r] >= 0 ? env[r] : 0.0;
   if (tid == 0) a.recall[ridx] = (double)total_tp / dnp;
 }
 
-// ---- workspace: {keys, sorted keys} u64 [N] each, values u32 [N], order S u32 [N], cell keys u32 [N] x 2, cell order u32 [N],
-// cell offsets i32 [I*K + 2], image offsets i32 [I + 2], the taken table u8 [NG * A*T], then the sort block
-struct LeWs { size_t keys64, keys64_sorted, vals, order_s, keys32, keys32_sorted, cell_order, off, img_off, taken, sort, total; };
-static LeWs le_layout(long N, long NG, long I, long K, long A, long T) {
+// ---- workspace: the ordering stage's blocks, image offsets i32 [I + 2], the taken table u8 [NG * A*T], then the sort block.
+// ws == nullptr: the sizes alone
+struct LeWs { EvalOrderWs o; int* img_off; uint8_t* taken; EvalSorter sort; size_t total; };
+static LeWs le_layout(void* ws, long N, long NG, long I, long K, long A, long T) {
+  EvalLayout l = {(uintptr_t)ws, 0};
   LeWs w;
-  size_t p = 0;
-  w.keys64 = p; p += eval_up((size_t)N * 8);
-  w.keys64_sorted = p; p += eval_up((size_t)N * 8);
-  w.vals = p; p += eval_up((size_t)N * 4);
-  w.order_s = p; p += eval_up((size_t)N * 4);
-  w.keys32 = p; p += eval_up((size_t)N * 4);
-  w.keys32_sorted = p; p += eval_up((size_t)N * 4);
-  w.cell_order = p; p += eval_up((size_t)N * 4);
-  w.off = p; p += eval_up((size_t)(I * K + 2) * 4);
-  w.img_off = p; p += eval_up((size_t)(I + 2) * 4);
-  w.taken = p; p += eval_up((size_t)NG * A * T);
-  w.sort = p; p += eval_sort_bytes(N);
-  w.total = p;
+  w.o = eval_order_layout(l, N, I * K);
+  w.img_off = l.take<int>(I + 2);
+  w.taken = l.take<uint8_t>((size_t)NG * A * T);
+  w.sort = eval_sort_layout(l, "lviseval", N);
+  w.total = l.p;
   return w;
 }
 
@@ -280,7 +230,7 @@ extern "C" {
 
 size_t ctdet_lviseval_workspace_bytes(int64_t N, int64_t NG, int32_t I, int32_t K, int32_t A, int32_t T) {
   if (le_check_dims("lviseval_workspace_bytes", N, NG, I, K, A, T)) return 0;
-  return le_layout(N, NG, I, K, A, T).total;
+  return le_layout(nullptr, N, NG, I, K, A, T).total;
 }
 
 int32_t ctdet_lviseval_match(const float* boxes, const float* scores, const int32_t* classes, const int32_t* image, int64_t N,
@@ -288,65 +238,33 @@ int32_t ctdet_lviseval_match(const float* boxes, const float* scores, const int3
                              int64_t NG, const uint8_t* lists, int32_t I, int32_t K, const double* iou_thrs, int32_t T,
                              const double* area_rngs, int32_t A, int32_t max_det, void* workspace, int32_t* order,
                              int32_t* cls_off, uint8_t* flags, int32_t* npig, int32_t* status, void* stream) {
-  CTDET_CHECK(gt_off, "lviseval_match: null pointer gt_off");
-  CTDET_CHECK(lists, "lviseval_match: null pointer lists");
-  CTDET_CHECK(iou_thrs, "lviseval_match: null pointer iou_thrs");
-  CTDET_CHECK(area_rngs, "lviseval_match: null pointer area_rngs");
-  CTDET_CHECK(workspace, "lviseval_match: null pointer workspace");
-  CTDET_CHECK(cls_off, "lviseval_match: null pointer cls_off");
-  CTDET_CHECK(npig, "lviseval_match: null pointer npig");
-  CTDET_CHECK(status, "lviseval_match: null pointer status");
-  CTDET_CHECK(NG <= 0 || gt_boxes, "lviseval_match: null pointer gt_boxes");
-  CTDET_CHECK(NG <= 0 || gt_area, "lviseval_match: null pointer gt_area");
-  CTDET_CHECK(NG <= 0 || gt_ignore, "lviseval_match: null pointer gt_ignore");
-  CTDET_CHECK(N <= 0 || boxes, "lviseval_match: null pointer boxes");
-  CTDET_CHECK(N <= 0 || scores, "lviseval_match: null pointer scores");
-  CTDET_CHECK(N <= 0 || classes, "lviseval_match: null pointer classes");
-  CTDET_CHECK(N <= 0 || image, "lviseval_match: null pointer image");
-  CTDET_CHECK(N <= 0 || order, "lviseval_match: null pointer order");
-  CTDET_CHECK(N <= 0 || flags, "lviseval_match: null pointer flags");
+  const char* what = "lviseval_match";
+  if (const int rc = eval_check_match_ptrs(what, N, NG, boxes, scores, classes, image, gt_boxes, gt_off, workspace, order,
+                                           cls_off, flags, status))
+    return rc;
+  EVAL_CHECK_PTR(what, lists);
+  EVAL_CHECK_PTR(what, iou_thrs);
+  EVAL_CHECK_PTR(what, area_rngs);
+  EVAL_CHECK_PTR(what, npig);
+  EVAL_CHECK_PTR_IF(what, NG, gt_area);
+  EVAL_CHECK_PTR_IF(what, NG, gt_ignore);
   CTDET_CHECK(max_det >= 1, "lviseval_match: max_det=%d", max_det);
-  const int rc = le_check_dims("lviseval_match", N, NG, I, K, A, T);
-  if (rc) return rc;
+  if (const int rc = le_check_dims(what, N, NG, I, K, A, T)) return rc;
   EVAL_CHECK_WORKSPACE("lviseval_match", workspace);
   CTDET_KERNEL("le_match_kernel<wave per cell,%d matchers>", A * T);
   hipStream_t s = (hipStream_t)stream;
-  const LeWs w = le_layout(N, NG, I, K, A, T);
-  char* ws = (char*)workspace;
-  LeMatchArgs a;
-  a.boxes = boxes; a.scores = scores; a.classes = classes; a.image = image; a.N = N;
-  a.gt_boxes = gt_boxes; a.gt_area = gt_area; a.gt_ignore = gt_ignore; a.gt_off = gt_off; a.lists = lists; a.I = I; a.K = K;
-  a.iou_thrs = iou_thrs; a.T = T; a.area_rngs = area_rngs; a.A = A; a.max_det = max_det;
-  a.keys64 = (uint64_t*)(ws + w.keys64); a.vals = (uint32_t*)(ws + w.vals); a.order_s = (const uint32_t*)(ws + w.order_s);
-  a.keys32 = (uint32_t*)(ws + w.keys32); a.cell_order = (const uint32_t*)(ws + w.cell_order);
-  a.img_off = (const int*)(ws + w.img_off); a.dt_off = (int*)(ws + w.off); a.taken = (uint8_t*)(ws + w.taken);
-  a.flags = flags; a.npig = npig; a.status = status;
-  uint64_t* k64s = (uint64_t*)(ws + w.keys64_sorted);
-  uint32_t* k32s = (uint32_t*)(ws + w.keys32_sorted);
+  const LeWs w = le_layout(workspace, N, NG, I, K, A, T);
+  const LeMatchArgs a = {{boxes, scores, classes, image, N, I, K}, gt_boxes, gt_area, gt_ignore, gt_off, lists, iou_thrs, T,
+                         area_rngs, A, max_det, w.o, w.img_off, w.taken, flags, npig, status};
   const int ncell = I * K;
-  const unsigned nb = (unsigned)((N + 255) / 256);
-  const auto sort = [&](auto* kin, auto* kout, const uint32_t* vin, uint32_t* vout, int bits) {     // tmp: the sort block
-    return eval_sort("lviseval", kin, kout, vin, vout, N, bits, ws + w.sort, w.total - w.sort, s);
-  };
-  hipLaunchKernelGGL(le_clear_kernel, dim3((K * A + 255) / 256), dim3(256), 0, s, npig, K * A, status);
-  if (N) {
-    hipLaunchKernelGGL(le_key_image_kernel, dim3(nb), dim3(256), 0, s, a);
-    const int src = sort(a.keys64, k64s, a.vals, (uint32_t*)(ws + w.order_s), 32 + eval_bits((unsigned long)I));
-    if (src) return src;
-  }
-  hipLaunchKernelGGL(le_offsets64_kernel, dim3((I + 1 + 255) / 256), dim3(256), 0, s, k64s, (long)N, I, (int*)(ws + w.img_off));
-  if (N) {
-    hipLaunchKernelGGL(le_key_class_kernel, dim3(nb), dim3(256), 0, s, a);
-    const int src = sort(a.keys64, k64s, a.order_s, (uint32_t*)order, 32 + eval_bits((unsigned long)K));
-    if (src) return src;
-  }
-  hipLaunchKernelGGL(le_offsets64_kernel, dim3((K + 1 + 255) / 256), dim3(256), 0, s, k64s, (long)N, K, cls_off);
-  if (N) {
-    hipLaunchKernelGGL(le_key_cell_kernel, dim3(nb), dim3(256), 0, s, a);
-    const int src = sort(a.keys32, k32s, a.order_s, (uint32_t*)(ws + w.cell_order), eval_bits((unsigned long)ncell));
-    if (src) return src;
-  }
-  hipLaunchKernelGGL(le_offsets32_kernel, dim3((ncell + 1 + 255) / 256), dim3(256), 0, s, k32s, (long)N, ncell, a.dt_off);
+  const dim3 nb((unsigned)((N + 255) / 256)), nt(256);
+  hipLaunchKernelGGL(eval_clear_kernel, dim3((K * A + 255) / 256), nt, 0, s, npig, K * A, status);
+  if (N) hipLaunchKernelGGL(le_key_image_kernel, nb, nt, 0, s, a);
+  if (const int rc = w.sort.sort_cut(w.o.keys64, w.o.keys64_sorted, w.o.vals, w.o.order_s, I, w.img_off, s)) return rc;
+  if (N) hipLaunchKernelGGL(le_key_class_kernel, nb, nt, 0, s, a);
+  if (const int rc = w.sort.sort_cut(w.o.keys64, w.o.keys64_sorted, w.o.order_s, (uint32_t*)order, K, cls_off, s)) return rc;
+  if (N) hipLaunchKernelGGL(le_key_cell_kernel, nb, nt, 0, s, a);
+  if (const int rc = w.sort.sort_cut(w.o.keys32, w.o.keys32_sorted, w.o.order_s, w.o.cell_order, ncell, w.o.dt_off, s)) return rc;
   hipLaunchKernelGGL(le_match_kernel, dim3(ncell), dim3(64), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -355,21 +273,19 @@ int32_t ctdet_lviseval_match(const float* boxes, const float* scores, const int3
 int32_t ctdet_lviseval_accumulate(const int32_t* order, const int32_t* cls_off, const uint8_t* flags, const int32_t* npig,
                                   int64_t N, int32_t K, int32_t A, int32_t T, const double* rec_thrs, int32_t R,
                                   double* precision, double* recall, void* stream) {
-  CTDET_CHECK(cls_off, "lviseval_accumulate: null pointer cls_off");
-  CTDET_CHECK(npig, "lviseval_accumulate: null pointer npig");
-  CTDET_CHECK(rec_thrs, "lviseval_accumulate: null pointer rec_thrs");
-  CTDET_CHECK(precision, "lviseval_accumulate: null pointer precision");
-  CTDET_CHECK(recall, "lviseval_accumulate: null pointer recall");
-  CTDET_CHECK(N <= 0 || order, "lviseval_accumulate: null pointer order");
-  CTDET_CHECK(N <= 0 || flags, "lviseval_accumulate: null pointer flags");
+  const char* what = "lviseval_accumulate";
+  EVAL_CHECK_PTR(what, cls_off);
+  EVAL_CHECK_PTR(what, npig);
+  EVAL_CHECK_PTR(what, rec_thrs);
+  EVAL_CHECK_PTR(what, precision);
+  EVAL_CHECK_PTR(what, recall);
+  EVAL_CHECK_PTR_IF(what, N, order);
+  EVAL_CHECK_PTR_IF(what, N, flags);
   CTDET_CHECK(R >= 1 && R <= 4096, "lviseval_accumulate: R=%d recall thresholds (1..4096)", R);
-  const int rc = le_check_dims("lviseval_accumulate", N, 0, 1, K, A, T);
-  if (rc) return rc;
+  if (const int rc = le_check_dims(what, N, 0, 1, K, A, T)) return rc;
   CTDET_CHECK((int64_t)K * A * T < (1LL << 31), "lviseval_accumulate: K*A*T too large");
   CTDET_KERNEL("le_accum_kernel<workgroup per (k,a,t),two passes>");
-  LeAccArgs a;
-  a.order = order; a.cls_off = cls_off; a.flags = flags; a.npig = npig; a.K = K; a.A = A; a.T = T; a.R = R;
-  a.rec_thrs = rec_thrs; a.precision = precision; a.recall = recall;
+  const LeAccArgs a = {order, cls_off, flags, npig, K, A, T, R, rec_thrs, precision, recall};
   hipLaunchKernelGGL(le_accum_kernel, dim3(K * A * T), dim3(LE_NT), (size_t)R * 12, (hipStream_t)stream, a);
   CTDET_LAUNCH_CHECK();
   return 0;

@@ -25,78 +25,57 @@
 //     hot-path library does not grow by it.  Error text and kernel labels go through the plumbing of libctdet_hip.so
 //     (ctdet_set_error / ctdet_last_error, CTDET_KERNEL), against which this library links.
 //   * the only atomics are integer (non-difficult ground truths per class, the status bits): two runs are bit-identical.
-//   * eval_common.h holds the scaffolding a box-AP scorer needs whatever its rule: the score key, the lower bound that cuts
-//     the sorted keys into segments, the packed workgroup scan, the in-LDS suffix maximum, the rocprim sort call, the
-//     workspace rounding and the common range checks.  The matcher and the AP passes are this scorer's own.  cocoeval.hip
-//     still carries its own copies of those pieces: it is part of the hot-path library, whose binary stays as it is.
+//   * what this scorer has in common with the LVIS one (lviseval.hip) -- the ordering stage around the keys, the checks, the
+//     start of a chunk of the AP walk -- is in eval_common.h.  Here are its keys, its matcher, its AP passes and its own
+//     workspace blocks (the chunk values, the taken words).
 #include "eval_common.h"
 #include "../../include/ctdet_voceval.h"
 #include <float.h>
 #include <limits.h>
+
+static_assert(CTDET_VOC_BAD_CLASS == EVAL_BAD_CLASS && CTDET_VOC_BAD_IMAGE == EVAL_BAD_IMAGE &&
+              CTDET_VOC_BAD_SCORE == EVAL_BAD_SCORE && CTDET_VOC_BAD_BOX == EVAL_BAD_BOX, "the public status bits");
 
 #define VE_LDS_TAKEN 128        // "taken" words (one u32 per ground truth) a cell keeps in LDS; a VOC cell has a few
 #define VE_NT 256               // AP workgroup = chunk of the class segment
 #define VE_POINTS 11            // recall points of the VOC2007 form
 
 struct VeMatchArgs {
-  const float* boxes; const float* scores; const int* classes; const int* image; long N;
-  const double* gt_boxes; const uint8_t* gt_difficult; const int* gt_off; int I, K;
+  EvalDets d;
+  const double* gt_boxes; const uint8_t* gt_difficult; const int* gt_off;
   const double* thrs; int T;
-  uint64_t* keys64; uint32_t* vals; const uint32_t* order_s; uint32_t* keys32;
-  const uint32_t* cell_order; int* dt_off; uint32_t* taken;
+  EvalOrderWs o; uint32_t* taken;
   uint8_t* flags; int* npos; int* status;
 };
-
-// status bits of a detection that takes no part (0: it does)
-__device__ __forceinline__ int ve_invalid(const VeMatchArgs& a, long i) {
-  const int c = a.classes[i], im = a.image[i];
-  int st = 0;
-  if (c < 0 || c >= a.K) st |= CTDET_VOC_BAD_CLASS;
-  if (im < 0 || im >= a.I) st |= CTDET_VOC_BAD_IMAGE;
-  if (!isfinite(a.scores[i])) st |= CTDET_VOC_BAD_SCORE;
-  const float* b = a.boxes + i * 4;
-  if (!(isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]))) st |= CTDET_VOC_BAD_BOX;
-  return st;
-}
-
-__global__ void __launch_bounds__(256) ve_clear_kernel(int* __restrict__ npos, int n, int* __restrict__ status) {
-  eval_clear(npos, n, status);
-}
 
 // order-S keys: ascending key = descending rint(score * 1000); equal quantised scores (-0 == +0 included) give equal keys
 __global__ void __launch_bounds__(256) ve_key_score_kernel(VeMatchArgs a) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.N) return;
-  const int st = ve_invalid(a, i);
+  if (i >= a.d.N) return;
+  const int st = eval_invalid(a.d, i);
   if (st) atomicOr(a.status, st);
-  a.keys64[i] = eval_score_key(rint((double)a.scores[i] * 1000.0));
-  a.vals[i] = (uint32_t)i;
+  a.o.keys64[i] = eval_score_key(rint((double)a.d.scores[i] * 1000.0));
+  a.o.vals[i] = (uint32_t)i;
 }
 
 // keys of the two orders taken from S: the class (by_cell == 0) or the (image, class) cell of the detection at position p of S;
 // a detection that takes no part gets the key behind the last one
 __global__ void __launch_bounds__(256) ve_key_group_kernel(VeMatchArgs a, int by_cell) {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.N) return;
-  const long i = a.order_s[p];
+  if (p >= a.d.N) return;
+  const long i = a.o.order_s[p];
+  const uint32_t K = (uint32_t)a.d.K;
   uint32_t key;
-  if (ve_invalid(a, i)) key = by_cell ? (uint32_t)a.I * (uint32_t)a.K : (uint32_t)a.K;
-  else key = by_cell ? (uint32_t)a.image[i] * (uint32_t)a.K + (uint32_t)a.classes[i] : (uint32_t)a.classes[i];
-  a.keys32[p] = key;
-}
-
-// off[c] = first position of the sorted keys that is >= c, c in [0, n]
-__global__ void __launch_bounds__(256) ve_offsets_kernel(const uint32_t* __restrict__ keys, long N, int n, int* __restrict__ off) {
-  const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c > n) return;
-  off[c] = eval_lower_bound(keys, N, c, [](uint32_t k) { return (long)k; });
+  if (eval_invalid(a.d, i)) key = by_cell ? (uint32_t)a.d.I * K : K;
+  else key = by_cell ? (uint32_t)a.d.image[i] * K + (uint32_t)a.d.classes[i] : (uint32_t)a.d.classes[i];
+  a.o.keys32[p] = key;
 }
 
 __global__ void __launch_bounds__(64) ve_match_kernel(VeMatchArgs a) {
   __shared__ uint32_t taken_lds[VE_LDS_TAKEN];
   const int cell = blockIdx.x, lane = threadIdx.x;
   const int g0 = a.gt_off[cell], G = a.gt_off[cell + 1] - g0;
-  const int d0 = a.dt_off[cell], D = a.dt_off[cell + 1] - d0;
+  const int d0 = a.o.dt_off[cell], D = a.o.dt_off[cell + 1] - d0;
   if (G == 0 && D == 0) return;
   const double* gb = a.gt_boxes + (long)g0 * 4;
   const uint8_t* gd = a.gt_difficult + g0;
@@ -105,7 +84,7 @@ __global__ void __launch_bounds__(64) ve_match_kernel(VeMatchArgs a) {
     for (int g = lane; g < G; g += 64) cnt += gd[g] == 0;
 #pragma unroll
     for (int o = 32; o; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if (lane == 0 && cnt) atomicAdd(&a.npos[cell % a.K], cnt);
+    if (lane == 0 && cnt) atomicAdd(&a.npos[cell % a.d.K], cnt);
   }
   if (D == 0) return;
   uint32_t* taken = G <= VE_LDS_TAKEN ? taken_lds : a.taken + g0;
@@ -114,11 +93,11 @@ __global__ void __launch_bounds__(64) ve_match_kernel(VeMatchArgs a) {
   const bool active = lane < a.T;
   const double thr = active ? a.thrs[lane] : 0.0;
   for (int d = 0; d < D; ++d) {
-    const long o = a.cell_order[d0 + d];
+    const long o = a.o.cell_order[d0 + d];
     // the reference's `xmin += 1` on an f32 scalar, then its "%.1f" round trip
-    const float fx1 = a.boxes[o * 4] + 1.0f, fy1 = a.boxes[o * 4 + 1] + 1.0f;
+    const float fx1 = a.d.boxes[o * 4] + 1.0f, fy1 = a.d.boxes[o * 4 + 1] + 1.0f;
     const double x1 = rint((double)fx1 * 10.0) / 10.0, y1 = rint((double)fy1 * 10.0) / 10.0;
-    const double x2 = rint((double)a.boxes[o * 4 + 2] * 10.0) / 10.0, y2 = rint((double)a.boxes[o * 4 + 3] * 10.0) / 10.0;
+    const double x2 = rint((double)a.d.boxes[o * 4 + 2] * 10.0) / 10.0, y2 = rint((double)a.d.boxes[o * 4 + 3] * 10.0) / 10.0;
     const double darea = (x2 - x1 + 1.0) * (y2 - y1 + 1.0);
     double best = -INFINITY;
     int jbest = INT_MAX;
@@ -179,18 +158,11 @@ __global__ void __launch_bounds__(VE_NT) ve_ap_kernel(VeApArgs a) {
   int ctp = 0, cfp = 0, nchunk = 0;
   for (int base = s0; base < s1; base += VE_NT, ++nchunk) {
     const int j = base + tid;
-    uint32_t tp = 0, fp = 0;
-    if (j < s1) {
-      const uint32_t f = a.flags[(long)a.order[j] * a.T + t];
-      tp = f == 1; fp = f == 2;
-    }
-    uint32_t tot;
-    const uint32_t sc = eval_scan_packed<VE_NT>(tp | (fp << 16), wsum, tot);     // two 16-bit counters
+    const EvalPos at = eval_chunk<VE_NT>(a.order, a.flags, a.T, t, 2, j, s1, wsum, ctp, cfp);     // flag 2: a false positive
     double prec = 0.0;
     if (j < s1) {
-      const int itp = ctp + (int)(sc & 0xFFFFu), ifp = cfp + (int)(sc >> 16);
-      const double rec = (double)itp / dnp;
-      prec = (double)itp / fmax((double)(itp + ifp), DBL_EPSILON);
+      const double rec = (double)at.itp / dnp;
+      prec = (double)at.itp / fmax((double)(at.itp + at.ifp), DBL_EPSILON);
       if (a.rec) a.rec[(long)t * a.N + j] = rec;
       if (a.prec) a.prec[(long)t * a.N + j] = prec;
 #pragma unroll
@@ -203,7 +175,6 @@ __global__ void __launch_bounds__(VE_NT) ve_ap_kernel(VeApArgs a) {
     if (lane == 0) sm[wv] = m;
     __syncthreads();
     if (tid == 0) cmax[nchunk] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
-    ctp += (int)(tot & 0xFFFFu); cfp += (int)(tot >> 16);
   }
   // ---- 11-point AP: the maxima over the workgroup (order-independent), then the reference's ordered sum
 #pragma unroll
@@ -241,48 +212,32 @@ __global__ void __launch_bounds__(VE_NT) ve_ap_kernel(VeApArgs a) {
   int c = 0;
   for (int base = s0; base < s1; base += VE_NT, ++c) {
     const int j = base + tid;
-    uint32_t tp = 0, fp = 0;
-    if (j < s1) {
-      const uint32_t f = a.flags[(long)a.order[j] * a.T + t];
-      tp = f == 1; fp = f == 2;
-    }
-    uint32_t tot;
-    const uint32_t sc = eval_scan_packed<VE_NT>(tp | (fp << 16), wsum, tot);     // two 16-bit counters
-    const int itp = ctp + (int)(sc & 0xFFFFu), ifp = cfp + (int)(sc >> 16);
-    eval_suffix_max<VE_NT>(sm, j < s1 ? (double)itp / fmax((double)(itp + ifp), DBL_EPSILON) : 0.0, 0.0);
+    const EvalPos at = eval_chunk<VE_NT>(a.order, a.flags, a.T, t, 2, j, s1, wsum, ctp, cfp);
+    eval_suffix_max<VE_NT>(sm, j < s1 ? (double)at.itp / fmax((double)(at.itp + at.ifp), DBL_EPSILON) : 0.0, 0.0);
     const double env = fmax(sm[tid], cmax[c]);
     __syncthreads();
     // recall changes exactly at a true positive: (tp / npos - (tp - 1) / npos) * envelope; 0 elsewhere, which adds nothing
-    sm[tid] = tp ? ((double)itp / dnp - (double)(itp - 1) / dnp) * env : 0.0;
+    sm[tid] = at.tp ? ((double)at.itp / dnp - (double)(at.itp - 1) / dnp) * env : 0.0;
     __syncthreads();
     if (tid == 0)
       for (int i = 0; i < VE_NT; ++i) ap = ap + sm[i];
     __syncthreads();
-    ctp += (int)(tot & 0xFFFFu); cfp += (int)(tot >> 16);
   }
   if (tid == 0) a.ap12[(long)k * a.T + t] = ap;
 }
 
-// ---- workspace: chunk values f64 [T * (N / 256 + K + 1)] (first: the AP call finds them without knowing NG or I), score keys
-// u64 [N] x 2, values / order S u32 [N] x 2, group keys u32 [N] x 2, cell order u32 [N], cell offsets i32 [I*K + 2], taken
-// words u32 [NG], then the sort block
-struct VeWs { size_t chunk, keys64, keys64_sorted, vals, order_s, keys32, keys32_sorted, cell_order, off, taken, sort, total; };
+// ---- workspace: chunk values f64 [T * (N / 256 + K + 1)] (first: the AP call finds them without knowing NG or I), the ordering
+// stage's blocks, taken words u32 [NG], then the sort block.  ws == nullptr: the sizes alone
+struct VeWs { double* chunk; EvalOrderWs o; uint32_t* taken; EvalSorter sort; size_t total; };
 static long ve_chunk_stride(long N, long K) { return N / VE_NT + K + 1; }
-static VeWs ve_layout(long N, long NG, long I, long K, long T) {
+static VeWs ve_layout(void* ws, long N, long NG, long I, long K, long T) {
+  EvalLayout l = {(uintptr_t)ws, 0};
   VeWs w;
-  size_t p = 0;
-  w.chunk = p; p += eval_up((size_t)T * (size_t)ve_chunk_stride(N, K) * 8);
-  w.keys64 = p; p += eval_up((size_t)N * 8);
-  w.keys64_sorted = p; p += eval_up((size_t)N * 8);
-  w.vals = p; p += eval_up((size_t)N * 4);
-  w.order_s = p; p += eval_up((size_t)N * 4);
-  w.keys32 = p; p += eval_up((size_t)N * 4);
-  w.keys32_sorted = p; p += eval_up((size_t)N * 4);
-  w.cell_order = p; p += eval_up((size_t)N * 4);
-  w.off = p; p += eval_up((size_t)(I * K + 2) * 4);
-  w.taken = p; p += eval_up((size_t)NG * 4);
-  w.sort = p; p += eval_sort_bytes(N);
-  w.total = p;
+  w.chunk = l.take<double>((size_t)T * (size_t)ve_chunk_stride(N, K));
+  w.o = eval_order_layout(l, N, I * K);
+  w.taken = l.take<uint32_t>(NG);
+  w.sort = eval_sort_layout(l, "voceval", N);
+  w.total = l.p;
   return w;
 }
 
@@ -296,63 +251,38 @@ extern "C" {
 
 size_t ctdet_voceval_workspace_bytes(int64_t N, int64_t NG, int32_t I, int32_t K, int32_t T) {
   if (ve_check_dims("voceval_workspace_bytes", N, NG, I, K, T)) return 0;
-  return ve_layout(N, NG, I, K, T).total;
+  return ve_layout(nullptr, N, NG, I, K, T).total;
 }
 
 int32_t ctdet_voceval_match(const float* boxes, const float* scores, const int32_t* classes, const int32_t* image, int64_t N,
                             const double* gt_boxes, const uint8_t* gt_difficult, const int32_t* gt_off, int64_t NG, int32_t I,
                             int32_t K, const double* thrs, int32_t T, void* workspace, int32_t* order, int32_t* cls_off,
                             uint8_t* flags, int32_t* npos, int32_t* status, void* stream) {
-  CTDET_CHECK(gt_off, "voceval_match: null pointer gt_off");
-  CTDET_CHECK(thrs, "voceval_match: null pointer thrs");
-  CTDET_CHECK(workspace, "voceval_match: null pointer workspace");
-  CTDET_CHECK(cls_off, "voceval_match: null pointer cls_off");
-  CTDET_CHECK(npos, "voceval_match: null pointer npos");
-  CTDET_CHECK(status, "voceval_match: null pointer status");
-  CTDET_CHECK(NG <= 0 || gt_boxes, "voceval_match: null pointer gt_boxes");
-  CTDET_CHECK(NG <= 0 || gt_difficult, "voceval_match: null pointer gt_difficult");
-  CTDET_CHECK(N <= 0 || boxes, "voceval_match: null pointer boxes");
-  CTDET_CHECK(N <= 0 || scores, "voceval_match: null pointer scores");
-  CTDET_CHECK(N <= 0 || classes, "voceval_match: null pointer classes");
-  CTDET_CHECK(N <= 0 || image, "voceval_match: null pointer image");
-  CTDET_CHECK(N <= 0 || order, "voceval_match: null pointer order");
-  CTDET_CHECK(N <= 0 || flags, "voceval_match: null pointer flags");
-  const int rc = ve_check_dims("voceval_match", N, NG, I, K, T);
-  if (rc) return rc;
+  const char* what = "voceval_match";
+  if (const int rc = eval_check_match_ptrs(what, N, NG, boxes, scores, classes, image, gt_boxes, gt_off, workspace, order,
+                                           cls_off, flags, status))
+    return rc;
+  EVAL_CHECK_PTR(what, thrs);
+  EVAL_CHECK_PTR(what, npos);
+  EVAL_CHECK_PTR_IF(what, NG, gt_difficult);
+  if (const int rc = ve_check_dims(what, N, NG, I, K, T)) return rc;
   EVAL_CHECK_WORKSPACE("voceval_match", workspace);
   CTDET_KERNEL("ve_match_kernel<wave per cell,%d thresholds>", T);
   hipStream_t s = (hipStream_t)stream;
-  const VeWs w = ve_layout(N, NG, I, K, T);
-  char* ws = (char*)workspace;
-  VeMatchArgs a;
-  a.boxes = boxes; a.scores = scores; a.classes = classes; a.image = image; a.N = N;
-  a.gt_boxes = gt_boxes; a.gt_difficult = gt_difficult; a.gt_off = gt_off; a.I = I; a.K = K; a.thrs = thrs; a.T = T;
-  a.keys64 = (uint64_t*)(ws + w.keys64); a.vals = (uint32_t*)(ws + w.vals); a.order_s = (const uint32_t*)(ws + w.order_s);
-  a.keys32 = (uint32_t*)(ws + w.keys32); a.cell_order = (const uint32_t*)(ws + w.cell_order); a.dt_off = (int*)(ws + w.off);
-  a.taken = (uint32_t*)(ws + w.taken); a.flags = flags; a.npos = npos; a.status = status;
-  const uint32_t* k32s = (const uint32_t*)(ws + w.keys32_sorted);
+  const VeWs w = ve_layout(workspace, N, NG, I, K, T);
+  const VeMatchArgs a = {{boxes, scores, classes, image, N, I, K}, gt_boxes, gt_difficult, gt_off, thrs, T, w.o, w.taken,
+                         flags, npos, status};
   const int ncell = I * K;
-  const unsigned nb = (unsigned)((N + 255) / 256);
-  const auto sort = [&](auto* kin, auto* kout, const uint32_t* vin, uint32_t* vout, int bits) {     // tmp: the sort block
-    return eval_sort("voceval", kin, kout, vin, vout, N, bits, ws + w.sort, w.total - w.sort, s);
-  };
-  hipLaunchKernelGGL(ve_clear_kernel, dim3((K + 255) / 256), dim3(256), 0, s, npos, K, status);
+  const dim3 nb((unsigned)((N + 255) / 256)), nt(256);
+  hipLaunchKernelGGL(eval_clear_kernel, dim3((K + 255) / 256), nt, 0, s, npos, K, status);
   if (N) {
-    hipLaunchKernelGGL(ve_key_score_kernel, dim3(nb), dim3(256), 0, s, a);
-    int src = sort(a.keys64, (uint64_t*)(ws + w.keys64_sorted), a.vals, (uint32_t*)(ws + w.order_s), 64);
-    if (src) return src;
-    hipLaunchKernelGGL(ve_key_group_kernel, dim3(nb), dim3(256), 0, s, a, 0);
-    src = sort(a.keys32, (uint32_t*)(ws + w.keys32_sorted), a.order_s, (uint32_t*)order, eval_bits((unsigned long)K));
-    if (src) return src;
+    hipLaunchKernelGGL(ve_key_score_kernel, nb, nt, 0, s, a);
+    if (const int rc = w.sort.sort(w.o.keys64, w.o.keys64_sorted, w.o.vals, w.o.order_s, 64, s)) return rc;
+    hipLaunchKernelGGL(ve_key_group_kernel, nb, nt, 0, s, a, 0);
   }
-  hipLaunchKernelGGL(ve_offsets_kernel, dim3((K + 1 + 255) / 256), dim3(256), 0, s, k32s, (long)N, K, cls_off);
-  if (N) {
-    hipLaunchKernelGGL(ve_key_group_kernel, dim3(nb), dim3(256), 0, s, a, 1);
-    const int src = sort(a.keys32, (uint32_t*)(ws + w.keys32_sorted), a.order_s, (uint32_t*)(ws + w.cell_order),
-                         eval_bits((unsigned long)ncell));
-    if (src) return src;
-  }
-  hipLaunchKernelGGL(ve_offsets_kernel, dim3((ncell + 1 + 255) / 256), dim3(256), 0, s, k32s, (long)N, ncell, a.dt_off);
+  if (const int rc = w.sort.sort_cut(w.o.keys32, w.o.keys32_sorted, w.o.order_s, (uint32_t*)order, K, cls_off, s)) return rc;
+  if (N) hipLaunchKernelGGL(ve_key_group_kernel, nb, nt, 0, s, a, 1);
+  if (const int rc = w.sort.sort_cut(w.o.keys32, w.o.keys32_sorted, w.o.order_s, w.o.cell_order, ncell, w.o.dt_off, s)) return rc;
   hipLaunchKernelGGL(ve_match_kernel, dim3(ncell), dim3(64), 0, s, a);
   CTDET_LAUNCH_CHECK();
   return 0;
@@ -361,25 +291,22 @@ int32_t ctdet_voceval_match(const float* boxes, const float* scores, const int32
 int32_t ctdet_voceval_ap(const int32_t* order, const int32_t* cls_off, const uint8_t* flags, const int32_t* npos, int64_t N,
                          int32_t K, int32_t T, const double* points, void* workspace, double* ap07, double* ap12, double* rec,
                          double* prec, void* stream) {
-  CTDET_CHECK(cls_off, "voceval_ap: null pointer cls_off");
-  CTDET_CHECK(npos, "voceval_ap: null pointer npos");
-  CTDET_CHECK(points, "voceval_ap: null pointer points");
-  CTDET_CHECK(workspace, "voceval_ap: null pointer workspace");
-  CTDET_CHECK(ap07, "voceval_ap: null pointer ap07");
-  CTDET_CHECK(ap12, "voceval_ap: null pointer ap12");
-  CTDET_CHECK(N <= 0 || order, "voceval_ap: null pointer order");
-  CTDET_CHECK(N <= 0 || flags, "voceval_ap: null pointer flags");
-  const int rc = ve_check_dims("voceval_ap", N, 0, 1, K, T);
-  if (rc) return rc;
+  const char* what = "voceval_ap";
+  EVAL_CHECK_PTR(what, cls_off);
+  EVAL_CHECK_PTR(what, npos);
+  EVAL_CHECK_PTR(what, points);
+  EVAL_CHECK_PTR(what, workspace);
+  EVAL_CHECK_PTR(what, ap07);
+  EVAL_CHECK_PTR(what, ap12);
+  EVAL_CHECK_PTR_IF(what, N, order);
+  EVAL_CHECK_PTR_IF(what, N, flags);
+  if (const int rc = ve_check_dims(what, N, 0, 1, K, T)) return rc;
   CTDET_CHECK((int64_t)K * T < (1LL << 31), "voceval_ap: K*T too large");
   EVAL_CHECK_WORKSPACE("voceval_ap", workspace);
   CTDET_KERNEL("ve_ap_kernel<workgroup per (k,t),two passes>");
   // the chunk values lead the layout and their size depends on N, K and T alone: the workspace of the match call serves
-  VeApArgs a;
-  a.order = order; a.cls_off = cls_off; a.flags = flags; a.npos = npos; a.N = N; a.K = K; a.T = T; a.points = points;
-  a.chunk_stride = ve_chunk_stride(N, K);
-  a.chunk = (double*)((char*)workspace + ve_layout(N, 0, 1, K, T).chunk);
-  a.ap07 = ap07; a.ap12 = ap12; a.rec = rec; a.prec = prec;
+  const VeApArgs a = {order, cls_off, flags, npos, N, K, T, points, ve_layout(workspace, N, 0, 1, K, T).chunk,
+                      ve_chunk_stride(N, K), ap07, ap12, rec, prec};
   hipLaunchKernelGGL(ve_ap_kernel, dim3(K * T), dim3(VE_NT), 0, (hipStream_t)stream, a);
   CTDET_LAUNCH_CHECK();
   return 0;

@@ -1,6 +1,7 @@
-"""What the COCO and the Pascal VOC box-AP scorers share on the Python side: `cells_csr`, the ground-truth layout both
-matchers read; `DeviceScorer`, the base of the device drivers (`COCOevalHIP`, `VOCevalHIP`); `BoxEvaluator`, the base of the
-dataset evaluators (`COCOEvaluator`, `PascalVOCDetectionEvaluator`).  A refusal names the class that makes it."""
+"""What the COCO, Pascal VOC and LVIS box-AP scorers share on the Python side: `cells_csr`, the ground-truth layout the
+matchers read; `DeviceScorer`, the base of the device drivers (`COCOevalHIP`; `VOCevalHIP` and `LVISevalHIP`, which also take
+their common outputs and their status-word check from it); `BoxEvaluator`, the base of the dataset evaluators.  A refusal
+names the class that makes it."""
 import ctypes as C
 
 import numpy as np
@@ -25,7 +26,11 @@ def ptr(t):
 
 
 class DeviceScorer:
-    """the detections of a whole dataset as DEVICE tensors, normalised in `_dt`: boxes f32 [N,4], scores f32, classes, image i32"""
+    """the detections of a whole dataset as DEVICE tensors, normalised in `_dt`: boxes f32 [N,4], scores f32, classes, image i32.
+    `IMAGE_LIST`, `status_message`, `_outputs` and `_check_status` serve only the scorers whose match call has a status word
+    (`VOCevalHIP`, `LVISevalHIP`); `COCOevalHIP` uses none of them."""
+
+    IMAGE_LIST = "the ground truth's image list"      # what a scorer calls the images its `image` indices point into
 
     def __init__(self, gt, boxes, scores, classes, image):
         for name, t in (("boxes", boxes), ("scores", scores), ("classes", classes), ("image", image)):
@@ -50,6 +55,24 @@ class DeviceScorer:
         """an entry point on the detections' device and its current stream (the last argument); a failure raises its text"""
         with torch.cuda.device(self._device):
             _lib.check(fn(*args, C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)), fn.__name__)
+
+    @classmethod
+    def status_message(cls, status):
+        """the causes in a match call's status word (the EVAL_BAD_* bits of csrc/eval_common.h)"""
+        causes = ((1, "a class index outside [0, K)"), (2, f"an image index outside {cls.IMAGE_LIST}"),
+                  (4, "a score that is not finite"), (8, "a box coordinate that is not finite"))
+        return "; ".join(text for bit, text in causes if status & bit)
+
+    def _outputs(self, N, K, ncol):
+        """what every match call writes: order i32 [N], cls_off i32 [K+1], flags u8 [N, ncol], the status word"""
+        return (torch.empty(N, dtype=torch.int32, device=self._device), torch.empty(K + 1, dtype=torch.int32, device=self._device),
+                torch.empty((N, ncol), dtype=torch.uint8, device=self._device), torch.empty(1, dtype=torch.int32, device=self._device))
+
+    def _check_status(self, status):
+        """the one synchronisation of a scorer: reads the status word into `self.status`; invalid detections raise their causes"""
+        self.status = int(status.item())
+        if self.status:
+            raise ValueError(f"{type(self).__name__}: the detections hold " + self.status_message(self.status))
 
 
 class BoxEvaluator(DatasetEvaluator):

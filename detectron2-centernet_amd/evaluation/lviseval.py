@@ -9,9 +9,6 @@ import torch
 from .. import _lib
 from .box_scoring import DeviceScorer, cells_csr, ptr as _ptr
 
-# status bits of ctdet_lviseval_match (CTDET_LVIS_BAD_* in include/ctdet_lviseval.h)
-STATUS_CAUSES = ((1, "a class index outside [0, K)"), (2, "an image index outside the ground truth's image list"),
-                 (4, "a score that is not finite"), (8, "a box coordinate that is not finite"))
 LIST_NEG, LIST_NEL = 1, 2          # CTDET_LVIS_NEG / CTDET_LVIS_NEL
 
 IOU_THRS = np.linspace(0.5, 0.95, 10)
@@ -48,10 +45,6 @@ def prepare_lvis_ground_truth(dataset):
                 lists[i, cat_index[c]] |= bit
     return {"image_ids": image_ids, "cat_ids": cat_ids, "boxes": boxes, "area": area, "ignore": ignore, "off": off,
             "image": image, "classes": classes, "lists": lists, "frequency": [c.get("frequency", "") for c in cats]}
-
-
-def status_message(status):
-    return "; ".join(text for bit, text in STATUS_CAUSES if status & bit)
 
 
 def summarize_lvis(precision, recall, frequency):
@@ -99,11 +92,8 @@ class LVISevalHIP(DeviceScorer):
         gt_boxes, gt_area, gt_ignore, gt_off = up(gt["boxes"], True), up(gt["area"], True), up(gt["ignore"]), up(gt["off"])
         lists = up(np.ascontiguousarray(gt["lists"], dtype=np.uint8).reshape(I, K))
         thrs, rngs, recs = up(iou_thrs, True), up(area_rngs, True), up(rec_thrs, True)
-        order = torch.empty(N, dtype=torch.int32, device=dev)
-        cls_off = torch.empty(K + 1, dtype=torch.int32, device=dev)
-        flags = torch.empty((N, A * T), dtype=torch.uint8, device=dev)
+        order, cls_off, flags, status = self._outputs(N, K, A * T)
         npig = torch.empty((K, A), dtype=torch.int32, device=dev)
-        status = torch.empty(1, dtype=torch.int32, device=dev)
         precision = torch.empty((T, R, K, A), dtype=torch.float64, device=dev)
         recall = torch.empty((T, K, A), dtype=torch.float64, device=dev)
         self._call(lib.ctdet_lviseval_match,
@@ -112,10 +102,7 @@ class LVISevalHIP(DeviceScorer):
                    _ptr(cls_off), _ptr(flags), _ptr(npig), _ptr(status))
         self._call(lib.ctdet_lviseval_accumulate,
                    _ptr(order), _ptr(cls_off), _ptr(flags), _ptr(npig), N, K, A, T, _ptr(recs), R, _ptr(precision), _ptr(recall))
-        # the one synchronisation of the scorer: the status word and the two tables
-        self.status = int(status.item())
-        if self.status:
-            raise ValueError("LVISevalHIP: the detections hold " + status_message(self.status))
+        self._check_status(status)     # the one synchronisation of the scorer: the status word and the two tables
         self.precision, self.recall = precision.cpu().numpy(), recall.cpu().numpy()
         self.order, self.cls_off, self.flags, self.npig = order, cls_off, flags, npig
         return self.precision, self.recall
@@ -126,3 +113,6 @@ class LVISevalHIP(DeviceScorer):
         self.ar = {k: v for k, v in res.items() if k.startswith("AR")}
         self.results = {k: v for k, v in res.items() if not k.startswith("AR")}
         return self.results
+
+
+status_message = LVISevalHIP.status_message     # the causes in a status word of ctdet_lviseval_match (CTDET_LVIS_BAD_*)

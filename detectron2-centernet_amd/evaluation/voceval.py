@@ -11,10 +11,6 @@ from .. import _lib
 from ..data.pascal_voc import read_voc_ids, read_voc_objects
 from .box_scoring import DeviceScorer, cells_csr, ptr as _ptr
 
-# status bits of ctdet_voceval_match (CTDET_VOC_BAD_* in include/ctdet_voceval.h)
-STATUS_CAUSES = ((1, "a class index outside [0, K)"), (2, "an image index outside the split's image list"),
-                 (4, "a score that is not finite"), (8, "a box coordinate that is not finite"))
-
 # the reference's `np.arange(0.0, 1.1, 0.1)`: the recall points of the 11-point form, as numpy rounds them
 RECALL_POINTS_07 = np.arange(0.0, 1.1, 0.1)
 
@@ -45,16 +41,14 @@ def parse_voc_ground_truth(dirname, split, class_names):
     return prepare_voc_ground_truth(ids, class_names, objects)
 
 
-def status_message(status):
-    return "; ".join(text for bit, text in STATUS_CAUSES if status & bit)
-
-
 class VOCevalHIP(DeviceScorer):
     """gt: `parse_voc_ground_truth(...)`.  Detections, concatenated over the dataset, as DEVICE tensors: boxes f32 [N,4] XYXY
     (0-based, as the model gives them), scores f32 [N], classes i32 [N] in [0,K), image i32 [N] (index into gt["image_ids"]).
 
     evaluate(thresholds, year) -> AP table f64 [K, T] (fractions): the 11-point form for 2007, the area form for 2012.  Both
     tables stay in `ap07` / `ap12`; with keep_pr=True `rec` / `prec` [T, N] (by position of the total order `order`) too."""
+
+    IMAGE_LIST = "the split's image list"
 
     def __init__(self, gt, boxes, scores, classes, image):
         super().__init__(gt, boxes, scores, classes, image)
@@ -72,11 +66,8 @@ class VOCevalHIP(DeviceScorer):
         ws, ws_ptr = self._workspace(lib.ctdet_voceval_workspace_bytes(N, NG, I, K, T), lambda text: ValueError(f"voceval: {text}"))
         gt_boxes, gt_diff, gt_off = up(gt["boxes"], True), up(gt["difficult"]), up(gt["off"])
         thrs, points = up(thresholds, True), up(RECALL_POINTS_07, True)
-        order = torch.empty(N, dtype=torch.int32, device=dev)
-        cls_off = torch.empty(K + 1, dtype=torch.int32, device=dev)
-        flags = torch.empty((N, T), dtype=torch.uint8, device=dev)
+        order, cls_off, flags, status = self._outputs(N, K, T)
         npos = torch.empty(K, dtype=torch.int32, device=dev)
-        status = torch.empty(1, dtype=torch.int32, device=dev)
         ap07 = torch.empty((K, T), dtype=torch.float64, device=dev)
         ap12 = torch.empty((K, T), dtype=torch.float64, device=dev)
         rec = torch.empty((T, N), dtype=torch.float64, device=dev) if keep_pr else None
@@ -87,10 +78,10 @@ class VOCevalHIP(DeviceScorer):
         self._call(lib.ctdet_voceval_ap,
                    _ptr(order), _ptr(cls_off), _ptr(flags), _ptr(npos), N, K, T, _ptr(points), ws_ptr, _ptr(ap07), _ptr(ap12),
                    _ptr(rec), _ptr(prec))
-        # the one synchronisation of the scorer: the status word and the two [K, T] tables
-        self.status = int(status.item())
-        if self.status:
-            raise ValueError("VOCevalHIP: the detections hold " + status_message(self.status))
+        self._check_status(status)     # the one synchronisation of the scorer: the status word and the two [K, T] tables
         self.ap07, self.ap12 = ap07.cpu().numpy(), ap12.cpu().numpy()
         self.order, self.cls_off, self.npos, self.flags, self.rec, self.prec = order, cls_off, npos, flags, rec, prec
         return self.ap07 if year == 2007 else self.ap12
+
+
+status_message = VOCevalHIP.status_message     # the causes in a status word of ctdet_voceval_match (CTDET_VOC_BAD_*)

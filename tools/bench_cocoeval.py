@@ -20,26 +20,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cocoeval_ref as CR  # noqa: E402
+from _evalbench import timed  # noqa: E402
 from detectron2_centernet_amd.data.catalog import DatasetCatalog, MetadataCatalog  # noqa: E402
 from detectron2_centernet_amd.evaluation import COCOEvaluator, COCOevalHIP, prepare_ground_truth  # noqa: E402
 from detectron2_centernet_amd.structures import Boxes, BoxMode, Instances  # noqa: E402
-
-
-def timed(fn, warmup, iters, repeats):
-    """ms per call: the mean of each of `repeats` windows of `iters` calls"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return out
 
 
 def main():

@@ -9,7 +9,6 @@ synthetic: `lvis_scale_inputs` of tests/lvis_cases.py, the oracle module this to
     alternative (its per-class part does not shrink with the subset, so the scaled figure is an upper estimate),
 and one JSON line with all of them."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -22,25 +21,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import lvis_cases as LC  # noqa: E402
+from _evalbench import f64, ptr as p, stream as current_stream, timed, workspace  # noqa: E402
 from detectron2_centernet_amd import _lib  # noqa: E402
 from detectron2_centernet_amd.evaluation import LVISevalHIP  # noqa: E402
-
-
-def timed(fn, warmup, iters, repeats):
-    """ms per call: the mean of each of `repeats` windows of `iters` calls"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return out
 
 
 def main():
@@ -73,19 +56,16 @@ def main():
         walls.append((time.perf_counter() - t0) * 1e3)
     # ---- the two calls on their own
     L = _lib.lviseval_lib()
-    p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
-    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)     # noqa: E731
-    gb, ga = f64(gt["boxes"]), f64(gt["area"])
+    gb, ga = f64(gt["boxes"], dev), f64(gt["area"], dev)
     gi, go, gl = (torch.as_tensor(gt[k]).to(dev) for k in ("ignore", "off", "lists"))
-    thr, rng, rec = f64(LC.IOU_THRS), f64(LC.AREA_RNGS), f64(LC.REC_THRS)
-    ws = torch.empty(L.ctdet_lviseval_workspace_bytes(N, NG, I, K, A, T) + 256, dtype=torch.uint8, device=dev)
-    wsp = C.c_void_p((ws.data_ptr() + 255) & ~255)
+    thr, rng, rec = f64(LC.IOU_THRS, dev), f64(LC.AREA_RNGS, dev), f64(LC.REC_THRS, dev)
+    ws, wsp = workspace(L.ctdet_lviseval_workspace_bytes(N, NG, I, K, A, T), dev)
     order, cls_off = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(K + 1, dtype=torch.int32, device=dev)
     flags, npig = torch.empty((N, A * T), dtype=torch.uint8, device=dev), torch.empty((K, A), dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     precision = torch.empty((T, R, K, A), dtype=torch.float64, device=dev)
     recall = torch.empty((T, K, A), dtype=torch.float64, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = current_stream(dev)
 
     def match():
         _lib.check(L.ctdet_lviseval_match(p(d[0]), p(d[1]), p(d[2]), p(d[3]), N, p(gb), p(ga), p(gi), p(go), NG, p(gl), I, K, p(thr),

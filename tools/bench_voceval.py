@@ -9,7 +9,6 @@ objects, synthetic: `voc_scale_inputs` of tests/voc_cases.py, the oracle module 
 and one JSON line with all of them.  --images-per-s puts the device time of the eval pass that produces the detections next
 to them (images / the images/s `bench.py` measured)."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -22,26 +21,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import voc_cases as VC  # noqa: E402
+from _evalbench import f64, ptr as p, stream as current_stream, timed, workspace  # noqa: E402
 from detectron2_centernet_amd import _lib  # noqa: E402
 from detectron2_centernet_amd.evaluation import VOCevalHIP  # noqa: E402
 from detectron2_centernet_amd.evaluation.voceval import RECALL_POINTS_07  # noqa: E402
-
-
-def timed(fn, warmup, iters, repeats):
-    """ms per call: the mean of each of `repeats` windows of `iters` calls"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return out
 
 
 def main():
@@ -72,17 +55,14 @@ def main():
         walls.append((time.perf_counter() - t0) * 1e3)
     # ---- the two calls on their own
     L = _lib.voceval_lib()
-    p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
-    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)     # noqa: E731
-    gb, gd, go = f64(gt["boxes"]), torch.as_tensor(gt["difficult"]).to(dev), torch.as_tensor(gt["off"]).to(dev)
-    thr, pts = f64(VC.THRESHOLDS), f64(RECALL_POINTS_07)
-    ws = torch.empty(L.ctdet_voceval_workspace_bytes(N, NG, I, K, T) + 256, dtype=torch.uint8, device=dev)
-    wsp = C.c_void_p((ws.data_ptr() + 255) & ~255)
+    gb, gd, go = f64(gt["boxes"], dev), torch.as_tensor(gt["difficult"]).to(dev), torch.as_tensor(gt["off"]).to(dev)
+    thr, pts = f64(VC.THRESHOLDS, dev), f64(RECALL_POINTS_07, dev)
+    ws, wsp = workspace(L.ctdet_voceval_workspace_bytes(N, NG, I, K, T), dev)
     order, cls_off = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(K + 1, dtype=torch.int32, device=dev)
     flags, npos = torch.empty((N, T), dtype=torch.uint8, device=dev), torch.empty(K, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     ap07, ap12 = (torch.empty((K, T), dtype=torch.float64, device=dev) for _ in range(2))
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = current_stream(dev)
 
     def match():
         _lib.check(L.ctdet_voceval_match(p(d[0]), p(d[1]), p(d[2]), p(d[3]), N, p(gb), p(gd), p(go), NG, I, K, p(thr), T, wsp,
